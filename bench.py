@@ -19,14 +19,19 @@
            estimated work; every rank loads the reads overlapping its region, counts only its own
            columns and the ranks all-gather their PASS-candidate call rows over RCCL.
 
+A plain run sets up, warms up, times --steps steps and prints the line.  --full also runs the legs beside the headline, after the clock
+unless said otherwise: the CPU baseline (before the timed steps), the re-counts of a resident store, the C4 one-shot leg and the
+end-to-end leg (the --no-* options and --e2e-reads leave them out one by one).  --dump-outputs DIR writes what the last timed step
+computed as float64 .npy files (dump_outputs).
+
 One JSON line on rank 0.  `roofline` is for the kernel that takes the most time of a step - k_tm_count_direct, the count made inside the
 load (one 2-byte load per entry and lane from the caller's events, counters in LDS) - priced by SURVEY 8(d)'s bytes alone: 2 B per
 admitted event + 24 B per admitted read + 168 B per row it emits (sort scratch and re-reads are NOT algorithmic), over its HIP-event
 time on its own stream.  `roofline.path_frac` prices the WHOLE step the same way: (2 E + 24 R + 168 S_emit) / ms_per_step / peak.
 `roofline.step_traffic` is the fabric traffic of every kernel of a step from the newest profiles/ file recorded for this build (sum and
-its ratio to the algorithmic bytes).  `config.recount_ms` is a count + call pass over a RESIDENT store (what the second pass of the
-re-annotation loop pays), measured after the clock on one extra load that keeps its store (`config.load_that_also_writes_the_store_ms`).
-`cpu_baseline` times the CPU oracle (oracle/, kind "port") on a bounded sample of the same workload on ALL of this box's host cores.
+its ratio to the algorithmic bytes).  `config.recount_ms` (--full) is a count + call pass over a RESIDENT store (what the second pass of
+the re-annotation loop pays), measured after the clock on one extra load that keeps its store (`config.load_that_also_writes_the_store_ms`).
+`cpu_baseline` (--full) times the CPU oracle (oracle/, kind "port") on a bounded sample of the same workload on all host cores.
 `roofline.traffic` is quoted from the newest profiles/ file only when that file was recorded for this build of the kernels (else null +
 traffic_stale).
 """
@@ -320,18 +325,76 @@ def recorded_traffic(kernel):
     return None, None, None, None
 
 
+DUMP_COUNT_ROWS = 1 << 15      # count rows sampled per cell type
+DUMP_CALLS = 1 << 14           # call records sampled
+DUMP_SEED = 20240601
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir, dev, step_result):
+    """--dump-outputs: what the last timed step computed, as a caller of that path receives it - the count rows of every cell type
+    (Engine.fetch_counts) and the call records (lsg_export_calls, kind 0: every merged site) - written as float64 .npy files.  At full size
+    they are far larger than 64 MB, so the rows go out as a fixed, seeded sample (sorted row indices in *_index.npy); the column sums of every
+    cell type's counts cover all of its rows.  step.npy: rows per cell type, counted columns, merged sites, step-1 candidates."""
+    import torch
+    from longsom_amd import _lib
+    os.makedirs(out_dir, exist_ok=True)
+    rows, cols, n_sites, n_cand = step_result
+    files = {"step": np.array(list(rows) + [cols, n_sites, n_cand], np.float64)}
+
+    def sample(n, k, salt):
+        if n <= k:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.default_rng(DUMP_SEED + salt).choice(n, size=k, replace=False))
+
+    for ct in range(len(rows)):
+        keys, ref, counts = eng.fetch_counts(ct)
+        idx = sample(len(keys), DUMP_COUNT_ROWS, ct)
+        files["counts_ct%d_index" % ct] = idx.astype(np.float64)
+        files["counts_ct%d_key" % ct] = keys[idx].astype(np.float64)
+        files["counts_ct%d_ref" % ct] = ref[idx].astype(np.float64)
+        files["counts_ct%d_counts" % ct] = counts[idx].astype(np.float64)
+        files["counts_ct%d_column_sums" % ct] = counts.sum(axis=0, dtype=np.uint64).astype(np.float64)
+        del keys, ref, counts
+    n = eng.export_calls(0)
+    assert n == n_sites, "lsg_export_calls selected %d of %d merged sites" % (n, n_sites)
+    buf = torch.empty((max(n, 1), CALL_BYTES), dtype=torch.uint8, device=dev)
+    if n:
+        eng.export_calls(0, buf.data_ptr(), n)
+    torch.cuda.synchronize()
+    idx = sample(n, DUMP_CALLS, 100)
+    calls = buf[torch.from_numpy(idx).to(dev)].cpu().numpy().view(np.dtype(_lib.Call)).reshape(-1)
+    del buf
+    torch.cuda.empty_cache()                                       # (the C4 leg of --full wants the device's memory)
+    files["calls_index"] = idx.astype(np.float64)
+    for f in calls.dtype.names:
+        if f != "pad":
+            files["calls_" + f] = calls[f].astype(np.float64)
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes" % total
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=80)          # (80 x 25.6 ms: the timed region keeps the GPU busy for 2 s)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reads", type=float, default=None, help="override the read count (development only; the reported config changes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c4", action="store_true", help="leave the C4 one-shot leg (config.c4_oneshot, after the timed steps, N=1 only) out")
-    ap.add_argument("--no-recount", action="store_true", help="leave the re-counts of the resident store after the timed steps out (profiling runs: every kernel launch then belongs to a step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the re-counts of a resident store, the C4 one-shot leg and the end-to-end leg (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-c4", action="store_true", help="--full without the C4 one-shot leg (config.c4_oneshot, after the timed steps, N=1 only)")
+    ap.add_argument("--no-recount", action="store_true", help="--full without the re-counts of the resident store after the timed steps")
     ap.add_argument("--e2e-reads", type=float, default=None,
-                    help="reads of the end-to-end leg (files in -> files out, after the timed steps, N=1 only); 0 = none; default 1e7 = the metric's whole BAM (none with --reads)")
+                    help="--full: reads of the end-to-end leg (files in -> files out, after the timed steps, N=1 only); 0 = none; default 1e7 = the metric's whole BAM (none with --reads)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.e2e_reads and not args.full:
+        ap.error("--e2e-reads sizes a leg of --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
 
@@ -376,7 +439,7 @@ def main():
     eng.set_barcodes(model.celltype_of, 2)
 
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         base = cpu_baseline(eng, model)
 
     lo, hi, g_lo, g_hi = region_shards(model, world)[rank]
@@ -480,10 +543,12 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     _, layout_ms, layout_bytes = eng.layout_info()
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank), dev, (rows, cols, n_sites, n_cand))
     # after the clock: counts of the SAME resident store (the re-annotation loop's second pass, a parameter sweep)
     torch.cuda.synchronize()
     t_re = time.perf_counter()
-    n_re = 0 if args.no_recount else 5
+    n_re = 5 if args.full and not args.no_recount else 0
     re_walk_ms = 0.0
     store_build_ms = None
     if n_re and direct:                                             # the timed loads kept no store: one load that does, for the re-counts
@@ -504,13 +569,15 @@ def main():
         print({f: (list(getattr(st, f)) if f.endswith("by_kernel") else getattr(st, f)) for f, _ in st._fields_ if f != "pad_"}, file=sys.stderr)
     shape_entries, _, shape_events = eng.store_shape()
     c4 = None
-    if rank == 0 and world == 1 and args.reads is None and not args.no_c4:
+    if rank == 0 and world == 1 and args.reads is None and args.full and not args.no_c4:
         eng.unload_reads()
         for b in ("send", "recv"):
             gather[b] = None
         c4 = c4_oneshot(local_rank)
     e2e = None
-    e2e_reads = int(args.e2e_reads) if args.e2e_reads is not None else (10_000_000 if args.reads is None else 0)
+    e2e_reads = 0
+    if args.full:
+        e2e_reads = int(args.e2e_reads) if args.e2e_reads is not None else (10_000_000 if args.reads is None else 0)
     if rank == 0 and world == 1 and e2e_reads > 0:
         e2e = end_to_end(e2e_reads)
     if dist_on:

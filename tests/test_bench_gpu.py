@@ -21,7 +21,7 @@ def run_bench(args, env=None, launcher=None):
 
 
 def test_contract_line_and_sharded_run():
-    one = run_bench(["--reads", "3e5", "--steps", "2", "--warmup", "1"])
+    one = run_bench(["--full", "--reads", "3e5", "--steps", "2", "--warmup", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
         assert k in one, k
@@ -34,7 +34,7 @@ def test_contract_line_and_sharded_run():
     assert "traffic_stale" in r and (r["traffic"] is None or r["traffic_stale"] is False)
     assert abs(one["value"] - one["config"]["sites_counted"] / (one["ms_per_step"] / 1e3)) < 1e-3 * one["value"]
 
-    two = run_bench(["--gpus", "2", "--reads", "3e5", "--steps", "2", "--warmup", "1"], env={"LSG_BENCH_DEVICE": "0", "LSG_BENCH_BACKEND": "gloo"},
+    two = run_bench(["--full", "--gpus", "2", "--reads", "3e5", "--steps", "2", "--warmup", "1"], env={"LSG_BENCH_DEVICE": "0", "LSG_BENCH_BACKEND": "gloo"},
                     launcher=[sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                               "--master-port", "29533"])
     assert two["n_gpus"] == 2 and "cpu_baseline" not in two
@@ -44,7 +44,7 @@ def test_contract_line_and_sharded_run():
     # the single fixed-capacity all-gather: a capacity that is too small at first is grown in warm-up and moves the same rows
     assert two["config"]["pass_rows_gathered"] is not None and two["config"]["pass_rows_gathered"] >= 0
     # ... and started the documented way: `python bench.py --gpus 2` with no WORLD_SIZE launches its own ranks (a child torch.distributed.run)
-    tight = run_bench(["--gpus", "2", "--reads", "3e5", "--steps", "1", "--warmup", "1"],
+    tight = run_bench(["--full", "--gpus", "2", "--reads", "3e5", "--steps", "1", "--warmup", "1"],
                       env={"LSG_BENCH_DEVICE": "0", "LSG_BENCH_BACKEND": "gloo", "LSG_BENCH_GATHER_CAP": "1"})
     assert tight["n_gpus"] == 2 and "gloo" in tight["config"]["exchange"]
     assert tight["config"]["pass_rows_gathered"] == two["config"]["pass_rows_gathered"]
@@ -53,8 +53,8 @@ def test_contract_line_and_sharded_run():
 def test_rccl_code_path_with_one_rank():
     """RCCL cannot host two ranks on one GPU, but a ONE-rank nccl group can: the bench's collective code (device tensors through
     all_gather_into_tensor, barrier, all_reduce on backend nccl = RCCL) runs for real, and moves the rows the gloo rehearsal moves"""
-    forced = run_bench(["--reads", "3e5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env={"LSG_BENCH_FORCE_DIST": "1"})
-    plain = run_bench(["--reads", "3e5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    forced = run_bench(["--full", "--reads", "3e5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env={"LSG_BENCH_FORCE_DIST": "1"})
+    plain = run_bench(["--full", "--reads", "3e5", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
     assert forced["n_gpus"] == 1 and "nccl" in forced["config"]["exchange"] and forced["config"]["pass_rows_gathered"] is not None
     for k in ("sites_counted", "rows_emitted", "merged_sites", "step1_candidates"):
         assert forced["config"][k] == plain["config"][k], k
@@ -82,9 +82,34 @@ def test_product_allgather_over_rccl_with_one_rank(tmp_path):
 
 def test_end_to_end_leg_is_measured_in_the_run():
     """config.end_to_end is a measurement of this run (a BAM written in the run, files in -> files out) or null: never a quoted file"""
-    one = run_bench(["--reads", "3e5", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--e2e-reads", "2e4"])
+    one = run_bench(["--full", "--reads", "3e5", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--e2e-reads", "2e4"])
     e = one["config"]["end_to_end"]
     assert e["measured"] == "in this run" and e["wall_s"] > 0 and e["step3_rows"] >= 0 and e["out_MB"]["step1"] > 0
     assert {"gpu_count_call", "step2", "step3"} <= set(e["seconds"])
-    none = run_bench(["--reads", "3e5", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    none = run_bench(["--full", "--reads", "3e5", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
     assert none["config"]["end_to_end"] is None
+
+
+def test_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """without --full the line carries the timed steps alone (no CPU baseline, re-counts, C4 or end-to-end leg); --dump-outputs writes
+    the last timed step's rows as float64 .npy files of at most 64 MB, the same whatever the number of steps, and they agree with the line"""
+    import numpy as np
+    args = ["--reads", "3e5", "--warmup", "1"]
+    a = run_bench(args + ["--steps", "2", "--dump-outputs", str(tmp_path / "a")])
+    b = run_bench(args + ["--steps", "3", "--dump-outputs", str(tmp_path / "b")])
+    assert a["steps"] == 2 and b["steps"] == 3 and a["ms_per_step"] > 0 and "cpu_baseline" not in a
+    assert a["config"]["recount_ms"] is None and a["config"]["c4_oneshot"] is None and a["config"]["end_to_end"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "step.npy" in names and "calls_key.npy" in names
+    arrays = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert all(x.dtype in (np.float32, np.float64) for x in arrays.values())
+    assert sum(x.nbytes for x in arrays.values()) <= 64 << 20
+    for n in names:
+        np.testing.assert_array_equal(arrays[n], np.load(tmp_path / "b" / n), err_msg=n)
+    c = a["config"]
+    assert arrays["step.npy"].tolist() == [arrays["step.npy"][0], arrays["step.npy"][1], c["sites_counted"], c["merged_sites"], c["step1_candidates"]]
+    assert arrays["step.npy"][:2].sum() == c["rows_emitted"]
+    for ct in range(2):
+        keys = arrays["counts_ct%d_key.npy" % ct]
+        assert len(keys) > 0 and (np.diff(keys) > 0).all() and arrays["counts_ct%d_counts.npy" % ct].shape == (len(keys), 42)
+    assert len(arrays["calls_key.npy"]) == min(c["merged_sites"], 1 << 14)

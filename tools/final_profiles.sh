@@ -14,10 +14,10 @@ for f in glob.glob("profiles/%s_bench_kernel_stats.csv" % tag) + glob.glob("prof
     shutil.copy(f, "gpurun_out/final/")
 PY
 # (after the counter passes: bench.py quotes roofline.traffic from the profiles/${TAG}_pmc_traffic.json the lines above just wrote for this build)
-echo "== default bench"; timeout -k 10 500 python3 bench.py > $F/${TAG}_bench_default_run.json 2> $F/bench_default.err; tail -c 600 $F/${TAG}_bench_default_run.json; echo
+echo "== default bench"; timeout -k 10 500 python3 bench.py --full > $F/${TAG}_bench_default_run.json 2> $F/bench_default.err; tail -c 600 $F/${TAG}_bench_default_run.json; echo
 echo "== the store-keeping step (k_tm_gather_count) and the re-counts over its store (k_tm_resolve, k_tm_walk)"
 export LSG_BENCH_KEEP_STORE=1
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/keep -o bench -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --e2e-reads 0 --no-c4 > $F/${TAG}_keep_store_bench.json 2> $F/keep.err || echo "keep-store trace failed"
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $F/../prof/keep -o bench -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --e2e-reads 0 --no-c4 > $F/${TAG}_keep_store_bench.json 2> $F/keep.err || echo "keep-store trace failed"
 unset LSG_BENCH_KEEP_STORE
 python3 - "$TAG" <<'PY'
 import csv, sys
