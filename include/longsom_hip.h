@@ -420,7 +420,8 @@ int lsg_get_count_stats(lsg_ctx* ctx, lsg_count_stats* out);
 
 /* What the load's tile store cost.  path: 2 = the store was built by the load alone, 3 = in the pass that also made the first count
  * (lsg_set_count_at_load), 4 = the load made its count and kept no store (lsg_set_store_policy), 5 = the same over tile-phased events
- * (LSG_LAYOUT_PHASED: every entry fetched as its one 128-byte line).  build_ms: wall time
+ * (LSG_LAYOUT_PHASED: every entry fetched as its one 128-byte line), 6 = the same with the entries binned by 128-position windows
+ * (events phased modulo 128, keys alone through the sort: every entry fetched as one 256-byte block).  build_ms: wall time
  * lsg_load_reads spent building the store (device kernels + their host synchronisations).  store_bytes: device memory the store, its
  * per-read / per-segment arrays, kept events and cached build temporaries hold.  No reference counterpart: the reference re-reads
  * the BAM per window (BaseCellCounter.py:198-225). */

@@ -167,12 +167,10 @@ struct lsg_ctx {
     int64_t max_live_reads = -1;          // layout.hip: bound on the reads live at once in the reference's pileup buffer (-1 = stale)
     int64_t max_live_all = -1;            // the same over all reads with a barcode: table-independent, cached per load
     int32_t wsh = 0;                      // build_store: the bins of the last load's entries - 0: the 64-position tiles, 1: 128-position windows (a load that kept no store)
-    bool win_off = false;                 // ... set while a load that could not be made by windows after all is made again by tiles
     int32_t events_layout = 0;            // lsg_set_events_layout: what the caller says about the events of the next loads (LSG_LAYOUT_*)
     const void* hint_phased_events = nullptr;      // the events array this library's own producer (synth.hip, ingest.hip) last laid out phased modulo 128
     bool src_phased = false;              // build_store: the last load's events were tile-phased (LSG_LAYOUT_PHASED): an entry = one 128-byte line
     bool line_loads = false;              // pileup.hip run_gather_count: the last direct count fetched every entry as its one 128-byte line (tile-phased events)
-    bool keys_only_off = false;           // build_store: this load sorts values with its keys (set while a load of keys alone is made again)
     int64_t max_live_exact = -1;          // per cell type at position resolution (asked only when the tile-level bounds cannot rule the cap out)
     lsg::DevBuf d_read_drop;              // layout.hip: per read, the pileup's max_depth rule under the last count's parameters: 1 = dropped in every window it overlaps, 2 = in some (d_drop_pairs)
     lsg::DevBuf d_drop_pairs; int64_t n_drop_pairs = 0;      // sorted (read << 32 | window of its contig) of the reads dropped in some windows only

@@ -2207,7 +2207,7 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
         }
         const unsigned grid = (unsigned)(c->n_cus * tune_int("LSG_GRID_TD", 12));
         // tile-phased events: an entry is fetched as its one 128-byte line (tm_add<.., true>: the quality compare reads the event's low byte)
-        const bool al = tg.src_shift == 6 && p->min_bq >= 1 && p->min_bq <= 255 && !getenv("LSG_NO_LINE_LOADS");
+        const bool al = tg.src_shift == 6 && p->min_bq >= 1 && p->min_bq <= 255;
         c->line_loads = al;
         if (tg.rdv && al) hipLaunchKernelGGL((k_tm_count_direct<false, true>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
         else if (tg.rdv) hipLaunchKernelGGL((k_tm_count_direct<false, false>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);

@@ -550,15 +550,6 @@ __global__ __launch_bounds__(TT_THREADS) void k_tt_offsets(TtArgs a) {
         crun += tc; brun += tb; nrun += tn;
     }
 }
-// per tile: blocks, and a flag for the non-empty ones
-__global__ void k_tile_blocks(const uint32_t* cap, uint32_t n_tiles, uint32_t* blk) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t <= n_tiles) blk[t] = t < n_tiles ? (cap[t] + 7u) / 8u : 0u;
-}
-struct CapNonZero {
-    const uint32_t* cap;
-    __host__ __device__ bool operator()(const uint32_t& t) const { return cap[t] != 0; }
-};
 // split: the segments of more than SORT_LARGE entries in (begin, end), the others in (begin2, end2) - each list names every tile, a tile of
 // the other class as an empty segment (the two sorts run side by side on two streams; an empty segment costs a sort a few lanes)
 constexpr uint32_t SORT_LARGE = 256;      // rocprim's block-per-segment kernel takes the segments beyond the warp sorts' 32 x 8 items (LsgSortConfig)
@@ -566,7 +557,6 @@ __global__ void k_seg_bounds(const uint32_t* netile, uint32_t n, const uint32_t*
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t t = netile[i], b = tile_off[t], e = tile_off[t + 1];
-    if (!begin2) { begin[i] = b; end[i] = e; return; }
     const bool large = e - b > SORT_LARGE;
     begin[i] = b; end[i] = large ? e : b;
     begin2[i] = b; end2[i] = large ? b : e;
@@ -694,7 +684,7 @@ __global__ __launch_bounds__(TMG_WAVES * 64) void k_tm_gather(const uint16_t* ev
         LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb_, (in), (out), (int)(n), st));       \
     } while (0)
 
-enum { BT_KEY_A = 0, BT_KEY_B, BT_VAL_A, BT_VAL_B, BT_PEX, BT_NETILE, BT_SEG_BEGIN, BT_SEG_END, BT_TMP, BT_PER_TILE, BT_OFFS, BT_SPAN, BT_SPAN_RUN, BT_BLK, BT_CURSOR, BT_LPT, BT_COPY_TMP, BT_N };
+enum { BT_KEY_A = 0, BT_KEY_B, BT_VAL_A, BT_VAL_B, BT_PEX, BT_NETILE, BT_SEG_BEGIN, BT_SEG_END, BT_TMP, BT_PER_TILE, BT_OFFS, BT_SPAN, BT_CURSOR, BT_LPT, BT_COPY_TMP, BT_N };
 
 void drop_store(lsg_ctx* c) {
     c->tm_valid = false; c->plan_n_ct = 0; c->plan1_n_ct = 0; c->tm_n = 0; c->tm_events = 0; c->tm_np = 0; c->tm_nblk = 0; c->tm_njobs = 0; c->tm_nchunks = 0;
@@ -732,29 +722,43 @@ static hipError_t lsg_segmented_sort(Args&&... args) { return rocprim::segmented
 template <unsigned RB, unsigned BS, unsigned IPT, class... Args>
 static hipError_t lsg_segmented_sort_keys(Args&&... args) { return rocprim::segmented_radix_sort_keys<LsgSortConfig<RB, BS, IPT>>(std::forward<Args>(args)...); }
 
-int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int64_t* seg_ev_off, const lsg_reads* src) {
+// Can the load make the count itself (lsg_set_count_at_load: at most two cell types, barcodes set, the copy stream for the plan)?  The gate
+// of every form of the load below that counts; each form adds conditions of its own.
+static bool count_in_load(const lsg_ctx* c) { return c->cal_enabled && c->n_ct >= 1 && c->n_ct <= 2 && c->n_cb > 0 && c->copy_stream; }
+
+// (diagnostic, LSG_TILE_HIST: how the entries spread over tile sizes; C2: DESIGN.md section 9)
+static int print_tile_hist(const lsg_ctx* c, uint32_t T) {
+    std::vector<uint32_t> caps(T);
+    LSG_HIP(hipMemcpy(caps.data(), c->d_tile_cap.p, (size_t)T * 4, hipMemcpyDeviceToHost));
+    unsigned long long nt[8] = {0}, ne[8] = {0}; uint32_t mx = 0;
+    const uint32_t lim[7] = {64, 256, 2048, 8192, 32768, 131072, 524288};
+    for (uint32_t i = 0; i < T; ++i) { const uint32_t v = caps[i]; if (!v) continue; int k = 0; while (k < 7 && v > lim[k]) ++k; ++nt[k]; ne[k] += v; if (v > mx) mx = v; }
+    for (int k = 0; k < 8; ++k) fprintf(stderr, "tiles <= %u: %llu tiles, %llu entries\n", k < 7 ? lim[k] : 0xffffffffu, nt[k], ne[k]);
+    fprintf(stderr, "largest tile: %u entries\n", mx);
+    return 0;
+}
+
+// The forms of a load, leanest first.  A load that cannot keep the form it was started in returns the rung to start again on
+// (build_store), always a lower one: windows and keys alone, tiles and keys alone, tiles and values.
+enum LoadRung { RUNG_WINDOWS = 1, RUNG_TILE_KEYS, RUNG_TILE_VALUES };
+
+static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int64_t* seg_ev_off, const lsg_reads* src, int rung) {
     drop_store(c);
     hipStream_t st = c->stream;
     const int64_t S = c->rd.n_segs, R = c->rd.n_reads;
+    // (the pass that counts takes 64 .. 2^39 events; the plan's tile-level half and the depth cap's bounds need the gate alone)
+    const bool counts = count_in_load(c) && n_events >= 64 && n_events < (1ll << 39);
+    const bool skip_store = c->cal_enabled && c->store_policy == LSG_STORE_SKIP_WHEN_COUNTED;
     // WINDOWS.  A load that will keep no store and sort keys alone (below), over events its producer says are phased modulo 128
     // (lsg_set_events_layout; this library's own producers say so themselves), bins its entries by 128-position windows - tiles (2 w, 2 w + 1) -
     // instead of tiles: 0.58 x as many entries through the scatter and the sort, and every entry one aligned 256-byte block for the count
     // (k_tm_count_win).  Everything here that is "per tile" is then per window (T bins); the count's units stay the tiles'.  Should the early
-    // look say otherwise (events not phased after all, a depth cap that could fire, ...), the load starts again by tiles (win_off).
-    const bool win = c->cal_enabled && c->store_policy == LSG_STORE_SKIP_WHEN_COUNTED && !getenv("LSG_NO_DIRECT_COUNT") && !getenv("LSG_NO_FUSED_LOAD") && !getenv("LSG_NO_KEYS_ONLY") &&
-                     !getenv("LSG_NO_WINDOWS") && !c->keys_only_off && !c->win_off && c->n_ct >= 1 && c->n_ct <= 2 && c->n_cb > 0 && c->copy_stream && n_events >= 128 && n_events < (1ll << 39) &&
+    // look say otherwise (events not phased after all, a depth cap that could fire, ...), the load starts again by tiles (RUNG_TILE_KEYS).
+    const bool win = rung == RUNG_WINDOWS && skip_store && counts && n_events >= 128 &&
                      (c->events_layout == LSG_LAYOUT_PHASED || (c->hint_phased_events && c->hint_phased_events == (const void*)events)) && ((uintptr_t)events & 255u) == 0 && c->plp_window >= 128 &&
                      c->cal_params.min_bq >= 1 && c->cal_params.min_bq <= 255 && (c->n_tiles & 1u) == 0;
     const int wsh = win ? 1 : 0;
     c->wsh = wsh;
-    auto start_again_by_tiles = [&]() -> int {
-        LSG_HIP(hipStreamSynchronize(st)); LSG_HIP(hipStreamSynchronize(c->copy_stream));
-        if (getenv("LSG_TIMING")) fprintf(stderr, "[lsg] load: not a load for 128-position windows after all, starting again by tiles\n");
-        c->win_off = true;
-        const int rc = build_store(c, events, n_events, seg_ev_off, src);
-        c->win_off = false;
-        return rc;
-    };
     const uint32_t T = c->n_tiles >> wsh;
     const auto t_wall = std::chrono::steady_clock::now();
     auto finish = [&]() {
@@ -781,7 +785,7 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     a.window = c->plp_window; c->st_window = c->plp_window; a.wsh = wsh;
     a.qhead = c->d_scalars.as<unsigned long long>(); a.bad = reinterpret_cast<uint32_t*>(c->d_scalars.as<unsigned long long>() + 2);
     a.n_ev = c->d_scalars.as<unsigned long long>() + 3;
-    if (c->bt[BT_SPAN].reserve(((size_t)T + 2) * 4) || c->bt[BT_SPAN_RUN].reserve(((size_t)T + 2) * 4)) return -1;
+    if (c->bt[BT_SPAN].reserve(((size_t)T + 2) * 4)) return -1;
     LSG_HIP(hipMemsetAsync(c->bt[BT_SPAN].p, 0, ((size_t)T + 2) * 4, st));
     a.span_diff = c->bt[BT_SPAN].as<int32_t>();
     uint32_t* d_small = reinterpret_cast<uint32_t*>(c->d_scalars.as<unsigned long long>() + 4);      // [0] max entries of a tile, [1] non-empty tiles, [2] largest barcode id, [3] the live-reads bound
@@ -794,7 +798,7 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     LSG_HIP(hipMemsetAsync(c->bt[BT_PER_TILE].p, 0, ((size_t)T + 2) * 4, st));
     a.cap_diff = c->bt[BT_PER_TILE].as<int32_t>();
     hipLaunchKernelGGL(k_seg_static, dim3(g_seg), dim3(256), 0, st, a);
-    if (c->bt[BT_NETILE].reserve(((size_t)T + 2) * 4) || c->bt[BT_BLK].reserve(((size_t)T + 2) * 4) || c->tm[TM_BLK_OFF].reserve(((size_t)T + 2) * 4)) return -1;
+    if (c->bt[BT_NETILE].reserve(((size_t)T + 2) * 4) || c->tm[TM_BLK_OFF].reserve(((size_t)T + 2) * 4)) return -1;
     uint32_t* blk_off = c->tm[TM_BLK_OFF].as<uint32_t>();
     unsigned long long* d_sum = c->d_scalars.as<unsigned long long>() + 8;
     {
@@ -804,8 +808,7 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
         tb = tmp.cap;
         if (R > 0) LSG_HIP(hipcub::DeviceReduce::Max(tmp.p, tb, in.read_cb, reinterpret_cast<int32_t*>(d_small + 2), (int)R, st));
     }
-    if (!getenv("LSG_NO_TILE_TABLES")) {
-        // everything that follows from the range marks, in five launches (k_tt_*): the sizes below reach the host in the load's ONE early
+    {   // everything that follows from the range marks, in five launches (k_tt_*): the sizes below reach the host in the load's ONE early
         // look (the scatter, the sort and the gather are then queued without waiting for one another)
         if (c->d_cub_tmp.reserve(64 * 1024)) return -1;
         TtArgs ta{};
@@ -823,48 +826,6 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
         hipLaunchKernelGGL(k_tt_caps, dim3(ta.n_chunks), dim3(TT_THREADS), 0, st, ta);
         hipLaunchKernelGGL(k_tt_scan2, dim3(1), dim3(TT_MAX_CHUNKS), 0, st, ta);
         hipLaunchKernelGGL(k_tt_offsets, dim3(ta.n_chunks), dim3(TT_THREADS), 0, st, ta);
-    } else {
-    {   // entries per tile = running sum of the segments' range marks
-        size_t tb = 0;
-        int32_t* cap = reinterpret_cast<int32_t*>(c->d_tile_cap.as<uint32_t>());
-        LSG_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, a.cap_diff, cap, (int)(T + 1), st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceScan::InclusiveSum(c->d_cub_tmp.p, tb, a.cap_diff, cap, (int)(T + 1), st));
-    }
-    SCAN_U32(c->d_tile_cap.as<uint32_t>(), c->d_tile_off.as<uint32_t>(), T + 1);
-    {   // the depth cap's table-independent bound (layout.hip live_read_bound_all): reads of any cell type whose span touches a tile, maximum over tiles
-        int32_t* run = c->bt[BT_SPAN_RUN].as<int32_t>();
-        size_t tb = 0, tb2 = 0;
-        LSG_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, a.span_diff, run, (int)(T + 1), st));
-        LSG_HIP(hipcub::DeviceReduce::Max(nullptr, tb2, run, reinterpret_cast<int32_t*>(d_small + 3), (int)(T + 1), st));
-        if (tmp.reserve((tb > tb2 ? tb : tb2) + 256)) return -1;
-        tb = tb2 = tmp.cap;
-        LSG_HIP(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, a.span_diff, run, (int)(T + 1), st));
-        LSG_HIP(hipcub::DeviceReduce::Max(tmp.p, tb2, run, reinterpret_cast<int32_t*>(d_small + 3), (int)(T + 1), st));
-    }
-    // the non-empty tiles (the sort's segments) and the blocks of every tile: all of it follows from the capacities, so the sizes below
-    // reach the host in the load's ONE early look (the scatter, the sort and the gather are then queued without waiting for one another)
-    {
-        hipcub::CountingInputIterator<uint32_t> tile_it(0);
-        CapNonZero pred{c->d_tile_cap.as<uint32_t>()};
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceSelect::If(nullptr, tb, tile_it, c->bt[BT_NETILE].as<uint32_t>(), d_small + 1, (int)T, pred, st));
-        if (tmp.reserve(tb + 256)) return -1;
-        tb = tmp.cap;
-        LSG_HIP(hipcub::DeviceSelect::If(tmp.p, tb, tile_it, c->bt[BT_NETILE].as<uint32_t>(), d_small + 1, (int)T, pred, st));
-    }
-    hipLaunchKernelGGL(k_tile_blocks, dim3((T + 256) / 256), dim3(256), 0, st, c->d_tile_cap.as<uint32_t>(), T, c->bt[BT_BLK].as<uint32_t>());
-    SCAN_U32(c->bt[BT_BLK].as<uint32_t>(), blk_off, T + 1);
-    // (a total of 2^32 or more wraps the 32-bit scan: the per-tile capacities are summed in 64 bits to tell)
-    {
-        size_t tb = 0;
-        hipcub::TransformInputIterator<unsigned long long, hipcub::CastOp<unsigned long long>, const uint32_t*> it(c->d_tile_cap.as<uint32_t>(), hipcub::CastOp<unsigned long long>());
-        LSG_HIP(hipcub::DeviceReduce::Sum(nullptr, tb, it, d_sum, (int)T, st));
-        if (tmp.reserve(tb + 256)) return -1;
-        tb = tmp.cap;
-        LSG_HIP(hipcub::DeviceReduce::Sum(tmp.p, tb, it, d_sum, (int)T, st));
-    }
     }
     uint32_t total = 0, bad = 0, n_netile = 0, nblk = 0; int32_t max_cb = 0, max_live = 0;
     unsigned long long n_ev = 0, sum = 0;
@@ -881,8 +842,8 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     }
     // tile-phased events (LSG_LAYOUT_PHASED): every entry lies inside one aligned 128-byte line of the caller's array; the key carries the line
     // (k_seg_static looked at the phase modulo the bins' width: 64, or 128 for windows)
-    if (win && (bad & 4u) && !(bad & 3u)) return start_again_by_tiles();
-    const int src_shift = !(bad & 4u) && ((uintptr_t)events & (wsh ? 255u : 127u)) == 0 && !getenv("LSG_NO_PHASED") ? 6 + wsh : 0;
+    if (win && (bad & 4u) && !(bad & 3u)) return RUNG_TILE_KEYS;
+    const int src_shift = !(bad & 4u) && ((uintptr_t)events & (wsh ? 255u : 127u)) == 0 ? 6 + wsh : 0;
     c->src_phased = src_shift != 0;
     if (bad & 2u) { set_error("lsg_load_reads: a segment's read index lies outside the read arrays"); return -2; }
     if (bad & 1u) { set_error("lsg_load_reads: a segment's event range lies outside the events array"); return -2; }
@@ -892,15 +853,7 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     c->tm_n = N; c->tm_events = (int64_t)n_ev;
     c->max_live_all = max_live > 0 ? max_live : 0;
     if (N == 0) return finish();
-    if (getenv("LSG_TILE_HIST")) {                                   // (diagnostic: how the entries spread over tile sizes; C2: DESIGN.md section 9)
-        std::vector<uint32_t> caps(T);
-        LSG_HIP(hipMemcpy(caps.data(), c->d_tile_cap.p, (size_t)T * 4, hipMemcpyDeviceToHost));
-        unsigned long long nt[8] = {0}, ne[8] = {0}; uint32_t mx = 0;
-        const uint32_t lim[7] = {64, 256, 2048, 8192, 32768, 131072, 524288};
-        for (uint32_t i = 0; i < T; ++i) { const uint32_t v = caps[i]; if (!v) continue; int k = 0; while (k < 7 && v > lim[k]) ++k; ++nt[k]; ne[k] += v; if (v > mx) mx = v; }
-        for (int k = 0; k < 8; ++k) fprintf(stderr, "tiles <= %u: %llu tiles, %llu entries\n", k < 7 ? lim[k] : 0xffffffffu, nt[k], ne[k]);
-        fprintf(stderr, "largest tile: %u entries\n", mx);
-    }
+    if (getenv("LSG_TILE_HIST")) { if (int rc = print_tile_hist(c, T)) return rc; }
     // ---- 2. scatter (queued BEFORE the copy stream's work below: those two dozen launches are 0.3 ms of host time the scatter need not wait for)
     int bits = 1; while (bits < 24 && (1ll << bits) <= (long long)max_cb) ++bits;      // the barcode bits of the sort key
     DevBuf &key_a = c->bt[BT_KEY_A], &key_b = c->bt[BT_KEY_B], &val_a = c->bt[BT_VAL_A], &val_b = c->bt[BT_VAL_B];
@@ -911,17 +864,15 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     // A load that is counted once, without a store, by a count that admits every stored read (the filters of the load) and whose depth cap
     // cannot fire needs nothing of an entry's value but two flags: they ride in the key (bits 62, 63, above a source field two bits
     // narrower) and the scatter, the sort and the count move 8 bytes an entry instead of 12.  Should the count not be made that way after
-    // all (its rows outgrow their buffer), the load starts again with values (keys_only_off).
-    bool keys_only = c->cal_enabled && c->store_policy == LSG_STORE_SKIP_WHEN_COUNTED && !getenv("LSG_NO_DIRECT_COUNT") && !getenv("LSG_NO_FUSED_LOAD") &&
-                     !getenv("LSG_NO_KEYS_ONLY") && !c->keys_only_off && c->n_ct >= 1 && c->n_ct <= 2 && c->n_cb > 0 && c->copy_stream && n_events >= 64 &&
-                     n_events < (1ll << 39) && (n_events >> src_shift) < (1ll << (50 - bits - 2 * wsh));
+    // all (its rows outgrow their buffer), the load starts again with values (RUNG_TILE_VALUES).
+    bool keys_only = rung <= RUNG_TILE_KEYS && skip_store && counts && (n_events >> src_shift) < (1ll << (50 - bits - 2 * wsh));
     // Can the depth cap of the count this load is to make fire at all?  The all-reads bound per tile (window) came with the early look; when it
     // cannot say no, the per-position bound of this table's cell types decides (layout.hip: ~10 ms at C4, whose tiles hold more than 200 000
     // reads that no position does) - here, before the scatter, because a count whose cap cannot fire may sort keys alone.
     bool cap_out = true;
     if (c->cal_enabled && c->cal_params.max_depth > 0 && c->max_live_all + 1 > (int64_t)c->cal_params.max_depth) {
         cap_out = false;
-        if (c->n_ct >= 1 && c->n_ct <= 2 && c->n_cb > 0 && c->copy_stream && !getenv("LSG_NO_FUSED_LOAD")) {
+        if (count_in_load(c)) {
             LSG_HIP(hipStreamSynchronize(c->copy_stream));          // (the handle's copies of the read arrays, which the bounds read, are made there)
             if (live_read_bound(c)) return -1;                      // first the tiles again, per cell type of this table (C4: 135 343 against 225 294 over all reads)
             cap_out = c->max_live_reads + 1 <= (int64_t)c->cal_params.max_depth;
@@ -937,7 +888,7 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
         if (!cap_out) keys_only = false;
         for (int t = 0; t < c->n_contigs && keys_only; ++t) if (!c->ref_ptr[t]) keys_only = false;
     }
-    if (win && !keys_only) return start_again_by_tiles();
+    if (win && !keys_only) return RUNG_TILE_KEYS;
     if (keys_only && getenv("LSG_TIMING")) fprintf(stderr, "[lsg] load: keys alone through the scatter and the sort (8 bytes an entry)%s\n", win ? ", entries binned by 128-position windows" : "");
     if (key_a.reserve(N * 8 + 16) || key_b.reserve(N * 8 + 16) || (!keys_only && (val_a.reserve(N * 4 + 16) || val_b.reserve(N * 4 + 16))) ||
         c->bt[BT_CURSOR].reserve(((size_t)T + 2) * 4)) return -1;
@@ -949,9 +900,9 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     LSG_HIP(hipEventRecord(c->evb[1], st));
     // ---- beside the scatter, on the copy stream: what follows from the capacities alone
     if (c->tm[TM_BLK_TILE].reserve(((size_t)nblk + 2) * 4)) return -1;
-    bool lpt = false, split_sort = false, blk_tiles_made = false;
+    bool blk_tiles_made = false;
+    const bool lpt = n_netile > 1;
     const uint32_t* lpt_tiles = nullptr;
-    const bool may_skip_store = c->cal_enabled && c->store_policy == LSG_STORE_SKIP_WHEN_COUNTED && !getenv("LSG_NO_DIRECT_COUNT");
     // (the scratch is BT_COPY_TMP, sized below before anything is queued on the copy stream; on the main stream - the fall-back - the
     // copy stream has been waited for)
     auto blk_tiles = [&](hipStream_t s_) -> int {
@@ -966,29 +917,27 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     };
     {
         hipStream_t bs = c->copy_stream;
-        const bool want_lpt = n_netile > 1 && !getenv("LSG_NO_LPT");
         DevBuf& lk = c->bt[BT_LPT];
         const size_t lpt_pitch = ((size_t)n_netile + 64) & ~(size_t)63;            // (every array on a 256-byte boundary)
-        if (want_lpt && lk.reserve(lpt_pitch * 4 * 3)) return -1;
+        if (lpt && lk.reserve(lpt_pitch * 4 * 3)) return -1;
         uint32_t* k_in = lk.as<uint32_t>(); uint32_t* k_out = k_in + lpt_pitch; uint32_t* t_out = k_out + lpt_pitch;
         uint32_t* bt_ = c->tm[TM_BLK_TILE].as<uint32_t>();
         // (the scratch of both is sized BEFORE either is queued: growing a buffer frees it, and work queued on this stream may still be reading it)
         size_t tb_lpt = 0, tb_blk = 0;
-        if (want_lpt) LSG_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb_lpt, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs));
+        if (lpt) LSG_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb_lpt, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs));
         LSG_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb_blk, bt_, bt_, hipcub::Max(), (int)nblk, bs));
         // (... and of the sort of the shallow tiles, which runs on this stream beside the deep tiles' sort: below)
         size_t tb_sort2 = 0;
-        if (n_netile && !getenv("LSG_NO_SPLIT_SORT")) {
+        if (n_netile) {
             if (keys_only) LSG_HIP((lsg_segmented_sort_keys<7, 256, 8>(nullptr, tb_sort2, (uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned)N, (unsigned)n_netile, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (unsigned)bits, bs, false)));
             else LSG_HIP((lsg_segmented_sort<7, 256, 8>(nullptr, tb_sort2, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned)N, (unsigned)n_netile,
                                                         (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (unsigned)bits, bs, false)));
         }
-        split_sort = tb_sort2 != 0;
         size_t tb_max = tb_lpt > tb_blk ? tb_lpt : tb_blk;
         if (tb_sort2 > tb_max) tb_max = tb_sort2;
         if (c->bt[BT_COPY_TMP].reserve(tb_max + 256)) return -1;
         void* scratch = c->bt[BT_COPY_TMP].p;
-        if (want_lpt) {
+        if (lpt) {
             // The sort's segments deepest first: rocprim gives every segment beyond its block sort to ONE workgroup, and the deepest tiles
             // (chrM: the last contig) would start last - their workgroups' tail is then hidden behind the rest.  A stable radix sort of the
             // non-empty tiles by capacity >> 11 (what lies above the block sort's 2048: the shallower ones keep their order).  The keys are
@@ -997,37 +946,35 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
             size_t tb = c->bt[BT_COPY_TMP].cap;
             LSG_HIP(hipcub::DeviceRadixSort::SortPairsDescending(scratch, tb, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs));
             LSG_HIP(hipEventRecord(c->ev_lpt, bs));
-            lpt = true; lpt_tiles = t_out;
+            lpt_tiles = t_out;
         }
         // the tile of every block (the re-counts' resolve and the plain gather read it; the fused pass does not) - left out when the load is
         // to keep no store (should it build one after all, blk_tiles() runs then)
-        if (!may_skip_store) { if (int rc = blk_tiles(bs)) return rc; }
+        if (!skip_store) { if (int rc = blk_tiles(bs)) return rc; }
     }
     // The plan's tile-level half (units, jobs and slabs per bin and their totals: it reads the capacities only) on the copy stream NOW, beside
     // the scatter - it ends in a host round trip that used to wait for the shallow bins' sort on that stream (0.25 ms of nothing between the
     // sort and the count for a rank's eighth of a sample) - whenever the load is to make its count
-    bool tiles_planned = false;
-    if (c->cal_enabled && c->n_ct >= 1 && c->n_ct <= 2 && c->n_cb > 0 && c->copy_stream && !getenv("LSG_NO_FUSED_LOAD") && !getenv("LSG_LATE_PLAN")) {
+    const bool tiles_planned = count_in_load(c);
+    if (tiles_planned) {
         if (int rc = plan_tiles(c, c->copy_stream)) return rc;
         plan_finish_tiles(c);
-        tiles_planned = true;
     }
     // ---- 3. every tile's entries by barcode
     if (n_netile) {
-        // (begin / end of the deep tiles' sort, then - split_sort - of the shallow tiles' sort: four arrays of n_netile + 1 in the two buffers)
+        // (begin / end of the deep tiles' sort, then of the shallow tiles' sort: four arrays of n_netile + 1 in the two buffers)
         const size_t seg_pitch = ((size_t)n_netile + 64) & ~(size_t)63;
         if (c->bt[BT_SEG_BEGIN].reserve(seg_pitch * 8) || c->bt[BT_SEG_END].reserve(seg_pitch * 8)) return -1;
         uint32_t* sb1 = c->bt[BT_SEG_BEGIN].as<uint32_t>(); uint32_t* se1 = c->bt[BT_SEG_END].as<uint32_t>();
-        uint32_t* sb2 = split_sort ? sb1 + seg_pitch : nullptr; uint32_t* se2 = split_sort ? se1 + seg_pitch : nullptr;
+        uint32_t* sb2 = sb1 + seg_pitch; uint32_t* se2 = se1 + seg_pitch;
         if (lpt) LSG_HIP(hipStreamWaitEvent(st, c->ev_lpt, 0));
         hipLaunchKernelGGL(k_seg_bounds, dim3((n_netile + 255) / 256), dim3(256), 0, st, lpt ? lpt_tiles : c->bt[BT_NETILE].as<uint32_t>(), n_netile, c->d_tile_off.as<uint32_t>(), sb1, se1, sb2, se2);
-        if (split_sort) LSG_HIP(hipEventRecord(c->ev_copy, st));      // (the second sort, queued below, starts here)
+        LSG_HIP(hipEventRecord(c->ev_copy, st));      // (the second sort, queued below, starts here)
         size_t tb = 0;
         // (64-bit keys sorted on their barcode bits only, begin_bit 0 .. end_bit `bits`: the rest of the key is payload)
         // (one configuration: 7 bits per pass, 256 x 8 items in the block sort - the sweep over 512 / 1024 threads, 4-16 items and 8 bits per pass
         // that used to be selectable here found nothing faster, and cost a minute of compile time)
-        const char* bb_env = getenv("LSG_SORT_BIG_BLOCKS");
-        const bool big_blocks = bb_env ? atoi(bb_env) != 0 : N < (64ull << 20);       // (C2: 23 M entries a rank in eight shards, 46 M in four, 92 M in two - where the big workgroups already lose)
+        const bool big_blocks = N < (64ull << 20);       // (C2: 23 M entries a rank in eight shards, 46 M in four, 92 M in two - where the big workgroups already lose)
         auto sort = [&](void* tmp_p, size_t& tmp_n) {
             // (a small load - a rank's share of a sharded sample - is bound by ONE workgroup working through its deepest tile, 2048 entries
             // an iteration: 512 threads take 4096 - C2 in eight shards 0.71 -> 0.42-0.55 ms, in four 0.76 -> 0.69; 1024 threads gain on the
@@ -1041,20 +988,18 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
         if (tmp.reserve(tb + 256)) return -1;
         tb = tmp.cap;
         LSG_HIP(sort(tmp.p, tb));
-        if (split_sort) {
-            // rocprim runs its three kernels (a block per segment beyond 256 entries: 2.7 ms at C2; the warp sorts of the segments up to 256 and up
-            // to 64: 0.55 ms) one after the other, and the first one's tail leaves most of the chip idle: the shallow tiles are sorted on the copy
-            // stream beside it (same output arrays, disjoint segments, scratch of its own); queued AFTER the deep tiles' sort so that the
-            // main stream does not wait for these launches
-            hipStream_t bs = c->copy_stream;
-            LSG_HIP(hipStreamWaitEvent(bs, c->ev_copy, 0));
-            size_t tb2 = c->bt[BT_COPY_TMP].cap;
-            if (keys_only) LSG_HIP((lsg_segmented_sort_keys<7, 256, 8>(c->bt[BT_COPY_TMP].p, tb2, key_a.as<uint64_t>(), key_b.as<uint64_t>(), (unsigned)N, (unsigned)n_netile, sb2, se2, 0u, (unsigned)bits, bs, false)));
-            else LSG_HIP((lsg_segmented_sort<7, 256, 8>(c->bt[BT_COPY_TMP].p, tb2, key_a.as<uint64_t>(), key_b.as<uint64_t>(), val_a.as<uint32_t>(), val_b.as<uint32_t>(), (unsigned)N, (unsigned)n_netile,
-                                                        sb2, se2, 0u, (unsigned)bits, bs, false)));
-            LSG_HIP(hipEventRecord(c->ev_lpt, bs));            // (the event of the tiles' order: waited for above, free again)
-        }
-        if (split_sort) LSG_HIP(hipStreamWaitEvent(st, c->ev_lpt, 0));      // both halves of the order are there
+        // rocprim runs its three kernels (a block per segment beyond 256 entries: 2.7 ms at C2; the warp sorts of the segments up to 256 and up
+        // to 64: 0.55 ms) one after the other, and the first one's tail leaves most of the chip idle: the shallow tiles are sorted on the copy
+        // stream beside it (same output arrays, disjoint segments, scratch of its own); queued AFTER the deep tiles' sort so that the
+        // main stream does not wait for these launches
+        hipStream_t bs = c->copy_stream;
+        LSG_HIP(hipStreamWaitEvent(bs, c->ev_copy, 0));
+        size_t tb2 = c->bt[BT_COPY_TMP].cap;
+        if (keys_only) LSG_HIP((lsg_segmented_sort_keys<7, 256, 8>(c->bt[BT_COPY_TMP].p, tb2, key_a.as<uint64_t>(), key_b.as<uint64_t>(), (unsigned)N, (unsigned)n_netile, sb2, se2, 0u, (unsigned)bits, bs, false)));
+        else LSG_HIP((lsg_segmented_sort<7, 256, 8>(c->bt[BT_COPY_TMP].p, tb2, key_a.as<uint64_t>(), key_b.as<uint64_t>(), val_a.as<uint32_t>(), val_b.as<uint32_t>(), (unsigned)N, (unsigned)n_netile,
+                                                    sb2, se2, 0u, (unsigned)bits, bs, false)));
+        LSG_HIP(hipEventRecord(c->ev_lpt, bs));            // (the event of the tiles' order: waited for above, free again)
+        LSG_HIP(hipStreamWaitEvent(st, c->ev_lpt, 0));      // both halves of the order are there
     }
     LSG_HIP(hipEventRecord(c->evb[2], st));
     // ---- 4. blocks and the per-entry words (the blocks' offsets and their number came with the load's early look)
@@ -1072,7 +1017,7 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
         size_t mem_free = 0, mem_total = 0;
         if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && ((size_t)nblk + TM_GROUP) * 1088 + (mem_total >> 5) > mem_free) {
             LSG_HIP(hipStreamSynchronize(st));
-            key_a.release(); val_a.release(); c->ws[WS_SEG_INFO].release(); c->bt[BT_SPAN].release(); c->bt[BT_SPAN_RUN].release(); c->bt[BT_PEX].release(); c->bt[BT_OFFS].release();
+            key_a.release(); val_a.release(); c->ws[WS_SEG_INFO].release(); c->bt[BT_SPAN].release(); c->bt[BT_PEX].release(); c->bt[BT_OFFS].release();
         }
         if (c->tm[TM_STORE].reserve(((size_t)nblk + TM_GROUP) * 1024)) return -1;
     }
@@ -1082,7 +1027,7 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     // The first count in the same pass (lsg_set_count_at_load): when its parameters and the barcode table are known now, the depth cap
     // cannot fire (the all-reads bound came with the early look) and one pass covers the cell types, the gather below is replaced by
     // pileup.hip's k_tm_gather_count, which builds the same store and counts while each block is in registers.
-    bool fused = c->cal_enabled && c->n_ct >= 1 && c->n_ct <= 2 && c->n_cb > 0 && c->copy_stream && n_events >= 64 && n_events < (1ll << 39) && !getenv("LSG_NO_FUSED_LOAD");
+    bool fused = counts;
     if (fused) {
         const lsg_count_params& q = c->cal_params;
         if (q.min_mq < c->st_min_mq || (c->st_flag_exclude & ~q.flag_exclude) != 0 || (c->st_ignore_orphans && !q.ignore_orphans)) fused = false;       // (the count would be refused)
@@ -1091,33 +1036,20 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
     }
     const bool dbg = getenv("LSG_DEBUG_SYNC") != nullptr;
     auto stage = [&](const char* what) { if (dbg) { const hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[lsg] fused load: %s: %s\n", what, hipGetErrorString(e)); fflush(stderr); } };
-    // the plan: its tile-level half on the copy stream while the scatter and the sort are at work (two small host round trips that
-    // wait for the copy stream only), its job-level half behind the sort - the jobs are cut at run starts read from the sorted keys
+    // the plan: its tile-level half was made on the copy stream while the scatter and the sort were at work (tiles_planned: a load that
+    // counts), its job-level half behind the sort - the jobs are cut at run starts read from the sorted keys
     auto fused_plan = [&]() -> int {
         stage("scatter + sort + block tables");
-        int rc = 0;
-        if (!tiles_planned) {
-            if ((rc = plan_tiles(c, c->copy_stream))) return rc;
-            plan_finish_tiles(c);
-        }
         c->tm_np = np; c->tm_nblk = nblk;
-        if ((rc = plan_jobs(c, false, key_b.as<uint64_t>(), bits))) return rc;
+        if (int rc = plan_jobs(c, false, key_b.as<uint64_t>(), bits)) return rc;
         stage("plan");
         return 0;
     };
     const GatherCountSrc gsrc{events, n_events, key_b.as<uint64_t>(), keys_only ? nullptr : val_b.as<uint32_t>(), bits, src_shift, wsh};
-    auto load_again_with_values = [&]() -> int {                 // (a load of keys alone that is not counted that way after all)
-        LSG_HIP(hipStreamSynchronize(st)); LSG_HIP(hipStreamSynchronize(c->copy_stream));
-        if (getenv("LSG_TIMING")) fprintf(stderr, "[lsg] load: the count from keys alone was not made, loading again with values\n");
-        c->keys_only_off = true;
-        const int rc = build_store(c, events, n_events, seg_ev_off, src);
-        c->keys_only_off = false;
-        return rc;
-    };
     bool planned = false;
-    if (win && !fused) return start_again_by_tiles();
-    if (keys_only && getenv("LSG_TEST_KEYS_ONLY_REFUSED")) return win ? start_again_by_tiles() : load_again_with_values();      // (test hook: the way a refused count of keys alone takes)
-    if (fused && c->store_policy == LSG_STORE_SKIP_WHEN_COUNTED && !getenv("LSG_NO_DIRECT_COUNT")) {
+    if (win && !fused) return RUNG_TILE_KEYS;
+    if (keys_only && getenv("LSG_TEST_KEYS_ONLY_REFUSED")) return win ? RUNG_TILE_KEYS : RUNG_TILE_VALUES;      // (test hook: the way a refused count of keys alone takes)
+    if (fused && skip_store) {
         // A load that is counted once and never again (lsg_set_store_policy): the count alone, from the caller's events through the
         // sort's output - no blocks, no per-entry words.  What needs a store afterwards is refused until the next load.
         if (int rc = fused_plan()) return rc;
@@ -1138,8 +1070,8 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
         c->counted = false;                                       // rows outgrew their buffer: the store is built after all, the count is made on request
         fused = false;
     }
-    if (win) return start_again_by_tiles();                  // (the windows' count was not made: rows outgrew their buffer, a count that is not the load's ...)
-    if (keys_only) return load_again_with_values();
+    if (win) return RUNG_TILE_KEYS;                          // (the windows' count was not made: rows outgrew their buffer, a count that is not the load's ...)
+    if (keys_only) return RUNG_TILE_VALUES;                  // (a load of keys alone that is not counted that way after all)
     if (int rc = reserve_store()) return rc;
     if (!blk_tiles_made) {                                       // (a load that was to keep no store builds one after all)
         LSG_HIP(hipStreamSynchronize(c->copy_stream));
@@ -1189,6 +1121,19 @@ int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int6
         fprintf(stderr, "[lsg] tile store: %llu entries, %u blocks (%.2f GB): capacities + scatter %.2f, sort %.2f, fill %.2f, gather %.2f ms\n",
                 (unsigned long long)N, nblk, (double)nblk * 1024 / 1e9, c->build_ms[0], c->build_ms[1], c->build_ms[2], c->build_ms[3]);
     return finish();
+}
+
+int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int64_t* seg_ev_off, const lsg_reads* src) {
+    // at most three attempts: an attempt that returns a rung returns a lower one than its own
+    int rc = build_once(c, events, n_events, seg_ev_off, src, RUNG_WINDOWS);
+    while (rc > 0) {
+        LSG_HIP(hipStreamSynchronize(c->stream)); LSG_HIP(hipStreamSynchronize(c->copy_stream));
+        if (getenv("LSG_TIMING"))
+            fprintf(stderr, rc == RUNG_TILE_KEYS ? "[lsg] load: not a load for 128-position windows after all, starting again by tiles\n"
+                                                 : "[lsg] load: the count from keys alone was not made, loading again with values\n");
+        rc = build_once(c, events, n_events, seg_ev_off, src, rc);
+    }
+    return rc;
 }
 
 // ================================================================================================

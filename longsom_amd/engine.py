@@ -354,8 +354,9 @@ class Engine:
         return s
 
     def layout_info(self):
-        """(path, build_ms, store_bytes): path 2 = the load built the store alone, 3 = in the pass that also made the first count (set_count_at_load), 4 = the load counted and kept no store (set_store_policy); wall time the last load spent building the
-        store; device bytes the store and what belongs to it hold (lsg_get_layout_info)"""
+        """(path, build_ms, store_bytes): path 2 = the load built the store alone, 3 = in the pass that also made the first count (set_count_at_load), 4 = the load counted and kept no store (set_store_policy),
+        5 = the same over tile-phased events (every entry fetched as its one 128-byte line), 6 = the same with the entries binned by
+        128-position windows (one 256-byte block per entry); wall time the last load spent building the store; device bytes the store and what belongs to it hold (lsg_get_layout_info)"""
         path = C.c_int32(0); ms = C.c_double(0.0); nbytes = C.c_int64(0)
         _lib.check(self._lib.lsg_get_layout_info(self._h, C.byref(path), C.byref(ms), C.byref(nbytes)), "lsg_get_layout_info")
         return int(path.value), float(ms.value), int(nbytes.value)

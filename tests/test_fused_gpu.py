@@ -50,7 +50,7 @@ def expected_direct_path(engine, p, phased, hinted, match_filter):
     if not (phased and 1 <= p.min_bq <= 255):
         return 4
     import os
-    keys_alone = (match_filter or engine.load_settings()["load_filter"] == (p.min_mq, p.flag_exclude, p.ignore_orphans)) and not os.environ.get("LSG_TEST_KEYS_ONLY_REFUSED") and not os.environ.get("LSG_NO_KEYS_ONLY")
+    keys_alone = (match_filter or engine.load_settings()["load_filter"] == (p.min_mq, p.flag_exclude, p.ignore_orphans)) and not os.environ.get("LSG_TEST_KEYS_ONLY_REFUSED")
     return 6 if hinted and keys_alone and engine.pileup_window >= 128 else 5
 
 
@@ -250,18 +250,3 @@ def test_loads_that_sort_keys_alone(engine, monkeypatch, capfd):
     finally:
         engine.set_load_filter()
 
-
-def test_library_paths_behind_the_switches_still_count_the_same(engine, monkeypatch):
-    """The tiles' tables as library calls (LSG_NO_TILE_TABLES), the 256-thread sort of a small load (LSG_SORT_BIG_BLOCKS=0) and a load that
-    carries values although it could sort keys alone (LSG_NO_KEYS_ONLY): the paths the defaults replaced, against the oracle."""
-    p = CountParams.longsom_defaults()
-    lens = [4000, 2000]
-    rec, refs, ct_of = make_case(3, 30000, lens, 3000, hot_regions=[(0, 1000, 1100), (1, 500, 520)], hot_frac=0.9)
-    engine.set_load_filter(p.min_mq, p.flag_exclude, p.ignore_orphans)
-    try:
-        for name, val in (("LSG_NO_TILE_TABLES", "1"), ("LSG_SORT_BIG_BLOCKS", "0"), ("LSG_NO_KEYS_ONLY", "1")):
-            monkeypatch.setenv(name, val)
-            fused_vs_oracle(engine, rec, lens, refs, ct_of, 2, p)
-            monkeypatch.delenv(name)
-    finally:
-        engine.set_load_filter()
