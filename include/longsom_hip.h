@@ -286,6 +286,23 @@ int lsg_set_count_at_load(lsg_ctx* ctx, const lsg_count_params* params);
  * reads.  Default off (the counting rules never see these reads; their events cost memory).  The host decoder's twin is
  * lsio_set_keep_unlisted. */
 int lsg_set_keep_unlisted(lsg_ctx* ctx, int32_t on);
+/* SplitBamCellTypes' read filters for the BAM loads that follow (lsg_load_bam, lsg_load_bam_range): --max_nM, --max_NH and --n_trim
+ * (SplitBamCellTypes.py:92-173, its flags :199-202).  A read whose cleaned CB is listed is checked in the reference's order: nM > max_nm
+ * or no nM tag, NH > max_nh or no NH tag, MAPQ < min_mapq; a read with an nM or NH reason is written to no cell type's BAM, so here it is
+ * never counted and is kept only as an unlisted read (lsg_set_keep_unlisted); MAPQ alone keeps its meaning (mapq_filtered, the load
+ * filter).  A passing read with n_trim > 0 has the qualities of its trim window set to 0 (:129-170): n_trim bases at either end, or at
+ * an end whose CIGAR operation is a soft clip of L bases (with more than one operation) L + n_trim, 30 + n_trim for 20 <= L < 30.  The
+ * tags: c C s S i I compare as integers, f as a float; a duplicated tag is read at its first occurrence (htslib bam_aux_get, which
+ * pysam's opt() calls).  Where the reference raises - an nM / NH tag of another type, a trim window longer than the read, a passing read
+ * without qualities when n_trim > 0 - the load fails with an error naming the read.  max_nm / max_nh < 0: that filter is off; (-1, -1,
+ * 0) = every filter off (default). */
+int lsg_set_split_filters(lsg_ctx* ctx, int32_t max_nm, int32_t max_nh, int32_t n_trim);
+/* The filter reasons of the last BAM load, the columns SplitBamCellTypes' report adds behind CB_not_matched (FILTER_dict, :114-116,
+ * 181-187): n[r] records and first_ordinal[r] = the smallest record ordinal of the load (-1: none) with reason
+ * r = nm * 6 + nh * 2 + mapq, nm and nh in {0 passed, 1 over the limit, 2 tag not found}, mapq in {0, 1}; r = 0 is Pass_reads.  The
+ * report's key of r joins the parts with ';' in that order ("nM_not_found;NH;MAPQ"), its columns come in the order in which the file
+ * first produced them: by first ordinal.  A range load counts the records of its key range only.  Both arrays hold 18 entries. */
+int lsg_get_split_reasons(lsg_ctx* ctx, int64_t* n, int64_t* first_ordinal);
 enum { LSG_STORE_KEEP = 0, LSG_STORE_SKIP_WHEN_COUNTED = 1 };
 int lsg_set_store_policy(lsg_ctx* ctx, int32_t policy);
 

@@ -12,19 +12,22 @@ from ._lib import CallParams, CountParams
 from .engine import Engine
 
 
+def _limit(text):
+    """--max_nM / --max_NH: an int, or off (None) for an empty value - what a rule renders when its config sets no limit (--max_nM=)"""
+    return None if text in ("", "None") else int(text)
+
+
 def split_bam(argv=None):
-    """SplitBamCellTypes.py --bam --meta --id --outdir --min_MQ  (SplitBamCellTypes.py:194-204)"""
+    """SplitBamCellTypes.py --bam --meta --id --max_nM --max_NH --min_MQ --n_trim --outdir  (SplitBamCellTypes.py:194-204)"""
     ap = argparse.ArgumentParser(description="Split a BAM into one BAM per cell type by CB tag")
     ap.add_argument("--bam", required=True); ap.add_argument("--meta", required=True); ap.add_argument("--id", default="Sample")
-    ap.add_argument("--max_nM", type=int, default=None); ap.add_argument("--max_NH", type=int, default=None)
+    ap.add_argument("--max_nM", type=_limit, default=None); ap.add_argument("--max_NH", type=_limit, default=None)
     ap.add_argument("--min_MQ", type=int, default=255); ap.add_argument("--n_trim", type=int, default=0); ap.add_argument("--outdir", default=".")
     a = ap.parse_args(argv)
-    if a.max_nM is not None or a.max_NH is not None or a.n_trim:
-        raise SystemExit("--max_nM / --max_NH / --n_trim are not used by LongSom's rules and are not implemented")
     t0 = time.time()
     table = hostio.read_barcodes(a.meta)
     outs = [os.path.join(a.outdir, "%s.%s.bam" % (a.id, ct)) for ct in table.celltype_names]
-    rep = hostio.split_bam(a.bam, table, outs, a.min_MQ)
+    rep = hostio.split_bam(a.bam, table, outs, a.min_MQ, hostio.SplitFilters(a.max_nM, a.max_NH, a.n_trim))
     pipeline.write_report(os.path.join(a.outdir, a.id + ".report.txt"), rep, time.time() - t0)
 
 
@@ -311,6 +314,9 @@ def snv(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--window_gb", type=float, default=0.0, help="stream the BAM in batches of about this many GiB of uncompressed BAM and count "
                     "window by window (for a BAM whose reads do not fit in HBM); 0 = the whole BAM at once")
+    # SplitBamCellTypes' read filters, with its names and defaults (SplitBamCellTypes.py:199-202); not SnvParams fields, so that the flag
+    # surfaces of `reannotation` and `pon` stay as they are
+    ap.add_argument("--max_nM", type=_limit, default=None); ap.add_argument("--max_NH", type=_limit, default=None); ap.add_argument("--n_trim", type=int, default=0)
     d = pipeline.SnvParams()
     _add_dataclass_flags(ap, d)
     _add_htslib_flag(ap); _add_gnomad_flag(ap)
@@ -323,7 +329,8 @@ def snv(argv=None):
     comm = regions.Comm.from_env()
     try:
         out = pipeline.run_snv(a.bam, a.meta, a.ref, a.outdir, a.id, params, a.editing or None, a.pon_SR or None, a.pon_LR or None,
-                               a.gnomAD_json or a.gnomAD_db or None, a.device, comm=comm, window_bytes=int(a.window_gb * (1 << 30)) or None)
+                               a.gnomAD_json or a.gnomAD_db or None, a.device, comm=comm, window_bytes=int(a.window_gb * (1 << 30)) or None,
+                               filters=pipeline.SplitFilters(a.max_nM, a.max_NH, a.n_trim))
         if comm.rank == 0:
             print(json.dumps({"outputs": {k: v for k, v in vars(out).items() if k not in ("timings", "resident", "_pending")}, "seconds": out.timings, "ranks": comm.world}))
     finally:

@@ -3,11 +3,12 @@
 // htslib / pysam column semantics of SURVEY.md §8a rows a4-a6).  No allocation, every loop bounded by the record's own length fields,
 // which validate() checks against the record's block_size before anything else walks them.
 //
-// Replaces, per record: read.opt("CB") + the barcode lookup + the MAPQ counters of split_bam (SplitBamCellTypes.py:65-124) and the
-// CIGAR -> column step of bam.pileup (BaseCellCounter.py:191-216; htslib resolve_cigar2).
+// Replaces, per record: read.opt("CB") + the barcode lookup + the nM / NH / MAPQ filters and counters of split_bam and its --n_trim
+// quality trim (SplitBamCellTypes.py:65-173) and the CIGAR -> column step of bam.pileup (BaseCellCounter.py:191-216; htslib resolve_cigar2).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include <string.h>
 
 #ifdef __HIPCC__
 #define LSR_FN __host__ __device__ __forceinline__
@@ -80,6 +81,94 @@ LSR_FN bool find_cb(const uint8_t* rec, uint32_t len, uint32_t* cb, uint32_t* ra
     return found;
 }
 
+// ---- SplitBamCellTypes' read filters (--max_nM, --max_NH, --n_trim; SplitBamCellTypes.py:92-173) --------------------------------------
+// An integer tag's value as read.opt() returns it: the aux types c C s S i I compare as integers, f as a float (Python compares either with
+// the int limit numerically).  Any other type (A Z H B) makes opt(...) > max_N raise TypeError in the reference: AUX_BAD.
+enum { AUX_NONE = 0, AUX_NUM = 1, AUX_BAD = 2 };
+struct AuxNum { uint32_t kind; int64_t i; float f; bool is_float; };
+LSR_FN bool aux_over(const AuxNum& a, int32_t max_v) { return a.is_float ? (double)a.f > (double)max_v : a.i > (int64_t)max_v; }
+
+// One pass over the aux fields: CB:Z as find_cb returns it (the LAST CB:Z wins) and the nM / NH tags.  A duplicated nM or NH follows
+// htslib's bam_aux_get, which pysam's opt() calls: the FIRST occurrence is the value.  Returns whether a CB:Z was found.
+LSR_FN bool scan_aux(const uint8_t* rec, uint32_t len, uint32_t* cb, uint32_t* raw, uint32_t* clean, AuxNum* nm, AuxNum* nh) {
+    const uint32_t l_name = rec[8], n_cigar = rd16(rec + 12), l_seq = rd32(rec + 16);
+    uint64_t a = 32ull + l_name + 4ull * n_cigar + (l_seq + 1) / 2 + l_seq;
+    const uint64_t end = len;
+    bool found = false;
+    nm->kind = AUX_NONE; nh->kind = AUX_NONE;
+    while (a + 3 <= end) {
+        const uint8_t t0 = rec[a], t1 = rec[a + 1], ty = rec[a + 2];
+        a += 3;
+        uint64_t sz = 0;
+        if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
+        else if (ty == 's' || ty == 'S') sz = 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
+        else if (ty == 'Z' || ty == 'H') {
+            uint64_t z = a;
+            while (z < end && rec[z]) ++z;
+            sz = (z - a) + 1;
+            if (t0 == 'C' && t1 == 'B' && ty == 'Z' && z < end) { *cb = (uint32_t)a; *raw = (uint32_t)(z - a); found = true; }
+        } else if (ty == 'B') {
+            if (a + 5 > end) break;
+            const uint8_t st = rec[a]; const uint64_t cnt = rd32(rec + a + 1);
+            sz = 5 + cnt * ((st == 'c' || st == 'C') ? 1u : (st == 's' || st == 'S') ? 2u : 4u);
+        } else break;
+        if (sz > end - a) break;                      // a field that claims more bytes than the record has
+        AuxNum* t = (t0 == 'n' && t1 == 'M') ? nm : (t0 == 'N' && t1 == 'H') ? nh : nullptr;
+        if (t && t->kind == AUX_NONE) {
+            const uint8_t* v = rec + a;
+            t->kind = AUX_NUM; t->is_float = false; t->i = 0; t->f = 0.f;
+            if (ty == 'c') t->i = (int8_t)v[0];
+            else if (ty == 'C') t->i = v[0];
+            else if (ty == 's') t->i = (int16_t)rd16(v);
+            else if (ty == 'S') t->i = rd16(v);
+            else if (ty == 'i') t->i = (int32_t)rd32(v);
+            else if (ty == 'I') t->i = rd32(v);
+            else if (ty == 'f') { const uint32_t w = rd32(v); float f; __builtin_memcpy(&f, &w, 4); t->f = f; t->is_float = true; }
+            else t->kind = AUX_BAD;
+        }
+        a += sz;
+    }
+    if (found) { uint32_t c = 0; while (c < *raw && rec[*cb + c] != '-') ++c; *clean = c; }
+    return found;
+}
+
+// The filter reasons of a matched record (SplitBamCellTypes.py:92-116): index = nm * 6 + nh * 2 + mapq with nm, nh in {0 none, 1 over the
+// limit, 2 tag not found} and mapq in {0, 1}; 0 = the read passes.  max_nm / max_nh < 0: that filter is off.  The report's key of index r
+// is ';'.join of the parts in that order (longsom_amd/hostio.py REASON_KEYS).
+enum { N_REASONS = 18 };
+LSR_FN uint32_t reason_of(const AuxNum& nm, const AuxNum& nh, int32_t max_nm, int32_t max_nh, bool low_mapq) {
+    const uint32_t a = max_nm < 0 ? 0u : nm.kind == AUX_NONE ? 2u : aux_over(nm, max_nm) ? 1u : 0u;
+    const uint32_t b = max_nh < 0 ? 0u : nh.kind == AUX_NONE ? 2u : aux_over(nh, max_nh) ? 1u : 0u;
+    return a * 6u + b * 2u + (low_mapq ? 1u : 0u);
+}
+
+// --n_trim's window of a passing read (SplitBamCellTypes.py:129-165): the qualities at query indices [0, start) and the last `end` ones
+// become 0.  With more than one CIGAR operation an end takes its soft clip's length + n_trim, or 30 + n_trim for a clip of 20-29 bases (the
+// 10x adapter rule), or n_trim when the end is any other operation; otherwise both ends take n_trim.
+struct Trim { uint32_t start, end; };
+LSR_FN uint32_t trim_of_op(uint32_t c, uint32_t n_trim) {
+    const uint32_t op = c & 0xf, L = c >> 4;
+    if (op != 4) return n_trim;
+    return (L >= 20 && L < 30) ? 30u + n_trim : L + n_trim;
+}
+LSR_FN Trim trim_window(const uint8_t* rec, uint32_t n_trim) {
+    if (!n_trim) return Trim{0, 0};
+    const uint32_t l_name = rec[8], n_cigar = rd16(rec + 12);
+    const uint8_t* cigar = rec + 32 + l_name;
+    if (n_cigar > 1) return Trim{trim_of_op(rd32(cigar), n_trim), trim_of_op(rd32(cigar + 4ull * (n_cigar - 1)), n_trim)};
+    return Trim{n_trim, n_trim};
+}
+// Where the reference raises on a passing read with n_trim > 0: 1 = a trim longer than the read (IndexError, :161-165), 2 = no quality
+// string (QUAL 0xff or no SEQ: query_qualities is None, TypeError).  0 = fine.
+enum { TRIM_OK = 0, TRIM_TOO_LONG = 1, TRIM_NO_QUAL = 2 };
+LSR_FN int trim_check(const uint8_t* rec, const Trim& t) {
+    const uint32_t l_name = rec[8], n_cigar = rd16(rec + 12), l_seq = rd32(rec + 16);
+    if (l_seq == 0 || rec[32 + l_name + 4ull * n_cigar + (l_seq + 1) / 2] == 0xff) return TRIM_NO_QUAL;
+    if (t.start > l_seq || t.end > l_seq) return TRIM_TOO_LONG;
+    return TRIM_OK;
+}
+
 LSR_FN uint64_t fnv64(const uint8_t* p, uint32_t n) {
     uint64_t h = 1469598103934665603ull;
     for (uint32_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; }
@@ -139,12 +228,17 @@ struct Shape { uint32_t n_segs; uint64_t n_events; };
 //                 n_events is the record's region: its last segment's end rounded up to 128.
 template <bool EMIT>
 LSR_FN Shape walk(const uint8_t* rec, int legacy_del_merge, uint32_t lane, uint32_t nlanes, uint32_t read_index,
-                  uint32_t* seg_read, int32_t* seg_start, int32_t* seg_len, int64_t* seg_ev_off, int64_t ev_base, uint16_t* events, bool phased = false) {
+                  uint32_t* seg_read, int32_t* seg_start, int32_t* seg_len, int64_t* seg_ev_off, int64_t ev_base, uint16_t* events, bool phased = false,
+                  uint32_t n_trim = 0) {
     const int32_t pos = (int32_t)rd32(rec + 4);
     const uint32_t l_name = rec[8], n_cigar = rd16(rec + 12), l_seq = rd32(rec + 16);
     const uint8_t* cigar = rec + 32 + l_name;
     const uint8_t* seq = cigar + 4ull * n_cigar;
     const uint8_t* qual = seq + (l_seq + 1) / 2;
+    // every quality goes through qv(): 0 beyond l_qseq and, for a read --n_trim trims, inside its trim window (n_trim = 0: [0, l_seq), as before)
+    const Trim tw = EMIT ? trim_window(rec, n_trim) : Trim{0, 0};
+    const uint32_t q_lo = tw.start, q_hi = tw.end < l_seq ? l_seq - tw.end : 0u;
+    auto qv = [&](uint32_t q) -> uint32_t { return q >= q_lo && q < q_hi ? (uint32_t)qual[q] : 0u; };
     int64_t x = pos, last_pos = -2;
     uint32_t y = 0, n_segs = 0;
     uint64_t ne = 0;
@@ -170,8 +264,7 @@ LSR_FN Shape walk(const uint8_t* rec, int legacy_del_merge, uint32_t lane, uint3
                         const uint32_t q = y + i;
                         uint32_t sym = q < l_seq ? nt16_sym((seq[q >> 1] >> ((~q & 1u) << 2)) & 0xfu) : 6u;      // beyond l_qseq pysam prints 'N'
                         if (i + 1 == L && over != 15) sym = over;
-                        const uint32_t qv = q < l_seq ? qual[q] : 0u;
-                        events[ev_base + (int64_t)ne + i] = (uint16_t)(sym < 8 ? (0x0800u | (sym << 8) | (qv & 0xffu)) : 0u);
+                        events[ev_base + (int64_t)ne + i] = (uint16_t)(sym < 8 ? (0x0800u | (sym << 8) | (qv(q) & 0xffu)) : 0u);
                     }
                 ne += L;
             }
@@ -180,10 +273,10 @@ LSR_FN Shape walk(const uint8_t* rec, int legacy_del_merge, uint32_t lane, uint3
             if (L) {
                 open(x, L);
                 if (EMIT) {
-                    const uint32_t qv = y < l_seq ? qual[y] : 0u;
+                    const uint32_t qd = qv(y);
                     for (uint32_t i = lane; i < L; i += nlanes) {
                         const uint32_t sym = (i + 1 == L && over != 15) ? over : 7u;
-                        events[ev_base + (int64_t)ne + i] = (uint16_t)(0x0800u | (sym << 8) | (qv & 0xffu));
+                        events[ev_base + (int64_t)ne + i] = (uint16_t)(0x0800u | (sym << 8) | (qd & 0xffu));
                     }
                 }
                 ne += L;
@@ -192,7 +285,7 @@ LSR_FN Shape walk(const uint8_t* rec, int legacy_del_merge, uint32_t lane, uint3
         } else {                                                            // N: '>' '<' are NA, except an indel flag on its last column
             if (L > 0 && over != 15) {
                 open(x + L - 1, 1);
-                if (EMIT && lane == 0) { const uint32_t qv = y < l_seq ? qual[y] : 0u; events[ev_base + (int64_t)ne] = (uint16_t)(0x0800u | (over << 8) | (qv & 0xffu)); }
+                if (EMIT && lane == 0) events[ev_base + (int64_t)ne] = (uint16_t)(0x0800u | (over << 8) | (qv(y) & 0xffu));
                 ne += 1;
             }
             x += L;

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../synth_model.h"
+#include "../bamrec_core.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -45,7 +46,38 @@ struct Local {   // per-thread decode output
     std::vector<uint16_t> events;
     int64_t total = 0, pass = 0, cb_not_found = 0, cb_not_matched = 0, mapq = 0;
     std::vector<int64_t> cb_pass, cb_low;      // per dense barcode id: matched reads with MAPQ >= / < min_mapq (report of a later table)
+    int64_t rsn_n[lsr::N_REASONS] = {}, rsn_first[lsr::N_REASONS];      // per filter reason (lsr::reason_of): records, smallest ordinal (-1: none)
+    int64_t err_ord = -1; int err_kind = 0;                              // the first record the reference's split_bam raises on (SPLIT_ERR_*)
+    Local() { for (auto& f : rsn_first) f = -1; }
 };
+
+// SplitBamCellTypes' --max_nM / --max_NH / --n_trim (lsio_stream_set_split_filters; -1 / -1 / 0 = off)
+struct SplitFilters { int32_t max_nm = -1, max_nh = -1, n_trim = 0; };
+enum { SPLIT_ERR_TRIM_LONG = 1, SPLIT_ERR_NO_QUAL = 2, SPLIT_ERR_NM_TYPE = 3, SPLIT_ERR_NH_TYPE = 4 };
+const char* split_err_text(int kind) {
+    switch (kind) {
+        case SPLIT_ERR_TRIM_LONG: return "its --n_trim window is longer than the read (the reference raises IndexError)";
+        case SPLIT_ERR_NO_QUAL: return "it has no base qualities to trim (the reference raises TypeError)";
+        case SPLIT_ERR_NM_TYPE: return "its nM tag is not a number (the reference raises TypeError)";
+        case SPLIT_ERR_NH_TYPE: return "its NH tag is not a number (the reference raises TypeError)";
+        default: return "?";
+    }
+}
+// The filter reason of a record whose cleaned CB is listed (SplitBamCellTypes.py:92-116) and, for a passing read, its --n_trim window
+// (:129-170); *err = SPLIT_ERR_* where the reference raises.  The same rules as the device ingest (bamrec_core.h, ingest.hip k_rec_info).
+uint32_t split_reason(const uint8_t* rec, const lsr::AuxNum& nm, const lsr::AuxNum& nh, int min_mapq, const SplitFilters& f, lsr::Trim* trim, int* err) {
+    *err = 0; *trim = lsr::Trim{0, 0};
+    if (f.max_nm >= 0 && nm.kind == lsr::AUX_BAD) *err = SPLIT_ERR_NM_TYPE;
+    else if (f.max_nh >= 0 && nh.kind == lsr::AUX_BAD) *err = SPLIT_ERR_NH_TYPE;
+    const uint32_t r = lsr::reason_of(nm, nh, f.max_nm, f.max_nh, (int)rec[9] < min_mapq);
+    if (r == 0 && f.n_trim > 0) {
+        *trim = lsr::trim_window(rec, (uint32_t)f.n_trim);
+        const int tc = lsr::trim_check(rec, *trim);
+        if (tc != lsr::TRIM_OK && !*err) *err = tc == lsr::TRIM_TOO_LONG ? SPLIT_ERR_TRIM_LONG : SPLIT_ERR_NO_QUAL;
+    }
+    return r;
+}
+std::string read_name(const uint8_t* rec) { const uint32_t l = rec[8]; return std::string((const char*)rec + 32, l ? strnlen((const char*)rec + 32, l - 1) : 0); }
 
 // htslib <= 1.10: the last column of a D operation followed by another D is a deletion anchor too ("1D2D": 'D' where htslib >= 1.11
 // gives 'O'); lsio_set_legacy_del_merge, default off = htslib >= 1.11
@@ -90,8 +122,9 @@ bool find_cb(const uint8_t* rec, uint32_t len, const char** cb_out, size_t* len_
     return false;
 }
 
-// Decode one BAM record (rec points at refID, i.e. after block_size) into L.
-void decode_record(const uint8_t* rec, uint32_t len, const std::unordered_map<std::string, int32_t>& cbmap, int min_mapq, Local& L) {
+// Decode one BAM record (rec points at refID, i.e. after block_size) into L; `ordinal` = its index in the batch.
+void decode_record(const uint8_t* rec, uint32_t len, const std::unordered_map<std::string, int32_t>& cbmap, int min_mapq, const SplitFilters& filt, int64_t ordinal,
+                   Local& L) {
     const int32_t tid = rdi32(rec), pos = rdi32(rec + 4);
     const uint32_t l_name = rec[8], mapq = rec[9], n_cigar = rd16(rec + 12), flag = rd16(rec + 14), l_seq = rd32(rec + 16);
     if (tid < 0) return;                              // infile.fetch() iterates reads placed on a reference
@@ -100,26 +133,14 @@ void decode_record(const uint8_t* rec, uint32_t len, const std::unordered_map<st
     const uint8_t* cigar = p; p += 4ull * n_cigar;
     const uint8_t* seq = p; p += (l_seq + 1) / 2;
     const uint8_t* qual = p; p += l_seq;
-    const uint8_t* aux = p; const uint8_t* end = rec + len;
-    // CB:Z tag (read.opt("CB"), SplitBamCellTypes.py:74-79)
+    // CB:Z tag (read.opt("CB"), SplitBamCellTypes.py:74-79; the last CB:Z wins) and the nM / NH tags, in one pass over the aux fields
     const char* cb = nullptr; size_t cb_len = 0;
-    while (aux + 3 <= end) {
-        const char t0 = (char)aux[0], t1 = (char)aux[1], ty = (char)aux[2];
-        aux += 3;
-        size_t sz = 0;
-        switch (ty) {
-            case 'A': case 'c': case 'C': sz = 1; break;
-            case 's': case 'S': sz = 2; break;
-            case 'i': case 'I': case 'f': sz = 4; break;
-            case 'Z': case 'H': { const uint8_t* z = aux; while (z < end && *z) ++z; sz = (size_t)(z - aux) + 1;
-                                  if (t0 == 'C' && t1 == 'B' && ty == 'Z' && z < end) { cb = (const char*)aux; cb_len = sz - 1; } break; }
-            case 'B': { if (aux + 5 > end) { aux = end; continue; } const char st = (char)aux[0]; const uint32_t cnt = rd32(aux + 1);
-                        const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4; sz = 5 + es * cnt; break; }
-            default: aux = end; continue;
-        }
-        if (sz > (size_t)(end - aux)) break;                  // a field that claims more bytes than the record has
-        aux += sz;
+    lsr::AuxNum nm, nh;
+    {
+        uint32_t at = 0, raw = 0, cl = 0;
+        if (lsr::scan_aux(rec, len, &at, &raw, &cl, &nm, &nh)) { cb = (const char*)rec + at; cb_len = raw; }
     }
+    lsr::Trim trim{0, 0};
     // A read without a listed barcode is never counted, but it takes a place in the buffer of a pileup over the UNSPLIT BAM
     // (HCCVSingleCellGenotype.py:121-122: max_depth is about every read that passes the pileup's own filters): lsio_set_keep_unlisted
     // keeps it, with cb = -1, for the replay of that rule (genotype.hip)
@@ -131,8 +152,16 @@ void decode_record(const uint8_t* rec, uint32_t len, const std::unordered_map<st
         if (it == cbmap.end()) ++L.cb_not_matched;
         else {
             cb_id = it->second;
-            if ((int)mapq < min_mapq) ++L.mapq; else ++L.pass;                       // report only; the device re-applies min_mq
-            if ((size_t)cb_id < L.cb_pass.size()) { if ((int)mapq < min_mapq) ++L.cb_low[(size_t)cb_id]; else ++L.cb_pass[(size_t)cb_id]; }
+            // the final filters (:92-116): MAPQ is report only (the device re-applies min_mq); a read with an nM / NH reason goes to no
+            // cell type's BAM: it loses its barcode and is kept only as an unlisted read
+            int err = 0;
+            const uint32_t r = split_reason(rec, nm, nh, min_mapq, filt, &trim, &err);
+            if (err && L.err_ord < 0) { L.err_ord = ordinal; L.err_kind = err; }
+            ++L.rsn_n[r];
+            if (L.rsn_first[r] < 0) L.rsn_first[r] = ordinal;
+            if (r == 1) ++L.mapq; else if (r == 0) ++L.pass;
+            if (r <= 1 && (size_t)cb_id < L.cb_pass.size()) { if (r) ++L.cb_low[(size_t)cb_id]; else ++L.cb_pass[(size_t)cb_id]; }
+            if (r >= 2) cb_id = -1;
         }
     }
     if (cb_id < 0 && !g_keep_unlisted.load(std::memory_order_relaxed)) return;
@@ -152,7 +181,8 @@ void decode_record(const uint8_t* rec, uint32_t len, const std::unordered_map<st
         L.events.push_back(LSG_EVENT(sym, q));
         last_pos = refpos;
     };
-    auto qual_at = [&](uint32_t q) -> uint32_t { return q < l_seq ? qual[q] : 0u; };
+    const uint32_t q_lo = trim.start, q_hi = trim.end < l_seq ? l_seq - trim.end : 0u;        // (no trim: [0, l_seq))
+    auto qual_at = [&](uint32_t q) -> uint32_t { return q >= q_lo && q < q_hi ? qual[q] : 0u; };
     auto base_sym = [&](uint32_t q) -> uint32_t { return q < l_seq ? NT16_SYM[(seq[q >> 1] >> ((~q & 1) << 2)) & 0xf] : 6u; };   // beyond l_qseq pysam prints 'N'
     for (uint32_t k = 0; k < n_cigar; ++k) {
         const uint32_t c = rd32(cigar + 4ull * k), op = c & 0xf, len_op = c >> 4;
@@ -212,6 +242,7 @@ typedef struct {
     int64_t total_reads, pass_reads, cb_not_found, cb_not_matched, mapq_filtered;
     int32_t n_barcodes; char* barcodes;      /* auto-barcode mode: the distinct cleaned CBs found, '\n'-joined, id = order of first appearance */
     int64_t n_tally; int64_t* cb_pass; int64_t* cb_low;   /* per dense barcode id (listed-barcode mode): matched reads with MAPQ >= / < min_mapq */
+    int64_t split_n[18], split_first[18];    /* per filter reason (lsg_get_split_reasons): records and the smallest ordinal of the batch (-1: none) */
 } lsio_decoded;
 
 const char* lsio_last_error(void) { return g_err; }
@@ -250,6 +281,7 @@ struct lsio_stream {
     std::unordered_map<std::string, int32_t> cbmap;
     bool auto_barcodes = false; std::string auto_joined; int32_t auto_n = 0; int64_t n_tally = 0;
     int min_mapq = 0, n_threads = 1;
+    SplitFilters filters;
     ~lsio_stream() { if (file && file != (const uint8_t*)MAP_FAILED && fsize) munmap((void*)file, fsize); if (fd >= 0) close(fd); }
 };
 
@@ -405,10 +437,16 @@ lsio_decoded* decode_records(lsio_stream& st, const uint8_t* d, const std::vecto
         for (int t = 0; t < T; ++t)
             th.emplace_back([&, t]() {
                 const size_t a = recs.size() * (size_t)t / (size_t)T, b = recs.size() * (size_t)(t + 1) / (size_t)T;
-                for (size_t i = a; i < b; ++i) decode_record(d + recs[i] + 4, rd32(d + recs[i]), st.cbmap, st.min_mapq, loc[(size_t)t]);
+                for (size_t i = a; i < b; ++i) decode_record(d + recs[i] + 4, rd32(d + recs[i]), st.cbmap, st.min_mapq, st.filters, (int64_t)i, loc[(size_t)t]);
             });
         for (auto& t : th) t.join();
     }
+    for (auto& l : loc)                      // (threads take ascending ranges: the first one with an error has the smallest ordinal)
+        if (l.err_ord >= 0) {
+            set_err("%s: read '%s' (record %lld of the batch): %s", st.path.c_str(), read_name(d + recs[(size_t)l.err_ord] + 4).c_str(), (long long)l.err_ord,
+                    split_err_text(l.err_kind));
+            return nullptr;
+        }
     lsio_decoded* o = (lsio_decoded*)calloc(1, sizeof(lsio_decoded));
     int64_t R = 0, S = 0, E = 0;
     for (auto& l : loc) { R += (int64_t)l.read_tid.size(); S += (int64_t)l.seg_read.size(); E += (int64_t)l.events.size(); }
@@ -444,6 +482,10 @@ lsio_decoded* decode_records(lsio_stream& st, const uint8_t* d, const std::vecto
     for (auto& l : loc) {
         o->total_reads += l.total; o->pass_reads += l.pass; o->cb_not_found += l.cb_not_found; o->cb_not_matched += l.cb_not_matched;
         o->mapq_filtered += l.mapq;
+    }
+    for (int r = 0; r < lsr::N_REASONS; ++r) {
+        o->split_first[r] = -1;
+        for (auto& l : loc) { o->split_n[r] += l.rsn_n[r]; if (o->split_first[r] < 0) o->split_first[r] = l.rsn_first[r]; }
     }
     o->n_tally = n_tally;
     o->cb_pass = (int64_t*)calloc((size_t)(n_tally ? n_tally : 1), 8); o->cb_low = (int64_t*)calloc((size_t)(n_tally ? n_tally : 1), 8);
@@ -506,22 +548,37 @@ int lsio_stream_next(lsio_stream* st, int64_t max_ubytes, lsio_decoded** out) {
         return 0;
     }
     *out = decode_records(*st, data.data(), recs);
-    return 1;
+    return *out ? 1 : -1;
 }
 
-int lsio_decode_bam(const char* path, const char* barcodes, int32_t n_barcodes, const int32_t* ids, int32_t min_mapq, int32_t n_threads,
-                    lsio_decoded** out) {
+// SplitBamCellTypes' --max_nM / --max_NH / --n_trim for the batches of this stream (lsg_set_split_filters is the device's twin): a read
+// with an nM / NH reason is kept only as an unlisted read, a passing read's trim window gets quality 0; the reasons are in split_n /
+// split_first of every batch.  max_nm / max_nh < 0: off.
+int lsio_stream_set_split_filters(lsio_stream* st, int32_t max_nm, int32_t max_nh, int32_t n_trim) {
+    if (!st || n_trim < 0) { set_err("lsio_stream_set_split_filters: bad arguments"); return -2; }
+    st->filters.max_nm = max_nm < 0 ? -1 : max_nm; st->filters.max_nh = max_nh < 0 ? -1 : max_nh; st->filters.n_trim = n_trim;
+    return 0;
+}
+
+int lsio_decode_bam_filtered(const char* path, const char* barcodes, int32_t n_barcodes, const int32_t* ids, int32_t min_mapq, int32_t max_nm, int32_t max_nh,
+                             int32_t n_trim, int32_t n_threads, lsio_decoded** out) {
     if (!path || !out) { set_err("lsio_decode_bam: bad arguments"); return -2; }
     *out = nullptr;
     lsio_stream* st = nullptr;
     int rc = lsio_stream_open(path, barcodes, n_barcodes, ids, min_mapq, n_threads, &st);
     if (rc != 0) return rc;
+    if ((rc = lsio_stream_set_split_filters(st, max_nm, max_nh, n_trim)) != 0) { delete st; return rc; }
     std::vector<uint8_t> data; std::vector<size_t> recs;
     rc = next_records(*st, (size_t)-1, data, recs);
     if (rc < 0 || !st->header_done) { if (rc >= 0) set_err("%s: no BAM header", path); delete st; return -1; }
     *out = decode_records(*st, data.data(), recs);
     delete st;
-    return 0;
+    return *out ? 0 : -1;
+}
+
+int lsio_decode_bam(const char* path, const char* barcodes, int32_t n_barcodes, const int32_t* ids, int32_t min_mapq, int32_t n_threads,
+                    lsio_decoded** out) {
+    return lsio_decode_bam_filtered(path, barcodes, n_barcodes, ids, min_mapq, -1, -1, 0, n_threads, out);
 }
 
 // ---- BGZF / BAM writing -------------------------------------------------------------------------
@@ -759,10 +816,13 @@ int lsio_synth_bam(const lsg_synth_model* m, const char* contig_names /* '\n'-jo
 }
 
 // SplitBamCellTypes' BAM outputs (split_bam, SplitBamCellTypes.py:39-192): one BAM per cell type with the
-// records whose cleaned CB maps to it and whose MAPQ >= min_mapq; header copied (template=infile, :57).
-// celltype_of_barcode[i] in [0, n_ct) for barcode i of the '\n'-joined list; out_paths '\n'-joined.
-int lsio_split_bam(const char* path, const char* barcodes, int32_t n_barcodes, const uint8_t* celltype_of_barcode, int32_t n_ct,
-                   const char* out_paths, int32_t min_mapq, int64_t* counters /* total, pass, cb_not_found, cb_not_matched, mapq */) {
+// records whose cleaned CB maps to it and that pass the final filters (nM <= max_nm, NH <= max_nh, MAPQ >= min_mapq: :92-116; a
+// filter < 0 is off), their qualities trimmed by --n_trim (:129-170); header copied (template=infile, :57).
+// celltype_of_barcode[i] in [0, n_ct) for barcode i of the '\n'-joined list; out_paths '\n'-joined.  reasons_n / reasons_first (may be
+// NULL): [18] records per filter reason and the smallest record ordinal of each (-1: none), as lsg_get_split_reasons returns them.
+int lsio_split_bam_filtered(const char* path, const char* barcodes, int32_t n_barcodes, const uint8_t* celltype_of_barcode, int32_t n_ct,
+                            const char* out_paths, int32_t min_mapq, int64_t* counters /* total, pass, cb_not_found, cb_not_matched, mapq */,
+                            int32_t max_nm, int32_t max_nh, int32_t n_trim, int64_t* reasons_n, int64_t* reasons_first) {
     if (!path || !barcodes || !out_paths || n_ct <= 0) { set_err("lsio_split_bam: bad arguments"); return -2; }
     std::unordered_map<std::string, int32_t> ctmap;
     { const char* s = barcodes; for (int32_t i = 0; i < n_barcodes; ++i) { const char* e = strchr(s, '\n'); size_t l = e ? (size_t)(e - s) : strlen(s); ctmap[std::string(s, l)] = celltype_of_barcode[i]; s += l + (e ? 1 : 0); } }
@@ -779,7 +839,12 @@ int lsio_split_bam(const char* path, const char* barcodes, int32_t n_barcodes, c
     std::vector<BgzfWriter> w((size_t)n_ct);
     for (int i = 0; i < n_ct; ++i) { w[(size_t)i].f = fopen(outs[(size_t)i].c_str(), "wb"); if (!w[(size_t)i].f) { set_err("lsio_split_bam: cannot write %s", outs[(size_t)i].c_str()); return -1; } w[(size_t)i].write(header.data(), header.size()); }
     int64_t cnt[5] = {0, 0, 0, 0, 0};
-    for (const size_t rec_at : recs) {
+    int64_t rn[lsr::N_REASONS] = {}, rf[lsr::N_REASONS];
+    for (auto& f : rf) f = -1;
+    SplitFilters filt; filt.max_nm = max_nm < 0 ? -1 : max_nm; filt.max_nh = max_nh < 0 ? -1 : max_nh; filt.n_trim = n_trim > 0 ? n_trim : 0;
+    std::vector<uint8_t> copy;
+    for (size_t ri = 0; ri < recs.size(); ++ri) {
+        const size_t rec_at = recs[ri];
         const uint32_t bs = rd32(d + rec_at); const uint8_t* rec = d + rec_at + 4;
         if (rdi32(rec) < 0) continue;
         ++cnt[0];
@@ -787,15 +852,43 @@ int lsio_split_bam(const char* path, const char* barcodes, int32_t n_barcodes, c
         if (!find_cb(rec, bs, &cb, &cl)) { ++cnt[2]; continue; }
         auto it = ctmap.find(std::string(cb, cl));
         if (it == ctmap.end()) { ++cnt[3]; continue; }
-        if (min_mapq > 0 && (int)rec[9] < min_mapq) { ++cnt[4]; continue; }
+        lsr::AuxNum nm, nh; uint32_t a0, a1, a2;
+        (void)lsr::scan_aux(rec, bs, &a0, &a1, &a2, &nm, &nh);
+        lsr::Trim trim; int err = 0;
+        const uint32_t r = split_reason(rec, nm, nh, min_mapq, filt, &trim, &err);
+        if (err) {
+            set_err("lsio_split_bam: %s: read '%s' (record %zu): %s", path, read_name(rec).c_str(), ri, split_err_text(err));
+            for (auto& x : w) x.close();
+            return -1;
+        }
+        ++rn[r];
+        if (rf[r] < 0) rf[r] = (int64_t)ri;
+        if (r) { if (r == 1) ++cnt[4]; continue; }
         ++cnt[1];
-        w[(size_t)it->second].write_record(d + rec_at, 4 + bs);
+        if (trim.start || trim.end) {                    // read.query_qualities = Q with the window's qualities 0 (:161-170)
+            copy.assign(d + rec_at, d + rec_at + 4 + bs);
+            const uint32_t l_seq = rd32(rec + 16);
+            uint8_t* q = copy.data() + 4 + 32 + rec[8] + 4ull * rd16(rec + 12) + (l_seq + 1) / 2;
+            for (uint32_t k = 0; k < trim.start; ++k) q[k] = 0;
+            for (uint32_t k = 0; k < trim.end; ++k) q[l_seq - 1 - k] = 0;
+            w[(size_t)it->second].write_record(copy.data(), copy.size());
+        } else {
+            w[(size_t)it->second].write_record(d + rec_at, 4 + bs);
+        }
     }
     bool ok = true;
     for (auto& x : w) { x.close(); ok = ok && x.ok; }
     if (counters) memcpy(counters, cnt, sizeof(cnt));
+    if (reasons_n) memcpy(reasons_n, rn, sizeof(rn));
+    if (reasons_first) memcpy(reasons_first, rf, sizeof(rf));
     if (!ok) { set_err("lsio_split_bam: write failed"); return -1; }
     return 0;
+}
+
+// the same with every filter off (MAPQ only)
+int lsio_split_bam(const char* path, const char* barcodes, int32_t n_barcodes, const uint8_t* celltype_of_barcode, int32_t n_ct,
+                   const char* out_paths, int32_t min_mapq, int64_t* counters) {
+    return lsio_split_bam_filtered(path, barcodes, n_barcodes, celltype_of_barcode, n_ct, out_paths, min_mapq, counters, -1, -1, 0, nullptr, nullptr);
 }
 
 // Host evaluation of the model's read-record arrays (the same arrays lsg_synth_reads generates in HBM).

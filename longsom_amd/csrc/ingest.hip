@@ -13,8 +13,8 @@
 //                  two repeat until nothing moves (one round for an htslib-written file; a file whose records straddle every block
 //                  needs a round per block: after LSG_CHAIN_ROUNDS the call gives up and the caller decodes on the host)
 //   k_rec_list     every record's offset
-//   k_rec_info     one thread per record (bamrec_core.h): validation, CB tag, barcode lookup, SplitBam's counters, shape of its
-//                  CIGAR walk (segments, events)
+//   k_rec_info     one thread per record (bamrec_core.h): validation, one pass over the aux tags (CB, nM, NH), barcode lookup,
+//                  SplitBam's read filters and counters, shape of its CIGAR walk (segments, events)
 //   k_rec_emit     one WAVE per kept record: lane 0 the read's and segments' words, all lanes the events of every CIGAR operation
 //   lsg_load_reads on the device arrays: the tile store (store.hip)
 #include "lsg_ctx.h"
@@ -147,15 +147,21 @@ struct RecArgs {
     int32_t range;                        // lsg_load_bam_range: a record cut by the end of the slice is skipped; SplitBam's counters and the tallies take the
     int64_t count_lo, count_hi;           //   records whose (tid << 32 | pos) lies in [count_lo, count_hi) only (the neighbouring slices count the others)
     unsigned long long* last_key;         // largest (tid << 32 | pos) of a complete record (2^63 - 1 for a read without a reference: they end the file)
+    int32_t max_nm, max_nh, n_trim;       // lsg_set_split_filters (-1, -1, 0: off)
+    unsigned long long* rsn_n;            // [N_REASONS] records per filter reason (bamrec_core.h reason_of) ...
+    unsigned long long* rsn_first;        // [N_REASONS] ... and the smallest record ordinal that gave it (~0: none)
+    unsigned long long* err;              // smallest (ordinal << 3 | kind) of a record the reference raises on (LOAD_ERR_*; ~0: none)
 };
+enum { LOAD_ERR_TRIM_LONG = 1, LOAD_ERR_NO_QUAL = 2, LOAD_ERR_NM_TYPE = 3, LOAD_ERR_NH_TYPE = 4 };
 __global__ void k_rec_info(RecArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long c_total = 0, c_pass = 0, c_nf = 0, c_nm = 0, c_low = 0, my_key = 0;
+    uint32_t reason = lsr::N_REASONS;     // the record's filter reason when it is matched and counted here (none: N_REASONS)
     if (i < a.n_rec) {
         const uint64_t p = a.rec_off[i];
         const uint32_t bs = lsr::rd32(a.u + p);
         const uint8_t* rec = a.u + p + 4;
-        uint8_t keep = 0; int32_t id = -1; uint32_t nseg = 0, nev = 0;
+        uint8_t keep = 0; int32_t id = -1; uint32_t nseg = 0, nev = 0; bool trim = false;
         if (p + 4ull + bs > a.total) { if (!a.range) atomicOr(a.status, 2u); }
         else {
             const int v = lsr::validate(rec, bs, a.n_ref, a.ref_len);
@@ -168,19 +174,31 @@ __global__ void k_rec_info(RecArgs a) {
                 if (mine) ++c_total;
                 const uint32_t mapq = rec[9], n_cigar = lsr::rd16(rec + 12), flag = lsr::rd16(rec + 14);
                 uint32_t cb = 0, raw = 0, clean = 0;
-                if (!lsr::find_cb(rec, bs, &cb, &raw, &clean)) c_nf += mine;                // read.opt("CB"), SplitBamCellTypes.py:74-79
+                lsr::AuxNum nm, nh;
+                if (!lsr::scan_aux(rec, bs, &cb, &raw, &clean, &nm, &nh)) c_nf += mine;     // read.opt("CB"), SplitBamCellTypes.py:74-79
                 else if ((id = lsr::cb_lookup(a.cbt, rec + cb, clean)) < 0) c_nm += mine;   // DICT[barcode], :83-90
                 else {
-                    const bool low = (int)mapq < a.min_mapq;                                 // report only: the store's load filter / the counts re-apply min_mq
-                    if (low) c_low += mine; else c_pass += mine;
-                    if (mine && (int64_t)id < a.n_tally) atomicAdd(low ? &a.cb_low[id] : &a.cb_pass[id], 1ull);
+                    // the final filters (:92-116): MAPQ is report only here (the store's load filter / the counts re-apply min_mq); a read that
+                    // fails nM or NH is never written to a cell type's BAM: it loses its barcode (id = -1) and is stored only as an unlisted read
+                    if (a.max_nm >= 0 && nm.kind == lsr::AUX_BAD) atomicMin(a.err, (i << 3) | LOAD_ERR_NM_TYPE);
+                    else if (a.max_nh >= 0 && nh.kind == lsr::AUX_BAD) atomicMin(a.err, (i << 3) | LOAD_ERR_NH_TYPE);
+                    const uint32_t r = lsr::reason_of(nm, nh, a.max_nm, a.max_nh, (int)mapq < a.min_mapq);
+                    if (r == 0) c_pass += mine; else if (r == 1) c_low += mine;
+                    if (mine && r <= 1 && (int64_t)id < a.n_tally) atomicAdd(r ? &a.cb_low[id] : &a.cb_pass[id], 1ull);
+                    if (mine) reason = r;
+                    if (r >= 2) id = -1;
+                    else if (r == 0 && a.n_trim > 0) {                                       // --n_trim (:129-173): only a passing read is trimmed
+                        const int tc = lsr::trim_check(rec, lsr::trim_window(rec, (uint32_t)a.n_trim));
+                        if (tc != lsr::TRIM_OK) atomicMin(a.err, (i << 3) | (tc == lsr::TRIM_TOO_LONG ? LOAD_ERR_TRIM_LONG : LOAD_ERR_NO_QUAL));
+                        trim = true;
+                    }
                 }
                 // (a read without a listed barcode stays, with cb = -1, when lsg_set_keep_unlisted asks: the pool of the genotyping pileup)
                 if (id >= 0 || a.keep_unlisted) {
                     if (!(flag & 0x4) && n_cigar) {
                         const lsr::Shape sh = lsr::walk<false>(rec, a.legacy, 0, 1, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, a.phased != 0);
                         if (sh.n_events >= (1ull << 31)) atomicOr(a.status, 16u);
-                        else { keep = (uint8_t)(1u | (id >= 0 && clean < raw ? 2u : 0u)); nseg = sh.n_segs; nev = (uint32_t)sh.n_events; }
+                        else { keep = (uint8_t)(1u | (id >= 0 && clean < raw ? 2u : 0u) | (trim ? 4u : 0u)); nseg = sh.n_segs; nev = (uint32_t)sh.n_events; }
                     }
                 }
             }
@@ -200,13 +218,23 @@ __global__ void k_rec_info(RecArgs a) {
         if (c_nm) atomicAdd(&a.counters[3], c_nm);
         if (c_low) atomicAdd(&a.counters[4], c_low);
     }
+    // the filter reasons: per wave a ballot per reason, then one atomic for its count and one for its first ordinal (the lowest set lane is
+    // the wave's smallest record index: the host orders the report's columns by it, SplitBamCellTypes.py:114-116 inserts them in file order)
+    const uint64_t wave0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u);
+    for (uint32_t r = 0; r < lsr::N_REASONS; ++r) {
+        const unsigned long long m = __ballot(reason == r);
+        if (m && (threadIdx.x & 63) == 0) {
+            atomicAdd(&a.rsn_n[r], (unsigned long long)__popcll(m));
+            atomicMin(&a.rsn_first[r], (unsigned long long)(wave0 + (uint64_t)(__ffsll((long long)m) - 1)));
+        }
+    }
 }
 
 struct KeepFlag { const uint8_t* k; __host__ __device__ uint32_t operator()(const uint32_t& i) const { return k[i] & 1u; } };
 struct Widen { const uint32_t* v; __host__ __device__ unsigned long long operator()(const uint32_t& i) const { return (unsigned long long)v[i]; } };
 
 struct EmitArgs {
-    const uint8_t* u; const uint64_t* rec_off; uint64_t n_rec; int32_t legacy, phased;
+    const uint8_t* u; const uint64_t* rec_off; uint64_t n_rec; int32_t legacy, phased, n_trim;
     const uint8_t* keep; const int32_t* cb; const uint32_t* ridx; const uint32_t* soff; const unsigned long long* eoff;
     int32_t* read_tid; int32_t* read_pos; uint16_t* read_flag; uint8_t* read_mapq; int32_t* read_cb;
     uint32_t* seg_read; int32_t* seg_start; int32_t* seg_len; int64_t* seg_ev_off; uint16_t* events;
@@ -226,7 +254,8 @@ __global__ __launch_bounds__(256) void k_rec_emit(EmitArgs a) {
             a.read_flag[r] = (uint16_t)((flag & 0x0fffu) | ((k & 2u) ? LSG_FLAG_CB_SUFFIX : 0u)); a.read_mapq[r] = rec[9]; a.read_cb[r] = a.cb[i];
         }
         const uint32_t s0 = a.soff[i];
-        (void)lsr::walk<true>(rec, a.legacy, lane, 64u, r, a.seg_read + s0, a.seg_start + s0, a.seg_len + s0, a.seg_ev_off + s0, (int64_t)a.eoff[i], a.events, a.phased != 0);
+        (void)lsr::walk<true>(rec, a.legacy, lane, 64u, r, a.seg_read + s0, a.seg_start + s0, a.seg_len + s0, a.seg_ev_off + s0, (int64_t)a.eoff[i], a.events, a.phased != 0,
+                                (k & 4u) ? (uint32_t)a.n_trim : 0u);
     }
 }
 
@@ -275,14 +304,16 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     const int64_t n_tally = cbt.n_tally;
     // ---- device buffers
     DevBuf d_comp, d_u, d_blk, d_in, d_land, d_nrec, d_base, d_status, d_recoff, d_keep, d_cb, d_nseg, d_nev, d_ridx, d_soff, d_eoff, d_cnt, d_tpass, d_tlow, d_tmp;
-    DevBuf d_h, d_id, d_so, d_sl, d_str;
+    DevBuf d_h, d_id, d_so, d_sl, d_str, d_rsn;
+    for (int r = 0; r < lsr::N_REASONS; ++r) { c->split_n[r] = 0; c->split_first[r] = -1; }
     auto done = [&](int rc) {
         for (DevBuf* b : {&d_comp, &d_u, &d_blk, &d_in, &d_land, &d_nrec, &d_base, &d_status, &d_recoff, &d_keep, &d_cb, &d_nseg, &d_nev, &d_ridx, &d_soff, &d_eoff, &d_cnt, &d_tpass,
-                          &d_tlow, &d_tmp, &d_h, &d_id, &d_so, &d_sl, &d_str}) b->release();
+                          &d_tlow, &d_tmp, &d_h, &d_id, &d_so, &d_sl, &d_str, &d_rsn}) b->release();
         return rc;
     };
     if (d_comp.reserve((size_t)n_bytes + 16) || d_u.reserve((size_t)utotal + 64) || d_blk.reserve((size_t)n_blk * sizeof(IngBlk) + 16) || d_in.reserve(((size_t)n_blk + 1) * 8) ||
         d_land.reserve(((size_t)n_blk + 1) * 8) || d_nrec.reserve(((size_t)n_blk + 2) * 4) || d_base.reserve(((size_t)n_blk + 2) * 4) || d_status.reserve(64) || d_cnt.reserve(64) ||
+        d_rsn.reserve((2 * lsr::N_REASONS + 2) * 8) ||
         d_tpass.reserve(((size_t)n_tally + 1) * 8) || d_tlow.reserve(((size_t)n_tally + 1) * 8) ||
         d_h.reserve(cbt.hash.size() * 8) || d_id.reserve(cbt.id.size() * 4) || d_so.reserve(cbt.str_off.size() * 4) || d_sl.reserve(cbt.str_len.size() * 4) || d_str.reserve(cbt.strs.size() + 16))
         return done(-1);
@@ -319,6 +350,8 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     ING_HIP(hipMemsetAsync(d_status.p, 0, 64, st));
     ING_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status.as<uint32_t>() + 1), (int)0x7fffffff, 2, st));
     ING_HIP(hipMemsetAsync(d_cnt.p, 0, 64, st));
+    ING_HIP(hipMemsetAsync(d_rsn.p, 0, lsr::N_REASONS * 8, st));                                    // reason counts 0, first ordinals and the error ~0
+    ING_HIP(hipMemsetAsync(d_rsn.as<unsigned long long>() + lsr::N_REASONS, 0xff, (lsr::N_REASONS + 1) * 8, st));
     ING_HIP(hipMemsetAsync(d_tpass.p, 0, ((size_t)n_tally + 1) * 8, st));
     ING_HIP(hipMemsetAsync(d_tlow.p, 0, ((size_t)n_tally + 1) * 8, st));
     ING_HIP(hipEventRecord(ev[1], st));
@@ -417,10 +450,31 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
         ra.counters = d_cnt.as<unsigned long long>(); ra.cb_pass = d_tpass.as<unsigned long long>(); ra.cb_low = d_tlow.as<unsigned long long>(); ra.n_tally = n_tally;
         ra.status = status;
         ra.range = range; ra.count_lo = count_lo; ra.count_hi = count_hi; ra.last_key = d_cnt.as<unsigned long long>() + 6;
+        ra.max_nm = c->split_max_nm; ra.max_nh = c->split_max_nh; ra.n_trim = c->split_n_trim;
+        ra.rsn_n = d_rsn.as<unsigned long long>(); ra.rsn_first = ra.rsn_n + lsr::N_REASONS; ra.err = ra.rsn_n + 2 * lsr::N_REASONS;
         ING_HIP(hipMemsetAsync(status, 0, 4, st));
         hipLaunchKernelGGL(k_rec_info, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, ra);
         ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
+        unsigned long long herr = ~0ull;
+        ING_HIP(hipMemcpyAsync(&herr, ra.err, 8, hipMemcpyDeviceToHost, st));
         ING_HIP(hipStreamSynchronize(st));
+        if (!hstat[0] && herr != ~0ull) {                  // a read the reference's split_bam raises on (SplitBamCellTypes.py:98-109,161-168): named, not crashed on
+            const uint64_t ord = herr >> 3; const unsigned kind = (unsigned)(herr & 7u);
+            uint64_t roff = 0; uint8_t head[32 + 256];
+            ING_HIP(hipMemcpyAsync(&roff, d_recoff.as<uint64_t>() + ord, 8, hipMemcpyDeviceToHost, st));
+            ING_HIP(hipStreamSynchronize(st));
+            const size_t n_head = (size_t)(utotal - (roff + 4)) < sizeof(head) ? (size_t)(utotal - (roff + 4)) : sizeof(head);
+            ING_HIP(hipMemcpyAsync(head, u + roff + 4, n_head, hipMemcpyDeviceToHost, st));
+            ING_HIP(hipStreamSynchronize(st));
+            const uint32_t l_name = head[8];                 // validated: the name lies inside the record
+            char name[256]; const size_t ln = l_name ? l_name - 1u : 0u;      // (<= 254: l_name is a byte)
+            memcpy(name, head + 32, ln); name[ln] = 0;
+            static const char* what[] = {"", "its --n_trim window is longer than the read (the reference raises IndexError)",
+                                         "it has no base qualities to trim (the reference raises TypeError)",
+                                         "its nM tag is not a number (the reference raises TypeError)", "its NH tag is not a number (the reference raises TypeError)"};
+            set_error("lsg_load_bam: read '%s' (record %llu of the load): %s", name, (unsigned long long)ord, what[kind < 5 ? kind : 0]);
+            return done_ev(-1);
+        }
         if (hstat[0]) {
             static const char* why[] = {"", "a record shorter than its fixed fields", "a record whose fields exceed its block_size", "a record on a reference the header does not list",
                                         "a CIGAR operation above 8", "a CIGAR that does not cover the stored sequence", "an alignment that leaves its reference"};
@@ -467,7 +521,7 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     if (phased && E) ING_HIP(hipMemsetAsync(o_events.p, 0, (size_t)E * 2, st));      // (the gaps between the segments hold 0)
     if (R) {
         EmitArgs ea{};
-        ea.u = u; ea.rec_off = d_recoff.as<uint64_t>(); ea.n_rec = n_rec; ea.legacy = legacy_del_merge ? 1 : 0; ea.phased = phased;
+        ea.u = u; ea.rec_off = d_recoff.as<uint64_t>(); ea.n_rec = n_rec; ea.legacy = legacy_del_merge ? 1 : 0; ea.phased = phased; ea.n_trim = c->split_n_trim;
         ea.keep = d_keep.as<uint8_t>(); ea.cb = d_cb.as<int32_t>(); ea.ridx = d_ridx.as<uint32_t>(); ea.soff = d_soff.as<uint32_t>(); ea.eoff = d_eoff.as<unsigned long long>();
         ea.read_tid = o_tid.as<int32_t>(); ea.read_pos = o_pos.as<int32_t>(); ea.read_flag = o_flag.as<uint16_t>(); ea.read_mapq = o_mapq.as<uint8_t>(); ea.read_cb = o_cb.as<int32_t>();
         ea.seg_read = o_sread.as<uint32_t>(); ea.seg_start = o_sstart.as<int32_t>(); ea.seg_len = o_slen.as<int32_t>(); ea.seg_ev_off = o_sevoff.as<int64_t>(); ea.events = o_events.as<uint16_t>();
@@ -478,6 +532,8 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     ING_HIP(hipEventRecord(ev[4], st));
     unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     ING_HIP(hipMemcpyAsync(cnt, d_cnt.p, 56, hipMemcpyDeviceToHost, st));
+    unsigned long long rsn[2 * lsr::N_REASONS];
+    ING_HIP(hipMemcpyAsync(rsn, d_rsn.p, sizeof(rsn), hipMemcpyDeviceToHost, st));
     if (cb_pass_out && cb_low_out) {
         const int64_t n_copy = n_tally < n_tally_out ? n_tally : n_tally_out;
         for (int64_t i = 0; i < n_tally_out; ++i) { cb_pass_out[i] = 0; cb_low_out[i] = 0; }
@@ -508,6 +564,7 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     info->ms_store = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_store).count();
     info->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_all).count();
     info->last_key = n_rec ? (int64_t)cnt[6] : -1;
+    for (int r = 0; r < lsr::N_REASONS; ++r) { c->split_n[r] = (int64_t)rsn[r]; c->split_first[r] = rsn[lsr::N_REASONS + r] == ~0ull ? -1 : (int64_t)rsn[lsr::N_REASONS + r]; }
     return done_ev(0);
 #undef ING_HIP
 }

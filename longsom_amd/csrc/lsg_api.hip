@@ -250,6 +250,19 @@ int lsg_set_keep_unlisted(lsg_ctx* c, int32_t on) {
     return 0;
 }
 
+int lsg_set_split_filters(lsg_ctx* c, int32_t max_nm, int32_t max_nh, int32_t n_trim) {
+    if (!c) { set_error("lsg_set_split_filters: NULL handle"); return -2; }
+    if (n_trim < 0) { set_error("lsg_set_split_filters: n_trim %d < 0", (int)n_trim); return -2; }
+    c->split_max_nm = max_nm < 0 ? -1 : max_nm; c->split_max_nh = max_nh < 0 ? -1 : max_nh; c->split_n_trim = n_trim;
+    return 0;
+}
+
+int lsg_get_split_reasons(lsg_ctx* c, int64_t* n, int64_t* first_ordinal) {
+    if (!c || !n || !first_ordinal) { set_error("lsg_get_split_reasons: bad arguments"); return -2; }
+    for (int r = 0; r < 18; ++r) { n[r] = c->split_n[r]; first_ordinal[r] = c->split_first[r]; }
+    return 0;
+}
+
 int lsg_set_store_policy(lsg_ctx* c, int32_t policy) {
     if (!c) { set_error("lsg_set_store_policy: NULL handle"); return -2; }
     if (policy != LSG_STORE_KEEP && policy != LSG_STORE_SKIP_WHEN_COUNTED) { set_error("lsg_set_store_policy: unknown policy %d", (int)policy); return -2; }

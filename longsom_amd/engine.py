@@ -92,7 +92,8 @@ class Engine:
         self.n_contigs = 0
         self.contig_len = None
         self.pileup_window = 50000
-        self._load_settings = {"load_filter": (0, 0, 0), "count_at_load": None, "store_policy": 0, "keep_unlisted": False}      # the library's defaults
+        self._load_settings = {"load_filter": (0, 0, 0), "count_at_load": None, "store_policy": 0, "keep_unlisted": False,      # the library's defaults
+                               "split_filters": (-1, -1, 0)}
         if stream is not None:
             self.set_stream(stream)
         if keep_reads:
@@ -131,6 +132,20 @@ class Engine:
         _lib.check(self._lib.lsg_set_keep_unlisted(self._h, 1 if on else 0), "lsg_set_keep_unlisted")
         self._load_settings["keep_unlisted"] = bool(on)
 
+    def set_split_filters(self, filters=None):
+        """SplitBam's --max_nM / --max_NH / --n_trim (a hostio.SplitFilters; None: off) for the BAM loads that follow: a read with an nM / NH
+        reason is never counted, a passing read's trim window is stored with quality 0 (lsg_set_split_filters)."""
+        args = (-1, -1, 0) if filters is None else tuple(filters.args())
+        _lib.check(self._lib.lsg_set_split_filters(self._h, *[int(x) for x in args]), "lsg_set_split_filters")
+        self._load_settings["split_filters"] = args
+
+    def split_reasons(self):
+        """(n[18], first_ordinal[18]) of the last BAM load: records per filter reason and the smallest record ordinal of each (-1: none);
+        hostio.split_report turns them into the report's columns (lsg_get_split_reasons)."""
+        n = np.zeros(18, np.int64); first = np.zeros(18, np.int64)
+        _lib.check(self._lib.lsg_get_split_reasons(self._h, _ptr(n), _ptr(first)), "lsg_get_split_reasons")
+        return n, first
+
     STORE_KEEP, STORE_SKIP_WHEN_COUNTED = 0, 1
 
     def set_store_policy(self, policy: int):
@@ -151,6 +166,9 @@ class Engine:
         self.set_count_at_load(saved["count_at_load"])
         self.set_store_policy(saved["store_policy"])
         self.set_keep_unlisted(saved["keep_unlisted"])
+        if "split_filters" in saved:
+            _lib.check(self._lib.lsg_set_split_filters(self._h, *[int(x) for x in saved["split_filters"]]), "lsg_set_split_filters")
+            self._load_settings["split_filters"] = tuple(saved["split_filters"])
 
     def unload_reads(self):
         """give the device memory of the resident load (reads, store, rows, call records, cached temporaries) back: lsg_unload_reads"""

@@ -2,7 +2,8 @@
 barcodes.tsv -> barcode table, synthetic BAM / FASTA writer.
 
   read_barcodes   <- meta_to_dict   workflow/scripts/PreProcessing/SplitBamCellTypes.py:16-36
-  decode_bam      <- split_bam's record loop (:65-124) + the CIGAR walk of pysam's pileup
+  decode_bam      <- split_bam's record loop (:65-173: filters, --n_trim) + the CIGAR walk of pysam's pileup
+  split_report    <- split_bam's FILTER_dict and report (:62,114-124,181-187)
 """
 import ctypes as C
 import os
@@ -29,7 +30,71 @@ class Decoded(C.Structure):
         ("mapq_filtered", C.c_int64),
         ("n_barcodes", C.c_int32), ("barcodes", C.c_char_p),
         ("n_tally", C.c_int64), ("cb_pass", C.c_void_p), ("cb_low", C.c_void_p),
+        ("split_n", C.c_int64 * 18), ("split_first", C.c_int64 * 18),
     ]
+
+
+N_REASONS = 18
+
+
+def _reason_key(r: int) -> Optional[str]:
+    nm, rest = divmod(r, 6)
+    nh, mq = divmod(rest, 2)
+    parts = [p for p in (("", "nM", "nM_not_found")[nm], ("", "NH", "NH_not_found")[nh], "MAPQ" if mq else "") if p]
+    return ";".join(parts) or None
+
+
+# the report key of filter reason r = nm * 6 + nh * 2 + mapq (lsg_get_split_reasons): ';'.join(FILTER), SplitBamCellTypes.py:92-116
+REASON_KEYS = [_reason_key(r) for r in range(N_REASONS)]
+
+
+@dataclass(frozen=True)
+class SplitFilters:
+    """SplitBamCellTypes' --max_nM / --max_NH / --n_trim (SplitBamCellTypes.py:92-173, flags :199-202); the defaults are the reference's
+    (off).  A read whose cleaned CB is listed and that has nM > max_nM or no nM tag (NH likewise) goes to no cell type's BAM: it is never
+    counted.  A passing read's qualities are set to 0 at its ends (n_trim bases, or its soft clip + n_trim, 30 + n_trim for a clip of
+    20-29 bases) before the pileup sees it."""
+    max_nM: Optional[int] = None
+    max_NH: Optional[int] = None
+    n_trim: int = 0
+
+    def __post_init__(self):
+        for name in ("max_nM", "max_NH"):
+            v = getattr(self, name)
+            if v is not None and int(v) < 0:
+                raise ValueError("--%s %d: a limit below 0 is not supported" % (name, int(v)))
+
+    @property
+    def off(self) -> bool:
+        return self.max_nM is None and self.max_NH is None and int(self.n_trim) <= 0
+
+    def args(self):
+        """(max_nm, max_nh, n_trim) as the C entry points take them: -1 = off (lsg_set_split_filters)"""
+        return (-1 if self.max_nM is None else int(self.max_nM), -1 if self.max_NH is None else int(self.max_NH), max(0, int(self.n_trim)))
+
+
+def split_report(counters, reasons=None) -> Dict[str, int]:
+    """SplitBamCellTypes' report (FILTER_dict, :62,114-124): Total_reads, Pass_reads, CB_not_found, CB_not_matched, then one column per
+    filter reason in the order in which the file first produced it.  counters = (total, pass, cb_not_found, cb_not_matched, mapq);
+    reasons: None (no reason arrays: MAPQ from counters[4], the only reason there is without --max_nM / --max_NH) or, per load in load order
+    (the ranks' regions, the windows: file order), its (n[18], first_ordinal[18]) - a reason's column goes where (load, ordinal) of its first
+    record puts it."""
+    c = [int(x) for x in counters]
+    rep = {"Total_reads": c[0], "Pass_reads": c[1], "CB_not_found": c[2], "CB_not_matched": c[3]}
+    if reasons is None:
+        if c[4]:
+            rep["MAPQ"] = c[4]
+        return rep
+    total = [0] * N_REASONS
+    first: Dict[int, tuple] = {}
+    for load, (n, f) in enumerate(reasons):
+        for r in range(1, N_REASONS):
+            if int(n[r]) > 0:
+                total[r] += int(n[r])
+                first.setdefault(r, (load, int(f[r])))
+    for r in sorted(first, key=first.get):
+        rep[REASON_KEYS[r]] = total[r]
+    return rep
 
 
 def load():
@@ -54,6 +119,14 @@ def load():
         lib.lsio_barcode.argtypes = [C.c_uint64, C.c_int64, C.c_char_p]
         lib.lsio_split_bam.restype = C.c_int
         lib.lsio_split_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p]
+        lib.lsio_split_bam_filtered.restype = C.c_int
+        lib.lsio_split_bam_filtered.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        lib.lsio_decode_bam_filtered.restype = C.c_int
+        lib.lsio_decode_bam_filtered.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.POINTER(C.POINTER(Decoded))]
+        lib.lsio_stream_set_split_filters.restype = C.c_int
+        lib.lsio_stream_set_split_filters.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         lib.lsio_build_bai.restype = C.c_int
         lib.lsio_build_bai.argtypes = [C.c_char_p, C.c_char_p]
         lib.lsio_set_legacy_del_merge.argtypes = [C.c_int]
@@ -149,10 +222,11 @@ class DecodedBam:
     records: ReadRecords
     contig_names: List[str]
     contig_len: np.ndarray
-    report: Dict[str, int]         # the counters of SplitBamCellTypes' report.txt (:62,117-124)
+    report: Dict[str, int]         # the counters of SplitBamCellTypes' report.txt (:62,114-124), columns in first-seen order (split_report)
     barcodes: Optional[List[str]] = None   # auto-barcode mode: the distinct cleaned CBs found (dense id = index)
     cb_pass: Optional[np.ndarray] = None   # listed-barcode mode: per barcode id, matched reads with MAPQ >= min_mapq ...
     cb_low: Optional[np.ndarray] = None    # ... and below it (for the report of a re-annotated barcode table)
+    reasons: Optional[tuple] = None        # the batch's SplitBam filter reasons: (n[18], first_ordinal[18]) as lsg_get_split_reasons returns them
 
     def report_for(self, keep: np.ndarray) -> Dict[str, int]:
         """SplitBamCellTypes' report had the barcode table listed only the barcodes where `keep` is set (re-annotation pass 2)."""
@@ -172,12 +246,10 @@ def _wrap(lib, out, barcodes) -> DecodedBam:
     rec = _take(d, owner)
     names = d.contig_names.decode().split("\n")[: d.n_contigs] if d.n_contigs else []
     lens = np.ctypeslib.as_array(C.cast(d.contig_len, C.POINTER(C.c_int64)), shape=(d.n_contigs,)).copy() if d.n_contigs else np.zeros(0, np.int64)
-    rep = {"Total_reads": d.total_reads, "Pass_reads": d.pass_reads, "CB_not_found": d.cb_not_found, "CB_not_matched": d.cb_not_matched}
-    if d.mapq_filtered:
-        rep["MAPQ"] = d.mapq_filtered
+    rep = split_report((d.total_reads, d.pass_reads, d.cb_not_found, d.cb_not_matched, d.mapq_filtered), [(list(d.split_n), list(d.split_first))])
     found = d.barcodes.decode().split("\n")[: d.n_barcodes] if barcodes is None else None
     tally = lambda ptr: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int64)), shape=(len(barcodes),)).copy() if barcodes is not None and d.n_tally >= len(barcodes) and len(barcodes) else None
-    return DecodedBam(rec, names, lens, rep, found, tally(d.cb_pass), tally(d.cb_low))
+    return DecodedBam(rec, names, lens, rep, found, tally(d.cb_pass), tally(d.cb_low), (np.asarray(d.split_n, np.int64), np.asarray(d.split_first, np.int64)))
 
 
 def bam_header(path: str):
@@ -227,17 +299,21 @@ def bam_header(path: str):
     return names, np.asarray(lens, np.int64), p
 
 
-def stream_bam(path: str, barcodes: Optional[Sequence[str]], min_mapq: int = 60, threads: int = 0, batch_bytes: int = 1 << 30):
+def stream_bam(path: str, barcodes: Optional[Sequence[str]], min_mapq: int = 60, threads: int = 0, batch_bytes: int = 1 << 30,
+               filters: Optional[SplitFilters] = None):
     """The BAM in file order, a batch at a time (about batch_bytes of uncompressed BAM each): yields DecodedBam objects whose
     records, counters and per-barcode tallies cover one batch.  The compressed file is mapped, a batch is inflated and decoded by
     `threads` host threads while the caller works on the previous one (the ctypes call releases the GIL).  This is the reference's
-    window-by-window reading (BaseCellCounter.py:81-113,190-191) without an index: file order is coordinate order."""
+    window-by-window reading (BaseCellCounter.py:81-113,190-191) without an index: file order is coordinate order.  filters: SplitBam's
+    --max_nM / --max_NH / --n_trim (SplitFilters); every batch's report counts its own records."""
     lib = load()
     h = C.c_void_p()
     joined = None if barcodes is None else "\n".join(barcodes).encode()
     if lib.lsio_stream_open(os.fsencode(path), joined, -1 if barcodes is None else len(barcodes), None, int(min_mapq), int(threads), C.byref(h)) != 0:
         _err("lsio_stream_open")
     try:
+        if filters is not None and lib.lsio_stream_set_split_filters(h, *filters.args()) != 0:
+            _err("lsio_stream_set_split_filters")
         while True:
             out = C.POINTER(Decoded)()
             rc = lib.lsio_stream_next(h, int(batch_bytes), C.byref(out))
@@ -265,35 +341,37 @@ def concat_records(parts: Sequence[ReadRecords]) -> ReadRecords:
                        np.concatenate([p.seg_ev_off + e0[i] for i, p in enumerate(parts)]), cat("events"))
 
 
-def decode_bam(path: str, barcodes: Optional[Sequence[str]], min_mapq: int = 60, threads: int = 0) -> DecodedBam:
+def decode_bam(path: str, barcodes: Optional[Sequence[str]], min_mapq: int = 60, threads: int = 0, filters: Optional[SplitFilters] = None) -> DecodedBam:
     """BAM -> read-record arrays.  Reads without a CB tag or whose cleaned CB is not in `barcodes` are dropped
     (they can never be counted); flags and MAPQ are kept for the device-side admission.  barcodes=None: every
-    distinct cleaned CB of the file is a cell (how BaseCellCounter sees a per-cell-type BAM)."""
+    distinct cleaned CB of the file is a cell (how BaseCellCounter sees a per-cell-type BAM).  filters: SplitBam's --max_nM / --max_NH /
+    --n_trim (SplitFilters): a read they refuse is dropped like an unlisted one, a passing read's trimmed qualities are 0 in its events;
+    a read the reference raises on raises RuntimeError naming it."""
     lib = load()
     out = C.POINTER(Decoded)()
+    fa = (filters or SplitFilters()).args()
     if barcodes is None:
-        rc = lib.lsio_decode_bam(os.fsencode(path), None, -1, None, int(min_mapq), int(threads), C.byref(out))
+        rc = lib.lsio_decode_bam_filtered(os.fsencode(path), None, -1, None, int(min_mapq), *fa, int(threads), C.byref(out))
     else:
         joined = "\n".join(barcodes).encode()
-        rc = lib.lsio_decode_bam(os.fsencode(path), joined, len(barcodes), None, int(min_mapq), int(threads), C.byref(out))
+        rc = lib.lsio_decode_bam_filtered(os.fsencode(path), joined, len(barcodes), None, int(min_mapq), *fa, int(threads), C.byref(out))
     if rc != 0:
         _err("lsio_decode_bam")
     return _wrap(lib, out, barcodes)
 
 
-def split_bam(path: str, table: "BarcodeTable", out_paths: Sequence[str], min_mapq: int = 60) -> Dict[str, int]:
-    """SplitBamCellTypes' BAM outputs: one BAM per cell type (out_paths in table.celltype_names order); returns the
-    report counters."""
+def split_bam(path: str, table: "BarcodeTable", out_paths: Sequence[str], min_mapq: int = 60, filters: Optional[SplitFilters] = None) -> Dict[str, int]:
+    """SplitBamCellTypes' BAM outputs: one BAM per cell type (out_paths in table.celltype_names order), under SplitBam's --max_nM /
+    --max_NH / --n_trim (filters; trimmed qualities are written as 0); returns the report counters."""
     lib = load()
     ct = np.ascontiguousarray(table.celltype_of, np.uint8)
     cnt = (C.c_int64 * 5)()
-    if lib.lsio_split_bam(os.fsencode(path), "\n".join(table.barcodes).encode(), len(table.barcodes), ct.ctypes.data_as(C.c_void_p),
-                          len(table.celltype_names), "\n".join(out_paths).encode(), int(min_mapq), cnt) != 0:
+    rn, rf = (C.c_int64 * N_REASONS)(), (C.c_int64 * N_REASONS)()
+    if lib.lsio_split_bam_filtered(os.fsencode(path), "\n".join(table.barcodes).encode(), len(table.barcodes), ct.ctypes.data_as(C.c_void_p),
+                                   len(table.celltype_names), "\n".join(out_paths).encode(), int(min_mapq), cnt,
+                                   *(filters or SplitFilters()).args(), rn, rf) != 0:
         _err("lsio_split_bam")
-    rep = {"Total_reads": cnt[0], "Pass_reads": cnt[1], "CB_not_found": cnt[2], "CB_not_matched": cnt[3]}
-    if cnt[4]:
-        rep["MAPQ"] = cnt[4]
-    return rep
+    return split_report(cnt, [(list(rn), list(rf))])
 
 
 def synth_barcodes(model) -> List[str]:

@@ -111,11 +111,15 @@ class Resident:
     seconds: Dict[str, float]
 
 
+SplitFilters = hostio.SplitFilters
+REPORT_KEYS = ("total_reads", "pass_reads", "cb_not_found", "cb_not_matched", "mapq_filtered")      # lsg_bam_info's SplitBam counters, split_report's order
+
 PILEUP_MAX_DEPTH = 200000   # bam.pileup(..., max_depth = 200000), BaseCellCounter.py:191 / HCCVSingleCellGenotype.py:122
 
 
 def load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, min_mapq: int, allow_depth_overflow: Optional[bool] = None,
-                ingest: Optional[str] = None, count_params: Optional[CountParams] = None, keep_store: bool = True, keep_unlisted: bool = False) -> Resident:
+                ingest: Optional[str] = None, count_params: Optional[CountParams] = None, keep_store: bool = True, keep_unlisted: bool = False,
+                filters: Optional[SplitFilters] = None) -> Resident:
     """count_params: the parameters of the count that follows, when the caller knows them (every fused rule does): the load then makes
     that count in the pass that builds the store (Engine.set_count_at_load) and the first pileup_count under them costs nothing.
     keep_store=False (with count_params): that count is the only one the caller will ask for - the load writes no tile store
@@ -124,12 +128,16 @@ def load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, min
     holds them in its max_depth buffer (HCCVSingleCellGenotype.py:121-122); the chains that genotype pass True.
     ingest: "device" = the BAM's bytes go to the GPU and are inflated, decoded and laid out there (lsg_load_bam); "host" = the host
     decoder (liblongsom_io) + lsg_load_reads; "auto" (default, or LONGSOM_INGEST) = device, and host for a BAM whose records are not
-    aligned to its BGZF blocks (not written by htslib).  Same store, same report either way (tests/test_ingest_gpu.py)."""
+    aligned to its BGZF blocks (not written by htslib).  Same store, same report either way (tests/test_ingest_gpu.py).
+    filters: SplitBam's --max_nM / --max_NH / --n_trim (SplitFilters; None = off) - the reads they refuse are never counted, trimmed
+    qualities are 0, the report gains their columns (SplitBamCellTypes.py:92-173)."""
     ingest = ingest or os.environ.get("LONGSOM_INGEST", "auto")
     saved = engine.load_settings()                 # (a caller's own engine keeps the load filter / store policy it came with)
     engine.set_count_at_load(count_params)
     engine.set_store_policy(engine.STORE_KEEP if keep_store or count_params is None else engine.STORE_SKIP_WHEN_COUNTED)
     engine.set_keep_unlisted(keep_unlisted)
+    if filters is not None:
+        engine.set_split_filters(filters)
     old_keep = hostio.set_keep_unlisted(keep_unlisted)
     # a BAM that is counted once under known parameters: the reads that count's own filters would refuse are not stored at all (what
     # SplitBamCellTypes.py:110-113 does to the BAM a rule counts) - every stored read is then admitted, and the load sorts keys alone
@@ -137,13 +145,13 @@ def load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, min
     if once:
         engine.set_load_filter(count_params.min_mq, count_params.flag_exclude, count_params.ignore_orphans)
     try:
-        return _load_sample(bam, barcodes_tsv, ref_fasta, engine, min_mapq, ingest)
+        return _load_sample(bam, barcodes_tsv, ref_fasta, engine, min_mapq, ingest, filters)
     finally:
         engine.restore_load_settings(saved)
         hostio.set_keep_unlisted(old_keep)
 
 
-def _load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, min_mapq: int, ingest: str) -> Resident:
+def _load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, min_mapq: int, ingest: str, filters: Optional[SplitFilters] = None) -> Resident:
     t = {}
     t0 = time.time()
     bc = hostio.read_barcodes(barcodes_tsv)
@@ -170,10 +178,7 @@ def _load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, mi
                 raise
             info = None
         if info is not None:
-            rep = {"Total_reads": int(info["total_reads"]), "Pass_reads": int(info["pass_reads"]), "CB_not_found": int(info["cb_not_found"]),
-                   "CB_not_matched": int(info["cb_not_matched"])}
-            if info["mapq_filtered"]:
-                rep["MAPQ"] = int(info["mapq_filtered"])
+            rep = hostio.split_report([info[k] for k in REPORT_KEYS], [engine.split_reasons()])
             dec = hostio.DecodedBam(None, names, np.asarray(lens, np.int64), rep, None, cb_pass, cb_low)
             t["decode"] = time.time() - t0                 # device ingest: H2D + inflate + decode + store build (info has the phases)
             t["load"] = 0.0
@@ -182,7 +187,7 @@ def _load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, mi
                     t["ingest_" + k[3:]] = float(v) / 1e3
             return Resident(engine, dec, bc, names, t)
         t0 = time.time()
-    dec = hostio.decode_bam(bam, bc.barcodes, min_mapq=min_mapq)
+    dec = hostio.decode_bam(bam, bc.barcodes, min_mapq=min_mapq, filters=filters)
     # the pileup is driven by the FASTA's contigs (MakeWindows, BaseCellCounter.py:84-86); BAM tids index dec.contig_names
     contig_names = dec.contig_names
     for n, l in zip(contig_names, dec.contig_len):
@@ -442,10 +447,11 @@ def _chain_steps23(out, s1, t, eng, contig_names, out_dir, sample_id, params, ed
 def run_snv(bam: str, barcodes_tsv: str, ref_fasta: str, out_dir: str, sample_id: str, params: Optional[SnvParams] = None,
             editing: Optional[str] = None, pon_sr: Optional[str] = None, pon_lr: Optional[str] = None,
             gnomad_af_json: Optional[str] = None, device: int = 0, engine: Optional[Engine] = None,
-            comm: Optional["regions.Comm"] = None, window_bytes: Optional[int] = None) -> SnvOutputs:
+            comm: Optional["regions.Comm"] = None, window_bytes: Optional[int] = None, filters: Optional[SplitFilters] = None) -> SnvOutputs:
     """One sample through the whole chain.  comm (world > 1): one rank per GPU, genomic regions sharded over the ranks, call
     `regions.Comm.from_env()` before anything touches the GPU.  window_bytes: stream the BAM in batches of about that many
-    uncompressed bytes and count window by window (a BAM whose reads do not fit in HBM; decode overlaps the GPU work)."""
+    uncompressed bytes and count window by window (a BAM whose reads do not fit in HBM; decode overlaps the GPU work).  filters: SplitBam's
+    --max_nM / --max_NH / --n_trim (SplitFilters; None = off), applied by every form of the ingest."""
     params = params or SnvParams()
     comm = comm or regions.Comm()
     own = engine is None
@@ -455,9 +461,10 @@ def run_snv(bam: str, barcodes_tsv: str, ref_fasta: str, out_dir: str, sample_id
             raise ValueError("window_bytes (--window_gb) streams one process's BAM window by window; with %d ranks every rank holds its region's reads at once: "
                              "use one or the other" % comm.world)
         if comm.world > 1 or window_bytes:
-            return _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, editing, pon_sr, pon_lr, gnomad_af_json, eng, comm, window_bytes, keep_store=not own)
+            return _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, editing, pon_sr, pon_lr, gnomad_af_json, eng, comm, window_bytes, keep_store=not own,
+                                    filters=filters)
         # (the chain counts its sample once: an engine of our own keeps no store for counts nobody will ask for)
-        res = load_sample(bam, barcodes_tsv, ref_fasta, eng, params.min_mapping_quality, count_params=params.count(), keep_store=not own)
+        res = load_sample(bam, barcodes_tsv, ref_fasta, eng, params.min_mapping_quality, count_params=params.count(), keep_store=not own, filters=filters)
         return run_chain(res, res.table.celltype_of, res.table.celltype_names, res.dec.report, out_dir, sample_id, params, editing, pon_sr, pon_lr,
                          gnomad_af_json)
     finally:
@@ -523,7 +530,7 @@ def _prefetch(gen, depth: int = 1):
 
 
 def _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, editing, pon_sr, pon_lr, gnomad_af_json, eng, comm, window_bytes,
-                     step3: bool = True, resident: Optional[dict] = None, table=None, keep_store: bool = True) -> SnvOutputs:
+                     step3: bool = True, resident: Optional[dict] = None, table=None, keep_store: bool = True, filters: Optional[SplitFilters] = None) -> SnvOutputs:
     """keep_store=False: a rank's slice is counted once and nothing else is asked of its reads (run_snv): the load keeps no tile store.
     resident / table / step3 serve the sharded two-pass loop (run_reannotation with several ranks): `resident` = SnvOutputs.resident of
     an earlier call on the same engine (the rank's reads stay in HBM, nothing is ingested again), `table` = (celltype_of per barcode
@@ -574,13 +581,11 @@ def _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, e
             names_b, lens_b, first_rec = hostio.bam_header(bam)
             hdr = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), {})
             setup(hdr)
-            keys = ("total_reads", "pass_reads", "cb_not_found", "cb_not_matched", "mapq_filtered")
+            keys = REPORT_KEYS
+            R = hostio.N_REASONS
 
-            def report_of(counts):
-                rep = {"Total_reads": int(counts[0]), "Pass_reads": int(counts[1]), "CB_not_found": int(counts[2]), "CB_not_matched": int(counts[3])}
-                if counts[4]:
-                    rep["MAPQ"] = int(counts[4])
-                return rep
+            def report_of(counts, reasons):
+                return hostio.split_report(counts[:5], reasons)
             bai = hostio.find_bai(bam) if os.environ.get("LONGSOM_SHARD_INGEST", "1") != "0" else None
             if bai is not None:
                 # every rank ingests the SLICE of the file its region needs, found through the .bai's linear index (regions.BaiPlan), as the
@@ -598,11 +603,13 @@ def _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, e
                     saved = eng.load_settings()
                     cp_slice = params.count()
                     eng.set_count_at_load(cp_slice)
+                    eng.set_split_filters(filters)
                     if not keep_store:
                         eng.set_load_filter(cp_slice.min_mq, cp_slice.flag_exclude, cp_slice.ignore_orphans)
                         eng.set_store_policy(eng.STORE_SKIP_WHEN_COUNTED)
                     try:
                         got = regions.ingest_slice(eng, bam, plan, lo, hi, bc.barcodes, params.min_mapping_quality)
+                        got_reasons = eng.split_reasons() if got is not None else None
                     finally:
                         eng.restore_load_settings(saved)
                 except _lib.LsgError as e:
@@ -615,22 +622,32 @@ def _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, e
                 comm.agree(fatal, "the ingest of a rank's slice of %s" % bam)      # (every rank raises when one did: nobody waits in the all-reduce below)
                 n_cb = len(bc.barcodes)
                 if int(comm.allreduce_sum(np.asarray([ok], np.int64))[0]) == comm.world:
-                    counts = np.zeros(5 + 2 * n_cb + 2 * comm.world, np.int64)      # SplitBam's counters, the tallies, and per rank: records and bytes of its slice
+                    # SplitBam's counters, the tallies, and per rank: records and bytes of its slice, its filter reasons (counts, first ordinals)
+                    counts = np.zeros(5 + 2 * n_cb + 2 * comm.world + 2 * R * comm.world, np.int64)
+                    at_r = 5 + 2 * n_cb + 2 * comm.world
                     if got is not None:
                         info, cb_pass, cb_low = got
                         counts[:5] = [info[k] for k in keys]; counts[5:5 + n_cb] = cb_pass; counts[5 + n_cb:5 + 2 * n_cb] = cb_low
                         counts[5 + 2 * n_cb + comm.rank] = info["n_records"]; counts[5 + 2 * n_cb + comm.world + comm.rank] = info["slice_bytes"]
+                        counts[at_r + R * comm.rank:at_r + R * (comm.rank + 1)] = got_reasons[0]
+                        counts[at_r + R * (comm.world + comm.rank):at_r + R * (comm.world + comm.rank + 1)] = got_reasons[1] + 1      # (+1: 0 = none)
                     else:
                         eng.load_reads(hostio.ReadRecords.empty())      # (no alignment in this rank's region)
                     counts = comm.allreduce_sum(counts)
                     t["ingest_records_by_rank"] = counts[5 + 2 * n_cb:5 + 2 * n_cb + comm.world].tolist()
-                    t["ingest_slice_MB_by_rank"] = [round(x / 1e6, 3) for x in counts[5 + 2 * n_cb + comm.world:].tolist()]
-                    dec = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), report_of(counts), None, counts[5:5 + n_cb].copy(), counts[5 + n_cb:5 + 2 * n_cb].copy())
+                    t["ingest_slice_MB_by_rank"] = [round(x / 1e6, 3) for x in counts[5 + 2 * n_cb + comm.world:at_r].tolist()]
+                    rs = [(counts[at_r + R * q:at_r + R * (q + 1)], counts[at_r + R * (comm.world + q):at_r + R * (comm.world + q + 1)] - 1) for q in range(comm.world)]
+                    dec = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), report_of(counts, rs), None, counts[5:5 + n_cb].copy(), counts[5 + n_cb:5 + 2 * n_cb].copy())
                     mine = None
             if dec is None:
                 try:
-                    info, cb_pass, cb_low = eng.load_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, first_record_offset=first_rec)
-                    dec = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), report_of([info[k] for k in keys]), None, cb_pass, cb_low)
+                    saved = eng.load_settings()
+                    eng.set_split_filters(filters)
+                    try:
+                        info, cb_pass, cb_low = eng.load_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, first_record_offset=first_rec)
+                    finally:
+                        eng.restore_load_settings(saved)
+                    dec = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), report_of([info[k] for k in keys], [eng.split_reasons()]), None, cb_pass, cb_low)
                     bounds = regions.balanced_boundaries(eng.reads_to_host(events=False), len(names_b), comm.world)
                     lo, hi = bounds[comm.rank], bounds[comm.rank + 1]
                     mine = None                                   # the rank's store holds the whole file; lsg_set_region makes the columns its own
@@ -639,7 +656,7 @@ def _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, e
                         raise
                     dec = None
         if dec is None:
-            dec = hostio.decode_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, threads=max(1, (os.cpu_count() or 1) // comm.world))
+            dec = hostio.decode_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, threads=max(1, (os.cpu_count() or 1) // comm.world), filters=filters)
             bounds = regions.balanced_boundaries(dec.records, len(dec.contig_names), comm.world)
             lo, hi = bounds[comm.rank], bounds[comm.rank + 1]
             mine = dec.records.subset(regions.reads_overlapping(dec.records, lo, hi))
@@ -661,19 +678,22 @@ def _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, e
             for r in range(n_win):
                 lo, hi = plan.bounds[r], plan.bounds[r + 1]
                 t0 = time.time()
-                got = regions.ingest_slice(eng, bam, plan, lo, hi, bc.barcodes, params.min_mapping_quality)
+                saved = eng.load_settings()
+                eng.set_split_filters(filters)
+                try:
+                    got = regions.ingest_slice(eng, bam, plan, lo, hi, bc.barcodes, params.min_mapping_quality)
+                finally:
+                    eng.restore_load_settings(saved)
                 t["decode"] += time.time() - t0
                 if got is None:
                     continue
                 info = got[0]
-                rep = {"Total_reads": int(info["total_reads"]), "Pass_reads": int(info["pass_reads"]), "CB_not_found": int(info["cb_not_found"]),
-                       "CB_not_matched": int(info["cb_not_matched"])}
-                if info["mapq_filtered"]:
-                    rep["MAPQ"] = int(info["mapq_filtered"])
+                # (the windows' reports are summed in file order below: a reason's column lands where its first window put it)
+                rep = hostio.split_report([info[k] for k in REPORT_KEYS], [eng.split_reasons()])
                 yield lo, hi, None, hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), rep)
         work = device_windows()
     else:
-        batches = hostio.stream_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, batch_bytes=int(window_bytes))
+        batches = hostio.stream_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, batch_bytes=int(window_bytes), filters=filters)
         first = next(batches, None)
         if first is None:
             raise ValueError("%s holds no BAM records" % bam)

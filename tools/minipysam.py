@@ -61,6 +61,7 @@ class AlignedSegment:
         self.cigartuples = [(c & 0xF, c >> 4) for c in struct.unpack_from("<%dI" % n_cigar, raw, p)] if n_cigar else None
         p += 4 * n_cigar
         self._seq = raw[p:p + (self.l_seq + 1) // 2]; p += (self.l_seq + 1) // 2
+        self._qual_at = p
         self._qual = raw[p:p + self.l_seq]; p += self.l_seq
         self._tags = {}
         while p + 3 <= len(raw):
@@ -98,6 +99,21 @@ class AlignedSegment:
     is_secondary = property(lambda s: bool(s.flag & 0x100))
     is_duplicate = property(lambda s: bool(s.flag & 0x400))
     is_supplementary = property(lambda s: bool(s.flag & 0x800))
+
+    # pysam: None without SEQ or when QUAL is absent (0xff); assigning writes the qualities back into the record (what a "wb" copy emits)
+    @property
+    def query_qualities(self):
+        if self.l_seq == 0 or self._qual[0] == 0xFF:
+            return None
+        return list(self._qual)
+
+    @query_qualities.setter
+    def query_qualities(self, q):
+        q = bytes(int(x) for x in q)
+        if len(q) != self.l_seq:
+            raise ValueError("quality and sequence mismatch: %d != %d" % (len(q), self.l_seq))
+        self.raw = self.raw[:self._qual_at] + q + self.raw[self._qual_at + self.l_seq:]
+        self._qual = q
 
     def base(self, q):
         return _NT16[(self._seq[q >> 1] >> (0 if q & 1 else 4)) & 0xF]

@@ -8,6 +8,11 @@
 
 GPU_SCRIPTS = str(workflow.basedir) + "/scripts_gpu"
 
+# SplitBamCellTypes' --max_nM / --max_NH / --n_trim from the optional config['SNVCalling']['SplitBam'] (SplitBamCellTypes.py:199-202); the
+# reference's config has no such section: --max_nM= and --max_NH= render empty (off), --n_trim=0
+SPLIT_FILTERS = {k: ("" if v is None else v) for k, v in
+                 {"max_nM": None, "max_NH": None, "n_trim": 0, **(config['SNVCalling'].get('SplitBam') or {})}.items()}
+
 rule SNVCalling_gpu:
     input:
         bam=f"{INPUT}/bam/{{id}}.bam",
@@ -36,6 +41,8 @@ rule SNVCalling_gpu:
         htslib="--htslib_legacy_del_merge" if config['Run'].get('htslib_legacy_del_merge', False) else "",
         # Run.allow_missing_gnomad: True runs step 2 without its gnomAD filter when the database cannot be read (default: the rule fails, as the reference's gnomAD_DB() does)
         no_gnomad="--allow_missing_gnomad" if config['Run'].get('allow_missing_gnomad', False) else "",
+        # SNVCalling.SplitBam.max_nM / max_NH / n_trim (optional): SplitBamCellTypes' read filters; absent = off (an empty --max_nM= is off)
+        max_nm=SPLIT_FILTERS['max_nM'], max_nh=SPLIT_FILTERS['max_NH'], n_trim=SPLIT_FILTERS['n_trim'],
         # GPUs of this node used by the rule: one rank per GPU, genomic regions sharded over the ranks
         launcher=lambda wc, resources: "python" if resources.gpu == 1 else f"python -m torch.distributed.run --standalone --local-addr 127.0.0.1 --nnodes=1 --nproc-per-node {resources.gpu}",
     resources:
@@ -49,7 +56,7 @@ rule SNVCalling_gpu:
         {params.launcher} {params.script} \
         --bam {input.bam} --meta {input.barcodes} --ref {input.ref} --id {wildcards.id} --outdir SNVCalling \
         --editing {input.RNA_editing} --pon_SR {input.pon_SR} --pon_LR {input.pon_LR} --gnomAD_db {params.gnomAD_db} {params.gz_compat} {params.htslib} {params.no_gnomad} \
-        --min_mapping_quality {params.mapq} \
+        --min_mapping_quality {params.mapq} --max_nM={params.max_nm} --max_NH={params.max_nh} --n_trim={params.n_trim} \
         --min_cell_types {params.c[Min_cell_types]} --min_distance {params.c[min_distance]} \
         --max_gnomad_vaf {params.c[max_gnomAD_VAF]} --delta_vaf {params.c[deltaVAF]} --delta_mcf {params.c[deltaMCF]} \
         --min_ac_reads {params.c[min_ac_reads]} --min_ac_cells {params.c[min_ac_cells]} --clust_dist {params.c[clust_dist]} \
@@ -65,5 +72,7 @@ rule SplitBam_gpu:
     params:
         script=GPU_SCRIPTS+"/PreProcessing/SplitBamCellTypes.py",
         mapq=config['SNVCalling']['BaseCellCounter']['min_mapping_quality'],
+        max_nm=SPLIT_FILTERS['max_nM'], max_nh=SPLIT_FILTERS['max_NH'], n_trim=SPLIT_FILTERS['n_trim'],
     shell:
-        "python {params.script} --bam {input.bam} --meta {input.barcodes} --id {wildcards.id} --outdir SNVCalling/SplitBam --min_MQ {params.mapq}"
+        "python {params.script} --bam {input.bam} --meta {input.barcodes} --id {wildcards.id} --outdir SNVCalling/SplitBam --min_MQ {params.mapq} "
+        "--max_nM={params.max_nm} --max_NH={params.max_nh} --n_trim={params.n_trim}"
