@@ -186,6 +186,13 @@ def step2_bytes(step1_text: bytes, engine, contig_names: Sequence[str], editing_
     return step2(step1_text.decode(), engine, contig_names, editing_keys, pon_sr_keys, pon_lr_keys, distance, gnomad_af, gnomad_max).encode()
 
 
+def step2_head(step1_head: bytes) -> bytes:
+    """the head step 2 writes over the rows it keeps of a step-1 table with this head: the comment lines, then the (last) column header -
+    what step2_bytes returns for the head alone, with a gnomAD source or without"""
+    lines = [l for l in step1_head.split(b"\n") if l]
+    return b"\n".join([l for l in lines if b"#CHROM" not in l] + [[l for l in lines if b"#CHROM" in l][-1]]) + b"\n"
+
+
 def step2(step1_text: str, engine, contig_names: Sequence[str], editing_keys, pon_sr_keys, pon_lr_keys, distance: int = 0,
           gnomad_af: Optional[Dict[str, float]] = None, gnomad_max: float = 0.01) -> str:
     """Returns the text of <prefix>.calling.step2.tsv.  gnomad_af: {"chrom:pos:ref:alt": AF}; the gnomAD

@@ -6,6 +6,7 @@ Mirrors the stages of LongSom's SNV chain as methods:
   pileup_count   <- run_interval over all windows       (BaseCellCounter.py:182-320)
   call_step1     <- merge + variant_calling_step1       (MergeBaseCellCounts.py:116-204, BaseCellCalling.step1.py:19-476)
 """
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass, field
@@ -157,9 +158,31 @@ class Engine:
         self._load_settings["store_policy"] = int(policy)
 
     def load_settings(self) -> dict:
-        """what the next loads will do, as this wrapper last set it (load filter, count at load, store policy, unlisted reads): a caller that
-        changes them for one load puts them back with restore_load_settings"""
+        """what the next loads will do, as this wrapper last set it (load filter, count at load, store policy, unlisted reads, split filters):
+        a caller that changes them for one load puts them back with restore_load_settings (or lets `loading` do both)"""
         return dict(self._load_settings)
+
+    @contextlib.contextmanager
+    def loading(self, count=None, keep_store: bool = True, keep_unlisted: Optional[bool] = None, filters=None):
+        """The load settings of the loads made inside the `with` block; the ones they replace are put back when it ends, on an error too.
+        count: the loads also make that count (set_count_at_load; None: no count at load).  keep_store=False with a count: it is the only
+        count anybody will ask of these reads - the loads keep no tile store (STORE_SKIP_WHEN_COUNTED) and, unless they keep unlisted
+        reads, do not store what the count's own read filters refuse (set_load_filter, what SplitBamCellTypes.py:110-113 does to the BAM a
+        rule counts: every stored read is then admitted and the load sorts keys alone).  keep_unlisted: set_keep_unlisted (None: as it
+        is).  filters: set_split_filters (a hostio.SplitFilters; None: off)."""
+        saved = self.load_settings()
+        try:
+            if keep_unlisted is not None:
+                self.set_keep_unlisted(keep_unlisted)
+            self.set_split_filters(filters)
+            once = count is not None and not keep_store
+            self.set_count_at_load(count)
+            self.set_store_policy(self.STORE_SKIP_WHEN_COUNTED if once else self.STORE_KEEP)
+            if once and not self._load_settings["keep_unlisted"]:
+                self.set_load_filter(count.min_mq, count.flag_exclude, count.ignore_orphans)
+            yield self
+        finally:
+            self.restore_load_settings(saved)
 
     def restore_load_settings(self, saved: dict):
         self.set_load_filter(*saved["load_filter"])

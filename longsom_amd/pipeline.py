@@ -6,8 +6,10 @@ the merge is fused into the call kernel; only text formatting and steps 2/3 (can
 on the host.  Every output file has the name and the bytes the reference's scripts give it (except
 the wall-clock ##fileDate line).
 """
+import itertools
 import json
 import os
+import shutil
 import sys
 import time
 from dataclasses import dataclass, field
@@ -70,6 +72,27 @@ class SnvOutputs:
     _pending: list = field(default_factory=list, repr=False, compare=False)
     resident: Optional[dict] = field(default=None, repr=False, compare=False)      # a rank's region and decode summary (sharded two-pass loop)
 
+    @classmethod
+    def under(cls, out_dir: str, sample_id: str, celltype_names, last: str = "step3", make_dirs: bool = False) -> "SnvOutputs":
+        """The files of a run under out_dir as the rules name them, up to the `last` it writes: "report", "step1" (with the count and merged
+        tables), "step2" or "step3" (with the unfiltered table); the later ones stay "".  make_dirs: their four directories are made."""
+        d = {k: os.path.join(out_dir, k) for k in ("SplitBam", "BaseCellCounter/" + sample_id, "MergeCounts", "BaseCellCalling")}
+        if make_dirs:
+            for p in d.values():
+                os.makedirs(p, exist_ok=True)
+        upto = ("report", "step1", "step2", "step3").index(last)
+        step = lambda name: os.path.join(d["BaseCellCalling"], "%s.calling.%s.tsv" % (sample_id, name))
+        out = cls(report=os.path.join(d["SplitBam"], sample_id + ".report.txt"), counts={}, merged="", step1="", step2="", step3="", step3_unfiltered="")
+        if upto >= 1:
+            out.counts = {name: os.path.join(d["BaseCellCounter/" + sample_id], "%s.%s.tsv" % (sample_id, name)) for name in celltype_names}
+            out.merged = os.path.join(d["MergeCounts"], sample_id + ".BaseCellCounts.AllCellTypes.tsv")
+            out.step1 = step("step1")
+        if upto >= 2:
+            out.step2 = step("step2")
+        if upto >= 3:
+            out.step3, out.step3_unfiltered = step("step3"), step("step3.unfiltered")
+        return out
+
     def start_background(self, fn) -> None:
         """run fn() (table writers) on a thread of its own; wait_for_tables joins it and re-raises what it raised"""
         import threading
@@ -131,23 +154,12 @@ def load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, min
     aligned to its BGZF blocks (not written by htslib).  Same store, same report either way (tests/test_ingest_gpu.py).
     filters: SplitBam's --max_nM / --max_NH / --n_trim (SplitFilters; None = off) - the reads they refuse are never counted, trimmed
     qualities are 0, the report gains their columns (SplitBamCellTypes.py:92-173)."""
-    ingest = ingest or os.environ.get("LONGSOM_INGEST", "auto")
-    saved = engine.load_settings()                 # (a caller's own engine keeps the load filter / store policy it came with)
-    engine.set_count_at_load(count_params)
-    engine.set_store_policy(engine.STORE_KEEP if keep_store or count_params is None else engine.STORE_SKIP_WHEN_COUNTED)
-    engine.set_keep_unlisted(keep_unlisted)
-    if filters is not None:
-        engine.set_split_filters(filters)
     old_keep = hostio.set_keep_unlisted(keep_unlisted)
-    # a BAM that is counted once under known parameters: the reads that count's own filters would refuse are not stored at all (what
-    # SplitBamCellTypes.py:110-113 does to the BAM a rule counts) - every stored read is then admitted, and the load sorts keys alone
-    once = count_params is not None and not keep_store and not keep_unlisted
-    if once:
-        engine.set_load_filter(count_params.min_mq, count_params.flag_exclude, count_params.ignore_orphans)
     try:
-        return _load_sample(bam, barcodes_tsv, ref_fasta, engine, min_mapq, ingest, filters)
+        # (a caller's own engine keeps the load filter / store policy it came with: Engine.loading puts them back)
+        with engine.loading(count=count_params, keep_store=keep_store, keep_unlisted=keep_unlisted, filters=filters):
+            return _load_sample(bam, barcodes_tsv, ref_fasta, engine, min_mapq, _ingest(ingest), filters)
     finally:
-        engine.restore_load_settings(saved)
         hostio.set_keep_unlisted(old_keep)
 
 
@@ -155,31 +167,19 @@ def _load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, mi
     t = {}
     t0 = time.time()
     bc = hostio.read_barcodes(barcodes_tsv)
-    names_fa, seqs = tsvio.read_fasta(ref_fasta)
-    seq_of = dict(zip(names_fa, seqs))
+    seq_of = dict(zip(*tsvio.read_fasta(ref_fasta)))
     if ingest in ("device", "auto"):
         names, lens, first = hostio.bam_header(bam)
-        for n, l in zip(names, lens):
-            if n not in seq_of or len(seq_of[n]) != int(l):
-                raise ValueError("contig %s of the BAM header is missing from %s or has another length" % (n, ref_fasta))
         t["header_fasta"] = time.time() - t0
         t0 = time.time()
-        engine.set_contigs(lens)
-        for tid, n in enumerate(names):
-            engine.load_reference(tid, seq_of[n])
-        engine.set_barcodes(bc.celltype_of, len(bc.celltype_names))
+        _bind_reference(engine, names, lens, seq_of, ref_fasta, bc.celltype_of, len(bc.celltype_names))
         engine.set_region()
         t["reference"] = time.time() - t0
         t0 = time.time()
-        try:
-            info, cb_pass, cb_low = engine.load_bam(bam, bc.barcodes, min_mapq=min_mapq, first_record_offset=first)
-        except _lib.LsgError as e:
-            if ingest == "device" or "straddle" not in str(e):
-                raise
-            info = None
-        if info is not None:
-            rep = hostio.split_report([info[k] for k in REPORT_KEYS], [engine.split_reasons()])
-            dec = hostio.DecodedBam(None, names, np.asarray(lens, np.int64), rep, None, cb_pass, cb_low)
+        got = _device_load(ingest, lambda: engine.load_bam(bam, bc.barcodes, min_mapq=min_mapq, first_record_offset=first))
+        if got is not None:
+            info, cb_pass, cb_low = got
+            dec = _decoded(names, lens, info, [engine.split_reasons()], cb_pass, cb_low)
             t["decode"] = time.time() - t0                 # device ingest: H2D + inflate + decode + store build (info has the phases)
             t["load"] = 0.0
             for k, v in info.items():                      # the phases of the device ingest, in seconds like everything else here
@@ -188,27 +188,59 @@ def _load_sample(bam: str, barcodes_tsv: str, ref_fasta: str, engine: Engine, mi
             return Resident(engine, dec, bc, names, t)
         t0 = time.time()
     dec = hostio.decode_bam(bam, bc.barcodes, min_mapq=min_mapq, filters=filters)
-    # the pileup is driven by the FASTA's contigs (MakeWindows, BaseCellCounter.py:84-86); BAM tids index dec.contig_names
-    contig_names = dec.contig_names
-    for n, l in zip(contig_names, dec.contig_len):
-        if n not in seq_of or len(seq_of[n]) != int(l):
-            raise ValueError("contig %s of the BAM header is missing from %s or has another length" % (n, ref_fasta))
     t["decode"] = time.time() - t0
     t0 = time.time()
-    engine.set_contigs(dec.contig_len)
-    for tid, n in enumerate(contig_names):
-        engine.load_reference(tid, seq_of[n])
-    engine.set_barcodes(bc.celltype_of, len(bc.celltype_names))
+    # the pileup is driven by the FASTA's contigs (MakeWindows, BaseCellCounter.py:84-86); BAM tids index dec.contig_names
+    _bind_reference(engine, dec.contig_names, dec.contig_len, seq_of, ref_fasta, bc.celltype_of, len(bc.celltype_names))
     engine.set_region()
     engine.load_reads(dec.records)
     t["load"] = time.time() - t0
-    return Resident(engine, dec, bc, contig_names, t)
+    return Resident(engine, dec, bc, dec.contig_names, t)
+
+
+def _ingest(mode: Optional[str] = None) -> str:
+    """how a BAM's reads reach the GPU (load_sample's `ingest`): the caller's choice, else LONGSOM_INGEST, else auto"""
+    return mode or os.environ.get("LONGSOM_INGEST", "auto")
+
+
+def _straddles(e: BaseException) -> bool:
+    """the device ingest refused a BAM whose records are not aligned to its BGZF blocks (not written by htslib)"""
+    return isinstance(e, _lib.LsgError) and "straddle" in str(e)
+
+
+def _device_load(ingest: str, load):
+    """load() - an ingest on the device - or None when the device refused a BAM whose records straddle its blocks and `ingest` ("auto")
+    leaves such a BAM to the host decoder"""
+    try:
+        return load()
+    except _lib.LsgError as e:
+        if ingest == "device" or not _straddles(e):
+            raise
+        return None
+
+
+def _bind_reference(eng: Engine, names, lens, seq_of: dict, ref_fasta: str, celltype_of, n_celltypes: int) -> None:
+    """the BAM's contigs - every one in the FASTA, with the same length - and their sequences on the device, then the barcode table"""
+    for n, l in zip(names, lens):
+        if n not in seq_of or len(seq_of[n]) != int(l):
+            raise ValueError("contig %s of the BAM header is missing from %s or has another length" % (n, ref_fasta))
+    eng.set_contigs(lens)
+    for tid, n in enumerate(names):
+        eng.load_reference(tid, seq_of[n])
+    eng.set_barcodes(celltype_of, n_celltypes)
+
+
+def _decoded(names, lens, info, reasons, cb_pass=None, cb_low=None) -> "hostio.DecodedBam":
+    """a device ingest's DecodedBam: no records; the report from its counters (lsg_bam_info) and its loads' Engine.split_reasons"""
+    rep = hostio.split_report([info[k] for k in REPORT_KEYS], reasons)
+    return hostio.DecodedBam(None, names, np.asarray(lens, np.int64), rep, None, cb_pass, cb_low)
 
 
 def chain_step1(res: Resident, celltype_of: np.ndarray, celltype_names: List[str], report: Dict[str, int], out_dir: str, sample_id: str,
-                params: SnvParams, write_tables: bool = True, background_tables: bool = False, kept_rows: bool = True):
+                params: SnvParams, write_tables: bool = True, background_tables: bool = False, kept_rows: bool = True, last: str = "step1"):
     """SplitBam report -> BaseCellCounter -> MergeCounts -> BaseCellCalling step 1 over the resident reads.  Returns (outputs, text of
-    the rows step 2 keeps, call records, timings); write_tables=False keeps everything off the disk except the report."""
+    the rows step 2 keeps, call records, timings); write_tables=False keeps everything off the disk except the report.  last: the last
+    table the caller writes (SnvOutputs.under): the outputs name its file and those before it."""
     eng, contig_names = res.engine, res.contig_names
     t = dict(res.seconds)
     t0 = time.time()
@@ -217,21 +249,13 @@ def chain_step1(res: Resident, celltype_of: np.ndarray, celltype_names: List[str
     n_sites, n_cand = eng.call_step1(params.call())
     t["gpu_count_call"] = time.time() - t0
     t0 = time.time()
-    d = {k: os.path.join(out_dir, k) for k in ("SplitBam", "BaseCellCounter/" + sample_id, "MergeCounts", "BaseCellCalling")}
-    for p in d.values():
-        os.makedirs(p, exist_ok=True)
-    out = SnvOutputs(report=os.path.join(d["SplitBam"], sample_id + ".report.txt"), counts={}, merged="", step1="", step2="", step3="",
-                     step3_unfiltered="")
+    out = SnvOutputs.under(out_dir, sample_id, celltype_names, last if write_tables else "report", make_dirs=True)
     write_report(out.report, report, t["decode"])
     if not write_tables:
         calls = eng.fetch_calls(candidates_only=True)
         t["fetch"] = time.time() - t0
         return out, None, calls, t
     date = tsvio.file_date()
-    for ct, name in enumerate(celltype_names):
-        out.counts[name] = os.path.join(d["BaseCellCounter/" + sample_id], "%s.%s.tsv" % (sample_id, name))
-    out.merged = os.path.join(d["MergeCounts"], sample_id + ".BaseCellCounts.AllCellTypes.tsv")
-    out.step1 = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step1.tsv")
     if os.environ.get("LONGSOM_HOST_TABLES", "0") != "1":
         return _device_tables(eng, out, contig_names, celltype_names, sample_id, params, date, background_tables, t, t0, (n_rows, n_cols, n_sites, n_cand), kept_rows)
     import threading
@@ -276,7 +300,7 @@ def chain_step1(res: Resident, celltype_of: np.ndarray, celltype_names: List[str
         out.row_digests = _row_digests(eng, len(celltype_names), (n_rows, n_cols, n_sites, n_cand), per_ct)
         t["row_digests"] = time.time() - t0
     t0 = time.time()
-    header = [l + "\n" for l in tsvio.merged_header(celltype_names, date).split("\n") if l.startswith("##")]
+    header = tsvio.merged_comment_lines(date)
     if background_tables:
         # Steps 2 and 3 only need the rows step 2 keeps: those are formatted first (a third of the step-1 table's rows, nothing written);
         # the per-cell-type and merged tables and the step-1 table itself are written by threads of their own (native writers, no GIL)
@@ -313,8 +337,7 @@ def _device_tables(eng, out: "SnvOutputs", contig_names, celltype_names, sample_
     come first - steps 2 and 3 wait for nothing else.  LONGSOM_HOST_TABLES=1 keeps the host writers (csrc/hostio/tsvwrite.cpp)."""
     import threading
     eng.set_table_names(contig_names, celltype_names)
-    header = [l + "\n" for l in tsvio.merged_header(celltype_names, date).split("\n") if l.startswith("##")]
-    head1 = tsvio.step1_header(header, celltype_names)
+    head1 = tsvio.step1_head(celltype_names, date)
     s1 = head1.encode()
     if kept_rows:                                    # (kept_rows=False: the caller runs step 2 on the device too and wants the header alone)
         n = eng.format_table(eng.TABLE_STEP1_KEPT)
@@ -365,11 +388,12 @@ def run_chain(res: Resident, celltype_of: np.ndarray, celltype_names: List[str],
     device23 = (os.environ.get("LONGSOM_HOST_TABLES", "0") != "1" and os.environ.get("LONGSOM_HOST_STEP2", "0") != "1" and not gnomad_af_json
                 and int(params.min_distance) == 0 and len(set(contig_names)) == len(contig_names)
                 and not any(ch in n for n in list(contig_names) + list(celltype_names) for ch in "\t\n"))
-    out, s1, _, t = chain_step1(res, celltype_of, celltype_names, report, out_dir, sample_id, params, background_tables=True, kept_rows=not device23)
+    out, s1, _, t = chain_step1(res, celltype_of, celltype_names, report, out_dir, sample_id, params, background_tables=True, kept_rows=not device23,
+                                last="step3" if step3 else "step2")
     try:
         if device23:
-            return _device_steps23(out, s1, t, eng, contig_names, out_dir, sample_id, params, editing, pon_sr, pon_lr, step3)
-        return _chain_steps23(out, s1, t, eng, contig_names, out_dir, sample_id, params, editing, pon_sr, pon_lr, gnomad_af_json, step3)
+            return _device_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3)
+        return _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad_af_json, step3)
     except BaseException:
         try:                                   # (the writers stream from the engine: nobody may close it under them)
             out.wait_for_tables()
@@ -378,19 +402,15 @@ def run_chain(res: Resident, celltype_of: np.ndarray, celltype_names: List[str],
         raise
 
 
-def _device_steps23(out, head1: bytes, t, eng, contig_names, out_dir, sample_id, params, editing, pon_sr, pon_lr, step3):
+def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3):
     """Steps 2 and 3 of run_chain with the step-2 table printed on the device (Engine.TABLE_STEP2: csrc/tables.hip): its text goes from
     the device straight into its file; the host sees the kinds of cell of its columns and the rows step 3 can keep
     (Engine.step2_summary), which is all calling.step3 reads of a table this large."""
     t0 = time.time()
-    keys = [calling.read_posset_keys(p, contig_names, params.reference_gz_compat) for p in (editing, pon_sr, pon_lr)]
-    for kind, k in zip((calling.KIND_EDITING, calling.KIND_PON_SR, calling.KIND_PON_LR), keys):
+    for kind, k in zip((calling.KIND_EDITING, calling.KIND_PON_SR, calling.KIND_PON_LR), _posset_keys(contig_names, params, editing, pon_sr, pon_lr)):
         eng.load_posset(kind, k)
-    # the table's head as step 2 writes it: the comment lines, then the column header (calling._step2_scanned)
-    lines = [l for l in head1.split(b"\n") if l]
-    hdr = b"\n".join([l for l in lines if b"#CHROM" not in l] + [[l for l in lines if b"#CHROM" in l][-1]]) + b"\n"
+    hdr = calling.step2_head(head1)                 # (the table's head as step 2 writes it)
     cols = hdr.decode().split("\n")[-2].split("\t")
-    out.step2 = os.path.join(out_dir, "BaseCellCalling", sample_id + ".calling.step2.tsv")
     with open(out.step2, "wb") as f:
         f.write(hdr)
     n2 = eng.format_table(eng.TABLE_STEP2)
@@ -401,14 +421,7 @@ def _device_steps23(out, head1: bytes, t, eng, contig_names, out_dir, sample_id,
     t["step2"] = time.time() - t0
     try:
         if step3:
-            t0 = time.time()
-            final, unfiltered = calling.step3_bytes(survivors, params.delta_vaf, params.delta_mcf, params.min_ac_reads, params.min_ac_cells, params.clust_dist,
-                                                    all_kinds=kinds, full_text=lambda: eng.table_bytes(eng.TABLE_STEP2, n2, prefix=hdr), survivors_only=True)
-            out.step3 = os.path.join(out_dir, "BaseCellCalling", sample_id + ".calling.step3.tsv")
-            out.step3_unfiltered = os.path.join(out_dir, "BaseCellCalling", sample_id + ".calling.step3.unfiltered.tsv")
-            tsvio.write_bytes(out.step3, final)
-            tsvio.write_bytes(out.step3_unfiltered, unfiltered)
-            t["step3"] = time.time() - t0
+            _write_step3(out, survivors, params, t, all_kinds=kinds, full_text=lambda: eng.table_bytes(eng.TABLE_STEP2, n2, prefix=hdr), survivors_only=True)
         t["tables_wait"] = out.wait_for_tables()
     finally:
         try:
@@ -419,29 +432,39 @@ def _device_steps23(out, head1: bytes, t, eng, contig_names, out_dir, sample_id,
     return out
 
 
-def _chain_steps23(out, s1, t, eng, contig_names, out_dir, sample_id, params, editing, pon_sr, pon_lr, gnomad_af_json, step3):
-    d = {"BaseCellCalling": os.path.join(out_dir, "BaseCellCalling")}
+def _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad_af_json, step3):
     t0 = time.time()
-    keys = [calling.read_posset_keys(p, contig_names, params.reference_gz_compat) for p in (editing, pon_sr, pon_lr)]
-    af = calling.open_gnomad(gnomad_af_json)              # a JSON table or a gnomad_db directory / sqlite file
-    s2 = calling.step2_bytes(s1, eng, contig_names, keys[0], keys[1], keys[2], params.min_distance, af, params.max_gnomad_vaf)
-    out.step2 = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step2.tsv")
+    s2 = _step2_for(eng, contig_names, params, editing, pon_sr, pon_lr, gnomad_af_json)(s1, params.min_distance)
     tsvio.write_bytes(out.step2, s2)
     t["step2"] = time.time() - t0
-    if not step3:
-        t["tables_wait"] = out.wait_for_tables()
-        out.timings = t
-        return out
-    t0 = time.time()
-    final, unfiltered = calling.step3_bytes(s2, params.delta_vaf, params.delta_mcf, params.min_ac_reads, params.min_ac_cells, params.clust_dist)
-    out.step3 = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step3.tsv")
-    out.step3_unfiltered = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step3.unfiltered.tsv")
-    tsvio.write_bytes(out.step3, final)
-    tsvio.write_bytes(out.step3_unfiltered, unfiltered)
-    t["step3"] = time.time() - t0
+    if step3:
+        _write_step3(out, s2, params, t)
     t["tables_wait"] = out.wait_for_tables()              # (what of the background writers' time steps 2 and 3 did not cover)
     out.timings = t
     return out
+
+
+def _posset_keys(contig_names, params: SnvParams, editing, pon_sr, pon_lr) -> list:
+    """the keys of step 2's position sets over the run's contigs: RNA editing, PoN_SR, PoN_LR"""
+    return [calling.read_posset_keys(p, contig_names, params.reference_gz_compat) for p in (editing, pon_sr, pon_lr)]
+
+
+def _step2_for(eng, contig_names, params: SnvParams, editing, pon_sr, pon_lr, gnomad_af_json):
+    """step 2 of one run: (text of a step-1 table, distance) -> text of the step-2 table.  The position sets are read and the gnomAD source
+    (a JSON table or a gnomad_db directory / sqlite file) is opened here, once: one that cannot be used stops the run (calling.open_gnomad)."""
+    ed, sr, lr = _posset_keys(contig_names, params, editing, pon_sr, pon_lr)
+    af = calling.open_gnomad(gnomad_af_json)
+    return lambda text, distance: calling.step2_bytes(text, eng, contig_names, ed, sr, lr, distance, af, params.max_gnomad_vaf)
+
+
+def _write_step3(out: SnvOutputs, s2: bytes, params: SnvParams, t, **kw) -> None:
+    """step 3 over the text of the step-2 table (or what of it step 3 reads: calling.step3's all_kinds / full_text / survivors_only in kw)
+    into its two files"""
+    t0 = time.time()
+    final, unfiltered = calling.step3_bytes(s2, params.delta_vaf, params.delta_mcf, params.min_ac_reads, params.min_ac_cells, params.clust_dist, **kw)
+    tsvio.write_bytes(out.step3, final)
+    tsvio.write_bytes(out.step3_unfiltered, unfiltered)
+    t["step3"] = time.time() - t0
 
 
 def run_snv(bam: str, barcodes_tsv: str, ref_fasta: str, out_dir: str, sample_id: str, params: Optional[SnvParams] = None,
@@ -531,319 +554,292 @@ def _prefetch(gen, depth: int = 1):
 
 def _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, editing, pon_sr, pon_lr, gnomad_af_json, eng, comm, window_bytes,
                      step3: bool = True, resident: Optional[dict] = None, table=None, keep_store: bool = True, filters: Optional[SplitFilters] = None) -> SnvOutputs:
-    """keep_store=False: a rank's slice is counted once and nothing else is asked of its reads (run_snv): the load keeps no tile store.
+    """The sharded and the windowed run, in three parts: where this rank's reads come from (_region_source), the count loop over its
+    windows, which writes their pieces of the tables (_count_windows), and rank 0's assembly of the pieces and steps 2-3 (_assemble).
+    keep_store=False: a rank's slice is counted once and nothing else is asked of its reads (run_snv): the load keeps no tile store.
     resident / table / step3 serve the sharded two-pass loop (run_reannotation with several ranks): `resident` = SnvOutputs.resident of
     an earlier call on the same engine (the rank's reads stay in HBM, nothing is ingested again), `table` = (celltype_of per barcode
     id, cell-type names, SplitBam report) of the pass, step3=False stops after the step-2 table (pass 1 of the reference has no step 3)."""
     t: Dict[str, float] = {"decode": 0.0, "load": 0.0, "gpu_count_call": 0.0, "fetch": 0.0, "write_tables": 0.0}
     t_all = time.time()
     bc = hostio.read_barcodes(barcodes_tsv)
-    names_fa, seqs = tsvio.read_fasta(ref_fasta)
-    seq_of = dict(zip(names_fa, seqs))
+    seq_of = dict(zip(*tsvio.read_fasta(ref_fasta)))
     cts = list(table[1]) if table is not None else bc.celltype_names
     ct_of = np.asarray(table[0], np.uint8) if table is not None else bc.celltype_of
-    d = {k: os.path.join(out_dir, k) for k in ("SplitBam", "BaseCellCounter/" + sample_id, "MergeCounts", "BaseCellCalling")}
+    out = SnvOutputs.under(out_dir, sample_id, cts, "step3" if step3 else "step2", make_dirs=comm.rank == 0)
     tmp = os.path.join(out_dir, "_pieces." + sample_id)
     if comm.rank == 0:
-        import shutil
         shutil.rmtree(tmp, ignore_errors=True)
-        for p in list(d.values()) + [tmp]:
-            os.makedirs(p, exist_ok=True)
+        os.makedirs(tmp, exist_ok=True)
     comm.barrier()
-    report: Dict[str, int] = {}
-    contig = {}
-
-    def setup(dec):
-        for n, l in zip(dec.contig_names, dec.contig_len):
-            if n not in seq_of or len(seq_of[n]) != int(l):
-                raise ValueError("contig %s of the BAM header is missing from %s or has another length" % (n, ref_fasta))
-        eng.set_contigs(dec.contig_len)
-        for tid, n in enumerate(dec.contig_names):
-            eng.load_reference(tid, seq_of[n])
-        eng.set_barcodes(ct_of, len(cts))
-        contig["names"] = dec.contig_names
-
-    if resident is not None:
-        # the reads of this rank's region are in HBM already: the pass differs by its barcode -> cell-type table only
-        if comm.world <= 1:
-            raise ValueError("a resident pass belongs to a run with several ranks")
-        lo, hi, dec = resident["lo"], resident["hi"], resident["dec"]
-        contig["names"] = dec.contig_names
-        eng.set_barcodes(ct_of, len(cts))
-        work = iter([(lo, hi, None, dec)])
-        report = dict(table[2]) if table is not None and table[2] is not None else dict(dec.report)
-    elif comm.world > 1:
-        t0 = time.time()
-        dec = None
-        if os.environ.get("LONGSOM_INGEST", "auto") in ("device", "auto"):
-            # every rank ingests the file on its OWN GPU (inflate, decode, store: 0.5 s per GB, nothing on the host's threads, which the
-            # ranks used to share); the regions are cut from the resident per-read / per-segment arrays, the same on every rank
-            names_b, lens_b, first_rec = hostio.bam_header(bam)
-            hdr = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), {})
-            setup(hdr)
-            keys = REPORT_KEYS
-            R = hostio.N_REASONS
-
-            def report_of(counts, reasons):
-                return hostio.split_report(counts[:5], reasons)
-            bai = hostio.find_bai(bam) if os.environ.get("LONGSOM_SHARD_INGEST", "1") != "0" else None
-            if bai is not None:
-                # every rank ingests the SLICE of the file its region needs, found through the .bai's linear index (regions.BaiPlan), as the
-                # reference's workers fetch their window through the index; SplitBam's counters are summed over the ranks (each record is
-                # counted by the rank whose region holds its start).  Any rank that cannot (records not aligned to the blocks of its
-                # slice) takes every rank to the whole-file path below: the ranks agree first.
-                plan = regions.BaiPlan(hostio.read_bai(bai), len(names_b), comm.world, os.path.getsize(bam))
-                bounds = plan.bounds
-                lo, hi = bounds[comm.rank], bounds[comm.rank + 1]
-                got, ok, fatal = None, 1, None
-                try:
-                    # the rank's region and the count's parameters are known before its slice is loaded: the load counts in the same pass
-                    # (for run_snv it is the slice's only count: under the count's own read filters, no tile store kept - what load_sample does for one GPU)
-                    eng.set_region(lo[0], lo[1], hi[0], hi[1])
-                    saved = eng.load_settings()
-                    cp_slice = params.count()
-                    eng.set_count_at_load(cp_slice)
-                    eng.set_split_filters(filters)
-                    if not keep_store:
-                        eng.set_load_filter(cp_slice.min_mq, cp_slice.flag_exclude, cp_slice.ignore_orphans)
-                        eng.set_store_policy(eng.STORE_SKIP_WHEN_COUNTED)
-                    try:
-                        got = regions.ingest_slice(eng, bam, plan, lo, hi, bc.barcodes, params.min_mapping_quality)
-                        got_reasons = eng.split_reasons() if got is not None else None
-                    finally:
-                        eng.restore_load_settings(saved)
-                except _lib.LsgError as e:
-                    if "straddle" in str(e):
-                        ok = 0
-                    else:
-                        fatal = e
-                except BaseException as e:                     # noqa: BLE001 - an index that is not this BAM's, a corrupt block, no memory ...
-                    fatal = e
-                comm.agree(fatal, "the ingest of a rank's slice of %s" % bam)      # (every rank raises when one did: nobody waits in the all-reduce below)
-                n_cb = len(bc.barcodes)
-                if int(comm.allreduce_sum(np.asarray([ok], np.int64))[0]) == comm.world:
-                    # SplitBam's counters, the tallies, and per rank: records and bytes of its slice, its filter reasons (counts, first ordinals)
-                    counts = np.zeros(5 + 2 * n_cb + 2 * comm.world + 2 * R * comm.world, np.int64)
-                    at_r = 5 + 2 * n_cb + 2 * comm.world
-                    if got is not None:
-                        info, cb_pass, cb_low = got
-                        counts[:5] = [info[k] for k in keys]; counts[5:5 + n_cb] = cb_pass; counts[5 + n_cb:5 + 2 * n_cb] = cb_low
-                        counts[5 + 2 * n_cb + comm.rank] = info["n_records"]; counts[5 + 2 * n_cb + comm.world + comm.rank] = info["slice_bytes"]
-                        counts[at_r + R * comm.rank:at_r + R * (comm.rank + 1)] = got_reasons[0]
-                        counts[at_r + R * (comm.world + comm.rank):at_r + R * (comm.world + comm.rank + 1)] = got_reasons[1] + 1      # (+1: 0 = none)
-                    else:
-                        eng.load_reads(hostio.ReadRecords.empty())      # (no alignment in this rank's region)
-                    counts = comm.allreduce_sum(counts)
-                    t["ingest_records_by_rank"] = counts[5 + 2 * n_cb:5 + 2 * n_cb + comm.world].tolist()
-                    t["ingest_slice_MB_by_rank"] = [round(x / 1e6, 3) for x in counts[5 + 2 * n_cb + comm.world:at_r].tolist()]
-                    rs = [(counts[at_r + R * q:at_r + R * (q + 1)], counts[at_r + R * (comm.world + q):at_r + R * (comm.world + q + 1)] - 1) for q in range(comm.world)]
-                    dec = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), report_of(counts, rs), None, counts[5:5 + n_cb].copy(), counts[5 + n_cb:5 + 2 * n_cb].copy())
-                    mine = None
-            if dec is None:
-                try:
-                    saved = eng.load_settings()
-                    eng.set_split_filters(filters)
-                    try:
-                        info, cb_pass, cb_low = eng.load_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, first_record_offset=first_rec)
-                    finally:
-                        eng.restore_load_settings(saved)
-                    dec = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), report_of([info[k] for k in keys], [eng.split_reasons()]), None, cb_pass, cb_low)
-                    bounds = regions.balanced_boundaries(eng.reads_to_host(events=False), len(names_b), comm.world)
-                    lo, hi = bounds[comm.rank], bounds[comm.rank + 1]
-                    mine = None                                   # the rank's store holds the whole file; lsg_set_region makes the columns its own
-                except _lib.LsgError as e:
-                    if os.environ.get("LONGSOM_INGEST", "auto") == "device" or "straddle" not in str(e):
-                        raise
-                    dec = None
-        if dec is None:
-            dec = hostio.decode_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, threads=max(1, (os.cpu_count() or 1) // comm.world), filters=filters)
-            bounds = regions.balanced_boundaries(dec.records, len(dec.contig_names), comm.world)
-            lo, hi = bounds[comm.rank], bounds[comm.rank + 1]
-            mine = dec.records.subset(regions.reads_overlapping(dec.records, lo, hi))
-        t["decode"] = time.time() - t0
-        work = iter([(lo, hi, mine, dec)])
-        report = dict(dec.report)
-    elif (os.environ.get("LONGSOM_INGEST", "auto") in ("device", "auto") and os.environ.get("LONGSOM_SHARD_INGEST", "1") != "0"
-          and hostio.find_bai(bam) is not None):
-        # windows of an INDEXED BAM: the regions a sharded run would give its ranks, taken one after the other by this one GPU — every
-        # window's slice of the file goes to the device as it is (regions.ingest_slice: no host decode, no carried reads: a slice
-        # holds every read that reaches into its region)
-        names_b, lens_b, first_rec = hostio.bam_header(bam)
-        first = hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), {})
-        n_win = max(1, -(-os.path.getsize(bam) * 3 // int(window_bytes)))          # (window_bytes counts uncompressed bytes: about a third as many in the file)
-        plan = regions.BaiPlan(hostio.read_bai(hostio.find_bai(bam)), len(names_b), n_win, os.path.getsize(bam))
-
-        def device_windows():
-            setup(first)
-            for r in range(n_win):
-                lo, hi = plan.bounds[r], plan.bounds[r + 1]
-                t0 = time.time()
-                saved = eng.load_settings()
-                eng.set_split_filters(filters)
-                try:
-                    got = regions.ingest_slice(eng, bam, plan, lo, hi, bc.barcodes, params.min_mapping_quality)
-                finally:
-                    eng.restore_load_settings(saved)
-                t["decode"] += time.time() - t0
-                if got is None:
-                    continue
-                info = got[0]
-                # (the windows' reports are summed in file order below: a reason's column lands where its first window put it)
-                rep = hostio.split_report([info[k] for k in REPORT_KEYS], [eng.split_reasons()])
-                yield lo, hi, None, hostio.DecodedBam(None, names_b, np.asarray(lens_b, np.int64), rep)
-        work = device_windows()
-    else:
-        batches = hostio.stream_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, batch_bytes=int(window_bytes), filters=filters)
-        first = next(batches, None)
-        if first is None:
-            raise ValueError("%s holds no BAM records" % bam)
-
-        def chained():
-            yield first
-            yield from batches
-        work = _prefetch(_windows(chained(), len(first.contig_names)))
-    kept: Dict[tuple, str] = {}
+    bind = lambda names, lens: _bind_reference(eng, names, lens, seq_of, ref_fasta, ct_of, len(cts))
+    names, work = _region_source(eng, bam, bc, bind, ct_of, len(cts), params, comm, window_bytes, resident, keep_store, filters, t)
     # Step 2 is row-local when its distance filter is off (LongSom's setting: min_distance 0) — position-set probes, the gnomAD lookup, the
     # FILTER tags and the blanked NA fields all look at one row — so every rank (every window) runs it over its own rows on its own GPU,
     # writes its pieces of the step-2 table, and only the rows that survive step 3's FILTER patterns travel to rank 0, whose step 3 needs
     # the candidates of every region for its cluster filter (step3.py:283-306).  With a distance filter the rows' neighbours matter and
-    # rank 0 runs step 2 over all kept rows, as before.
-    local_step2 = int(params.min_distance) == 0 and os.environ.get("LONGSOM_LOCAL_STEP2", "1") != "0"
-    s2_state: Dict[str, object] = {}
-
-    def step2_piece(rows: bytes) -> bytes:
-        """the step-2 rows of a piece of the step-1 table (rows only in, rows only out)"""
-        if "keys" not in s2_state:
-            s2_state["keys"] = [calling.read_posset_keys(p, contig["names"], params.reference_gz_compat) for p in (editing, pon_sr, pon_lr)]
-            s2_state["af"] = calling.open_gnomad(gnomad_af_json)
-            mh_ = tsvio.merged_header(cts, "##fileDate=x\n")
-            s2_state["head"] = tsvio.step1_header([l + "\n" for l in mh_.split("\n") if l.startswith("##")], cts).encode()
-            k = s2_state["keys"]
-            s2_state["head_out"] = len(calling.step2_bytes(s2_state["head"], eng, contig["names"], k[0], k[1], k[2], 0, s2_state["af"], params.max_gnomad_vaf))
-        k = s2_state["keys"]
-        out2 = calling.step2_bytes(s2_state["head"] + rows, eng, contig["names"], k[0], k[1], k[2], 0, s2_state["af"], params.max_gnomad_vaf)
-        return out2[s2_state["head_out"]:]
-    n_windows = 0
-    region_error = None
+    # rank 0 runs step 2 over all kept rows.
+    local_step2 = int(params.min_distance) == 0
+    new_step2 = lambda: _step2_for(eng, names, params, editing, pon_sr, pon_lr, gnomad_af_json)
+    got, region_error = None, None
     try:
-      for lo, hi, rec, dec in work:
-          if not contig:
-              setup(dec)
-          names = contig["names"]
-          if comm.world == 1:
-              for k, v in dec.report.items():
-                  report[k] = report.get(k, 0) + v
-          n_windows += 1
-          t0 = time.time()
-          if rec is not None:                                # (None: the device ingest loaded the reads already)
-              eng.load_reads(rec)
-          eng.set_region(lo[0], lo[1], hi[0], hi[1])
-          t["load"] += time.time() - t0
-          t0 = time.time()
-          eng.pileup_count(params.count())
-          eng.call_step1(params.call())
-          t["gpu_count_call"] += time.time() - t0
-          t0 = time.time()
-          per_ct = [eng.fetch_counts(ct) for ct in range(len(cts))]
-          calls = eng.fetch_calls()
-          t["fetch"] += time.time() - t0
-          t0 = time.time()
-          ckeys = calls["key"] if len(calls) else np.zeros(0, np.int64)
-          for tid in np.unique(ckeys >> 32).tolist():
-              k_lo, k_hi = tid << 32, (tid + 1) << 32
-              sl = [slice(int(np.searchsorted(k, k_lo)), int(np.searchsorted(k, k_hi))) for k, _, _ in per_ct]
-              sub = [(k[s_], r[s_], c[s_]) for (k, r, c), s_ in zip(per_ct, sl)]
-              c0, c1 = int(np.searchsorted(ckeys, k_lo)), int(np.searchsorted(ckeys, k_hi))
-              start1 = int(ckeys[c0] & 0xFFFFFFFF) + 1
-              chrom = names[tid]
-              for ct, name in enumerate(cts):
-                  if len(sub[ct][0]):
-                      tsvio.write_counts_tsv(regions.piece_path(tmp, chrom, start1, "counts." + name), *sub[ct], names, "", header=False)
-              tsvio.write_merged_tsv(regions.piece_path(tmp, chrom, start1, "merged"), sub, names, cts, header=False)
-              rows1 = tsvio.write_step1_tsv(regions.piece_path(tmp, chrom, start1, "step1"), calls[c0:c1], sub, names, cts, [], header=False, as_bytes=True)
-              if local_step2:
-                  t1 = time.time()
-                  rows2 = step2_piece(rows1) if rows1 else b""
-                  with open(regions.piece_path(tmp, chrom, start1, "step2"), "wb") as f:
-                      f.write(rows2)
-                  if rows2:      # what pandas' dtype inference over the WHOLE step-2 table will see in this piece's rows (calling.step3, all_kinds)
-                      kk = tsvio.column_kinds(rows2, rows2[:rows2.index(b"\n")].count(b"\t") + 1)
-                      s2_state["kinds"] = kk if "kinds" not in s2_state or len(s2_state["kinds"]) != len(kk) else (s2_state["kinds"] | kk)
-                  surv = calling._step3_survivors(rows2, 6) if rows2 and os.environ.get("LONGSOM_STEP3_FULL_PARSE", "0") != "1" else None
-                  kept[(chrom, start1)] = rows2 if surv is None else surv      # (Cell_types is column 6 of the step-1 / step-2 tables)
-                  t["step2"] = t.get("step2", 0.0) + time.time() - t1
-              else:
-                  kept[(chrom, start1)] = rows1
-          t["write_tables"] += time.time() - t0
+        got = _count_windows(eng, work, names, cts, params, tmp, new_step2 if local_step2 else None, t)
     except BaseException as e:                              # noqa: BLE001 - raised again by the vote below, on every rank
         region_error = e
-    # (no collective inside the loop above: a rank that failed there is heard of here, before anybody waits for its rows)
+    # (no collective inside the loop: a rank that failed there is heard of here, before anybody waits for its rows)
     comm.agree(region_error, "counting / writing a rank's region of %s" % bam)
-    if not contig:                                     # a rank (or a file) without reads: still needs the contig names for the headers
-        setup(dec if comm.world > 1 else first)
-    names = contig["names"]
+    kept, kinds, report, t["windows"], last = got
     # the candidate rows of every region on every rank (RCCL all-gather over xGMI when world > 1); then the pieces are complete
     payloads = comm.allgather_bytes(regions.pack_rows(kept))
     kinds_all = None
     if local_step2:                                    # the kinds of cell every rank saw in its rows of the step-2 table, OR-ed
-        for blob in comm.allgather_bytes(s2_state["kinds"].tobytes() if "kinds" in s2_state else b""):
+        for blob in comm.allgather_bytes(kinds.tobytes() if kinds is not None else b""):
             if blob:
-                kb = np.frombuffer(blob, np.uint8)
-                kinds_all = kb.copy() if kinds_all is None or len(kinds_all) != len(kb) else (kinds_all | kb)
+                kinds_all = _union_kinds(kinds_all, np.frombuffer(blob, np.uint8))
     comm.barrier()
-    out = SnvOutputs(report=os.path.join(d["SplitBam"], sample_id + ".report.txt"), counts={}, merged="", step1="", step2="", step3="", step3_unfiltered="")
-    for name in cts:
-        out.counts[name] = os.path.join(d["BaseCellCounter/" + sample_id], "%s.%s.tsv" % (sample_id, name))
-    out.merged = os.path.join(d["MergeCounts"], sample_id + ".BaseCellCounts.AllCellTypes.tsv")
-    out.step1 = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step1.tsv")
-    out.step2 = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step2.tsv")
-    out.step3 = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step3.tsv")
-    out.step3_unfiltered = os.path.join(d["BaseCellCalling"], sample_id + ".calling.step3.unfiltered.tsv")
-    t["windows"] = n_windows
+    if table is not None and table[2] is not None:     # (a pass under its own barcode table has its own SplitBam report)
+        report = dict(table[2])
     if comm.rank == 0:
-        t0 = time.time()
-        date = tsvio.file_date()
-        write_report(out.report, report, t["decode"] if comm.world > 1 else time.time() - t_all)
-        for name in cts:
-            regions.concatenate_pieces(tmp, "counts." + name, tsvio.counts_header("%s.%s" % (sample_id, name), date), out.counts[name])
-        mh = tsvio.merged_header(cts, date)
-        regions.concatenate_pieces(tmp, "merged", mh, out.merged)
-        s1h = tsvio.step1_header([l + "\n" for l in mh.split("\n") if l.startswith("##")], cts)
-        regions.concatenate_pieces(tmp, "step1", s1h, out.step1)
-        t["concatenate"] = time.time() - t0
-        t0 = time.time()
-        if local_step2:
-            # the pieces of the step-2 table are on disk; what came over the wire is the rows step 3 still looks at
-            keys = [calling.read_posset_keys(p, names, params.reference_gz_compat) for p in (editing, pon_sr, pon_lr)]
-            s2h = calling.step2_bytes(s1h.encode(), eng, names, keys[0], keys[1], keys[2], 0, calling.open_gnomad(gnomad_af_json), params.max_gnomad_vaf)
-            regions.concatenate_pieces(tmp, "step2", s2h.decode(), out.step2)
-            s2 = s2h + regions.unpack_rows_bytes(payloads)
-            t["step2"] = t.get("step2", 0.0) + time.time() - t0
-        else:
-            s1 = s1h.encode() + regions.unpack_rows_bytes(payloads)
-            keys = [calling.read_posset_keys(p, names, params.reference_gz_compat) for p in (editing, pon_sr, pon_lr)]
-            s2 = calling.step2_bytes(s1, eng, names, keys[0], keys[1], keys[2], params.min_distance, calling.open_gnomad(gnomad_af_json), params.max_gnomad_vaf)
-            open(out.step2, "wb").write(s2)
-            t["step2"] = time.time() - t0
-        if step3:
-            t0 = time.time()
-            # (s2 holds the survivors of every region when step 2 ran where the rows are: the whole table's dtypes come with kinds_all, the
-            # whole table itself - should a foreign cell make its printed form depend on them - from the file rank 0 has just assembled)
-            final, unfiltered = calling.step3_bytes(s2, params.delta_vaf, params.delta_mcf, params.min_ac_reads, params.min_ac_cells, params.clust_dist,
-                                                    all_kinds=kinds_all if local_step2 else None,
-                                                    full_text=(lambda: open(out.step2, "rb").read()) if local_step2 else None)
-            open(out.step3, "wb").write(final)
-            open(out.step3_unfiltered, "wb").write(unfiltered)
-            t["step3"] = time.time() - t0
-        import shutil
-        shutil.rmtree(tmp, ignore_errors=True)
+        _assemble(out, tmp, sample_id, cts, report, t["decode"] if comm.world > 1 else time.time() - t_all, payloads, kinds_all,
+                  None if local_step2 else new_step2, params, step3, t)
     comm.barrier()
     out.timings = t
-    if not step3:
-        out.step3 = out.step3_unfiltered = ""
     if comm.world > 1:
+        lo, hi, dec = last
         out.resident = {"lo": lo, "hi": hi, "dec": dec, "table": bc}
     return out
+
+
+def _region_source(eng, bam, bc, bind, ct_of, n_ct, params, comm, window_bytes, resident, keep_store, filters, t):
+    """How this rank's reads reach the GPU, decided once: (contig names, the windows the count loop takes: (lo, hi, records to load or
+    None when they are loaded already, DecodedBam with the window's report)).  bind(names, lens): _bind_reference for this pass."""
+    if resident is not None:
+        if comm.world <= 1:
+            raise ValueError("a resident pass belongs to a run with several ranks")
+        return _resident_window(eng, resident, ct_of, n_ct)
+    ingest = _ingest()
+    if comm.world > 1:
+        return _rank_region(eng, bam, bc, bind, params, comm, ingest, keep_store, filters, t)
+    bai = hostio.find_bai(bam) if ingest in ("device", "auto") else None
+    if bai is not None:
+        return _indexed_windows(eng, bam, bai, bc, bind, params, window_bytes, filters, t)
+    return _streamed_windows(bam, bc, bind, params, window_bytes, filters)
+
+
+def _resident_window(eng, resident, ct_of, n_ct):
+    """pass 2 of the sharded two-pass loop: the rank's reads are in HBM already, the pass differs by its barcode table only"""
+    eng.set_barcodes(ct_of, n_ct)
+    dec = resident["dec"]
+    return dec.contig_names, [(resident["lo"], resident["hi"], None, dec)]
+
+
+def _rank_region(eng, bam, bc, bind, params, comm, ingest, keep_store, filters, t):
+    """One rank's region of a sharded run.  Every rank ingests the file on its OWN GPU (inflate, decode, store: 0.5 s per GB, nothing on
+    the host's threads, which the ranks used to share): the slice its region needs when the BAM has an index (_rank_slice), else the
+    whole file (_rank_of_whole_file).  The host decoder takes the file under host ingest, or when the device refused it (records that
+    straddle its blocks); every rank then decodes all of it and loads the reads of its region."""
+    t0 = time.time()
+    device = ingest in ("device", "auto")
+    win = None
+    if device:
+        names, lens, first = hostio.bam_header(bam)
+        bind(names, lens)
+        bai = hostio.find_bai(bam)
+        if bai is not None:
+            win = _rank_slice(eng, bam, bai, names, lens, bc, params, comm, keep_store, filters, t)
+        if win is None:
+            win = _device_load(ingest, lambda: _rank_of_whole_file(eng, bam, names, lens, first, bc, params, comm, filters))
+    if win is None:
+        dec = hostio.decode_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, threads=max(1, (os.cpu_count() or 1) // comm.world), filters=filters)
+        bounds = regions.balanced_boundaries(dec.records, len(dec.contig_names), comm.world)
+        lo, hi = bounds[comm.rank], bounds[comm.rank + 1]
+        win = (lo, hi, dec.records.subset(regions.reads_overlapping(dec.records, lo, hi)), dec)
+    t["decode"] = time.time() - t0
+    if device:                                         # (the header's contigs are bound already)
+        return names, [win]
+    return win[3].contig_names, _bound_on_arrival(bind, win[3], [win])
+
+
+def _rank_slice(eng, bam, bai, names, lens, bc, params, comm, keep_store, filters, t):
+    """Every rank ingests the SLICE of the file its region needs, found through the .bai's linear index (regions.BaiPlan), as the
+    reference's workers fetch their window through the index; SplitBam's counters are summed over the ranks (each record is counted by the
+    rank whose region holds its start).  The rank's region and the count's parameters are known before its slice is loaded: the load
+    counts in the same pass (keep_store=False, run_snv: it is the slice's only count - what load_sample does for one GPU).  Any rank that
+    cannot (records not aligned to the blocks of its slice) takes every rank to the whole file: the ranks agree first, and all return None."""
+    plan = regions.BaiPlan(hostio.read_bai(bai), len(names), comm.world, os.path.getsize(bam))
+    lo, hi = plan.bounds[comm.rank], plan.bounds[comm.rank + 1]
+    got, reasons, ok, fatal = None, None, 1, None
+    try:
+        eng.set_region(lo[0], lo[1], hi[0], hi[1])
+        with eng.loading(count=params.count(), keep_store=keep_store, filters=filters):
+            got = regions.ingest_slice(eng, bam, plan, lo, hi, bc.barcodes, params.min_mapping_quality)
+            reasons = eng.split_reasons() if got is not None else None
+    except BaseException as e:                     # noqa: BLE001 - an index that is not this BAM's, a corrupt block, no memory ...
+        ok, fatal = (0, None) if _straddles(e) else (1, e)
+    comm.agree(fatal, "the ingest of a rank's slice of %s" % bam)      # (every rank raises when one did: nobody waits in the all-reduce below)
+    if int(comm.allreduce_sum(np.asarray([ok], np.int64))[0]) != comm.world:
+        return None
+    # SplitBam's counters, the tallies, and per rank: records and bytes of its slice, its filter reasons (counts, first ordinals + 1: 0 = none)
+    n_cb, R, W, r = len(bc.barcodes), hostio.N_REASONS, comm.world, comm.rank
+    at_n = 5 + 2 * n_cb
+    at_r = at_n + 2 * W
+    counts = np.zeros(at_r + 2 * R * W, np.int64)
+    if got is not None:
+        info, cb_pass, cb_low = got
+        counts[:5] = [info[k] for k in REPORT_KEYS]; counts[5:5 + n_cb] = cb_pass; counts[5 + n_cb:at_n] = cb_low
+        counts[at_n + r] = info["n_records"]; counts[at_n + W + r] = info["slice_bytes"]
+        counts[at_r + R * r:at_r + R * (r + 1)] = reasons[0]
+        counts[at_r + R * (W + r):at_r + R * (W + r + 1)] = reasons[1] + 1
+    else:
+        eng.load_reads(hostio.ReadRecords.empty())      # (no alignment in this rank's region)
+    counts = comm.allreduce_sum(counts)
+    t["ingest_records_by_rank"] = counts[at_n:at_n + W].tolist()
+    t["ingest_slice_MB_by_rank"] = [round(x / 1e6, 3) for x in counts[at_n + W:at_r].tolist()]
+    rs = [(counts[at_r + R * q:at_r + R * (q + 1)], counts[at_r + R * (W + q):at_r + R * (W + q + 1)] - 1) for q in range(W)]
+    return lo, hi, None, _decoded(names, lens, dict(zip(REPORT_KEYS, counts[:5])), rs, counts[5:5 + n_cb].copy(), counts[5 + n_cb:at_n].copy())
+
+
+def _rank_of_whole_file(eng, bam, names, lens, first, bc, params, comm, filters):
+    """the whole file on every rank's GPU; the regions come from its resident per-read arrays, the same on every rank (the rank's store
+    holds the whole file, lsg_set_region makes its region's columns its own)"""
+    with eng.loading(filters=filters):
+        info, cb_pass, cb_low = eng.load_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, first_record_offset=first)
+    dec = _decoded(names, lens, info, [eng.split_reasons()], cb_pass, cb_low)
+    bounds = regions.balanced_boundaries(eng.reads_to_host(events=False), len(names), comm.world)
+    return bounds[comm.rank], bounds[comm.rank + 1], None, dec
+
+
+def _indexed_windows(eng, bam, bai, bc, bind, params, window_bytes, filters, t):
+    """windows of an INDEXED BAM: the regions a sharded run would give its ranks, taken one after the other by this one GPU — every
+    window's slice of the file goes to the device as it is (regions.ingest_slice: no host decode, no carried reads: a slice holds every
+    read that reaches into its region)"""
+    names, lens, _ = hostio.bam_header(bam)
+    n_win = max(1, -(-os.path.getsize(bam) * 3 // int(window_bytes)))          # (window_bytes counts uncompressed bytes: about a third as many in the file)
+    plan = regions.BaiPlan(hostio.read_bai(bai), len(names), n_win, os.path.getsize(bam))
+
+    def windows():
+        bind(names, lens)
+        for lo, hi in zip(plan.bounds, plan.bounds[1:]):
+            t0 = time.time()
+            with eng.loading(filters=filters):
+                got = regions.ingest_slice(eng, bam, plan, lo, hi, bc.barcodes, params.min_mapping_quality)
+            t["decode"] += time.time() - t0
+            if got is not None:
+                # (the windows' reports are summed in file order: a reason's column lands where its first window put it)
+                yield lo, hi, None, _decoded(names, lens, got[0], [eng.split_reasons()])
+    return names, windows()
+
+
+def _streamed_windows(bam, bc, bind, params, window_bytes, filters):
+    """windows of a BAM without an index (or under host ingest): the host decoder's batches in file order (hostio.stream_bam), cut where
+    the next batch starts with the reads that reach past that point carried over (_windows), decoded a window ahead (_prefetch)"""
+    batches = hostio.stream_bam(bam, bc.barcodes, min_mapq=params.min_mapping_quality, batch_bytes=int(window_bytes), filters=filters)
+    first = next(batches, None)
+    if first is None:
+        raise ValueError("%s holds no BAM records" % bam)
+    return first.contig_names, _bound_on_arrival(bind, first, _prefetch(_windows(itertools.chain([first], batches), len(first.contig_names))))
+
+
+def _bound_on_arrival(bind, dec, windows):
+    """the windows, dec's contigs bound as the first of them arrives (in the count loop, whose errors the ranks vote on)"""
+    for i, w in enumerate(windows):
+        if i == 0:
+            bind(dec.contig_names, dec.contig_len)
+        yield w
+
+
+def _count_windows(eng, work, names, cts, params, tmp, new_step2, t):
+    """The count loop of a region run, no collective inside: per window the load, count and step-1 call, per contig its pieces of the
+    tables (regions.piece_path) - of the step-2 table too with new_step2 (row-local step 2, _step2_for).  Returns (the rows rank 0 still
+    needs per piece, the kinds of cell of the step-2 rows, the report summed over the windows, windows, the last (lo, hi, DecodedBam))."""
+    kept: Dict[tuple, bytes] = {}
+    kinds, report, n, last = None, {}, 0, None
+    if new_step2 is not None:
+        t0 = time.time()
+        step2 = new_step2()
+        head1 = tsvio.step1_head(cts, "##fileDate=x\n").encode()         # (any date: the head is cut off the step-2 text again)
+        cut = len(calling.step2_head(head1))
+        t["step2"] = time.time() - t0
+    for lo, hi, rec, dec in work:
+        for k, v in dec.report.items():
+            report[k] = report.get(k, 0) + v
+        n, last = n + 1, (lo, hi, dec)
+        t0 = time.time()
+        if rec is not None:                                # (None: the device ingest loaded the reads already)
+            eng.load_reads(rec)
+        eng.set_region(lo[0], lo[1], hi[0], hi[1])
+        t["load"] += time.time() - t0
+        t0 = time.time()
+        eng.pileup_count(params.count())
+        eng.call_step1(params.call())
+        t["gpu_count_call"] += time.time() - t0
+        t0 = time.time()
+        per_ct = [eng.fetch_counts(ct) for ct in range(len(cts))]
+        calls = eng.fetch_calls()
+        t["fetch"] += time.time() - t0
+        t0 = time.time()
+        ckeys = calls["key"] if len(calls) else np.zeros(0, np.int64)
+        for tid in np.unique(ckeys >> 32).tolist():
+            k_lo, k_hi = tid << 32, (tid + 1) << 32
+            sl = [slice(int(np.searchsorted(k, k_lo)), int(np.searchsorted(k, k_hi))) for k, _, _ in per_ct]
+            sub = [(k[s_], r[s_], c[s_]) for (k, r, c), s_ in zip(per_ct, sl)]
+            c0, c1 = int(np.searchsorted(ckeys, k_lo)), int(np.searchsorted(ckeys, k_hi))
+            start1 = int(ckeys[c0] & 0xFFFFFFFF) + 1
+            chrom = names[tid]
+            for ct, name in enumerate(cts):
+                if len(sub[ct][0]):
+                    tsvio.write_counts_tsv(regions.piece_path(tmp, chrom, start1, "counts." + name), *sub[ct], names, "", header=False)
+            tsvio.write_merged_tsv(regions.piece_path(tmp, chrom, start1, "merged"), sub, names, cts, header=False)
+            rows1 = tsvio.write_step1_tsv(regions.piece_path(tmp, chrom, start1, "step1"), calls[c0:c1], sub, names, cts, [], header=False, as_bytes=True)
+            if new_step2 is None:
+                kept[(chrom, start1)] = rows1
+                continue
+            t1 = time.time()
+            rows2 = step2(head1 + rows1, 0)[cut:] if rows1 else b""
+            with open(regions.piece_path(tmp, chrom, start1, "step2"), "wb") as f:
+                f.write(rows2)
+            if rows2:      # what pandas' dtype inference over the WHOLE step-2 table will see in this piece's rows (calling.step3, all_kinds)
+                kinds = _union_kinds(kinds, tsvio.column_kinds(rows2, rows2[:rows2.index(b"\n")].count(b"\t") + 1))
+            surv = calling._step3_survivors(rows2, 6) if rows2 and os.environ.get("LONGSOM_STEP3_FULL_PARSE", "0") != "1" else None
+            kept[(chrom, start1)] = rows2 if surv is None else surv      # (Cell_types is column 6 of the step-1 / step-2 tables)
+            t["step2"] += time.time() - t1
+        t["write_tables"] += time.time() - t0
+    return kept, kinds, report, n, last
+
+
+def _union_kinds(a, b):
+    """the kinds of cell (tsvio.column_kinds) of two parts of one table, OR-ed; a part with another number of columns starts over"""
+    return b.copy() if a is None or len(a) != len(b) else (a | b)
+
+
+def _assemble(out, tmp, sample_id, cts, report, report_seconds, payloads, kinds, new_step2, params, step3, t):
+    """Rank 0's part of a region run: the report; every table as its head and its pieces in (chrom string, start) order; steps 2 and 3
+    over the rows that came over the wire - step 2 here only when it did not run where the rows are (new_step2, a distance filter)."""
+    t0 = time.time()
+    date = tsvio.file_date()
+    write_report(out.report, report, report_seconds)
+    for name in cts:
+        regions.concatenate_pieces(tmp, "counts." + name, tsvio.counts_header("%s.%s" % (sample_id, name), date), out.counts[name])
+    regions.concatenate_pieces(tmp, "merged", tsvio.merged_header(cts, date), out.merged)
+    head1 = tsvio.step1_head(cts, date)
+    regions.concatenate_pieces(tmp, "step1", head1, out.step1)
+    t["concatenate"] = time.time() - t0
+    t0 = time.time()
+    if new_step2 is None:
+        # the pieces of the step-2 table are on disk; what came over the wire is the rows step 3 still looks at
+        head2 = calling.step2_head(head1.encode())
+        regions.concatenate_pieces(tmp, "step2", head2.decode(), out.step2)
+        s2 = head2 + regions.unpack_rows_bytes(payloads)
+    else:
+        s2 = new_step2()(head1.encode() + regions.unpack_rows_bytes(payloads), params.min_distance)
+        tsvio.write_bytes(out.step2, s2)
+    t["step2"] = t.get("step2", 0.0) + time.time() - t0
+    if step3:
+        # (s2 holds the survivors of every region when step 2 ran where the rows are: the whole table's dtypes come with `kinds`, the
+        # whole table itself - should a foreign cell make its printed form depend on them - from the file just assembled)
+        local = {} if new_step2 is not None else {"all_kinds": kinds, "full_text": lambda: open(out.step2, "rb").read()}
+        _write_step3(out, s2, params, t, **local)
+    shutil.rmtree(tmp, ignore_errors=True)
 
 
 @dataclass
@@ -934,12 +930,8 @@ def run_reannotation(bam: str, barcodes_tsv: str, ref_fasta: str, out_dir: str, 
             raise ValueError("the two passes must share min_mapping_quality to share one decode (SplitBam report)")
         if out.n_cells_kept == 0:
             return out
-        new = hostio.read_barcodes(out.barcodes)
-        idx = {b: i for i, b in enumerate(res.table.barcodes)}
-        ct2 = np.full(len(res.table.barcodes), 255, np.uint8)
-        for b, c in zip(new.barcodes, new.celltype_of):
-            ct2[idx[b]] = c
-        out.pass2 = run_chain(res, ct2, new.celltype_names, res.dec.report_for(ct2 != 255), os.path.join(out_dir, "SNVCalling"), sample_id, sp, editing,
+        ct2, names2 = _pass2_table(out.barcodes, res.table)
+        out.pass2 = run_chain(res, ct2, names2, res.dec.report_for(ct2 != 255), os.path.join(out_dir, "SNVCalling"), sample_id, sp, editing,
                               pon_sr, pon_lr, gnomad_af_json)
         return out
     finally:
@@ -1000,14 +992,21 @@ def _run_reannotation_ranks(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, rp
     t["reannotation"] = time.time() - t0
     if out.n_cells_kept == 0:
         return out
-    new = hostio.read_barcodes(out.barcodes)
+    ct2, names2 = _pass2_table(out.barcodes, table)
+    out.pass2 = _run_snv_regions(bam, barcodes_tsv, ref_fasta, os.path.join(out_dir, "SNVCalling"), sample_id, sp, editing, pon_sr, pon_lr, gnomad_af_json, eng, comm,
+                                 None, resident=state, table=(ct2, names2, dec.report_for(ct2 != 255)))
+    return out
+
+
+def _pass2_table(barcodes_tsv: str, table: "hostio.BarcodeTable"):
+    """the re-annotated barcodes.tsv over the barcode ids of the decode (`table`, pass 1's): (cell type per barcode id, 255 = no longer
+    listed; the cell-type names)"""
+    new = hostio.read_barcodes(barcodes_tsv)
     idx = {b: i for i, b in enumerate(table.barcodes)}
     ct2 = np.full(len(table.barcodes), 255, np.uint8)
     for b, c in zip(new.barcodes, new.celltype_of):
         ct2[idx[b]] = c
-    out.pass2 = _run_snv_regions(bam, barcodes_tsv, ref_fasta, os.path.join(out_dir, "SNVCalling"), sample_id, sp, editing, pon_sr, pon_lr, gnomad_af_json, eng, comm,
-                                 None, resident=state, table=(ct2, new.celltype_names, dec.report_for(ct2 != 255)))
-    return out
+    return ct2, new.celltype_names
 
 
 @dataclass

@@ -350,9 +350,19 @@ def merged_header(celltype_names, date_line=None) -> str:
     return "".join([date_line or file_date(), _CONCEPTS, "\t".join(["#CHROM", "Start", "End", "REF", "INFO"] + list(celltype_names)) + "\n"])
 
 
+def merged_comment_lines(date_line=None) -> List[str]:
+    """the '##' lines of the merged table, which step 1 copies to the top of its own (step1.py:34-35)"""
+    return [l + "\n" for l in merged_header((), date_line).split("\n") if l.startswith("##")]
+
+
 def step1_header(header_lines: List[str], celltype_names) -> str:
     return "".join(list(header_lines) + [l + "\n" for l in STEP1_INFO_LINES] +
                    ["\t".join(["#CHROM", "Start", "End", "REF", "\t".join(STEP1_COLUMNS), "INFO"] + list(celltype_names)) + "\n"])
+
+
+def step1_head(celltype_names, date_line=None) -> str:
+    """the head of the step-1 table: the merged table's '##' lines, step 1's own, the column header"""
+    return step1_header(merged_comment_lines(date_line), celltype_names)
 
 
 def write_counts_tsv(path, keys, refs, counts, contig_names, sample_id, date_line=None, threads: int = 0, header: bool = True) -> None:
@@ -369,13 +379,13 @@ def write_counts_tsv(path, keys, refs, counts, contig_names, sample_id, date_lin
 def write_merged_tsv(path, per_ct, contig_names, celltype_names, date_line=None, threads: int = 0, header: bool = True) -> List[str]:
     """format_merged_tsv straight to `path`; returns the '##' header lines (step 1 copies them through)."""
     lib = _io()
-    head = [date_line or file_date(), _CONCEPTS]
+    date_line = date_line or file_date()
     with open(path, "w") as f:
-        f.write(merged_header(celltype_names, head[0]) if header else "")
+        f.write(merged_header(celltype_names, date_line) if header else "")
     ks, rs, cs, pk, pr, pc, n = _per_ct_ptrs(per_ct)
     _check(lib, lib.lsio_write_merged_rows(os.fsencode(path), "\n".join(contig_names).encode(), len(contig_names), len(per_ct), pk, pr, pc, n.ctypes.data, threads),
            "lsio_write_merged_rows")
-    return [l + "\n" for l in "".join(head).split("\n") if l.startswith("##")]
+    return merged_comment_lines(date_line)
 
 
 def write_step1_tsv(path, calls, per_ct, contig_names, celltype_names, header_lines: List[str], threads: int = 0, header: bool = True,

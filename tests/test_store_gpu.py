@@ -215,7 +215,7 @@ def test_unload_gives_the_memory_back_and_the_handle_stays_usable():
 
 
 def test_a_load_without_reads_counts_nothing(engine):
-    """what a rank of a sharded run does when no alignment falls into its region (pipeline._run_snv_regions): an empty load, a count, a
+    """what a rank of a sharded run does when no alignment falls into its region (pipeline._rank_slice): an empty load, a count, a
     call, fetches — all of them empty, none of them an error"""
     from longsom_amd import hostio
     m = synth.named("C1", n_reads=1000)
