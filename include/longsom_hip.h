@@ -348,10 +348,13 @@ int lsg_export_calls(lsg_ctx* ctx, int32_t kind, void* dst_device, int64_t capac
  *                         FILTER tagged "RNA_editing_db" / "PoN_SR" / "PoN_LR" by the resident position sets (lsg_load_posset; GetExtraFilters,
  *                         BaseCellCalling.step2.py:142-158; a tag replaces a bare "PASS"), "NA" cells empty (step2.py's pandas round trip)
  *   LSG_TABLE_STEP3_ROWS  the rows of LSG_TABLE_STEP2 step 3 can keep (made by lsg_step2_summary, not by lsg_format_table)
+ *   LSG_TABLE_CELL_LONG   <id>.SingleCellGenotype.tsv rows      CellClustering/SingleCellGenotype.py:181-224,305 (see lsg_cellgeno_count below)
+ *   LSG_TABLE_CELL_DP / _ALT / _VAF / _BIN   the rows of <id>.DpMatrix.tsv, AltMatrix, VAFMatrix, BinaryMatrix (SingleCellGenotype.py:351-379)
  * Rows only (the header lines are the caller's), in the reference's order: contigs in Python string order, positions ascending.
  * At 24 M sites these are 17 GB of text: a kernel prints them from the count rows and call records where they lie (two passes:
  * lengths, then bytes), the host only moves bytes.  The merged and step-1 tables need lsg_call_step1 (its merged site list). */
-enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG_TABLE_STEP1, LSG_TABLE_STEP1_KEPT, LSG_TABLE_STEP2, LSG_TABLE_STEP3_ROWS, LSG_TABLE_SLOTS };
+enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG_TABLE_STEP1, LSG_TABLE_STEP1_KEPT, LSG_TABLE_STEP2, LSG_TABLE_STEP3_ROWS,
+                 LSG_TABLE_CELL_LONG, LSG_TABLE_CELL_DP, LSG_TABLE_CELL_ALT, LSG_TABLE_CELL_VAF, LSG_TABLE_CELL_BIN, LSG_TABLE_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -418,6 +421,51 @@ int lsg_betabinom_sf4(lsg_ctx* ctx, int64_t n_items, const uint32_t* k, const ui
 /* The same tails with the UNROUNDED fp64 value beside the rounded one: what the exactness audit measures (how far every p of a
  * workload lies from a 4-decimal rounding tie of round(betabinom.sf(...), 4), BaseCellCalling.step1.py:196,201; tools/p_margins.py). */
 int lsg_betabinom_sf(lsg_ctx* ctx, int64_t n_items, const uint32_t* k, const uint32_t* n, double alpha, double beta, int32_t* out_p4, double* out_p);
+
+/* ---- per-cell verdicts and cell-by-variant matrices -----------------------
+ * CellClustering/SingleCellGenotype.py (rule SingleCellGenotype, rules/CellClustering.smk:4-103): the twin of the script above re-piled at
+ * the final SNVs, with a verdict per cell and four matrices.  lsg_cellgeno_count counts Dp / Alt as lsg_genotype_cells_grouped does
+ * (run_interval, :84-178; this script cleans the CB tag before the lookup, :164-169: strict_cb = 0) and, with the counts where they lie,
+ * gives every (site, barcode) cell (:181-218)
+ *   vaf4    round(ALT / DP, 4) * 1e4 (:194), -1 where DP = 0 (the script prints ".")
+ *   p4      round(betabinom.sf(ALT - 0.001, DP, alpha2, beta2), 4) * 1e4 (:204), -1 where the script prints "." (DP = 0, ALT = 0, or a
+ *           site flagged in is_chrm: --chrM_contaminant True and a contig named exactly chrM, :197)
+ *   status  LSG_CELL_NOCOVERAGE (DP = 0), _NOALT (ALT = 0), _LOWVAF_CHRM (flagged site, VAF < 0.3 i.e. vaf4 < 3000), _BETABIN_PROBLEM
+ *           (p4 / 10000.0 >= pvalue), _PASS (:192-211)
+ *   bin     BinMutationStatus: 1 PASS, 3 NoCoverage, 0 otherwise (:213-218)
+ * and every barcode the number of sites with DP > 0 (n_covered) and with PASS (n_pass).  The arrays [n_sites][n_cb] stay on the device
+ * until the next lsg_cellgeno_count / lsg_cellgeno_load_counts; lsg_cellgeno_fetch copies them out (any pointer may be NULL).
+ * lsg_cellgeno_load_counts classifies Dp / Alt tables the caller brings (counts summed over ranks, test grids) instead of counting. */
+enum { LSG_CELL_NOCOVERAGE = 0, LSG_CELL_NOALT, LSG_CELL_LOWVAF_CHRM, LSG_CELL_BETABIN_PROBLEM, LSG_CELL_PASS };
+int lsg_cellgeno_count(lsg_ctx* ctx, const lsg_genotype_params* params, int32_t max_depth, int64_t n_sites, const int64_t* site_keys,
+                       const uint8_t* alt_sym, const uint8_t* is_chrm, int64_t n_groups, const int64_t* group_off,
+                       double alpha2, double beta2, double pvalue);
+int lsg_cellgeno_load_counts(lsg_ctx* ctx, int64_t n_sites, int32_t n_cb, const uint32_t* dp, const uint32_t* alt, const uint8_t* is_chrm,
+                             double alpha2, double beta2, double pvalue);
+int lsg_cellgeno_fetch(lsg_ctx* ctx, uint32_t* dp, uint32_t* alt, int32_t* vaf4, int32_t* p4, uint8_t* status, uint8_t* bin,
+                       int64_t* n_covered, int64_t* n_pass);
+/* The strings and orders the five tables print (uploaded once; string i of a blob = blob[off[i] .. off[i + 1])):
+ *   head   per site: "#CHROM .. Num_cells_expected", the first seven columns joined by tabs (:222)
+ *   index  per site: INDEX = CHROM:POS:ALT_expected up to its first comma (:221)
+ *   label  per site: the matrices' first column (INDEX after sort_chr_index, :342-348)
+ *   cb, ct per barcode: CB and Cell_type_observed
+ *   long_order   the sites in the long table's order (windows by chromosome text and smallest position, :309-317; a site appears once)
+ *   mat_order    the sites in the matrices' row order (natsorted INDEX with chrM last, :342-345)
+ *   col_src      per matrix column (distinct CB, sorted as pandas' pivot sorts them): its barcode, or -1 for a barcode only the fusion
+ *                file names - an empty cell;  float_cells != 0: the integer matrices print "3.0" (pandas, a pivot with gaps)
+ * lsg_format_table(LSG_TABLE_CELL_LONG) then prints n_long x n_cb rows of 16 columns, LSG_TABLE_CELL_DP .. _BIN one row per site of
+ * mat_order: label, then n_cols cells.  Header lines and the fusion rows (a handful) are the caller's. */
+typedef struct {
+    const char* head;  const uint32_t* head_off;
+    const char* index; const uint32_t* index_off;
+    const char* label; const uint32_t* label_off;
+    const char* cb;    const uint32_t* cb_off;
+    const char* ct;    const uint32_t* ct_off;
+    int64_t n_long; const int32_t* long_order;
+    int64_t n_mat;  const int32_t* mat_order;
+    int32_t n_cols; int32_t float_cells; const int32_t* col_src;
+} lsg_cellgeno_text;
+int lsg_cellgeno_set_text(lsg_ctx* ctx, const lsg_cellgeno_text* text);
 
 /* ---- measurement helpers --------------------------------------------------------------------*/
 /* Statistics of the last lsg_pileup_count: admitted reads / segments / events (events that passed

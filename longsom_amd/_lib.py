@@ -63,6 +63,14 @@ class GenotypeParams(C.Structure):
         return p
 
 
+class CellGenoText(C.Structure):
+    """lsg_cellgeno_text: the strings and orders the SingleCellGenotype tables print (blob + offsets per kind of string)"""
+    _fields_ = [("head", C.c_char_p), ("head_off", C.c_void_p), ("index", C.c_char_p), ("index_off", C.c_void_p), ("label", C.c_char_p), ("label_off", C.c_void_p),
+                ("cb", C.c_char_p), ("cb_off", C.c_void_p), ("ct", C.c_char_p), ("ct_off", C.c_void_p),
+                ("n_long", C.c_int64), ("long_order", C.c_void_p), ("n_mat", C.c_int64), ("mat_order", C.c_void_p),
+                ("n_cols", C.c_int32), ("float_cells", C.c_int32), ("col_src", C.c_void_p)]
+
+
 class CallParams(C.Structure):
     _fields_ = [
         ("alpha1", C.c_double), ("beta1", C.c_double), ("alpha2", C.c_double), ("beta2", C.c_double),
@@ -162,6 +170,10 @@ SIGNATURES = {
     "lsg_probe_posset": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "lsg_genotype_cells": (C.c_int, [C.c_void_p, C.POINTER(GenotypeParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "lsg_genotype_cells_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "lsg_cellgeno_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "lsg_cellgeno_load_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "lsg_cellgeno_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_cellgeno_set_text": (C.c_int, [C.c_void_p, C.POINTER(CellGenoText)]),
     "lsg_betabinom_sf4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "lsg_betabinom_sf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "lsg_max_live_reads": (C.c_int64, [C.c_void_p]),

@@ -259,6 +259,40 @@ def single_cell_genotype(argv=None):
                                     min_mq=a.min_mq, alpha2=a.alpha2, beta2=a.beta2, pvalue=a.pvalue, chrm_contaminant=a.chrM_contaminant)
 
 
+def cell_genotype_matrices(argv=None):
+    """SingleCellGenotype.py --bam --infile --ref --meta --fusions [FILE] --outfile PREFIX [--alt_flag --nprocs --bin --min_bq --min_mq --tissue
+    --tmp_dir --alpha2 --beta2 --pvalue --chrM_contaminant]  (scripts/CellClustering/SingleCellGenotype.py:381-400).  Writes
+    PREFIX.SingleCellGenotype.tsv and PREFIX.{Dp,Alt,VAF,Binary}Matrix.tsv.  --ref is accepted and not needed (:127,140)."""
+    from . import cellclust
+    ap = argparse.ArgumentParser(description="SNVs / fusions observed in every cell and the cell-by-variant matrices, on the GPU")
+    ap.add_argument("--bam", required=True); ap.add_argument("--infile", required=True); ap.add_argument("--ref", required=True)
+    ap.add_argument("--meta", required=True); ap.add_argument("--fusions", nargs="?", const="", required=True); ap.add_argument("--outfile", default="Matrix.tsv")
+    ap.add_argument("--alt_flag", default="All", choices=["Alt", "All"]); ap.add_argument("--nprocs", type=int, default=1)
+    ap.add_argument("--bin", type=int, default=50000); ap.add_argument("--min_bq", type=int, default=30); ap.add_argument("--min_mq", type=int, default=255)
+    ap.add_argument("--tissue", default=None); ap.add_argument("--tmp_dir", default="tmpDir")
+    ap.add_argument("--alpha2", type=float, default=0.2474528917555431); ap.add_argument("--beta2", type=float, default=162.03696139428595)
+    ap.add_argument("--pvalue", type=float, default=0.01); ap.add_argument("--chrM_contaminant", default="True")
+    ap.add_argument("--device", type=int, default=0)
+    _add_htslib_flag(ap)
+    a = ap.parse_args(argv)
+    _apply_htslib_flag(a)
+    if a.tissue is not None:
+        raise SystemExit("--tissue is not used by LongSom's rules and is not implemented")
+    print("Outfile prefix: ", a.outfile, "\n")
+    os.makedirs(a.tmp_dir, exist_ok=True)              # the rule declares it as an output (R:CellClustering.smk:18)
+    table = hostio.read_barcodes(a.meta)
+    dec = hostio.decode_bam(a.bam, table.barcodes, min_mapq=0)
+    with Engine(a.device) as eng:
+        eng.set_contigs(dec.contig_len)
+        eng.set_barcodes(table.celltype_of, len(table.celltype_names))
+        eng.load_reads(dec.records)
+        try:
+            cellclust.cell_genotype_matrices(eng, a.infile, table, dec.contig_names, a.outfile, a.fusions or None, alt_flag=a.alt_flag, window=a.bin,
+                                             min_bq=a.min_bq, min_mq=a.min_mq, alpha2=a.alpha2, beta2=a.beta2, pvalue=a.pvalue, chrm_contaminant=a.chrM_contaminant)
+        except cellclust.NoTargets as e:
+            raise SystemExit(str(e))
+
+
 def celltype_reannotation(argv=None):
     """CellTypeReannotation.py --SNVs --fusions --outfile --meta [--min_variants --min_frac]  (:67-77)."""
     from . import reanno

@@ -1,0 +1,343 @@
+// Per-cell verdicts at the final SNVs and the cell-by-variant matrices, everything after the counts.
+//
+// Replaces, of workflow/scripts/CellClustering/SingleCellGenotype.py (rule SingleCellGenotype, rules/CellClustering.smk:4-103),
+//   the per-cell loop of run_interval        :181-224   VAF, BetaBin, MutationStatus, BinMutationStatus (k_cell_classify; the tallies per
+//                                                       barcode are what CellTypeReannotation.py:9-18 counts off such a table)
+//   the rows of <id>.SingleCellGenotype.tsv  :222-224,305-317   16 columns, one row per (site, barcode)              (k_cell_row_len / _put)
+//   pivot_long_dataframe + sort_chr_index    :342-379   the rows of DpMatrix / AltMatrix / VAFMatrix / BinaryMatrix    (k_cell_matrix)
+// The counts themselves (:84-178) are genotype.hip's k_geno_sites with the depth cap of lsg_genotype_cells_grouped; they are classified
+// where they lie.  The orders (long table: windows by chromosome text; matrices: natsorted INDEX; columns: sorted CB) and every string a
+// row prints are the host's (longsom_amd/cellclust.py), uploaded once: the device prints n_sites x n_cb rows and four matrices from them.
+// The text is printed twice, as in tables.hip: lengths, a scan, then the bytes.
+#include "lsg_ctx.h"
+#include "bb_tail.h"
+#include "text_sink.h"
+#include <cmath>
+#include <cstring>
+#include <vector>
+#include <hipcub/hipcub.hpp>
+
+namespace lsg {
+int run_genotype(lsg_ctx* c, const lsg_genotype_params* p, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
+                 uint32_t* dp, uint32_t* alt, int on_device, int32_t max_depth, int64_t n_groups, const int64_t* group_off);
+
+namespace {
+
+// round(a / b, 4) * 1e4 as Python rounds the double quotient (text_sink.h put_ratio states the rule); b > 0
+__device__ __forceinline__ int32_t ratio4(uint32_t a, uint32_t b) {
+    const double x = (double)a / (double)b;
+    const double hi = x * 10000.0, lo = fma(x, 10000.0, -hi);
+    const double fl = floor(hi);
+    int64_t k = (int64_t)fl;
+    const double t = ((hi - fl) - 0.5) + lo;
+    if (t > 0.0 || (t == 0.0 && (k & 1))) ++k;
+    return (int32_t)k;
+}
+
+// SingleCellGenotype.py:188-218 for every cell; the tail is evaluated for cells with ALT > 0 outside the flagged sites only
+__global__ __launch_bounds__(256) void k_cell_classify(const uint32_t* dp, const uint32_t* alt, const uint8_t* is_chrm, int64_t n_cells, int32_t n_cb,
+                                                       double al, double be, double lgc0, double lgcn, double pvalue,
+                                                       int32_t* vaf4, int32_t* p4, uint8_t* status, uint8_t* bin) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cells; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t DP = dp[i], ALT = alt[i];
+        int32_t v = -1, p = -1;
+        int st = LSG_CELL_NOCOVERAGE;
+        if (DP > 0) {
+            v = ratio4(ALT, DP);                                                           // :194
+            if (ALT == 0) st = LSG_CELL_NOALT;                                             // :211
+            else if (is_chrm[i / n_cb]) st = v < 3000 ? LSG_CELL_LOWVAF_CHRM : LSG_CELL_PASS;      // :197-201
+            else {
+                p = round4(bb_upper_tail(ALT, DP, al, be, bb_pm0(DP, al, be, lgc0), lgcn));        // :204
+                st = (double)p / 10000.0 < pvalue ? LSG_CELL_PASS : LSG_CELL_BETABIN_PROBLEM;       // :206-209
+            }
+        }
+        vaf4[i] = v; p4[i] = p; status[i] = (uint8_t)st;
+        bin[i] = (uint8_t)(st == LSG_CELL_PASS ? 1 : st == LSG_CELL_NOCOVERAGE ? 3 : 0);   // :213-218
+    }
+}
+
+// per barcode: sites with coverage, sites with PASS (a thread per barcode walks the sites: neighbours read neighbouring bytes)
+__global__ __launch_bounds__(256) void k_cell_tally(const uint8_t* status, int64_t n_sites, int32_t n_cb, int64_t* n_cov, int64_t* n_pass) {
+    const int cb = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cb >= n_cb) return;
+    int64_t cov = 0, pass = 0;
+    for (int64_t s = 0; s < n_sites; ++s) {
+        const int st = status[s * n_cb + cb];
+        cov += st != LSG_CELL_NOCOVERAGE; pass += st == LSG_CELL_PASS;
+    }
+    n_cov[cb] = cov; n_pass[cb] = pass;
+}
+
+struct CellArgs {
+    const uint32_t* dp; const uint32_t* alt; const int32_t* vaf4; const int32_t* p4; const uint8_t* status; const uint8_t* bin;
+    int32_t n_cb, n_cols, float_cells, kind;
+    const char* head; const char* index; const char* label; const char* cb; const char* ct;
+    const uint32_t* head_off; const uint32_t* index_off; const uint32_t* label_off; const uint32_t* cb_off; const uint32_t* ct_off;
+    const int32_t* order; int64_t n;                  // the sites in the table's order; n = rows of the table (long: sites x n_cb)
+    const int32_t* col_src;
+    uint32_t* len; const uint64_t* off; char* text;
+};
+
+template <class S> __device__ __forceinline__ void put_str(S& s, const char* txt, const uint32_t* off, int64_t i) {
+    s.str(txt + off[i], (int)(off[i + 1] - off[i]));
+}
+__device__ __forceinline__ const char* status_name(int st, int& n) {
+    switch (st) {
+        case LSG_CELL_NOCOVERAGE: n = 10; return "NoCoverage";
+        case LSG_CELL_NOALT: n = 10; return "NoAltReads";
+        case LSG_CELL_LOWVAF_CHRM: n = 10; return "LowVAFChrM";
+        case LSG_CELL_BETABIN_PROBLEM: n = 15; return "BetaBin_problem";
+        default: n = 4; return "PASS";
+    }
+}
+
+// one row of <id>.SingleCellGenotype.tsv (:222): row r = (r / n_cb)-th site of the order, barcode r % n_cb
+template <class S> __device__ void long_row(S& s, const CellArgs& a, int64_t r) {
+    const int64_t j = r / a.n_cb;
+    const int cb = (int)(r - j * a.n_cb);
+    const int64_t site = a.order[j], cell = site * a.n_cb + cb;
+    put_str(s, a.head, a.head_off, site); s.ch('\t');
+    put_str(s, a.cb, a.cb_off, cb); s.ch('\t'); put_str(s, a.ct, a.ct_off, cb); s.ch('\t');
+    s.u64(a.dp[cell]); s.ch('\t'); s.u64(a.alt[cell]); s.ch('\t');
+    const int st = a.status[cell];
+    if (st == LSG_CELL_NOCOVERAGE) s.ch('.'); else put_p4(s, a.vaf4[cell]);
+    s.ch('\t');
+    if (a.p4[cell] < 0) s.ch('.'); else put_p4(s, a.p4[cell]);
+    s.ch('\t');
+    int n; const char* name = status_name(st, n); s.str(name, n);
+    s.ch('\t'); s.ch((char)('0' + a.bin[cell])); s.ch('\t');
+    put_str(s, a.index, a.index_off, site); s.ch('\n');
+}
+__global__ __launch_bounds__(256) void k_cell_row_len(CellArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > a.n) return;
+    LenSink s;
+    if (i < a.n) long_row(s, a, i);
+    a.len[i] = s.n;
+}
+__global__ __launch_bounds__(256) void k_cell_row_put(CellArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    PutSink s{a.text + a.off[i]};
+    long_row(s, a, i);
+}
+
+enum { M_DP = 0, M_ALT, M_VAF, M_BIN };
+// one cell of a matrix, with the tab before it: the value of (site, barcode of the column), nothing for a column no barcode of the
+// sample stands behind (a barcode of the fusion file alone); float_cells: pandas prints the integer matrices of a pivot with gaps as floats
+template <class S> __device__ __forceinline__ void mat_cell(S& s, const CellArgs& a, int64_t site, int col) {
+    s.ch('\t');
+    const int src = a.col_src[col];
+    if (src < 0) return;
+    const int64_t cell = site * a.n_cb + src;
+    if (a.kind == M_VAF) {                                           // the long table's own string
+        if (a.status[cell] == LSG_CELL_NOCOVERAGE) s.ch('.'); else put_p4(s, a.vaf4[cell]);
+        return;
+    }
+    s.u64(a.kind == M_DP ? a.dp[cell] : a.kind == M_ALT ? a.alt[cell] : (uint32_t)a.bin[cell]);
+    if (a.float_cells) LIT(s, ".0");
+}
+// a workgroup per matrix row: label, then the cells 256 at a time, a block scan of their lengths giving each its place.  PUT = false:
+// the row's length only (block n: the scan's end marker)
+template <bool PUT> __global__ __launch_bounds__(256) void k_cell_matrix(CellArgs a) {
+    using Scan = hipcub::BlockScan<uint32_t, 256>;
+    __shared__ typename Scan::TempStorage tmp;
+    const int64_t r = blockIdx.x;
+    if (r >= a.n) { if (!PUT && r == a.n && threadIdx.x == 0) a.len[r] = 0; return; }
+    const int64_t site = a.order[r];
+    const uint32_t l0 = a.label_off[site], lab = a.label_off[site + 1] - l0;
+    char* out = PUT ? a.text + a.off[r] : nullptr;
+    if (PUT) for (uint32_t q = threadIdx.x; q < lab; q += blockDim.x) out[q] = a.label[l0 + q];
+    uint32_t base = lab;
+    for (int c0 = 0; c0 < a.n_cols; c0 += 256) {
+        const int col = c0 + (int)threadIdx.x;
+        LenSink ls;
+        if (col < a.n_cols) mat_cell(ls, a, site, col);
+        uint32_t excl, total;
+        Scan(tmp).ExclusiveSum(ls.n, excl, total);
+        __syncthreads();
+        if (PUT && col < a.n_cols) { PutSink ps{out + base + excl}; mat_cell(ps, a, site, col); }
+        base += total;
+    }
+    if (threadIdx.x == 0) { if (PUT) out[base] = '\n'; else a.len[r] = base + 1; }
+}
+
+struct Widen { __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)v; } };
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+int reserve_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb) {
+    CellGeno& g = c->cg;
+    const size_t cells = (size_t)(n_sites > 0 ? n_sites : 1) * (size_t)n_cb;
+    if (g.dp.reserve(cells * 4) || g.alt.reserve(cells * 4) || g.vaf4.reserve(cells * 4) || g.p4.reserve(cells * 4) || g.status.reserve(cells) ||
+        g.bin.reserve(cells) || g.is_chrm.reserve((size_t)(n_sites > 0 ? n_sites : 1)) || g.n_cov.reserve((size_t)n_cb * 8) || g.n_pass.reserve((size_t)n_cb * 8)) return -1;
+    return 0;
+}
+
+// the verdicts and tallies of the resident dp / alt
+int classify(lsg_ctx* c, const char* who, int64_t n_sites, int32_t n_cb, const uint8_t* is_chrm, double al, double be, double pvalue) {
+    CellGeno& g = c->cg;
+    hipStream_t st = c->stream;
+    const int64_t cells = n_sites * (int64_t)n_cb;
+    if (n_sites > 0) {
+        LSG_HIP(hipMemcpyAsync(g.is_chrm.p, is_chrm, (size_t)n_sites, hipMemcpyHostToDevice, st));
+        unsigned blocks = (unsigned)((cells + 255) / 256); if (blocks > (unsigned)(c->n_cus * 32)) blocks = (unsigned)(c->n_cus * 32);
+        hipLaunchKernelGGL(k_cell_classify, dim3(blocks), dim3(256), 0, st, g.dp.as<uint32_t>(), g.alt.as<uint32_t>(), g.is_chrm.as<uint8_t>(), cells, n_cb, al, be,
+                           lgamma(al + be) - lgamma(be), lgamma(al + be) - lgamma(al), pvalue, g.vaf4.as<int32_t>(), g.p4.as<int32_t>(), g.status.as<uint8_t>(), g.bin.as<uint8_t>());
+    }
+    hipLaunchKernelGGL(k_cell_tally, dim3((unsigned)((n_cb + 255) / 256)), dim3(256), 0, st, g.status.as<uint8_t>(), n_sites, n_cb, g.n_cov.as<int64_t>(), g.n_pass.as<int64_t>());
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { set_error("%s: kernel failed", who); return -1; }
+    g.n_sites = n_sites; g.n_cb = n_cb; g.valid = true;
+    return 0;
+}
+
+int check_tail_params(const char* who, double al, double be, double pvalue) {
+    if (!(al > 0.0) || !(be > 0.0) || !(pvalue == pvalue)) { set_error("%s: alpha2 and beta2 must be positive, pvalue a number", who); return -2; }
+    return 0;
+}
+
+} // namespace
+
+int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_depth, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
+                       const uint8_t* is_chrm, int64_t n_groups, const int64_t* group_off, double alpha2, double beta2, double pvalue) {
+    const char* who = "lsg_cellgeno_count";
+    CellGeno& g = c->cg;
+    g.valid = g.text_valid = false;
+    for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
+    if (int rc = check_tail_params(who, alpha2, beta2, pvalue)) return rc;
+    if (c->n_contigs <= 0) { set_error("%s: no contigs set", who); return -2; }
+    if (c->n_cb <= 0) { set_error("%s: no barcodes set", who); return -2; }
+    if (c->store_skipped) { set_error("%s: the load kept no store (lsg_set_store_policy): load the reads again with LSG_STORE_KEEP", who); return -2; }
+    if (!c->tm_valid) { set_error("%s: no reads loaded", who); return -2; }
+    for (int64_t i = 1; i < n_sites; ++i)
+        if (site_keys[i] <= site_keys[i - 1]) { set_error("%s: site keys must be strictly ascending", who); return -2; }
+    if ((double)n_sites * (double)c->n_cb >= 2147483648.0) { set_error("%s: %lld sites x %d barcodes", who, (long long)n_sites, c->n_cb); return -2; }
+    if (reserve_cells(c, n_sites, c->n_cb) || g.keys.reserve((size_t)(n_sites > 0 ? n_sites : 1) * 8) || g.alt_sym.reserve((size_t)(n_sites > 0 ? n_sites : 1))) return -1;
+    if (n_sites > 0) {
+        LSG_HIP(hipMemcpyAsync(g.keys.p, site_keys, (size_t)n_sites * 8, hipMemcpyHostToDevice, c->stream));
+        LSG_HIP(hipMemcpyAsync(g.alt_sym.p, alt_sym, (size_t)n_sites, hipMemcpyHostToDevice, c->stream));
+        // the counts land in the arrays the verdicts are made from: no host copy in between
+        if (int rc = run_genotype(c, p, n_sites, g.keys.as<int64_t>(), g.alt_sym.as<uint8_t>(), g.dp.as<uint32_t>(), g.alt.as<uint32_t>(), 1, max_depth, n_groups, group_off)) return rc;
+    }
+    return classify(c, who, n_sites, c->n_cb, is_chrm, alpha2, beta2, pvalue);
+}
+
+int run_cellgeno_load_counts(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint32_t* dp, const uint32_t* alt, const uint8_t* is_chrm, double alpha2, double beta2, double pvalue) {
+    const char* who = "lsg_cellgeno_load_counts";
+    CellGeno& g = c->cg;
+    g.valid = g.text_valid = false;
+    for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
+    if (int rc = check_tail_params(who, alpha2, beta2, pvalue)) return rc;
+    if ((double)n_sites * (double)n_cb >= 2147483648.0) { set_error("%s: %lld sites x %d barcodes", who, (long long)n_sites, n_cb); return -2; }
+    if (reserve_cells(c, n_sites, n_cb)) return -1;
+    if (n_sites > 0) {
+        const size_t bytes = (size_t)n_sites * (size_t)n_cb * 4;
+        LSG_HIP(hipMemcpyAsync(g.dp.p, dp, bytes, hipMemcpyHostToDevice, c->stream));
+        LSG_HIP(hipMemcpyAsync(g.alt.p, alt, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return classify(c, who, n_sites, n_cb, is_chrm, alpha2, beta2, pvalue);
+}
+
+int run_cellgeno_fetch(lsg_ctx* c, uint32_t* dp, uint32_t* alt, int32_t* vaf4, int32_t* p4, uint8_t* status, uint8_t* bin, int64_t* n_covered, int64_t* n_pass) {
+    CellGeno& g = c->cg;
+    if (!g.valid) { set_error("lsg_cellgeno_fetch: nothing classified (lsg_cellgeno_count first)"); return -2; }
+    const size_t cells = (size_t)g.n_sites * (size_t)g.n_cb;
+    auto get = [&](void* dst, const DevBuf& src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess; };
+    LSG_HIP(get(dp, g.dp, cells * 4)); LSG_HIP(get(alt, g.alt, cells * 4)); LSG_HIP(get(vaf4, g.vaf4, cells * 4)); LSG_HIP(get(p4, g.p4, cells * 4));
+    LSG_HIP(get(status, g.status, cells)); LSG_HIP(get(bin, g.bin, cells));
+    LSG_HIP(get(n_covered, g.n_cov, (size_t)g.n_cb * 8)); LSG_HIP(get(n_pass, g.n_pass, (size_t)g.n_cb * 8));
+    LSG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int run_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* t) {
+    const char* who = "lsg_cellgeno_set_text";
+    CellGeno& g = c->cg;
+    g.text_valid = false;
+    for (int q = LSG_TABLE_CELL_LONG; q < LSG_TABLE_SLOTS; ++q) c->tab_bytes[q] = -1;
+    if (!g.valid) { set_error("%s: nothing classified (lsg_cellgeno_count first)", who); return -2; }
+    const int64_t S = g.n_sites; const int32_t B = g.n_cb;
+    if (t->n_long < 0 || t->n_long > S || t->n_mat < 0 || t->n_mat > S || t->n_cols < 0 || (t->n_long > 0 && !t->long_order) || (t->n_mat > 0 && !t->mat_order) ||
+        (t->n_cols > 0 && !t->col_src) || !t->head_off || !t->index_off || !t->label_off || !t->cb_off || !t->ct_off) { set_error("%s: bad arguments", who); return -2; }
+    // every index a kernel follows is checked here
+    auto offsets_ok = [](const uint32_t* off, int64_t n) { if (off[0] != 0) return false; for (int64_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return false; return true; };
+    if (!offsets_ok(t->head_off, S) || !offsets_ok(t->index_off, S) || !offsets_ok(t->label_off, S) || !offsets_ok(t->cb_off, B) || !offsets_ok(t->ct_off, B)) { set_error("%s: string offsets must start at 0 and ascend", who); return -2; }
+    for (int64_t i = 0; i < t->n_long; ++i) if (t->long_order[i] < 0 || t->long_order[i] >= S) { set_error("%s: long_order[%lld] is not a site", who, (long long)i); return -2; }
+    for (int64_t i = 0; i < t->n_mat; ++i) if (t->mat_order[i] < 0 || t->mat_order[i] >= S) { set_error("%s: mat_order[%lld] is not a site", who, (long long)i); return -2; }
+    for (int32_t i = 0; i < t->n_cols; ++i) if (t->col_src[i] < -1 || t->col_src[i] >= B) { set_error("%s: col_src[%d] is not a barcode", who, i); return -2; }
+    if ((double)t->n_long * (double)B >= 2147483648.0) { set_error("%s: %lld x %d rows", who, (long long)t->n_long, B); return -2; }
+    const size_t n_head = t->head_off[S], n_index = t->index_off[S], n_label = t->label_off[S], n_cbt = t->cb_off[B], n_ctt = t->ct_off[B];
+    if ((n_head && !t->head) || (n_index && !t->index) || (n_label && !t->label) || (n_cbt && !t->cb) || (n_ctt && !t->ct)) { set_error("%s: bad arguments", who); return -2; }
+    size_t at = 0;
+    auto place = [&](size_t bytes) { const size_t here = at; at = align_up(at + bytes, 8); return here; };
+    g.head_off_at = place((size_t)(S + 1) * 4); g.index_off_at = place((size_t)(S + 1) * 4); g.label_off_at = place((size_t)(S + 1) * 4);
+    g.cb_off_at = place((size_t)(B + 1) * 4); g.ct_off_at = place((size_t)(B + 1) * 4);
+    g.long_order_at = place((size_t)t->n_long * 4); g.mat_order_at = place((size_t)t->n_mat * 4); g.col_src_at = place((size_t)t->n_cols * 4);
+    g.head_at = place(n_head); g.index_at = place(n_index); g.label_at = place(n_label); g.cb_at = place(n_cbt); g.ct_at = place(n_ctt);
+    std::vector<char> host(at + 8, 0);
+    auto copy = [&](size_t where, const void* src, size_t bytes) { if (bytes) memcpy(host.data() + where, src, bytes); };
+    copy(g.head_off_at, t->head_off, (size_t)(S + 1) * 4); copy(g.index_off_at, t->index_off, (size_t)(S + 1) * 4); copy(g.label_off_at, t->label_off, (size_t)(S + 1) * 4);
+    copy(g.cb_off_at, t->cb_off, (size_t)(B + 1) * 4); copy(g.ct_off_at, t->ct_off, (size_t)(B + 1) * 4);
+    copy(g.long_order_at, t->long_order, (size_t)t->n_long * 4); copy(g.mat_order_at, t->mat_order, (size_t)t->n_mat * 4); copy(g.col_src_at, t->col_src, (size_t)t->n_cols * 4);
+    copy(g.head_at, t->head, n_head); copy(g.index_at, t->index, n_index); copy(g.label_at, t->label, n_label); copy(g.cb_at, t->cb, n_cbt); copy(g.ct_at, t->ct, n_ctt);
+    if (g.text.reserve(host.size())) return -1;
+    LSG_HIP(hipMemcpyAsync(g.text.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
+    LSG_HIP(hipStreamSynchronize(c->stream));
+    g.n_long = t->n_long; g.n_mat = t->n_mat; g.n_cols = t->n_cols; g.float_cells = t->float_cells ? 1 : 0;
+    g.text_valid = true;
+    return 0;
+}
+
+int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
+    if (n_bytes) *n_bytes = 0;
+    CellGeno& g = c->cg;
+    if (!g.valid || !g.text_valid) { set_error("lsg_format_table: table %d needs lsg_cellgeno_count and lsg_cellgeno_set_text first", table); return -2; }
+    hipStream_t st = c->stream;
+    const bool is_long = table == LSG_TABLE_CELL_LONG;
+    const char* tx = g.text.as<char>();
+    CellArgs a{};
+    a.dp = g.dp.as<uint32_t>(); a.alt = g.alt.as<uint32_t>(); a.vaf4 = g.vaf4.as<int32_t>(); a.p4 = g.p4.as<int32_t>(); a.status = g.status.as<uint8_t>(); a.bin = g.bin.as<uint8_t>();
+    a.n_cb = g.n_cb; a.n_cols = g.n_cols; a.float_cells = g.float_cells;
+    a.kind = table == LSG_TABLE_CELL_DP ? M_DP : table == LSG_TABLE_CELL_ALT ? M_ALT : table == LSG_TABLE_CELL_VAF ? M_VAF : M_BIN;
+    a.head = tx + g.head_at; a.index = tx + g.index_at; a.label = tx + g.label_at; a.cb = tx + g.cb_at; a.ct = tx + g.ct_at;
+    a.head_off = reinterpret_cast<const uint32_t*>(tx + g.head_off_at); a.index_off = reinterpret_cast<const uint32_t*>(tx + g.index_off_at);
+    a.label_off = reinterpret_cast<const uint32_t*>(tx + g.label_off_at); a.cb_off = reinterpret_cast<const uint32_t*>(tx + g.cb_off_at);
+    a.ct_off = reinterpret_cast<const uint32_t*>(tx + g.ct_off_at);
+    a.order = reinterpret_cast<const int32_t*>(tx + (is_long ? g.long_order_at : g.mat_order_at));
+    a.col_src = reinterpret_cast<const int32_t*>(tx + g.col_src_at);
+    a.n = is_long ? g.n_long * (int64_t)g.n_cb : g.n_mat;
+    c->tab_bytes[table] = -1;
+    if (a.n == 0) { c->tab_bytes[table] = 0; return 0; }
+    // scratch: len[n + 1] | off[n + 1]
+    const size_t at_off = align_up((size_t)(a.n + 1) * 4, 256), total = at_off + (size_t)(a.n + 1) * 8;
+    if (g.scratch.reserve(total)) return -1;
+    a.len = g.scratch.as<uint32_t>();
+    uint64_t* off = reinterpret_cast<uint64_t*>(g.scratch.as<char>() + at_off);
+    a.off = off;
+    const unsigned row_blocks = (unsigned)((a.n + 1 + 255) / 256);
+    if (is_long) hipLaunchKernelGGL(k_cell_row_len, dim3(row_blocks), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_cell_matrix<false>, dim3((unsigned)(a.n + 1)), dim3(256), 0, st, a);
+    {
+        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> in(a.len, Widen());
+        size_t tb = 0;
+        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, off, (int)(a.n + 1), st));
+        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
+        tb = c->d_cub_tmp.cap;
+        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, in, off, (int)(a.n + 1), st));
+    }
+    LSG_HIP(hipMemcpyAsync(c->h_pin, off + a.n, 8, hipMemcpyDeviceToHost, st));
+    LSG_HIP(hipStreamSynchronize(st));
+    const int64_t bytes = (int64_t)c->h_pin[0];
+    if (bytes > 0) {
+        if (c->tab_text[table].reserve((size_t)bytes)) return -1;
+        a.text = c->tab_text[table].as<char>();
+        if (is_long) hipLaunchKernelGGL(k_cell_row_put, dim3(row_blocks), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_cell_matrix<true>, dim3((unsigned)a.n), dim3(256), 0, st, a);
+        LSG_HIP(hipGetLastError());
+        LSG_HIP(hipStreamSynchronize(st));
+    }
+    c->tab_bytes[table] = bytes;
+    if (n_bytes) *n_bytes = bytes;
+    return 0;
+}
+
+} // namespace lsg

@@ -2,6 +2,9 @@
 // SNVCalling/SingleCellGenotype.py:84-228.  A target site is one position of one tile of the store: a workgroup per site walks the
 // tile's blocks, a thread takes the 16-byte row of the site's position (eight entries' events there) and adds every entry that has a
 // countable event to the site's per-barcode (Dp, Alt) pair.  Target sites are a few thousand; the pass reads the targets' tiles only.
+// CellClustering/SingleCellGenotype.py:84-178 (rule SingleCellGenotype) counts the same way at the final SNVs with the CB tag cleaned before
+// the lookup (strict_cb = 0); what it does with the counts - the verdict per cell, its long table, the four matrices - is cellgeno.hip,
+// which hands run_genotype its own resident arrays (on_device = 1).
 #include "lsg_ctx.h"
 #include <algorithm>
 #include <cstring>

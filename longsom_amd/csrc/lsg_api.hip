@@ -24,6 +24,12 @@ int run_free_table(lsg_ctx* c, int32_t table);
 int run_step2_summary(lsg_ctx* c, int32_t n_cols, uint8_t* kinds, int64_t* n_survivor_bytes);
 int run_genotype(lsg_ctx* c, const lsg_genotype_params* p, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
                  uint32_t* dp, uint32_t* alt, int on_device, int32_t max_depth, int64_t n_groups, const int64_t* group_off);
+int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_depth, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
+                       const uint8_t* is_chrm, int64_t n_groups, const int64_t* group_off, double alpha2, double beta2, double pvalue);
+int run_cellgeno_load_counts(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint32_t* dp, const uint32_t* alt, const uint8_t* is_chrm, double alpha2, double beta2, double pvalue);
+int run_cellgeno_fetch(lsg_ctx* c, uint32_t* dp, uint32_t* alt, int32_t* vaf4, int32_t* p4, uint8_t* status, uint8_t* bin, int64_t* n_covered, int64_t* n_pass);
+int run_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* t);
+int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes);
 int run_sf4(lsg_ctx* c, int64_t items, const uint32_t* k, const uint32_t* n, double al, double be, int32_t* out, double* raw);
 
 // copy a host or device array into a grow-only device buffer of the handle (the caller's array is free again when the call returns)
@@ -96,6 +102,7 @@ void lsg_destroy(lsg_ctx* c) {
     for (auto& b : c->syn) b.release();
     for (auto& b : c->gen) b.release();
     (void)run_free_table(c, -1);
+    c->cg.release();
     c->tab_names.release();
     for (auto& b : c->ws) b.release();
     for (auto& b : c->tm) b.release();
@@ -458,6 +465,7 @@ int lsg_set_table_names(lsg_ctx* c, int32_t n_contigs, const char* contig_names,
 int lsg_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     if (!c) { set_error("lsg_format_table: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
+    if (table >= LSG_TABLE_CELL_LONG && table < LSG_TABLE_SLOTS) return run_format_cell_table(c, table, n_bytes);
     return run_format_table(c, table, n_bytes);
 }
 int lsg_copy_table(lsg_ctx* c, int32_t table, char* dst_host, int64_t capacity) {
@@ -514,6 +522,30 @@ int lsg_genotype_cells_grouped(lsg_ctx* c, const lsg_genotype_params* params, in
     if (int rc = check_load_filter(c, "lsg_genotype_cells_grouped", params->min_mq, params->flag_exclude, params->ignore_orphans)) return rc;
     if (n_groups > 0 && (group_off[0] != 0 || group_off[n_groups] != n_sites)) { set_error("lsg_genotype_cells_grouped: the groups must cover the sites"); return -2; }
     return run_genotype(c, params, n_sites, site_keys, alt_sym, dp, alt, on_device, max_depth, n_groups, group_off);
+}
+
+int lsg_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* params, int32_t max_depth, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
+                       const uint8_t* is_chrm, int64_t n_groups, const int64_t* group_off, double alpha2, double beta2, double pvalue) {
+    if (!c || !params || n_sites < 0 || n_groups < 0 || (n_groups > 0 && !group_off) || (n_sites > 0 && (!site_keys || !alt_sym || !is_chrm))) { set_error("lsg_cellgeno_count: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    if (int rc = check_load_filter(c, "lsg_cellgeno_count", params->min_mq, params->flag_exclude, params->ignore_orphans)) return rc;
+    if (n_groups > 0 && (group_off[0] != 0 || group_off[n_groups] != n_sites)) { set_error("lsg_cellgeno_count: the groups must cover the sites"); return -2; }
+    return run_cellgeno_count(c, params, max_depth, n_sites, site_keys, alt_sym, is_chrm, n_groups, group_off, alpha2, beta2, pvalue);
+}
+int lsg_cellgeno_load_counts(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint32_t* dp, const uint32_t* alt, const uint8_t* is_chrm, double alpha2, double beta2, double pvalue) {
+    if (!c || n_sites < 0 || n_cb <= 0 || (n_sites > 0 && (!dp || !alt || !is_chrm))) { set_error("lsg_cellgeno_load_counts: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_cellgeno_load_counts(c, n_sites, n_cb, dp, alt, is_chrm, alpha2, beta2, pvalue);
+}
+int lsg_cellgeno_fetch(lsg_ctx* c, uint32_t* dp, uint32_t* alt, int32_t* vaf4, int32_t* p4, uint8_t* status, uint8_t* bin, int64_t* n_covered, int64_t* n_pass) {
+    if (!c) { set_error("lsg_cellgeno_fetch: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_cellgeno_fetch(c, dp, alt, vaf4, p4, status, bin, n_covered, n_pass);
+}
+int lsg_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* text) {
+    if (!c || !text) { set_error("lsg_cellgeno_set_text: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_cellgeno_set_text(c, text);
 }
 
 int lsg_betabinom_sf4(lsg_ctx* c, int64_t n_items, const uint32_t* k, const uint32_t* n, double alpha, double beta, int32_t* out_p4) {

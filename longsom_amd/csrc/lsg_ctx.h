@@ -57,6 +57,17 @@ struct DevBuf {
 
 struct PosSet { DevBuf keys; int64_t n = 0; };
 
+// cellgeno.hip: what lsg_cellgeno_count / lsg_cellgeno_load_counts leave resident ([n_sites][n_cb] per cell, per barcode the two
+// tallies) and what lsg_cellgeno_set_text uploaded (one buffer; the *_at fields are byte offsets into it)
+struct CellGeno {
+    DevBuf keys, alt_sym, is_chrm, dp, alt, vaf4, p4, status, bin, n_cov, n_pass, text, scratch;
+    int64_t n_sites = 0; int32_t n_cb = 0; bool valid = false;
+    bool text_valid = false; int64_t n_long = 0, n_mat = 0; int32_t n_cols = 0, float_cells = 0;
+    size_t head_off_at = 0, index_off_at = 0, label_off_at = 0, cb_off_at = 0, ct_off_at = 0, long_order_at = 0, mat_order_at = 0, col_src_at = 0,
+           head_at = 0, index_at = 0, label_at = 0, cb_at = 0, ct_at = 0;
+    void release() { for (DevBuf* b : {&keys, &alt_sym, &is_chrm, &dp, &alt, &vaf4, &p4, &status, &bin, &n_cov, &n_pass, &text, &scratch}) b->release(); valid = text_valid = false; }
+};
+
 // workspace buffers (lsg_ctx::ws)
 enum { WS_NE_NSLOT = 0, WS_NE_ACC, WS_NE_GEOM, WS_MULTI_LIST, WS_MACC, WS_EXPORT_K, WS_EXPORT_R,
        WS_EXPORT_C, WS_CALL_FLAGS, WS_CALL_SEL, WS_CALL_CANDS, WS_CALL_TASKS, WS_SEG_INFO };
@@ -207,8 +218,11 @@ struct lsg_ctx {
     uint64_t tab_rows_serial[LSG_MAX_CELLTYPES] = {0, 0, 0, 0};      // count_serial the flat copy was made of (0 = none)
     uint64_t count_serial = 0;            // bumped by every count / lsg_load_counts
     lsg::DevBuf tab_text[LSG_TABLE_SLOTS];
-    int64_t tab_bytes[LSG_TABLE_SLOTS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};      // -1: not formatted
+    int64_t tab_bytes[LSG_TABLE_SLOTS];   // -1: not formatted
+    lsg_ctx() { for (auto& b : tab_bytes) b = -1; }
     int32_t tab_n_contigs = 0, tab_n_ct = 0; uint32_t tab_ct_off_at = 0, tab_order_at = 0, tab_ct_txt_at = 0, tab_contig_txt_at = 0;
+
+    lsg::CellGeno cg;                     // cellgeno.hip: the per-cell verdicts of the last lsg_cellgeno_count and the strings their tables print
 
     lsg::PosSet posset[3];
     lsg::DevBuf syn[12];                  // synthetic-model tables + scan scratch (synth.hip)

@@ -451,6 +451,7 @@ class Engine:
 
     # ---- the tables' text, printed on the device (include/longsom_hip.h: enum lsg_table) ----
     TABLE_COUNTS, TABLE_MERGED, TABLE_STEP1, TABLE_STEP1_KEPT, TABLE_STEP2, TABLE_STEP3_ROWS = 0, 4, 5, 6, 7, 8
+    TABLE_CELL_LONG, TABLE_CELL_DP, TABLE_CELL_ALT, TABLE_CELL_VAF, TABLE_CELL_BIN = 9, 10, 11, 12, 13
 
     def set_table_names(self, contig_names, celltype_names) -> None:
         """Names the rows print (contigs in set_contigs order, cell types in index order)."""
@@ -532,6 +533,68 @@ class Engine:
             _lib.check(self._lib.lsg_genotype_cells_grouped(self._h, C.byref(params), int(max_depth), len(site_keys), _ptr(site_keys), _ptr(alt_sym),
                                                             len(group_off) - 1, _ptr(group_off), _ptr(dp), _ptr(alt), 0), "lsg_genotype_cells_grouped")
         return dp, alt
+
+    # ---- per-cell verdicts and cell-by-variant matrices (CellClustering/SingleCellGenotype.py; csrc/cellgeno.hip) ----
+    CELL_NOCOVERAGE, CELL_NOALT, CELL_LOWVAF_CHRM, CELL_BETABIN_PROBLEM, CELL_PASS = 0, 1, 2, 3, 4
+    CELL_STATUS_NAMES = ["NoCoverage", "NoAltReads", "LowVAFChrM", "BetaBin_problem", "PASS"]
+
+    def cellgeno_count(self, site_keys, alt_sym, is_chrm, group_off, params=None, max_depth: int = 200000, alpha2: float = 0.2474528917555431,
+                       beta2: float = 162.03696139428595, pvalue: float = 0.01) -> None:
+        """genotype_cells_grouped + the verdict of every (site, barcode) cell (SingleCellGenotype.py:181-218), all left on the device:
+        cellgeno_fetch copies them out, cellgeno_set_text + format_table(TABLE_CELL_*) print them.  is_chrm: per site, 1 where the
+        chrM rule applies (--chrM_contaminant True and a contig named chrM)."""
+        from ._lib import GenotypeParams
+        params = params or GenotypeParams.longsom_defaults(strict_cb=0)
+        site_keys = np.ascontiguousarray(site_keys, dtype=np.int64)
+        alt_sym = np.ascontiguousarray(alt_sym, dtype=np.uint8)
+        is_chrm = np.ascontiguousarray(is_chrm, dtype=np.uint8)
+        group_off = np.ascontiguousarray(group_off, dtype=np.int64)
+        assert len(site_keys) == len(alt_sym) == len(is_chrm)
+        _lib.check(self._lib.lsg_cellgeno_count(self._h, C.byref(params), int(max_depth), len(site_keys), _ptr(site_keys), _ptr(alt_sym), _ptr(is_chrm),
+                                                max(len(group_off) - 1, 0), _ptr(group_off), float(alpha2), float(beta2), float(pvalue)), "lsg_cellgeno_count")
+        self._cell_shape = (len(site_keys), self.n_cb)
+
+    def cellgeno_load_counts(self, dp, alt, is_chrm, alpha2: float = 0.2474528917555431, beta2: float = 162.03696139428595, pvalue: float = 0.01) -> None:
+        """The same verdicts for Dp / Alt tables [n_sites, n_cb] the caller brings instead of a count."""
+        dp = np.ascontiguousarray(dp, dtype=np.uint32); alt = np.ascontiguousarray(alt, dtype=np.uint32)
+        is_chrm = np.ascontiguousarray(is_chrm, dtype=np.uint8)
+        assert dp.ndim == 2 and dp.shape == alt.shape and len(is_chrm) == dp.shape[0]
+        _lib.check(self._lib.lsg_cellgeno_load_counts(self._h, dp.shape[0], dp.shape[1], _ptr(dp), _ptr(alt), _ptr(is_chrm), float(alpha2), float(beta2), float(pvalue)),
+                   "lsg_cellgeno_load_counts")
+        self._cell_shape = dp.shape
+
+    def cellgeno_fetch(self, cells: bool = True) -> dict:
+        """dp, alt, vaf4, p4, status, bin [n_sites, n_cb] (cells=False: not these) and n_covered, n_pass [n_cb] of the last cellgeno_count /
+        cellgeno_load_counts."""
+        shape = getattr(self, "_cell_shape", None)
+        if shape is None:
+            raise _lib.LsgError("cellgeno_fetch: nothing classified (cellgeno_count first)")
+        out = {"n_covered": np.zeros(shape[1], np.int64), "n_pass": np.zeros(shape[1], np.int64)}
+        if cells:
+            out.update(dp=np.zeros(shape, np.uint32), alt=np.zeros(shape, np.uint32), vaf4=np.zeros(shape, np.int32), p4=np.zeros(shape, np.int32),
+                       status=np.zeros(shape, np.uint8), bin=np.zeros(shape, np.uint8))
+        _lib.check(self._lib.lsg_cellgeno_fetch(self._h, *[_ptr(out.get(k)) for k in ("dp", "alt", "vaf4", "p4", "status", "bin", "n_covered", "n_pass")]), "lsg_cellgeno_fetch")
+        return out
+
+    def cellgeno_set_text(self, heads, indexes, labels, barcodes, celltypes, long_order, mat_order, col_src, float_cells: bool) -> None:
+        """The strings (per site: heads, indexes, labels; per barcode: barcodes, celltypes) and orders the tables TABLE_CELL_* print
+        (include/longsom_hip.h: lsg_cellgeno_text)."""
+        from ._lib import CellGenoText
+
+        def blob(strings):
+            enc = [s.encode() for s in strings]
+            off = np.zeros(len(enc) + 1, np.uint32)
+            if enc:
+                off[1:] = np.cumsum([len(e) for e in enc])
+            return b"".join(enc), off
+        parts = [blob(x) for x in (heads, indexes, labels, barcodes, celltypes)]
+        lo = np.ascontiguousarray(long_order, dtype=np.int32); mo = np.ascontiguousarray(mat_order, dtype=np.int32); cs = np.ascontiguousarray(col_src, dtype=np.int32)
+        t = CellGenoText()
+        for name, (b, off) in zip(("head", "index", "label", "cb", "ct"), parts):
+            setattr(t, name, b); setattr(t, name + "_off", off.ctypes.data)
+        t.n_long, t.long_order, t.n_mat, t.mat_order = len(lo), lo.ctypes.data, len(mo), mo.ctypes.data
+        t.n_cols, t.float_cells, t.col_src = len(cs), 1 if float_cells else 0, cs.ctypes.data
+        _lib.check(self._lib.lsg_cellgeno_set_text(self._h, C.byref(t)), "lsg_cellgeno_set_text")
 
     def betabinom_sf4(self, k, n, alpha: float, beta: float) -> np.ndarray:
         """round(betabinom.sf(k - 0.001, n, alpha, beta), 4) * 1e4 as int32, evaluated on the device."""
