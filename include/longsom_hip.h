@@ -473,12 +473,12 @@ int lsg_cellgeno_set_text(lsg_ctx* ctx, const lsg_cellgeno_text* text);
 typedef struct {
     int64_t n_reads_admitted, n_segs_admitted, n_events_admitted;
     int64_t n_entries, n_units, n_deep_units;
-    int64_t n_events_wave, n_events_deep;  /* events loaded by k_pileup_wave / k_pileup_deep      */
+    int64_t n_events_wave, n_events_deep;  /* events read by nobody (0) / by the count's range kernel */
     int64_t n_rows_wave, n_rows_deep;      /* rows emitted by each kernel (all cell types)         */
     float   ms_bin, ms_deep, ms_wave, ms_total;   /* HIP-event times of the last call             */
-    float   ms_walk;                       /* k_walk_block alone (HIP events around the launch)    */
+    float   ms_walk;                       /* the range kernel alone (HIP events around the launch) */
     float   pad_;
-    int64_t rows_by_kernel[4];             /* rows emitted by: 0 k_pileup_wave, 1 k_walk_block, 2 k_pileup_huge, 3 k_finalize_multi */
+    int64_t rows_by_kernel[4];             /* rows emitted by: 0 nobody, 1 the count's range kernel (k_tm_walk, k_tm_gather_count, k_tm_count_direct or k_tm_count_win: tiles that are one job), 2 nobody (always 0: a job of the wide walk belongs to a multi-job tile, its sums go to a slab), 3 k_finalize_multi */
     int64_t events_by_kernel[4];           /* events loaded by the same kernels (3 = 0)            */
 } lsg_count_stats;
 int lsg_get_count_stats(lsg_ctx* ctx, lsg_count_stats* out);

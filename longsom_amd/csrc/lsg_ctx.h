@@ -90,8 +90,8 @@ constexpr int TM_GROUP = 4;                 // blocks a wave of the walk loads p
 enum { TM_STORE = 0, TM_S0, TM_B, TM_RD, TM_META, TM_BLK_TILE, TM_BLK_OFF, TM_EXT,                                // per load
        TM_JOBS, TM_NE_UNITS, TM_NE_GEOM, TM_NE_NSLOT, TM_NE_ACC, TM_MULTI, TM_CHUNKS, TM_NBUF };                          // the plan: per load and number of cell types
 // one job of the walk: a tile, or a run-aligned piece of a deep one.  e0, e1: padded-entry range; w0: unit of (tile, cell type 0);
-// slab: of (job, cell type 0) or ~0; nj: jobs of the tile, bit 31 = the job is longer than the packed planes' fields hold (k_tm_walk_wide
-// takes it); cnt: entries of the tile; emid: where the job's second wave starts (a run start, or e1)
+// slab: of (job, cell type 0) or ~0; nj: jobs of the tile, bit 31 = the job is longer than the packed planes' fields hold (k_tm_walk_wide<SRC>
+// takes it, from the store or from the sorted keys); cnt: entries of the tile; emid: where the job's second wave starts (a run start, or e1)
 // base, off: the tile's first padded entry (8 x blocks before it) and its first entry in the sort's output; tstart, tid: the tile's
 // first position and contig - everything a job's workgroup needs in ONE record (k_tm_gather_count fetches the next job's while it works)
 struct TmJob { uint32_t e0, e1, w0, slab, nj, cnt, tile, emid, base, off; int32_t tstart, tid; };

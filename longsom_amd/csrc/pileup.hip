@@ -4,21 +4,28 @@
 //   split_bam's read routing            workflow/scripts/PreProcessing/SplitBamCellTypes.py:65-124
 //   run_interval (pileup + counting)    workflow/scripts/SNVCalling/BaseCellCounter.py:182-320
 //
-// ONE form of the count.  The store holds every (segment x 64-position tile) entry of the load, a tile's entries adjacent and sorted
-// by barcode, eight entries to a transposed 1 KB block; what a count decides per entry is admission (SAM flag, MAPQ, the pileup's
-// max_depth drops: THIS count's parameters) and the cell type of its barcode (THIS table):
-//   k_tm_resolve   one 32-bit meta word per entry, laid out so that the walk uses its fields as operands
-//   k_tm_walk      workgroup = two waves = one job (a tile, or a run-aligned piece of a deep one): streams the job's blocks with 16-byte
-//                  loads (lane = position, eight entries per load), adds into two pairs of LDS planes (both cell types of the pass in
-//                  one sweep: a barcode's run belongs to one cell type), distinct-cell numbers = counts minus duplicates inside a run;
-//                  then each wave finishes one cell type's unit (gates + rows) or writes its partial sums to the job's slab
-//   k_tm_walk_wide the same for a job a single barcode's run stretches past what the packed planes hold (32-bit planes, plain C++)
-//   k_finalize_multi  adds the slabs of multi-job tiles, gates, rows
+// A load's entries are (segment x 64-position tile), a tile's entries adjacent and sorted by barcode; what a count decides per entry is
+// admission (SAM flag, MAPQ, the pileup's max_depth drops: THIS count's parameters) and the cell type of its barcode (THIS table).  One
+// plan (store.hip: jobs, units, slabs), one run logic and one row format; FOUR forms of the range a wave counts, which differ in where an
+// entry's words and events come from.  build_store's ladder (store.hip) picks the form that makes a load's first count, run_count uses
+// the first form for every later one:
+//   k_tm_resolve + k_tm_walk  over the resident store (eight entries to a transposed 1 KB block): one 32-bit meta word per entry, laid
+//                  out so that the walk uses its fields as operands; the walk streams a job's blocks with 16-byte loads (lane =
+//                  position, eight entries per load).  Every count of a load that kept its store (run_count)
+//   k_tm_gather_count         counts while the load's gather writes the store: a load with lsg_set_count_at_load that keeps its store
+//   k_tm_count_direct<KO, AL> counts from the caller's events where they lie and keeps no store (lsg_set_store_policy): KO the sort
+//                  carried keys alone, AL tile-phased events fetched as 128-byte lines
+//   k_tm_count_win            the same over entries binned by 128-position windows (events phased modulo 128, keys alone, no store)
+// Around the range all four are one frame: workgroup = two waves = one job (a tile, or a run-aligned piece of a deep one); both cell
+// types of the pass go into LDS planes in one sweep (a barcode's run belongs to one cell type), distinct-cell numbers = counts minus
+// duplicates inside a run; then a wave finishes a unit (gates + rows) or writes its partial sums to the job's slab (tm_finish).
+//   k_tm_walk_wide<SRC>  a job a single barcode's run stretches past what the packed planes hold: 32-bit planes, plain C++, ONE walk
+//                  whose entry source is the store, the sorted keys by tiles or the sorted keys by windows (after the form that left it)
+//   k_finalize_multi     adds the slabs of multi-job tiles, gates, rows
 // More than two cell types: one resolve + walk pass per pair of cell types.  No global atomics on the event path, integer arithmetic
 // only (HBM- and issue-bound; no MFMA).
 #include "lsg_ctx.h"
 #include <hipcub/hipcub.hpp>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,7 +41,7 @@ constexpr int ARENA = 256;           // rows reserved per wave per allocation: t
 // ~90 per microsecond whichever of its words they name.
 enum { SC_COLS = 8, SC_OVERFLOW = 9, SC_READS = 10, SC_SEGS = 11, SC_EVENTS = 12, SC_ROWS_DEEP = 15,
        SC_ROWS = 16, SC_ROWS_SRC = 28, SC_NENT = 38, SC_QWALK = 48,
-       SC_ROWALLOC = 160, SC_ROWALLOC_STRIDE = 16, SC_COUNT = SC_ROWALLOC + SC_ROWALLOC_STRIDE * LSG_MAX_CELLTYPES };   // ROWS_SRC[4]: 1 k_tm_walk, 2 k_tm_walk_wide, 3 k_finalize_multi
+       SC_ROWALLOC = 160, SC_ROWALLOC_STRIDE = 16, SC_COUNT = SC_ROWALLOC + SC_ROWALLOC_STRIDE * LSG_MAX_CELLTYPES };   // ROWS_SRC[4]: 1 the four forms of the count (k_tm_walk, k_tm_gather_count, k_tm_count_direct, k_tm_count_win), 2 nobody (a wide job's sums go to a slab), 3 k_finalize_multi
 
 struct CountArgs {
     // reads
@@ -670,6 +677,81 @@ __device__ __forceinline__ void tm_walk_range(const TmArgs& tm, TmState& st, uin
     st.nc += st.mask & 0x10001u; st.mask = 0;                  // the run left open at the end (mask is 0 when none is)
 }
 
+// ================================================================================================
+// The frame around a range: what the four forms of the count do before and after a wave walks its entries, said once.
+// A job's record in registers (TmJob, lsg_ctx.h): jw holds its words in lanes 0..11.  (k_tm_count_win: a job is a window and `tile` its index.)
+struct JobRec {
+    uint32_t e0, e1, w0, slab, nj, tcnt, tile, emid, base, off; int32_t tstart; int tid;
+    __device__ __forceinline__ void load(uint32_t jw) {
+        e0 = rl(jw, 0); e1 = rl(jw, 1); w0 = rl(jw, 2); slab = rl(jw, 3); nj = rl(jw, 4); tcnt = rl(jw, 5); tile = rl(jw, 6); emid = rl(jw, 7); base = rl(jw, 8); off = rl(jw, 9);
+        tstart = (int32_t)rl(jw, 10); tid = (int)rl(jw, 11);
+    }
+};
+// a workgroup's planes (PLANE_WORDS of them) and its nc_sh (NC_WORDS) zeroed by its two waves
+template <int PLANE_WORDS, int NC_WORDS>
+__device__ __forceinline__ void tm_zero_planes(uint32_t* pl, uint32_t* nc_sh) {
+#pragma unroll
+    for (int i = 0; i < PLANE_WORDS / (4 * TMW_WAVES * 64); ++i) reinterpret_cast<uint4*>(pl)[i * (TMW_WAVES * 64) + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+    for (int i = 0; i < NC_WORDS / (TMW_WAVES * 64); ++i) nc_sh[i * (TMW_WAVES * 64) + threadIdx.x] = 0;
+}
+// A job's finish for one unit by one wave.  pc: the unit's counters (CNT reads them: TmCounters, or TwCounters of the windows' count); nc:
+// the lane's runs that counted an event; slab: the unit's slab of this job (tiles of several jobs).  A tile that is one job gets its gates
+// and rows here, narrow when no value can reach 2^16 (arena_slot: the wave's arena for narrow rows of this cell type, the next one for
+// wide rows); else the packed counters are unpacked into the slab, which k_finalize_multi adds to the tile's other jobs'.
+// (book: a pointer, as emit_unit takes it - through a reference the compiler knows it is not null, drops emit_unit's path without a book
+// and allocates k_tm_count_direct<true, false> differently: 36 bytes of scratch a lane where it has 28)
+template <class CNT>
+__device__ __forceinline__ void tm_finish(const CountArgs& a, const uint32_t* pc, uint32_t nc, uint32_t unit, uint32_t slab, uint32_t nj, uint32_t tcnt, int ct, int tid, int32_t tstart,
+                                          int lane, WaveBook* book, int refb, int arena_slot) {
+    CNT tot{pc, lane, 0u};
+    uint32_t dp = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dp += tot.BC(k);
+    tot.ncdup = dp - nc;
+    if (nj == 1) {
+        if (tcnt <= 256u) emit_unit<CNT, true>(a, tot, unit, ct, tid, tstart, lane, book, false, refb, arena_slot);
+        else emit_unit<CNT, false>(a, tot, unit, ct, tid, tstart, lane, book, false, refb, arena_slot + 1);
+    } else {
+        uint32_t* dst = a.macc + (uint64_t)slab * (NCTR * 64);
+        dst[lane] = tot.NCDUP();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            dst[(1 + k) * 64 + lane] = tot.DUP(k); dst[(9 + k) * 64 + lane] = tot.BC(k);
+            dst[(17 + k) * 64 + lane] = tot.BQ(k); dst[(25 + k) * 64 + lane] = tot.BCF(k);
+        }
+    }
+}
+// the workgroup's end: its waves' books added up by the first wave, one global atomic per counter
+__device__ __forceinline__ void books_flush(const CountArgs& a, const WaveBook (&books)[TMW_WAVES], int lane) {
+    if (threadIdx.x < 64) {
+        uint32_t rt = 0, cols = 0, rsrc = 0;
+        for (int w = 0; w < TMW_WAVES; ++w) {
+            const WaveBook& b = books[w];
+            if (lane < a.n_ct) rt += b.rows_true[lane];
+            cols += b.cols; rsrc += b.rows_src;
+        }
+        if (lane < a.n_ct && rt) atomicAdd(&a.scalars[SC_ROWS + lane], (unsigned long long)rt);
+        if (lane == 0) {
+            if (cols) atomicAdd(&a.scalars[SC_COLS], (unsigned long long)cols);
+            if (rsrc) atomicAdd(&a.scalars[SC_ROWS_SRC + 1], (unsigned long long)rsrc);
+        }
+    }
+}
+// admitted events / segments / entries a wave has seen, into the stat slot `who` picks (k_resolve_stats adds the slots up)
+struct TgStat { uint32_t ev, sg, ne; };
+__device__ __forceinline__ void stat_add(unsigned long long* stat_slots, uint32_t who, unsigned long long ev, unsigned long long sg, unsigned long long ne, int lane) {
+    if (lane == 0 && ne) {
+        unsigned long long* slot = stat_slots + (size_t)(who % IX_STAT_SLOTS) * 8;
+        atomicAdd(&slot[0], ev); atomicAdd(&slot[1], sg); atomicAdd(&slot[2], ne);
+    }
+}
+__device__ __forceinline__ void stat_flush(unsigned long long* stat_slots, const TgStat& stat, int lane, int wv) {      // (a lane's own entries: summed over the wave)
+    unsigned long long ev = stat.ev, sg = stat.sg, ne = stat.ne;
+    for (int o = 32; o > 0; o >>= 1) { ev += __shfl_down(ev, o); sg += __shfl_down(sg, o); ne += __shfl_down(ne, o); }
+    stat_add(stat_slots, blockIdx.x * TMW_WAVES + wv, ev, sg, ne, lane);
+}
+
 // Workgroup = two waves = one job at a time: each wave walks half of the job's entries (cut at a run start) into the job's planes
 // (8 KB per workgroup: 4 KB per wave, which is what lets 6-8 waves per SIMD be resident), then each wave finishes one cell type's unit.
 __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(8))) void k_tm_walk(CountArgs a, TmArgs tm) {
@@ -704,9 +786,7 @@ __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
             int refb = 'N';
             if (nj == 1) { const int64_t pos = (int64_t)tstart + lane; if (pos >= 1 && pos < a.contig_len[tid]) refb = a.ref_ptr[tid][pos]; }
             __syncthreads();                                   // both waves are done with the job before
-#pragma unroll
-            for (int i = 0; i < 2 * 2 * 8 * 64 / (4 * TMW_WAVES * 64); ++i) reinterpret_cast<uint4*>(pl)[i * (TMW_WAVES * 64) + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-            (&nc_sh[0][0])[threadIdx.x] = 0;
+            tm_zero_planes<2 * 2 * 8 * 64, 2 * 64>(pl, &nc_sh[0][0]);
             __syncthreads();
             TmState st; st.nc = 0; st.mask = 0;
             const uint32_t s0 = wv ? emid : e0, s1 = wv ? e1 : emid;
@@ -718,43 +798,12 @@ __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
             __syncthreads();
             // the tile's units of this pass: wave = cell type
             const int ct = tm.ct_base + wv;
-            if (ct < a.n_ct) {
-                const uint32_t* pc = pl + wv * 1024;
-                uint32_t dp = 0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) dp += pc[512 + k * 64 + lane] & 0xffffu;
-                const TmCounters tot{pc, lane, dp - nc_sh[wv][lane]};
-                if (nj == 1) {
-                    if (tcnt <= 256u) emit_unit<TmCounters, true>(a, tot, w0 + ct, ct, tid, tstart, lane, &book, false, refb, 0);
-                    else emit_unit<TmCounters, false>(a, tot, w0 + ct, ct, tid, tstart, lane, &book, false, refb, 1);
-                } else {
-                    uint32_t* dst = a.macc + (uint64_t)(slab + (uint32_t)ct * nj) * (NCTR * 64);
-                    dst[lane] = tot.NCDUP();
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const uint32_t lo = pc[k * 64 + lane], hi = pc[512 + k * 64 + lane];
-                        dst[(1 + k) * 64 + lane] = hi >> 16; dst[(9 + k) * 64 + lane] = hi & 0xffffu;
-                        dst[(17 + k) * 64 + lane] = lo & 0xfffffu; dst[(25 + k) * 64 + lane] = lo >> 20;
-                    }
-                }
-            }
+            if (ct < a.n_ct) tm_finish<TmCounters>(a, pl + wv * 1024, nc_sh[wv][lane], w0 + ct, slab + (uint32_t)ct * nj, nj, tcnt, ct, tid, tstart, lane, &book, refb, 0);
         }
     }
     lds_fence();
     __syncthreads();
-    if (threadIdx.x < 64) {
-        uint32_t rt = 0, cols = 0, rsrc = 0;
-        for (int w = 0; w < TMW_WAVES; ++w) {
-            const WaveBook& b = books[w];
-            if (lane < a.n_ct) rt += b.rows_true[lane];
-            cols += b.cols; rsrc += b.rows_src;
-        }
-        if (lane < a.n_ct && rt) atomicAdd(&a.scalars[SC_ROWS + lane], (unsigned long long)rt);
-        if (lane == 0) {
-            if (cols) atomicAdd(&a.scalars[SC_COLS], (unsigned long long)cols);
-            if (rsrc) atomicAdd(&a.scalars[SC_ROWS_SRC + 1], (unsigned long long)rsrc);
-        }
-    }
+    books_flush(a, books, lane);
 }
 
 // ================================================================================================
@@ -790,7 +839,6 @@ typedef uint32_t tg_u32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(2))) TgU4A2 { tg_u32x4 v; };
 constexpr uint32_t TG_RV_WHI = 1u << 29, TG_RV_SEGFIRST = 1u << 30, TG_RV_FWD = 1u << 31, TG_RV_READ = TG_RV_WHI - 1u;      // (store.hip RV_*)
 struct TgKeys { uint64_t k; uint32_t v; };
-struct TgStat { uint32_t ev, sg, ne; };
 struct TgPre { uint32_t bits, ctv, admw; };      // an entry's meta word in the making: flags | bit of its read | events, and the two table words looked up for it
 
 // ---- K  the sorted (key, value) of the 32 entries from padded entry p0 on (lanes 0..31), and the keys on either side (lanes 32, 33).
@@ -1003,85 +1051,42 @@ __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
         // instead of four dependent round trips (chunk -> job -> tile offsets -> keys)
         uint32_t jw = 0;
         if (lane < TM_JOB_WORDS) jw = reinterpret_cast<const uint32_t*>(tm.jobs + jx0)[lane];
-        uint32_t e0 = rl(jw, 0), e1 = rl(jw, 1), w0 = rl(jw, 2), slab = rl(jw, 3), nj = rl(jw, 4), tcnt = rl(jw, 5), tile = rl(jw, 6), emid = rl(jw, 7), base = rl(jw, 8), off = rl(jw, 9);
-        int32_t tstart = (int32_t)rl(jw, 10); int tid = (int)rl(jw, 11);
-        TgKeys K0 = tg_load_keys(tg, ((wv ? emid : e0) >> 3) * 8, base, off, tcnt, lane);
+        JobRec jb; jb.load(jw);
+        TgKeys K0 = tg_load_keys(tg, ((wv ? jb.emid : jb.e0) >> 3) * 8, jb.base, jb.off, jb.tcnt, lane);
         for (uint32_t jx = jx0; jx < jx_end; ++jx) {
             {   // (every lane loads - a clamped place past the chunk's last job - so that nothing here has to wait)
                 const uint32_t jn = jx + 1 < jx_end ? jx + 1 : jx;
                 jw = reinterpret_cast<const uint32_t*>(tm.jobs + jn)[lane < TM_JOB_WORDS ? lane : 0];
             }
-            const bool in_region = tile >= a.tile_lo && tile < a.tile_hi, counting = in_region && !(nj & TMJ_WIDE);
+            const bool in_region = jb.tile >= a.tile_lo && jb.tile < a.tile_hi, counting = in_region && !(jb.nj & TMJ_WIDE);
             int refb = 'N';
-            if (nj == 1 && counting) { const int64_t pos = (int64_t)tstart + lane; if (pos >= 1 && pos < a.contig_len[tid]) refb = a.ref_ptr[tid][pos]; }
+            if (jb.nj == 1 && counting) { const int64_t pos = (int64_t)jb.tstart + lane; if (pos >= 1 && pos < a.contig_len[jb.tid]) refb = a.ref_ptr[jb.tid][pos]; }
             __syncthreads();                                   // both waves are done with the job before
-            if (counting) {
-#pragma unroll
-                for (int i = 0; i < 2 * 2 * 8 * 64 / (4 * TMW_WAVES * 64); ++i) reinterpret_cast<uint4*>(pl)[i * (TMW_WAVES * 64) + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-                (&nc_sh[0][0])[threadIdx.x] = 0;
-            }
+            if (counting) tm_zero_planes<2 * 2 * 8 * 64, 2 * 64>(pl, &nc_sh[0][0]);
             __syncthreads();
             TmState st; st.nc = 0; st.mask = 0;
-            const uint32_t s0r = wv ? emid : e0, s1r = wv ? e1 : emid;
+            const uint32_t s0r = wv ? jb.emid : jb.e0, s1r = wv ? jb.e1 : jb.emid;
             if (s1r > s0r) {
-                tg_range(a, tm, tg, st, stat, s0r, s1r, base, off, tcnt, in_region, counting, thr, pkl0, one, lane, xts[wv], tmask, K0);
+                tg_range(a, tm, tg, st, stat, s0r, s1r, jb.base, jb.off, jb.tcnt, in_region, counting, thr, pkl0, one, lane, xts[wv], tmask, K0);
                 if (counting) {
                     if (st.nc & 0xffffu) atomicAdd(&nc_sh[0][lane], st.nc & 0xffffu);
                     if (st.nc >> 16) atomicAdd(&nc_sh[1][lane], st.nc >> 16);
                 }
             }
             // this job's fields for the emission below; then the next job's (its record has arrived long ago) and its first keys
-            const uint32_t c_w0 = w0, c_slab = slab, c_nj = nj, c_tcnt = tcnt; const int32_t c_tstart = tstart; const int c_tid = tid;
-            e0 = rl(jw, 0); e1 = rl(jw, 1); w0 = rl(jw, 2); slab = rl(jw, 3); nj = rl(jw, 4); tcnt = rl(jw, 5); tile = rl(jw, 6); emid = rl(jw, 7); base = rl(jw, 8); off = rl(jw, 9);
-            tstart = (int32_t)rl(jw, 10); tid = (int)rl(jw, 11);
-            K0 = tg_load_keys(tg, ((wv ? emid : e0) >> 3) * 8, base, off, tcnt, lane);
+            const JobRec cj = jb;
+            jb.load(jw);
+            K0 = tg_load_keys(tg, ((wv ? jb.emid : jb.e0) >> 3) * 8, jb.base, jb.off, jb.tcnt, lane);
             __syncthreads();
             const int ct = tm.ct_base + wv;
-            if (counting && ct < a.n_ct) {                   // the tile's units of this pass: wave = cell type (as in k_tm_walk)
-                const uint32_t* pc = pl + wv * 1024;
-                uint32_t dp = 0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) dp += pc[512 + k * 64 + lane] & 0xffffu;
-                const TmCounters tot{pc, lane, dp - nc_sh[wv][lane]};
-                if (c_nj == 1) {
-                    if (c_tcnt <= 256u) emit_unit<TmCounters, true>(a, tot, c_w0 + ct, ct, c_tid, c_tstart, lane, &book, false, refb, 0);
-                    else emit_unit<TmCounters, false>(a, tot, c_w0 + ct, ct, c_tid, c_tstart, lane, &book, false, refb, 1);
-                } else {
-                    uint32_t* dst = a.macc + (uint64_t)(c_slab + (uint32_t)ct * c_nj) * (NCTR * 64);
-                    dst[lane] = tot.NCDUP();
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const uint32_t lo = pc[k * 64 + lane], hi = pc[512 + k * 64 + lane];
-                        dst[(1 + k) * 64 + lane] = hi >> 16; dst[(9 + k) * 64 + lane] = hi & 0xffffu;
-                        dst[(17 + k) * 64 + lane] = lo & 0xfffffu; dst[(25 + k) * 64 + lane] = lo >> 20;
-                    }
-                }
-            }
+            if (counting && ct < a.n_ct)                     // the tile's units of this pass: wave = cell type (as in k_tm_walk)
+                tm_finish<TmCounters>(a, pl + wv * 1024, nc_sh[wv][lane], cj.w0 + ct, cj.slab + (uint32_t)ct * cj.nj, cj.nj, cj.tcnt, ct, cj.tid, cj.tstart, lane, &book, refb, 0);
         }
     }
     lds_fence();
     __syncthreads();
-    {   // admitted events / segments / entries of this workgroup (k_resolve_stats adds the slots up)
-        unsigned long long ev = stat.ev, sg = stat.sg, ne = stat.ne;
-        for (int o = 32; o > 0; o >>= 1) { ev += __shfl_down(ev, o); sg += __shfl_down(sg, o); ne += __shfl_down(ne, o); }
-        if (lane == 0 && ne) {
-            unsigned long long* slot = tg.stat_slots + (size_t)((blockIdx.x * TMW_WAVES + wv) % IX_STAT_SLOTS) * 8;
-            atomicAdd(&slot[0], ev); atomicAdd(&slot[1], sg); atomicAdd(&slot[2], ne);
-        }
-    }
-    if (threadIdx.x < 64) {
-        uint32_t rt = 0, cols = 0, rsrc = 0;
-        for (int w = 0; w < TMW_WAVES; ++w) {
-            const WaveBook& b = books[w];
-            if (lane < a.n_ct) rt += b.rows_true[lane];
-            cols += b.cols; rsrc += b.rows_src;
-        }
-        if (lane < a.n_ct && rt) atomicAdd(&a.scalars[SC_ROWS + lane], (unsigned long long)rt);
-        if (lane == 0) {
-            if (cols) atomicAdd(&a.scalars[SC_COLS], (unsigned long long)cols);
-            if (rsrc) atomicAdd(&a.scalars[SC_ROWS_SRC + 1], (unsigned long long)rsrc);
-        }
-    }
+    stat_flush(tg.stat_slots, stat, lane, wv);
+    books_flush(a, books, lane);
 }
 
 // ================================================================================================
@@ -1253,6 +1258,56 @@ __device__ __forceinline__ void td_range64(const CountArgs& a, const TmArgs& tm,
     st.nc += st.mask & 0x10001u; st.mask = 0;
 }
 
+// WHO takes WHICH job, in the two counts that keep no store (k_tm_count_direct, k_tm_count_win: a job = a tile or a window, or a piece of one).
+// The jobs lie in tile order, and a segment's entries in two adjacent tiles are adjacent in the caller's array: the
+// 128-byte line that holds the end of the one holds the start of the other, and the fabric moves 1.77 lines per entry (44.9 GB a launch
+// for 19.9 GB of events and keys) where 0.8 would do if every line were fetched once.  The jobs are dealt in blocks of 64 consecutive
+// ones to the eight XCDs, and the workgroups of an XCD take the jobs of its blocks ONE BY ONE off the XCD's queue, so that at any moment
+// an XCD works on a few hundred consecutive tiles, started a fraction of a microsecond apart, whose shared lines could meet in its L2.
+// Measured: they mostly do not (42.1 GB; 12 % of the L2's read requests hit) - a job lasts ~50 us, the two tiles' runs through the
+// same barcodes drift apart by more than the ~6 us a line stays in 4 MB of L2 - but the finer hand-out balances the tail better than
+// chunks did (8.4 -> 8.2 ms with twelve workgroups per CU), so it stays.  A workgroup whose XCD has run dry helps the next one.  The id
+// of the job after next is asked for (one atomic of thread 0) while this job is counted; the next job's record and first keys travel
+// as before.
+struct XcdQueue {
+    static constexpr uint32_t NO_JOB = 0xffffffffu;
+    unsigned long long* queues;                // the XCDs' queues, 128 bytes apart
+    uint32_t njobs, nblocks, xcd;
+    uint32_t steal;                            // (thread 0's: queues it has found empty)
+    uint32_t q_q, q_n;                         // the question that is under way: queue, and (thread 0's) its answer
+    __device__ __forceinline__ XcdQueue(unsigned long long* queues_, uint32_t njobs_)
+        : queues(queues_), njobs(njobs_), nblocks((njobs_ + 63u) >> 6), xcd(blockIdx.x & 7u), steal(0), q_q(0), q_n(0) {}      // (workgroups are dealt to the XCDs round-robin)
+    __device__ __forceinline__ uint32_t job_of(uint32_t q, uint32_t n) const {            // n-th job of XCD q's blocks, or NO_JOB past them
+        const uint32_t blk = 8u * (n >> 6) + q;
+        const uint32_t jx = (blk << 6) + (n & 63u);
+        return blk < nblocks && jx < njobs ? jx : NO_JOB;
+    }
+    __device__ __forceinline__ uint32_t take() {                                          // (thread 0)
+        while (steal < 8u) {
+            const uint32_t q = (xcd + steal) & 7u;
+            const uint32_t n = (uint32_t)atomicAdd(queues + q * 16u, 1ull);
+            const uint32_t jx = job_of(q, n);
+            if (jx != NO_JOB) return jx;
+            if (8u * (n >> 6) + q >= nblocks) ++steal;                                    // (past the queue's last block; a short last block: ask again)
+        }
+        return NO_JOB;
+    }
+    // the job after next: the fast way is ONE atomic whose answer is looked at after this job's entries (a queue that has run dry is rare)
+    __device__ __forceinline__ void ask() {
+        q_n = 0;
+        q_q = (xcd + steal) & 7u;
+        if (threadIdx.x == 0 && steal < 8u) q_n = (uint32_t)atomicAdd(queues + q_q * 16u, 1ull);
+    }
+    __device__ __forceinline__ uint32_t answer() {                                        // (thread 0)
+        uint32_t jn2 = NO_JOB;
+        if (steal < 8u) {
+            jn2 = job_of(q_q, q_n);
+            if (jn2 == NO_JOB) { if (8u * (q_n >> 6) + q_q >= nblocks) ++steal; jn2 = take(); }
+        }
+        return jn2;
+    }
+};
+
 template <bool KO, bool AL>
 __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(LSG_TD_WAVES))) void k_tm_count_direct(CountArgs a, TmArgs tm, TgArgs tg) {
     __shared__ __attribute__((aligned(8192))) uint32_t planes[2][2][8 * 64];
@@ -1268,136 +1323,55 @@ __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     uint32_t one = 1u;
     asm volatile("" : "+v"(one));
     TgStat stat; stat.ev = 0; stat.sg = 0; stat.ne = 0;
-    // WHO takes WHICH job.  The jobs lie in tile order, and a segment's entries in two adjacent tiles are adjacent in the caller's array: the
-    // 128-byte line that holds the end of the one holds the start of the other, and the fabric moves 1.77 lines per entry (44.9 GB a launch
-    // for 19.9 GB of events and keys) where 0.8 would do if every line were fetched once.  The jobs are dealt in blocks of 64 consecutive
-    // ones to the eight XCDs, and the workgroups of an XCD take the jobs of its blocks ONE BY ONE off the XCD's queue, so that at any moment
-    // an XCD works on a few hundred consecutive tiles, started a fraction of a microsecond apart, whose shared lines could meet in its L2.
-    // Measured: they mostly do not (42.1 GB; 12 % of the L2's read requests hit) - a job lasts ~50 us, the two tiles' runs through the
-    // same barcodes drift apart by more than the ~6 us a line stays in 4 MB of L2 - but the finer hand-out balances the tail better than
-    // chunks did (8.4 -> 8.2 ms with twelve workgroups per CU), so it stays.  A workgroup whose XCD has run dry helps the next one.  The id
-    // of the job after next is asked for (one atomic of thread 0) while this job is counted; the next job's record and first keys travel
-    // as before.
-    const uint32_t njobs = tm.njobs, nblocks = (njobs + 63u) >> 6;
-    const uint32_t xcd = blockIdx.x & 7u;      // (workgroups are dealt to the XCDs round-robin)
-    constexpr uint32_t NO_JOB = 0xffffffffu;
-    uint32_t steal = 0;                                                                   // (thread 0's: queues it has found empty)
-    auto job_of = [&](uint32_t q, uint32_t n) -> uint32_t {                               // n-th job of XCD q's blocks, or NO_JOB past them
-        const uint32_t blk = 8u * (n >> 6) + q;
-        const uint32_t jx = (blk << 6) + (n & 63u);
-        return blk < nblocks && jx < njobs ? jx : NO_JOB;
-    };
-    auto take = [&]() -> uint32_t {                                                       // (thread 0)
-        while (steal < 8u) {
-            const uint32_t q = (xcd + steal) & 7u;
-            const uint32_t n = (uint32_t)atomicAdd(tg.queues + q * 16u, 1ull);
-            const uint32_t jx = job_of(q, n);
-            if (jx != NO_JOB) return jx;
-            if (8u * (n >> 6) + q >= nblocks) ++steal;                                    // (past the queue's last block; a short last block: ask again)
-        }
-        return NO_JOB;
-    };
-    if (threadIdx.x == 0) { s_q[0] = take(); s_q[1] = take(); }
+    XcdQueue q(tg.queues, tm.njobs);
+    if (threadIdx.x == 0) { s_q[0] = q.take(); s_q[1] = q.take(); }
     __syncthreads();
     uint32_t cur = rl(s_q[0], 0), nxt = rl(s_q[1], 0);
-    if (cur != NO_JOB) {
+    if (cur != XcdQueue::NO_JOB) {
         uint32_t jw = 0;
         if (lane < TM_JOB_WORDS) jw = reinterpret_cast<const uint32_t*>(tm.jobs + cur)[lane];
-        uint32_t e0 = rl(jw, 0), e1 = rl(jw, 1), w0 = rl(jw, 2), slab = rl(jw, 3), nj = rl(jw, 4), tcnt = rl(jw, 5), tile = rl(jw, 6), emid = rl(jw, 7), base = rl(jw, 8), off = rl(jw, 9);
-        int32_t tstart = (int32_t)rl(jw, 10); int tid = (int)rl(jw, 11);
+        JobRec jb; jb.load(jw);
         // (the first group's keys of the wave's range, and the entry before it)
-        auto first_i = [&]() -> uint32_t { return (wv ? emid : e0) - base; };
+        auto first_i = [&]() -> uint32_t { return (wv ? jb.emid : jb.e0) - jb.base; };
         TdKeys64 K64{}; uint64_t kb = 0;
-        auto prefetch = [&]() { const uint32_t i = first_i(); K64 = td_load_keys64<KO>(tg, i, off, tcnt, lane); kb = __builtin_nontemporal_load(tg.key + off + (i ? i - 1u : 0u)); };
+        auto prefetch = [&]() { const uint32_t i = first_i(); K64 = td_load_keys64<KO>(tg, i, jb.off, jb.tcnt, lane); kb = __builtin_nontemporal_load(tg.key + jb.off + (i ? i - 1u : 0u)); };
         prefetch();
         while (true) {
-            jw = reinterpret_cast<const uint32_t*>(tm.jobs + (nxt != NO_JOB ? nxt : cur))[lane < TM_JOB_WORDS ? lane : 0];      // (every lane loads: nothing here waits)
-            const bool counting = tile >= a.tile_lo && tile < a.tile_hi && !(nj & TMJ_WIDE);      // (the wide jobs: k_tm_walk_wide_direct)
+            jw = reinterpret_cast<const uint32_t*>(tm.jobs + (nxt != XcdQueue::NO_JOB ? nxt : cur))[lane < TM_JOB_WORDS ? lane : 0];      // (every lane loads: nothing here waits)
+            const bool counting = jb.tile >= a.tile_lo && jb.tile < a.tile_hi && !(jb.nj & TMJ_WIDE);      // (the wide jobs: k_tm_walk_wide)
             int refb = 'N';
-            if (nj == 1 && counting) { const int64_t pos = (int64_t)tstart + lane; if (pos >= 1 && pos < a.contig_len[tid]) refb = a.ref_ptr[tid][pos]; }
+            if (jb.nj == 1 && counting) { const int64_t pos = (int64_t)jb.tstart + lane; if (pos >= 1 && pos < a.contig_len[jb.tid]) refb = a.ref_ptr[jb.tid][pos]; }
             __syncthreads();                                   // both waves are done with the job before
-            // the job after next: the fast way is ONE atomic whose answer is looked at after this job's entries (a queue that has run dry is rare)
-            uint32_t q_n = 0;
-            const uint32_t q_q = (xcd + steal) & 7u;
-            if (threadIdx.x == 0 && steal < 8u) q_n = (uint32_t)atomicAdd(tg.queues + q_q * 16u, 1ull);
-            if (counting) {
-#pragma unroll
-                for (int i = 0; i < 2 * 2 * 8 * 64 / (4 * TMW_WAVES * 64); ++i) reinterpret_cast<uint4*>(pl)[i * (TMW_WAVES * 64) + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-                (&nc_sh[0][0])[threadIdx.x] = 0;
-            }
+            q.ask();
+            if (counting) tm_zero_planes<2 * 2 * 8 * 64, 2 * 64>(pl, &nc_sh[0][0]);
             __syncthreads();
             // the tile's entries [i0, i1) of this wave, as indices into the tile's part of the sort's output (the plan cuts jobs in padded
             // store indices: base is the tile's first one)
-            const uint32_t s0r = wv ? emid : e0, s1r = wv ? e1 : emid;
-            const uint32_t i0 = s0r - base, i1 = s1r - base < tcnt ? s1r - base : tcnt;
+            const uint32_t s0r = wv ? jb.emid : jb.e0, s1r = wv ? jb.e1 : jb.emid;
+            const uint32_t i0 = s0r - jb.base, i1 = s1r - jb.base < jb.tcnt ? s1r - jb.base : jb.tcnt;
             if (counting && i1 > i0) {
                 TmState st; st.nc = 0; st.mask = 0;
-                td_range64<KO, AL>(a, tm, tg, st, stat, i0, i1, off, tcnt, thr, pkl0, one, lane, K64, kb);
+                td_range64<KO, AL>(a, tm, tg, st, stat, i0, i1, jb.off, jb.tcnt, thr, pkl0, one, lane, K64, kb);
                 if (st.nc & 0xffffu) atomicAdd(&nc_sh[0][lane], st.nc & 0xffffu);
                 if (st.nc >> 16) atomicAdd(&nc_sh[1][lane], st.nc >> 16);
             }
-            if (threadIdx.x == 0) {
-                uint32_t jn2 = NO_JOB;
-                if (steal < 8u) {
-                    jn2 = job_of(q_q, q_n);
-                    if (jn2 == NO_JOB) { if (8u * (q_n >> 6) + q_q >= nblocks) ++steal; jn2 = take(); }
-                }
-                s_q[2] = jn2;
-            }
-            const uint32_t c_w0 = w0, c_slab = slab, c_nj = nj, c_tcnt = tcnt; const int32_t c_tstart = tstart; const int c_tid = tid;
-            e0 = rl(jw, 0); e1 = rl(jw, 1); w0 = rl(jw, 2); slab = rl(jw, 3); nj = rl(jw, 4); tcnt = rl(jw, 5); tile = rl(jw, 6); emid = rl(jw, 7); base = rl(jw, 8); off = rl(jw, 9);
-            tstart = (int32_t)rl(jw, 10); tid = (int)rl(jw, 11);
+            if (threadIdx.x == 0) s_q[2] = q.answer();
+            const JobRec cj = jb;
+            jb.load(jw);
             prefetch();
             __syncthreads();
             const uint32_t nn = rl(s_q[2], 0);
             const int ct = tm.ct_base + wv;
-            if (counting && ct < a.n_ct) {                   // the tile's units of this pass: wave = cell type (as in k_tm_walk)
-                const uint32_t* pc = pl + wv * 1024;
-                uint32_t dp = 0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) dp += pc[512 + k * 64 + lane] & 0xffffu;
-                const TmCounters tot{pc, lane, dp - nc_sh[wv][lane]};
-                if (c_nj == 1) {
-                    if (c_tcnt <= 256u) emit_unit<TmCounters, true>(a, tot, c_w0 + ct, ct, c_tid, c_tstart, lane, &book, false, refb, 0);
-                    else emit_unit<TmCounters, false>(a, tot, c_w0 + ct, ct, c_tid, c_tstart, lane, &book, false, refb, 1);
-                } else {
-                    uint32_t* dst = a.macc + (uint64_t)(c_slab + (uint32_t)ct * c_nj) * (NCTR * 64);
-                    dst[lane] = tot.NCDUP();
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const uint32_t lo = pc[k * 64 + lane], hi = pc[512 + k * 64 + lane];
-                        dst[(1 + k) * 64 + lane] = hi >> 16; dst[(9 + k) * 64 + lane] = hi & 0xffffu;
-                        dst[(17 + k) * 64 + lane] = lo & 0xfffffu; dst[(25 + k) * 64 + lane] = lo >> 20;
-                    }
-                }
-            }
-            if (nxt == NO_JOB) break;
+            if (counting && ct < a.n_ct)                     // the tile's units of this pass: wave = cell type (as in k_tm_walk)
+                tm_finish<TmCounters>(a, pl + wv * 1024, nc_sh[wv][lane], cj.w0 + ct, cj.slab + (uint32_t)ct * cj.nj, cj.nj, cj.tcnt, ct, cj.tid, cj.tstart, lane, &book, refb, 0);
+            if (nxt == XcdQueue::NO_JOB) break;
             cur = nxt; nxt = nn;
         }
     }
     lds_fence();
     __syncthreads();
-    {
-        unsigned long long ev = stat.ev, sg = stat.sg, ne = stat.ne;
-        for (int o = 32; o > 0; o >>= 1) { ev += __shfl_down(ev, o); sg += __shfl_down(sg, o); ne += __shfl_down(ne, o); }
-        if (lane == 0 && ne) {
-            unsigned long long* slot = tg.stat_slots + (size_t)((blockIdx.x * TMW_WAVES + wv) % IX_STAT_SLOTS) * 8;
-            atomicAdd(&slot[0], ev); atomicAdd(&slot[1], sg); atomicAdd(&slot[2], ne);
-        }
-    }
-    if (threadIdx.x < 64) {
-        uint32_t rt = 0, cols = 0, rsrc = 0;
-        for (int w = 0; w < TMW_WAVES; ++w) {
-            const WaveBook& b = books[w];
-            if (lane < a.n_ct) rt += b.rows_true[lane];
-            cols += b.cols; rsrc += b.rows_src;
-        }
-        if (lane < a.n_ct && rt) atomicAdd(&a.scalars[SC_ROWS + lane], (unsigned long long)rt);
-        if (lane == 0) {
-            if (cols) atomicAdd(&a.scalars[SC_COLS], (unsigned long long)cols);
-            if (rsrc) atomicAdd(&a.scalars[SC_ROWS_SRC + 1], (unsigned long long)rsrc);
-        }
-    }
+    stat_flush(tg.stat_slots, stat, lane, wv);
+    books_flush(a, books, lane);
 }
 
 // One entry of a 128-position WINDOW at the lane's two positions (k_tm_count_win below): what two tm_add<.., true> calls do - the lane's
@@ -1664,65 +1638,39 @@ __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
     uint32_t one = 1u;
     asm volatile("" : "+v"(one));
     TgStat stat; stat.ev = 0; stat.sg = 0; stat.ne = 0;
-    // (who takes which job: k_tm_count_direct's queues, a job = a window or a run-aligned piece of a deep one)
-    const uint32_t njobs = tm.njobs, nblocks = (njobs + 63u) >> 6;
-    const uint32_t xcd = blockIdx.x & 7u;
-    constexpr uint32_t NO_JOB = 0xffffffffu;
-    uint32_t steal = 0;
-    auto job_of = [&](uint32_t q, uint32_t nn) -> uint32_t {
-        const uint32_t blk = 8u * (nn >> 6) + q;
-        const uint32_t jx = (blk << 6) + (nn & 63u);
-        return blk < nblocks && jx < njobs ? jx : NO_JOB;
-    };
-    auto take = [&]() -> uint32_t {
-        while (steal < 8u) {
-            const uint32_t q = (xcd + steal) & 7u;
-            const uint32_t nn = (uint32_t)atomicAdd(tg.queues + q * 16u, 1ull);
-            const uint32_t jx = job_of(q, nn);
-            if (jx != NO_JOB) return jx;
-            if (8u * (nn >> 6) + q >= nblocks) ++steal;
-        }
-        return NO_JOB;
-    };
-    if (threadIdx.x == 0) { s_q[0] = take(); s_q[1] = take(); }
+    XcdQueue q(tg.queues, tm.njobs);      // (a job = a window or a run-aligned piece of a deep one)
+    if (threadIdx.x == 0) { s_q[0] = q.take(); s_q[1] = q.take(); }
     __syncthreads();
     uint32_t cur = rl(s_q[0], 0), nxt = rl(s_q[1], 0);
-    if (cur != NO_JOB) {
+    if (cur != XcdQueue::NO_JOB) {
         uint32_t jw = 0;
         if (lane < TM_JOB_WORDS) jw = reinterpret_cast<const uint32_t*>(tm.jobs + cur)[lane];
-        uint32_t e0 = rl(jw, 0), e1 = rl(jw, 1), w0 = rl(jw, 2), slab = rl(jw, 3), nj = rl(jw, 4), tcnt = rl(jw, 5), win = rl(jw, 6), emid = rl(jw, 7), base = rl(jw, 8), off = rl(jw, 9);
-        int32_t tstart = (int32_t)rl(jw, 10); int tid = (int)rl(jw, 11);
-        auto first_i = [&]() -> uint32_t { return (wv ? emid : e0) - base; };
+        JobRec jb; jb.load(jw);
+        auto first_i = [&]() -> uint32_t { return (wv ? jb.emid : jb.e0) - jb.base; };
         uint64_t K64 = 0, kb = 0;
         auto prefetch = [&]() {
-            const uint32_t i = first_i(), ie = i + (uint32_t)(lane & (TW_G - 1)), ic = ie < tcnt ? ie : tcnt - 1u;
-            K64 = __builtin_nontemporal_load(tg.key + off + ic); kb = __builtin_nontemporal_load(tg.key + off + (i ? i - 1u : 0u));
+            const uint32_t i = first_i(), ie = i + (uint32_t)(lane & (TW_G - 1)), ic = ie < jb.tcnt ? ie : jb.tcnt - 1u;
+            K64 = __builtin_nontemporal_load(tg.key + jb.off + ic); kb = __builtin_nontemporal_load(tg.key + jb.off + (i ? i - 1u : 0u));
         };
         prefetch();
         while (true) {
-            jw = reinterpret_cast<const uint32_t*>(tm.jobs + (nxt != NO_JOB ? nxt : cur))[lane < TM_JOB_WORDS ? lane : 0];
+            jw = reinterpret_cast<const uint32_t*>(tm.jobs + (nxt != XcdQueue::NO_JOB ? nxt : cur))[lane < TM_JOB_WORDS ? lane : 0];
             // the wave's tile of the window: tile 2 win + wv, whose units this wave finishes
-            const uint32_t my_tile = 2u * win + (uint32_t)wv;
+            const uint32_t win = jb.tile;
             const bool in_a = 2u * win >= a.tile_lo && 2u * win < a.tile_hi, in_b = 2u * win + 1u >= a.tile_lo && 2u * win + 1u < a.tile_hi;
-            const bool counting = (in_a || in_b) && !(nj & TMJ_WIDE);
+            const bool counting = (in_a || in_b) && !(jb.nj & TMJ_WIDE);
             const bool mine = counting && (wv ? in_b : in_a);
             int refb = 'N';
-            if (nj == 1 && mine) { const int64_t pos = (int64_t)tstart + 64 * wv + lane; if (pos >= 1 && pos < a.contig_len[tid]) refb = a.ref_ptr[tid][pos]; }
+            if (jb.nj == 1 && mine) { const int64_t pos = (int64_t)jb.tstart + 64 * wv + lane; if (pos >= 1 && pos < a.contig_len[jb.tid]) refb = a.ref_ptr[jb.tid][pos]; }
             __syncthreads();
-            uint32_t q_n = 0;
-            const uint32_t q_q = (xcd + steal) & 7u;
-            if (threadIdx.x == 0 && steal < 8u) q_n = (uint32_t)atomicAdd(tg.queues + q_q * 16u, 1ull);
-            if (counting) {
-#pragma unroll
-                for (int i = 0; i < 2 * 2 * 2 * 8 * 64 / (4 * TMW_WAVES * 64); ++i) reinterpret_cast<uint4*>(pl)[i * (TMW_WAVES * 64) + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-                (&nc_sh[0][0][0])[threadIdx.x] = 0; (&nc_sh[0][0][0])[TMW_WAVES * 64 + threadIdx.x] = 0;
-            }
+            q.ask();
+            if (counting) tm_zero_planes<2 * 2 * 2 * 8 * 64, 2 * 2 * 64>(pl, &nc_sh[0][0][0]);
             __syncthreads();
-            const uint32_t s0r = wv ? emid : e0, s1r = wv ? e1 : emid;
-            const uint32_t i0 = s0r - base, i1 = s1r - base < tcnt ? s1r - base : tcnt;
+            const uint32_t s0r = wv ? jb.emid : jb.e0, s1r = wv ? jb.e1 : jb.emid;
+            const uint32_t i0 = s0r - jb.base, i1 = s1r - jb.base < jb.tcnt ? s1r - jb.base : jb.tcnt;
             if (counting && i1 > i0) {
                 TmState st0, st1; st0.nc = 0; st0.mask = 0; st1.nc = 0; st1.mask = 0;
-                tw_range(a, tm, tg, st0, st1, stat, i0, i1, off, tcnt, thr, pkl0, one, lane, K64, kb);
+                tw_range(a, tm, tg, st0, st1, stat, i0, i1, jb.off, jb.tcnt, thr, pkl0, one, lane, K64, kb);
                 // the lane's positions: 2 (lane & 31) and the one after it, of tile lane >> 5
                 uint32_t* nq = &nc_sh[0][lane >> 5][2 * (lane & 31)];
                 if (st0.nc & 0xffffu) atomicAdd(nq, st0.nc & 0xffffu);
@@ -1730,86 +1678,42 @@ __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
                 if (st1.nc & 0xffffu) atomicAdd(nq + 1, st1.nc & 0xffffu);
                 if (st1.nc >> 16) atomicAdd(nq + 129, st1.nc >> 16);
             }
-            if (threadIdx.x == 0) {
-                uint32_t jn2 = NO_JOB;
-                if (steal < 8u) {
-                    jn2 = job_of(q_q, q_n);
-                    if (jn2 == NO_JOB) { if (8u * (q_n >> 6) + q_q >= nblocks) ++steal; jn2 = take(); }
-                }
-                s_q[2] = jn2;
-            }
-            const uint32_t c_w0 = w0, c_slab = slab, c_nj = nj, c_tcnt = tcnt; const int32_t c_tstart = tstart; const int c_tid = tid;
-            e0 = rl(jw, 0); e1 = rl(jw, 1); w0 = rl(jw, 2); slab = rl(jw, 3); nj = rl(jw, 4); tcnt = rl(jw, 5); win = rl(jw, 6); emid = rl(jw, 7); base = rl(jw, 8); off = rl(jw, 9);
-            tstart = (int32_t)rl(jw, 10); tid = (int)rl(jw, 11);
+            if (threadIdx.x == 0) s_q[2] = q.answer();
+            const JobRec cj = jb;
+            jb.load(jw);
             prefetch();
             __syncthreads();
             const uint32_t nn = rl(s_q[2], 0);
-            (void)my_tile;
             if (mine) {                                   // the units of the wave's tile, cell type by cell type
                 for (int v = 0; v < 2; ++v) {
                     const int ct = tm.ct_base + v;
                     if (ct >= a.n_ct) break;
-                    const uint32_t* pc = pl + v * 1024 + wv * 512;
-                    uint32_t dp = 0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) dp += pc[(lane & 1) * 2048 + k * 64 + (lane >> 1) * 2 + 1] & 0x1fffu;
-                    const TwCounters tot{pc, lane, dp - nc_sh[v][wv][lane]};
-                    const uint32_t unit = c_w0 + (uint32_t)wv * (uint32_t)a.n_ct + (uint32_t)ct;
-                    if (c_nj == 1) {
-                        // (the wave writes both cell types' rows, narrow and wide: an arena per cell type and format)
-                        if (c_tcnt <= 256u) emit_unit<TwCounters, true>(a, tot, unit, ct, c_tid, c_tstart + 64 * wv, lane, &book, false, refb, 2 * v);
-                        else emit_unit<TwCounters, false>(a, tot, unit, ct, c_tid, c_tstart + 64 * wv, lane, &book, false, refb, 2 * v + 1);
-                    } else {
-                        uint32_t* dst = a.macc + (uint64_t)(c_slab + ((uint32_t)wv * (uint32_t)a.n_ct + (uint32_t)ct) * c_nj) * (NCTR * 64);
-                        dst[lane] = tot.NCDUP();
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) {
-                            dst[(1 + k) * 64 + lane] = tot.DUP(k); dst[(9 + k) * 64 + lane] = tot.BC(k);
-                            dst[(17 + k) * 64 + lane] = tot.BQ(k); dst[(25 + k) * 64 + lane] = tot.BCF(k);
-                        }
-                    }
+                    const uint32_t uw = (uint32_t)wv * (uint32_t)a.n_ct + (uint32_t)ct;      // the unit among the window's: tile by tile
+                    // (the wave writes both cell types' rows, narrow and wide: an arena per cell type and format)
+                    tm_finish<TwCounters>(a, pl + v * 1024 + wv * 512, nc_sh[v][wv][lane], cj.w0 + uw, cj.slab + uw * cj.nj, cj.nj, cj.tcnt, ct, cj.tid, cj.tstart + 64 * wv,
+                                          lane, &book, refb, 2 * v);
                 }
             }
-            if (nxt == NO_JOB) break;
+            if (nxt == XcdQueue::NO_JOB) break;
             cur = nxt; nxt = nn;
         }
     }
     lds_fence();
     __syncthreads();
-    {
-        unsigned long long ev = stat.ev, sg = stat.sg, ne = stat.ne;
-        for (int o = 32; o > 0; o >>= 1) { ev += __shfl_down(ev, o); sg += __shfl_down(sg, o); ne += __shfl_down(ne, o); }
-        if (lane == 0 && ne) {
-            unsigned long long* slot = tg.stat_slots + (size_t)((blockIdx.x * TMW_WAVES + wv) % IX_STAT_SLOTS) * 8;
-            atomicAdd(&slot[0], ev); atomicAdd(&slot[1], sg); atomicAdd(&slot[2], ne);
-        }
-    }
-    if (threadIdx.x < 64) {
-        uint32_t rt = 0, cols = 0, rsrc = 0;
-        for (int w = 0; w < TMW_WAVES; ++w) {
-            const WaveBook& b = books[w];
-            if (lane < a.n_ct) rt += b.rows_true[lane];
-            cols += b.cols; rsrc += b.rows_src;
-        }
-        if (lane < a.n_ct && rt) atomicAdd(&a.scalars[SC_ROWS + lane], (unsigned long long)rt);
-        if (lane == 0) {
-            if (cols) atomicAdd(&a.scalars[SC_COLS], (unsigned long long)cols);
-            if (rsrc) atomicAdd(&a.scalars[SC_ROWS_SRC + 1], (unsigned long long)rsrc);
-        }
-    }
+    stat_flush(tg.stat_slots, stat, lane, wv);
+    books_flush(a, books, lane);
 }
 
 // A job longer than TM_JOB_LIMIT entries (a single barcode owning thousands of a tile's entries: its run cannot be cut) does not fit the
-// packed planes of k_tm_walk.  One wave per such job, 32-bit planes (quality sum, forward, count, duplicates per symbol and cell type),
-// the run logic spelled out: a run start closes the run before it; an entry that is there adds its event where the lane counts it and
-// is a duplicate when its symbol was seen in the run already.  Rare by construction; correctness, not speed.
-struct WideCounters {
-    const uint32_t* pl; int lane; uint32_t ncdup;           // pl: this cell type's [4][8 * 64] planes
-    __device__ __forceinline__ uint32_t BQ(int k) const { return pl[k * 64 + lane]; }
-    __device__ __forceinline__ uint32_t BCF(int k) const { return pl[512 + k * 64 + lane]; }
-    __device__ __forceinline__ uint32_t BC(int k) const { return pl[1024 + k * 64 + lane]; }
-    __device__ __forceinline__ uint32_t DUP(int k) const { return pl[1536 + k * 64 + lane]; }
-    __device__ __forceinline__ uint32_t NCDUP() const { return ncdup; }
+// packed planes of the four forms above.  One wave per such job, 32-bit planes (quality sum, forward, count, duplicates per symbol and
+// cell type), the run logic spelled out: a run start closes the run before it; an entry that is there adds its event where the lane
+// counts it and is a duplicate when its symbol was seen in the run already.  Rare by construction; correctness, not speed.
+// ONE walk; what differs after each form of the count is where an entry's words and events come from: an entry source, whose entry()
+// says of entry p of job jb what the walk needs to know.
+struct WideEntry {
+    bool rs; uint32_t cls; bool fwd;       // run start; cell type of the pass (0, 1) or 2 = not counted; forward strand
+    uint32_t nev; bool segfirst;           // for the stat slots (0 / false where somebody else has counted the entry already)
+    uint32_t ev[2];                        // the lane's event in either tile half of the job (zero: none); filled for a counted entry
 };
 // one entry's meta word as k_tm_resolve makes it (the wide walk right after a fused load: nobody has resolved the store yet)
 __device__ __forceinline__ uint32_t tm_meta_one(const CountArgs& a, const TmArgs& tm, uint64_t p) {
@@ -1823,185 +1727,92 @@ __device__ __forceinline__ uint32_t tm_meta_one(const CountArgs& a, const TmArgs
     if (s & TM_RUNSTART) m |= TMM_RS;
     return m;
 }
-// n_wide: the plan's number of such jobs where it lies on the device (a launch that does not know it yet ends at once when there are
-// none), or null; inline_meta: no k_tm_resolve has run for this count
-__global__ __launch_bounds__(64) void k_tm_walk_wide(CountArgs a, TmArgs tm, const uint32_t* n_wide, int inline_meta) {
-    __shared__ uint32_t pl[2][4][8 * 64];
-    __shared__ WaveBook book;
-    const int lane = threadIdx.x;
-    if (n_wide && rl(*n_wide, 0) == 0u) return;
-    book_init(book, lane);
-    if (lane == 0) book.src = 2;
-    const uint32_t thr = bq_threshold(a);
-    const uint16_t* ev16 = reinterpret_cast<const uint16_t*>(tm.store);
-    for (uint32_t jx = blockIdx.x; jx < tm.njobs; jx += gridDim.x) {
-        const TmJob jb = tm.jobs[jx];
-        if (!(jb.nj & TMJ_WIDE) || jb.tile < a.tile_lo || jb.tile >= a.tile_hi) continue;
-        const uint32_t nj = jb.nj & ~TMJ_WIDE;
-        lds_fence();
-        for (int i = lane; i < 2 * 4 * 8 * 64; i += 64) (&pl[0][0][0])[i] = 0;
-        lds_fence();
-        uint32_t nc[2] = {0u, 0u}, mask = 0, run_ct = 0;
-        for (uint32_t p = jb.e0; p < jb.e1; ++p) {
-            const uint32_t m = rl(inline_meta ? tm_meta_one(a, tm, p) : tm.meta[p], 0);
-            if (m & TMM_RS) { nc[run_ct] += mask ? 1u : 0u; mask = 0; }
-            if (m & TMM_SKIP) continue;
-            run_ct = (m & TMM_CT4) ? 1u : 0u;
+// The store (after k_tm_walk and k_tm_gather_count): events from the 16-bit store inside the block's extent, the meta word from
+// k_tm_resolve - or made here (inline_meta: no k_tm_resolve has run for this count).  The statistics are the resolve's or the gather's.
+struct WideFromStore {
+    static constexpr int H = 1;
+    int inline_meta;
+    __device__ __forceinline__ unsigned long long* stat_slots() const { return nullptr; }
+    __device__ __forceinline__ WideEntry entry(const CountArgs& a, const TmArgs& tm, const TmJob&, uint32_t p, int lane) const {
+        const uint32_t m = rl(inline_meta ? tm_meta_one(a, tm, p) : tm.meta[p], 0);
+        WideEntry e{(m & TMM_RS) != 0, (m & TMM_SKIP) ? 2u : ((m & TMM_CT4) ? 1u : 0u), (m & TMM_FWD) != 0, 0u, false, {0u, 0u}};
+        if (e.cls < 2) {
             const uint32_t x = tm.ext[p >> 3];                                        // rows outside the block's extent hold no event (and were never written)
-            const uint32_t ev = (uint32_t)lane >= (x & 0xffu) && (uint32_t)lane < (x >> 8) ? ev16[((uint64_t)(p >> 3) * 64 + lane) * 8 + (p & 7u)] : 0u;
-            if ((ev & 0x8ffu) >= thr) {
-                const uint32_t sym = (ev >> 8) & 7u;
-                uint32_t* q = &pl[run_ct][0][sym * 64 + lane];
-                q[0] += ev & 0xffu; q[512] += (m & TMM_FWD) ? 1u : 0u; q[1024] += 1u; q[1536] += (mask >> sym) & 1u;
-                mask |= 1u << sym;
-            }
+            if ((uint32_t)lane >= (x & 0xffu) && (uint32_t)lane < (x >> 8)) e.ev[0] = reinterpret_cast<const uint16_t*>(tm.store)[((uint64_t)(p >> 3) * 64 + lane) * 8 + (p & 7u)];
         }
-        nc[run_ct] += mask ? 1u : 0u;
-        lds_fence();
-        const int2 geom = a.ne_geom[jb.w0];
-        const int tid = geom.y & 0xffffff;
-        for (int v = 0; v < 2; ++v) {
-            const int ct = tm.ct_base + v;
-            if (ct >= a.n_ct) break;
-            const uint32_t* pc = &pl[v][0][0];
-            uint32_t dp = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dp += pc[1024 + k * 64 + lane];
-            const WideCounters tot{pc, lane, dp - nc[v]};
-            if (nj == 1) emit_unit<WideCounters, false>(a, tot, jb.w0 + ct, ct, tid, geom.x, lane, &book, false);
-            else {
-                uint32_t* dst = a.macc + (uint64_t)(jb.slab + (uint32_t)ct * nj) * (NCTR * 64);
-                dst[lane] = tot.NCDUP();
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    dst[(1 + k) * 64 + lane] = tot.DUP(k); dst[(9 + k) * 64 + lane] = tot.BC(k);
-                    dst[(17 + k) * 64 + lane] = tot.BQ(k); dst[(25 + k) * 64 + lane] = tot.BCF(k);
-                }
-            }
-        }
+        return e;
     }
-    book_flush(a, book, lane);
-}
-
-// ... and after a load that kept no store: the entry's words from the sort's output, its events from the caller's array
-__global__ __launch_bounds__(64) void k_tm_walk_wide_direct(CountArgs a, TmArgs tm, TgArgs tg, const uint32_t* n_wide) {
-    __shared__ uint32_t pl[2][4][8 * 64];
-    __shared__ WaveBook book;
+};
+// The sort's output (after a load that kept no store): the entry's words from its key (and value, where the sort carried one), its events
+// from the caller's array.  WSH 0: entries by tiles (k_tm_count_direct: rdv present or absent, the admission bitmap, src_shift 0 or 6);
+// WSH 1: by 128-position windows (k_tm_count_win: keys alone, every read admitted, src_shift 7, seven bits each for the first position
+// and the events - 1; the lane takes its position in either tile of the window)
+template <int WSH>
+struct WideFromKeys {
+    static constexpr int H = 1 << WSH;
+    TgArgs tg;
+    __device__ __forceinline__ unsigned long long* stat_slots() const { return tg.stat_slots; }
+    __device__ __forceinline__ WideEntry entry(const CountArgs& a, const TmArgs& tm, const TmJob& jb, uint32_t p, int lane) const {
+        constexpr uint32_t PB = 6 + WSH, PM = (1u << PB) - 1u;                        // bits of a position of the bin
+        const uint32_t i = p - jb.base, cbm = (1u << tg.cb_bits) - 1u;
+        const uint64_t k = tg.key[jb.off + i];
+        const uint32_t v = tg.rdv ? tg.rdv[jb.off + i] : (uint32_t)(k >> 32) & (TG_RV_FWD | TG_RV_SEGFIRST), cb = (uint32_t)k & cbm, r = v & TG_RV_READ;
+        const uint32_t geom = (uint32_t)(k >> tg.cb_bits), first = geom & PM, nev = ((geom >> PB) & PM) + 1u;
+        const uint64_t src = (((k >> (tg.cb_bits + 2 * PB)) & tg.src_mask) << tg.src_shift) | (tg.src_shift ? first : 0u);
+        uint32_t cls = 2;
+        bool ok = cb < (uint32_t)a.n_cb;
+        if (ok && a.adm) ok = (reinterpret_cast<const uint32_t*>(a.adm)[r >> 5] >> (r & 31u)) & 1u;
+        if (ok) { const uint32_t ct = a.celltype_of[cb]; if (ct < (uint32_t)a.n_ct && (ct >> 1) == (uint32_t)(tm.ct_base >> 1)) cls = ct & 1u; }
+        WideEntry e{i == 0 || ((uint32_t)tg.key[jb.off + i - 1] & cbm) != cb, cls, (v & TG_RV_FWD) != 0, nev, (v & TG_RV_SEGFIRST) != 0, {0u, 0u}};
+        if (cls < 2)
+            for (int h = 0; h < H; ++h) { const uint32_t q = (uint32_t)(64 * h + lane) - first; if (q < nev) e.ev[h] = tg.events[src + q]; }
+        return e;
+    }
+};
+// A tile of at most job_tgt entries is ONE job (store.hip k_tm_tiles), job_tgt <= TM_JOB_TGT (plan_tiles), and a one-job tile's job has
+// exactly the tile's entries (tm_make_job: e1 - e0 = n): a job of more than TM_JOB_LIMIT entries always belongs to a tile of several jobs.
+// So a wide job's sums go to its slab and k_finalize_multi makes the rows: the wide walk emits none (rows_by_kernel[2] stays 0).
+static_assert(TM_JOB_TGT <= TM_JOB_LIMIT, "a one-job tile's job fits the packed planes: the wide walk writes slabs only");
+// n_wide: the plan's number of such jobs where it lies on the device (a launch that does not know it yet ends at once when there are
+// none), or null.  A job covers SRC::H tile halves (a window: two): units and slabs tile by tile, as the plan lays them out.
+template <class SRC>
+__global__ __launch_bounds__(64) void k_tm_walk_wide(CountArgs a, TmArgs tm, SRC src, const uint32_t* n_wide) {
+    constexpr int H = SRC::H;
+    __shared__ uint32_t pl[H][2][4][8 * 64];               // [tile half][cell type][quality sum, forward, count, duplicates][symbol x position]
     const int lane = threadIdx.x;
     if (n_wide && rl(*n_wide, 0) == 0u) return;
-    book_init(book, lane);
-    if (lane == 0) book.src = 2;
-    const uint32_t thr = bq_threshold(a), cbm = (1u << tg.cb_bits) - 1u;
+    const uint32_t thr = bq_threshold(a);
     unsigned long long s_ev = 0, s_sg = 0, s_ne = 0;
     for (uint32_t jx = blockIdx.x; jx < tm.njobs; jx += gridDim.x) {
         const TmJob jb = tm.jobs[jx];
-        if (!(jb.nj & TMJ_WIDE) || jb.tile < a.tile_lo || jb.tile >= a.tile_hi) continue;
+        bool in_t[H], any = false;
+        for (int h = 0; h < H; ++h) { const uint32_t t = (uint32_t)H * jb.tile + h; in_t[h] = t >= a.tile_lo && t < a.tile_hi; any |= in_t[h]; }
+        if (!(jb.nj & TMJ_WIDE) || !any) continue;
         const uint32_t nj = jb.nj & ~TMJ_WIDE;
         lds_fence();
-        for (int i = lane; i < 2 * 4 * 8 * 64; i += 64) (&pl[0][0][0])[i] = 0;
+        for (int i = lane; i < H * 2 * 4 * 8 * 64; i += 64) (&pl[0][0][0][0])[i] = 0;
         lds_fence();
-        uint32_t nc[2] = {0u, 0u}, mask = 0, run_ct = 0;
-        for (uint32_t p = jb.e0; p < jb.e1 && p - jb.base < jb.cnt; ++p) {
-            const uint32_t i = p - jb.base;
-            const uint64_t k = tg.key[jb.off + i];
-            const uint32_t v = tg.rdv ? tg.rdv[jb.off + i] : (uint32_t)(k >> 32) & (TG_RV_FWD | TG_RV_SEGFIRST), cb = (uint32_t)k & cbm, r = v & TG_RV_READ;
-            const bool rs = i == 0 || ((uint32_t)tg.key[jb.off + i - 1] & cbm) != cb;
-            const uint32_t geom = (uint32_t)(k >> tg.cb_bits), first = geom & 63u, nev = ((geom >> 6) & 63u) + 1u;
-            const uint64_t src = (((k >> (tg.cb_bits + 12)) & tg.src_mask) << tg.src_shift) | (tg.src_shift ? first : 0u);
-            uint32_t cls = 2;
-            bool ok = cb < (uint32_t)a.n_cb;
-            if (ok && a.adm) ok = (reinterpret_cast<const uint32_t*>(a.adm)[r >> 5] >> (r & 31u)) & 1u;
-            if (ok) { const uint32_t ct = a.celltype_of[cb]; if (ct < (uint32_t)a.n_ct && (ct >> 1) == (uint32_t)(tm.ct_base >> 1)) cls = ct & 1u; }
-            if (rs) { nc[run_ct] += mask ? 1u : 0u; mask = 0; }
-            if (cls >= 2) continue;
-            s_ev += nev; s_sg += (v & TG_RV_SEGFIRST) ? 1u : 0u; ++s_ne;
-            run_ct = cls;
-            const uint32_t ev = (uint32_t)lane - first < nev ? tg.events[src + ((uint32_t)lane - first)] : 0u;
-            if ((ev & 0x8ffu) >= thr) {
-                const uint32_t sym = (ev >> 8) & 7u;
-                uint32_t* q = &pl[run_ct][0][sym * 64 + lane];
-                q[0] += ev & 0xffu; q[512] += (v & TG_RV_FWD) ? 1u : 0u; q[1024] += 1u; q[1536] += (mask >> sym) & 1u;
-                mask |= 1u << sym;
-            }
-        }
-        nc[run_ct] += mask ? 1u : 0u;
-        lds_fence();
-        const int2 geom = a.ne_geom[jb.w0];
-        const int tid = geom.y & 0xffffff;
-        for (int v = 0; v < 2; ++v) {
-            const int ct = tm.ct_base + v;
-            if (ct >= a.n_ct) break;
-            const uint32_t* pc = &pl[v][0][0];
-            uint32_t dp = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dp += pc[1024 + k * 64 + lane];
-            const WideCounters tot{pc, lane, dp - nc[v]};
-            if (nj == 1) emit_unit<WideCounters, false>(a, tot, jb.w0 + ct, ct, tid, geom.x, lane, &book, false);
-            else {
-                uint32_t* dst = a.macc + (uint64_t)(jb.slab + (uint32_t)ct * nj) * (NCTR * 64);
-                dst[lane] = tot.NCDUP();
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    dst[(1 + k) * 64 + lane] = tot.DUP(k); dst[(9 + k) * 64 + lane] = tot.BC(k);
-                    dst[(17 + k) * 64 + lane] = tot.BQ(k); dst[(25 + k) * 64 + lane] = tot.BCF(k);
-                }
-            }
-        }
-    }
-    if (lane == 0 && s_ne) {
-        unsigned long long* slot = tg.stat_slots + (size_t)(blockIdx.x % IX_STAT_SLOTS) * 8;
-        atomicAdd(&slot[0], s_ev); atomicAdd(&slot[1], s_sg); atomicAdd(&slot[2], s_ne);
-    }
-    book_flush(a, book, lane);
-}
-
-// ... and its wide walk (k_tm_walk_wide_direct over windows: an entry is up to 128 events, the lane takes its position in either tile)
-__global__ __launch_bounds__(64) void k_tm_walk_wide_win(CountArgs a, TmArgs tm, TgArgs tg, const uint32_t* n_wide) {
-    __shared__ uint32_t pl[2][2][4][8 * 64];               // [tile of the window][cell type][quality sum, forward, count, duplicates][symbol x position]
-    __shared__ WaveBook book;
-    const int lane = threadIdx.x;
-    if (n_wide && rl(*n_wide, 0) == 0u) return;
-    book_init(book, lane);
-    if (lane == 0) book.src = 2;
-    const uint32_t thr = bq_threshold(a), cbm = (1u << tg.cb_bits) - 1u;
-    unsigned long long s_ev = 0, s_sg = 0, s_ne = 0;
-    for (uint32_t jx = blockIdx.x; jx < tm.njobs; jx += gridDim.x) {
-        const TmJob jb = tm.jobs[jx];
-        const uint32_t t0 = 2u * jb.tile;
-        const bool in_t[2] = {t0 >= a.tile_lo && t0 < a.tile_hi, t0 + 1u >= a.tile_lo && t0 + 1u < a.tile_hi};
-        if (!(jb.nj & TMJ_WIDE) || !(in_t[0] || in_t[1])) continue;
-        const uint32_t nj = jb.nj & ~TMJ_WIDE;
-        lds_fence();
-        for (int i = lane; i < 2 * 2 * 4 * 8 * 64; i += 64) (&pl[0][0][0][0])[i] = 0;
-        lds_fence();
-        uint32_t nc[2][2] = {{0u, 0u}, {0u, 0u}}, mask[2] = {0u, 0u}, run_ct = 0;      // [tile][cell type]; the open run's symbols per tile
-        for (uint32_t p = jb.e0; p < jb.e1 && p - jb.base < jb.cnt; ++p) {
-            const uint32_t i = p - jb.base;
-            const uint64_t k = tg.key[jb.off + i];
-            const uint32_t v = (uint32_t)(k >> 32) & (TG_RV_FWD | TG_RV_SEGFIRST), cb = (uint32_t)k & cbm;
-            const bool rs = i == 0 || ((uint32_t)tg.key[jb.off + i - 1] & cbm) != cb;
-            const uint32_t geom = (uint32_t)(k >> tg.cb_bits), first = geom & 127u, nev = ((geom >> 7) & 127u) + 1u;
-            const uint64_t src = (((k >> (tg.cb_bits + 14)) & tg.src_mask) << 7) | first;
-            uint32_t cls = 2;
-            if (cb < (uint32_t)a.n_cb) { const uint32_t ct = a.celltype_of[cb]; if (ct < (uint32_t)a.n_ct && (ct >> 1) == (uint32_t)(tm.ct_base >> 1)) cls = ct & 1u; }
-            if (rs) { for (int h = 0; h < 2; ++h) { nc[h][run_ct] += mask[h] ? 1u : 0u; mask[h] = 0; } }
-            if (cls >= 2) continue;
-            s_ev += nev; s_sg += (v & TG_RV_SEGFIRST) ? 1u : 0u; ++s_ne;
-            run_ct = cls;
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t q = (uint32_t)(64 * h + lane) - first;
-                const uint32_t ev = q < nev ? tg.events[src + q] : 0u;
+        uint32_t nc[H][2], mask[H], run_ct = 0;             // runs that counted an event per tile half and cell type; the open run's symbols per tile half
+        for (int h = 0; h < H; ++h) { nc[h][0] = nc[h][1] = 0; mask[h] = 0; }
+        for (uint32_t p = jb.e0; p < jb.e1 && p - jb.base < jb.cnt; ++p) {      // (past cnt: the tile's pad entries)
+            const WideEntry e = src.entry(a, tm, jb, p, lane);
+            if (e.rs) for (int h = 0; h < H; ++h) { nc[h][run_ct] += mask[h] ? 1u : 0u; mask[h] = 0; }
+            if (e.cls >= 2) continue;
+            s_ev += e.nev; s_sg += e.segfirst ? 1u : 0u; ++s_ne;
+            run_ct = e.cls;
+            for (int h = 0; h < H; ++h) {
+                const uint32_t ev = e.ev[h];
                 if ((ev & 0x8ffu) >= thr) {
                     const uint32_t sym = (ev >> 8) & 7u;
                     uint32_t* w = &pl[h][run_ct][0][sym * 64 + lane];
-                    w[0] += ev & 0xffu; w[512] += (v & TG_RV_FWD) ? 1u : 0u; w[1024] += 1u; w[1536] += (mask[h] >> sym) & 1u;
+                    w[0] += ev & 0xffu; w[512] += e.fwd ? 1u : 0u; w[1024] += 1u; w[1536] += (mask[h] >> sym) & 1u;
                     mask[h] |= 1u << sym;
                 }
             }
         }
-        for (int h = 0; h < 2; ++h) nc[h][run_ct] += mask[h] ? 1u : 0u;
+        for (int h = 0; h < H; ++h) nc[h][run_ct] += mask[h] ? 1u : 0u;
         lds_fence();
-        for (int h = 0; h < 2; ++h) {
+        for (int h = 0; h < H; ++h) {
             if (!in_t[h]) continue;
             for (int v = 0; v < 2; ++v) {
                 const int ct = tm.ct_base + v;
@@ -2010,26 +1821,17 @@ __global__ __launch_bounds__(64) void k_tm_walk_wide_win(CountArgs a, TmArgs tm,
                 uint32_t dp = 0;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) dp += pc[1024 + k * 64 + lane];
-                const WideCounters tot{pc, lane, dp - nc[h][v]};
-                const uint32_t unit = jb.w0 + (uint32_t)h * (uint32_t)a.n_ct + (uint32_t)ct;
-                if (nj == 1) emit_unit<WideCounters, false>(a, tot, unit, ct, jb.tid, jb.tstart + 64 * h, lane, &book, false, -1, v);
-                else {
-                    uint32_t* dst = a.macc + (uint64_t)(jb.slab + ((uint32_t)h * (uint32_t)a.n_ct + (uint32_t)ct) * nj) * (NCTR * 64);
-                    dst[lane] = tot.NCDUP();
+                uint32_t* dst = a.macc + (uint64_t)(jb.slab + ((uint32_t)h * (uint32_t)a.n_ct + (uint32_t)ct) * nj) * (NCTR * 64);
+                dst[lane] = dp - nc[h][v];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        dst[(1 + k) * 64 + lane] = tot.DUP(k); dst[(9 + k) * 64 + lane] = tot.BC(k);
-                        dst[(17 + k) * 64 + lane] = tot.BQ(k); dst[(25 + k) * 64 + lane] = tot.BCF(k);
-                    }
+                for (int k = 0; k < 8; ++k) {
+                    dst[(1 + k) * 64 + lane] = pc[1536 + k * 64 + lane]; dst[(9 + k) * 64 + lane] = pc[1024 + k * 64 + lane];
+                    dst[(17 + k) * 64 + lane] = pc[k * 64 + lane]; dst[(25 + k) * 64 + lane] = pc[512 + k * 64 + lane];
                 }
             }
         }
     }
-    if (lane == 0 && s_ne) {
-        unsigned long long* slot = tg.stat_slots + (size_t)(blockIdx.x % IX_STAT_SLOTS) * 8;
-        atomicAdd(&slot[0], s_ev); atomicAdd(&slot[1], s_sg); atomicAdd(&slot[2], s_ne);
-    }
-    book_flush(a, book, lane);
+    if (unsigned long long* slots = src.stat_slots()) stat_add(slots, blockIdx.x, s_ev, s_sg, s_ne, lane);      // (every lane has seen every entry)
 }
 
 // Everything a count needs before its first kernel: the plan's unit tables where the call stage and the exports read them, row
@@ -2124,7 +1926,7 @@ static int count_passes(lsg_ctx* c, CountLaunch& L, int first_pass, bool wide_of
         if (pass == 0) { LSG_HIP(hipEventRecord(c->ev[1], st)); LSG_HIP(hipEventRecord(c->ev[3], st)); }
         if (c->tm_njobs && !wide_only) hipLaunchKernelGGL(k_tm_walk, dim3(L.grid_walk), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm);
         if (pass == 0) LSG_HIP(hipEventRecord(c->ev[4], st));
-        if (grid_wide) hipLaunchKernelGGL(k_tm_walk_wide, dim3(grid_wide), dim3(64), 0, st, L.a, L.tm, (const uint32_t*)nullptr, 0);
+        if (grid_wide) hipLaunchKernelGGL(k_tm_walk_wide<WideFromStore>, dim3(grid_wide), dim3(64), 0, st, L.a, L.tm, WideFromStore{0}, (const uint32_t*)nullptr);
     }
     return 0;
 }
@@ -2186,25 +1988,25 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
     auto stage = [&](const char* what) { if (dbg) { const hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[lsg] fused load: %s: %s\n", what, hipGetErrorString(e)); fflush(stderr); } };
     stage("count prepared");
     LSG_HIP(hipEventRecord(c->ev[1], st)); LSG_HIP(hipEventRecord(c->ev[3], st));
+    // which range kernel counts, and which entry source its wide jobs are left to
+    enum { GATHER, TILES, WINDOWS } form = !direct ? GATHER : (src.wsh ? WINDOWS : TILES);
+    const char* what = "k_tm_gather_count";
     if (direct) {
-        // no store (lsg_set_store_policy): 80 registers per lane: 6 waves per SIMD = 12 workgroups per CU (8: 9.3 ms, 10: 8.5, 12: 8.2)
+        // no store (lsg_set_store_policy): the XCDs' job queues
         if (c->d_xcd_queues.reserve(8 * 128)) return -1;
         LSG_HIP(hipMemsetAsync(c->d_xcd_queues.p, 0, 8 * 128, st));
         tg.queues = c->d_xcd_queues.as<unsigned long long>();
-        if (src.wsh) {
-            // entries binned by 128-position windows (store.hip build_store): one 256-byte block per entry; 17 KB of LDS a workgroup: 9 per CU
-            if (tg.rdv || L.a.adm || p->min_bq < 1 || p->min_bq > 255 || tg.src_shift != 7) return 1;      // (build_store makes such a load by tiles)
-            tg.src_mask = (1ull << (48 - src.cb_bits)) - 1ull;      // (seven bits each for the first position and the events - 1)
-            c->line_loads = true;
-            const unsigned gridw = (unsigned)(c->n_cus * tune_int("LSG_GRID_TW", 9));
-            hipLaunchKernelGGL(k_tm_count_win, dim3(gridw), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
-            LSG_HIP(hipEventRecord(c->ev[4], st));
-            LSG_HIP(hipEventRecord(c->evb[4], st));
-            stage("k_tm_count_win");
-            hipLaunchKernelGGL(k_tm_walk_wide_win, dim3((unsigned)(c->n_cus * 2)), dim3(64), 0, st, L.a, L.tm, tg, (const uint32_t*)c->d_plan_misc);
-            stage("wide walk");
-            return count_finish(c, p, L);
-        }
+    }
+    if (form == WINDOWS) {
+        // entries binned by 128-position windows (store.hip build_store): one 256-byte block per entry; 17 KB of LDS a workgroup: 9 per CU
+        if (tg.rdv || L.a.adm || p->min_bq < 1 || p->min_bq > 255 || tg.src_shift != 7) return 1;      // (build_store makes such a load by tiles)
+        tg.src_mask = (1ull << (48 - src.cb_bits)) - 1ull;      // (seven bits each for the first position and the events - 1)
+        c->line_loads = true;
+        const unsigned gridw = (unsigned)(c->n_cus * tune_int("LSG_GRID_TW", 9));
+        hipLaunchKernelGGL(k_tm_count_win, dim3(gridw), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
+        what = "k_tm_count_win";
+    } else if (form == TILES) {
+        // 80 registers per lane: 6 waves per SIMD = 12 workgroups per CU (8: 9.3 ms, 10: 8.5, 12: 8.2)
         const unsigned grid = (unsigned)(c->n_cus * tune_int("LSG_GRID_TD", 12));
         // tile-phased events: an entry is fetched as its one 128-byte line (tm_add<.., true>: the quality compare reads the event's low byte)
         const bool al = tg.src_shift == 6 && p->min_bq >= 1 && p->min_bq <= 255;
@@ -2213,21 +2015,22 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
         else if (tg.rdv) hipLaunchKernelGGL((k_tm_count_direct<false, false>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
         else if (al) hipLaunchKernelGGL((k_tm_count_direct<true, true>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
         else hipLaunchKernelGGL((k_tm_count_direct<true, false>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
-        LSG_HIP(hipEventRecord(c->ev[4], st));
-        LSG_HIP(hipEventRecord(c->evb[4], st));
-        stage("k_tm_count_direct");
-        hipLaunchKernelGGL(k_tm_walk_wide_direct, dim3((unsigned)(c->n_cus * 2)), dim3(64), 0, st, L.a, L.tm, tg, (const uint32_t*)c->d_plan_misc);
-        stage("wide walk");
-        return count_finish(c, p, L);
+        what = "k_tm_count_direct";
+    } else {
+        // 17 KB of LDS per workgroup (planes + the two waves' transposition tiles): 9 workgroups per CU
+        const unsigned grid = (unsigned)(c->n_cus * tune_int("LSG_GRID_TG", 9));
+        hipLaunchKernelGGL(k_tm_gather_count, dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
     }
-    // 17 KB of LDS per workgroup (planes + the two waves' transposition tiles): 9 workgroups per CU
-    const unsigned grid = (unsigned)(c->n_cus * tune_int("LSG_GRID_TG", 9));
-    hipLaunchKernelGGL(k_tm_gather_count, dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
     LSG_HIP(hipEventRecord(c->ev[4], st));
     LSG_HIP(hipEventRecord(c->evb[4], st));
-    stage("k_tm_gather_count");
-    // jobs too long for the packed planes were gathered, not counted: the wide walk takes them from the store (it ends at once when the plan has none)
-    hipLaunchKernelGGL(k_tm_walk_wide, dim3((unsigned)(c->n_cus * 2)), dim3(64), 0, st, L.a, L.tm, (const uint32_t*)c->d_plan_misc, 1);
+    stage(what);
+    // jobs too long for the packed planes were left out (gathered, not counted, where a store is written): the wide walk takes them from
+    // where the range kernel took its entries (it ends at once when the plan has none)
+    const dim3 grid_wide((unsigned)(c->n_cus * 2));
+    const uint32_t* n_wide = c->d_plan_misc;
+    if (form == WINDOWS) hipLaunchKernelGGL(k_tm_walk_wide<WideFromKeys<1>>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromKeys<1>{tg}, n_wide);
+    else if (form == TILES) hipLaunchKernelGGL(k_tm_walk_wide<WideFromKeys<0>>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromKeys<0>{tg}, n_wide);
+    else hipLaunchKernelGGL(k_tm_walk_wide<WideFromStore>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromStore{1}, n_wide);
     stage("wide walk");
     return count_finish(c, p, L);
 }

@@ -222,7 +222,7 @@ def test_entries_cut_at_pileup_window_edges_count_the_same(engine):
 
 def test_loads_that_sort_keys_alone(engine, monkeypatch, capfd):
     """A load that keeps no store and is counted under its own read filters carries keys alone through the scatter and the sort
-    (store.hip build_store, keys_only; pileup.hip k_tm_count_direct<true>): deep tiles cut into jobs, a tile left to the wide walk,
+    (store.hip build_store, keys_only; pileup.hip k_tm_count_direct<KO = true, AL>): deep tiles cut into jobs, a job left to the wide walk (k_tm_walk_wide over the sorted keys),
     and a load whose count from keys alone is refused (the test hook) and that is made again with values."""
     monkeypatch.setenv("LSG_TIMING", "1")
     p = CountParams.longsom_defaults()

@@ -72,8 +72,8 @@ def test_four_cell_types_take_two_passes(engine):
 
 
 def test_one_barcode_owning_a_tile(engine):
-    """a single barcode's run of more entries than the packed planes' fields hold cannot be cut: the wide walk takes that job,
-    in a single-job tile and in a multi-job one"""
+    """a single barcode's run of more entries than the packed planes' fields hold cannot be cut: the wide walk takes that job
+    (always one of a multi-job tile: a tile that is one job has at most TM_JOB_TGT entries), with many barcodes beside the owner and with three"""
     lens = [2500]
     rec, refs, ct_of = make_case(14, 30000, lens, 30, hot_regions=[(0, 700, 760)], hot_frac=0.97, cb_skew=0.9)
     ct_of[0] = 0
