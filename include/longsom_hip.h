@@ -350,11 +350,13 @@ int lsg_export_calls(lsg_ctx* ctx, int32_t kind, void* dst_device, int64_t capac
  *   LSG_TABLE_STEP3_ROWS  the rows of LSG_TABLE_STEP2 step 3 can keep (made by lsg_step2_summary, not by lsg_format_table)
  *   LSG_TABLE_CELL_LONG   <id>.SingleCellGenotype.tsv rows      CellClustering/SingleCellGenotype.py:181-224,305 (see lsg_cellgeno_count below)
  *   LSG_TABLE_CELL_DP / _ALT / _VAF / _BIN   the rows of <id>.DpMatrix.tsv, AltMatrix, VAFMatrix, BinaryMatrix (SingleCellGenotype.py:351-379)
+ *   LSG_TABLE_BNPC_BIN / _VAF   the SNV rows of BnpC_input/<id>.BinaryMatrix.tsv and VAFMatrix.tsv (FormatInputBnpC.py:16-34; see lsg_cellgeno_filter)
  * Rows only (the header lines are the caller's), in the reference's order: contigs in Python string order, positions ascending.
  * At 24 M sites these are 17 GB of text: a kernel prints them from the count rows and call records where they lie (two passes:
  * lengths, then bytes), the host only moves bytes.  The merged and step-1 tables need lsg_call_step1 (its merged site list). */
 enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG_TABLE_STEP1, LSG_TABLE_STEP1_KEPT, LSG_TABLE_STEP2, LSG_TABLE_STEP3_ROWS,
-                 LSG_TABLE_CELL_LONG, LSG_TABLE_CELL_DP, LSG_TABLE_CELL_ALT, LSG_TABLE_CELL_VAF, LSG_TABLE_CELL_BIN, LSG_TABLE_SLOTS };
+                 LSG_TABLE_CELL_LONG, LSG_TABLE_CELL_DP, LSG_TABLE_CELL_ALT, LSG_TABLE_CELL_VAF, LSG_TABLE_CELL_BIN,
+                 LSG_TABLE_BNPC_BIN, LSG_TABLE_BNPC_VAF, LSG_TABLE_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -466,6 +468,26 @@ typedef struct {
     int32_t n_cols; int32_t float_cells; const int32_t* col_src;
 } lsg_cellgeno_text;
 int lsg_cellgeno_set_text(lsg_ctx* ctx, const lsg_cellgeno_text* text);
+
+/* ---- BnpC's input from the resident cells (CellClustering/FormatInputBnpC.py:6-35, rule FormatInputBnpC, rules/CellClustering.smk:105-133)
+ * The script reads BinaryMatrix and VAFMatrix back with 3 and "." as NA (:7-8) and filters them.  lsg_cellgeno_filter does so where the
+ * cells lie, over the rows of mat_order and the columns of col_src (lsg_cellgeno_set_text first):
+ *   a row is kept iff the number of its cells with bin == 1, over the columns with col_src >= 0, is > min_cells_per_mut   (:16)
+ *   a column is kept iff the number of its cells with bin != 3 over the KEPT rows is > min_pos_cov; col_src == -1 counts 0  (:19)
+ *   a column prints as integers iff col_int_ok[col] != 0 (the caller's half: no float text and no gap in the matrix the script would
+ *   have read, fusion rows included) and it is covered at all n_mat rows - pandas gives a column with an NA the dtype float64 (:7)
+ * A negative threshold keeps everything.  The fusion rows (labels with "--", :11-13,27) are never filtered by row and never counted:
+ * they are the caller's.  lsg_format_table(LSG_TABLE_BNPC_BIN / _VAF) then prints the kept rows over the kept columns, both in input
+ * order (:21-27,33-34): label, then per column a tab and nothing for an NA, else "0" / "1" (".0" appended unless the column is
+ * integer) resp. repr(vaf4 / 1e4).  lsg_cellgeno_filter_fetch copies out, per row of mat_order, row_keep and row_mut (its count of 1s)
+ * and, per column, col_keep, col_cov_kept, col_cov_all (covered cells over the kept / over all rows) and col_int; any pointer may be NULL.
+ * A new count, load or lsg_cellgeno_set_text invalidates the filter and both tables. */
+int lsg_cellgeno_filter(lsg_ctx* ctx, int32_t min_cells_per_mut, int32_t min_pos_cov, const uint8_t* col_int_ok, int64_t* n_rows_kept, int32_t* n_cols_kept);
+int lsg_cellgeno_filter_fetch(lsg_ctx* ctx, uint8_t* row_keep, uint8_t* col_keep, int32_t* row_mut, int32_t* col_cov_kept, int32_t* col_cov_all, uint8_t* col_int);
+/* The cells of matrices that were parsed from files: bin [n_sites][n_cb] in {0, 1, 3}, vaf4 = VAF * 1e4 or -1 for NA.  They become the
+ * resident bin / vaf4, with status LSG_CELL_NOCOVERAGE where bin == 3 (LSG_CELL_PASS where 1, LSG_CELL_NOALT where 0).  The state holds
+ * no counts and no tails: LSG_TABLE_CELL_LONG, _DP and _ALT and the dp / alt / p4 of lsg_cellgeno_fetch are refused until the next count. */
+int lsg_cellgeno_load_cells(lsg_ctx* ctx, int64_t n_sites, int32_t n_cb, const uint8_t* bin, const int32_t* vaf4);
 
 /* ---- measurement helpers --------------------------------------------------------------------*/
 /* Statistics of the last lsg_pileup_count: admitted reads / segments / events (events that passed

@@ -138,10 +138,12 @@ def plan_sites(variant_file: str, contig_names: Sequence[str], window: int, chrm
 def cell_genotype_matrices(engine, variant_file: str, table, contig_names: Sequence[str], out_prefix: str, fusion_file: Optional[str] = None, *,
                            alt_flag: str = "All", window: int = 50000, min_bq: int = 30, min_mq: int = 255, alpha2: float = 0.2474528917555431,
                            beta2: float = 162.03696139428595, pvalue: float = 0.01, chrm_contaminant: str = "True", max_depth: int = 200000,
-                           stats: Optional[dict] = None) -> int:
+                           stats: Optional[dict] = None, bnpc_prefix: Optional[str] = None, bnpc_barcodes: Optional[str] = None, min_cells_per_mut: int = 5,
+                           min_pos_cov: int = 3) -> int:
     """The reads, contigs and `table` (hostio.BarcodeTable) must be resident in `engine`.  Writes <out_prefix>.SingleCellGenotype.tsv and
     the four <out_prefix>.{Dp,Alt,VAF,Binary}Matrix.tsv; returns the rows of the long table.  stats (a dict, filled in): per barcode the
-    sites with coverage ("covered") and with MutationStatus PASS ("mutated"), as the twin step counts them."""
+    sites with coverage ("covered") and with MutationStatus PASS ("mutated"), as the twin step counts them.  bnpc_prefix: also write
+    BnpC's input (format_bnpc_input: rule FormatInputBnpC with bnpc_barcodes as its --barcodes) from the cells while they are resident."""
     from ._lib import GenotypeParams
     plan = plan_sites(variant_file, contig_names, window, chrm_contaminant)
     if plan is None:
@@ -192,7 +194,176 @@ def cell_genotype_matrices(engine, variant_file: str, table, contig_names: Seque
             with open(path, "a") as f:
                 f.write("".join(rows))
         engine.free_table(slots[m])
+    if bnpc_prefix:
+        fusion_order = [matrix_label(all_index[i]) for i in order if i >= len(listed)]
+        if any("--" not in f for f in fusion_order) or any("--" in matrix_label(indexes[i]) for i in mat_order):
+            # FormatInputBnpC.py:11 tells a fusion row by the "--" in its label: where that is not the fusion file's rows, the files decide
+            format_bnpc_input_host(out_prefix + ".BinaryMatrix.tsv", out_prefix + ".VAFMatrix.tsv", bnpc_barcodes, bnpc_prefix, min_cells_per_mut, min_pos_cov)
+        else:
+            format_bnpc_input(engine, columns, fusions, bnpc_barcodes, bnpc_prefix, min_cells_per_mut, min_pos_cov, float_cells=float_cells, fusion_order=fusion_order)
     if stats is not None:
         stats["covered"] = {bc: int(v) for bc, v in zip(barcodes, tally["n_covered"]) if v}
         stats["mutated"] = {bc: int(v) for bc, v in zip(barcodes, tally["n_pass"]) if v}
     return len(long_order) * n_cb
+
+
+# ---- BnpC's input: scripts/CellClustering/FormatInputBnpC.py:6-35 (rule FormatInputBnpC, rules/CellClustering.smk:105-133) ----------------
+# The script reads BinaryMatrix and VAFMatrix back with 3 and "." as NA (:7-8), sets the fusion rows (labels with "--") aside (:11-13),
+# keeps the SNV rows more than min_cells_per_mut cells carry as 1 (:16), then the columns covered at more than min_pos_cov of those rows
+# (:19), and prints the kept SNV rows, then all fusion rows, over the kept columns (:21-34) with the listed barcodes' table (:26,30,35).
+# The two filters, the compaction and the SNV rows' text are the device's (csrc/cellgeno.hip: lsg_cellgeno_filter, tables
+# LSG_TABLE_BNPC_*); the fusion rows, the header and Barcodes.tsv are written here.
+BNPC_OUTPUTS = ("BinaryMatrix", "VAFMatrix", "Barcodes")
+_BIN_CODE = {"0": 0, "1": 1, "3": 3, "0.0": 0, "1.0": 1, "3.0": 3, "": 3}                   # what :7 reads a Binary cell as (3 = NA)
+_BIN_INT_TEXT = ("0", "1")                                                                  # ... and the texts that leave a column int64
+
+
+class HandBack(Exception):
+    """a matrix file holds something the device form does not state: the host twin takes the step"""
+
+
+def write_bnpc_barcodes(barcodes_file: str, kept_columns: Sequence[str], out_path: str) -> int:
+    """:9,26,30,35 - the rows of --barcodes whose Index is a kept column, in that file's order, with the re-annotation's colour"""
+    import pandas as pd
+    bc = pd.read_csv(barcodes_file, sep="\t")
+    bc = bc[bc["Index"].isin(list(kept_columns))].copy()
+    bc["Cell_Reanno_Colors"] = ["#94C773" if x == "Non-Cancer" else "#8F79A1" for x in bc["Reannotated_cell_type"]]
+    bc.to_csv(out_path, sep="\t", index=False)
+    return len(bc)
+
+
+def format_bnpc_input_host(bin_path: str, vaf_path: str, barcodes_path: str, out_prefix: str, min_cells_per_mut: int = 5, min_pos_cov: int = 3):
+    """The whole step in pandas, restated from the rules above: the twin the device forms are tested against, and the path a matrix file
+    the device form does not state is handed back to.  Returns (rows written, columns kept)."""
+    import pandas as pd
+    na = [3, "."]
+    b = pd.read_csv(bin_path, sep="\t", index_col=0, na_values=na)                        # :7
+    v = pd.read_csv(vaf_path, sep="\t", index_col=0, na_values=na)                        # :8
+    fusion = np.array(["--" in str(i) for i in b.index], bool)                             # :11
+    snv = b[~fusion]
+    snv = snv[(snv.notna() & (snv != 0)).sum(axis=1) > min_cells_per_mut]                  # :16 (NA and 0 are not counted)
+    snv = snv.loc[:, snv.notna().sum(axis=0) > min_pos_cov]                                # :19 (over the kept SNV rows alone)
+    rows = list(snv.index) + list(b.index[fusion])                                         # :21
+    pd.concat([snv, b.loc[fusion, snv.columns]]).to_csv(out_prefix + ".BinaryMatrix.tsv", sep="\t")      # :27,33
+    v.loc[rows, snv.columns].to_csv(out_prefix + ".VAFMatrix.tsv", sep="\t")               # :25,34
+    write_bnpc_barcodes(barcodes_path, [str(c) for c in snv.columns], out_prefix + ".Barcodes.tsv")
+    return len(rows), len(snv.columns)
+
+
+def bnpc_col_int_ok(columns: Sequence[str], fusions: Sequence[Tuple[str, str]], float_cells: bool) -> List[int]:
+    """The host's half of a Binary column's dtype in the fused form: pandas reads a column of <id>.BinaryMatrix.tsv as int64 iff no cell
+    of it is empty or float text, over all rows.  SingleCellGenotype.py prints every cell as a float when its pivot had a gap
+    (float_cells), and a fusion row is empty wherever the barcode does not carry the fusion.  (Coverage at every site is the device's half.)"""
+    pairs = set(fusions)
+    names = list(dict.fromkeys(f for f, _ in fusions))
+    return [int(not float_cells and all((f, c) in pairs for f in names)) for c in columns]
+
+
+def _vaf_code(text: str, cache: dict) -> int:
+    """a VAF cell as the device states it: -1 for NA, else k with text == repr(k / 1e4) (or the integers 0 and 1)"""
+    k = cache.get(text)
+    if k is None:
+        if text in ("", "."):
+            k = -1
+        else:
+            try:
+                k = int(round(float(text) * 10000))
+            except (ValueError, OverflowError):                                         # ("inf" parses and cannot be rounded)
+                raise HandBack("VAF cell %r" % text)
+            if not (0 <= k <= 10000 and (repr(k / 10000.0) == text or text in ("0", "1"))):
+                raise HandBack("VAF cell %r is not a 4-decimal repr" % text)
+        cache[text] = k
+    return k
+
+
+def read_bnpc_matrices(bin_path: str, vaf_path: str):
+    """The two matrix files as the device takes them.  Returns (columns, SNV labels, bin [n_snv, n_cols] uint8, vaf4 int32, fusion labels,
+    their bin and vaf4 rows, col_int_ok).  Raises HandBack for whatever lsg_cellgeno_load_cells cannot state as pandas would read it:
+    quoting, blank or ragged lines, duplicate labels or columns, VAF rows or columns other than Binary's, a Binary value outside
+    {0, 1, 3, empty and their .0 forms}, a VAF text that is not repr(k / 1e4), a VAF column that pandas would read as integers."""
+    def table(path):
+        import gzip
+        with (gzip.open(path, "rt", newline="") if path.endswith(".gz") else open(path, newline="")) as f:
+            text = f.read()
+        if '"' in text or "\r" in text or not text.endswith("\n"):
+            raise HandBack("%s: quoting, carriage returns or no final newline" % path)
+        lines = text[:-1].split("\n")
+        head = lines[0].split("\t")
+        rows = [l.split("\t") for l in lines[1:]]
+        if head[0] != "" or len(set(head[1:])) != len(head) - 1 or any(len(r) != len(head) or r[0] == "" for r in rows) or not rows:
+            raise HandBack("%s: not a labelled matrix with unique columns" % path)
+        return head[1:], rows
+    columns, brows = table(bin_path)
+    vcolumns, vrows = table(vaf_path)
+    labels = [r[0] for r in brows]
+    if not columns or vcolumns != columns or [r[0] for r in vrows] != labels or len(set(labels)) != len(labels):
+        raise HandBack("the matrices differ in rows or columns, or a label repeats")
+    n, m = len(labels), len(columns)
+    bin_ = np.zeros((n, m), np.uint8); vaf4 = np.zeros((n, m), np.int32)
+    int_ok = np.ones(m, bool); vaf_float = np.zeros(m, bool)
+    cache: dict = {}
+    try:
+        for i, (br, vr) in enumerate(zip(brows, vrows)):
+            bin_[i] = [_BIN_CODE[t] for t in br[1:]]
+            int_ok &= [t in _BIN_INT_TEXT for t in br[1:]]
+            vaf4[i] = [_vaf_code(t, cache) for t in vr[1:]]
+            vaf_float |= [t not in _BIN_INT_TEXT for t in vr[1:]]
+    except KeyError as e:
+        raise HandBack("Binary cell %s" % e)
+    if not vaf_float.all():
+        raise HandBack("a VAF column of integers")
+    fusion = np.array(["--" in l for l in labels], bool)
+    pick = lambda flag: [l for l, f in zip(labels, fusion) if f == flag]
+    return columns, pick(False), bin_[~fusion], vaf4[~fusion], pick(True), bin_[fusion], vaf4[fusion], int_ok.astype(np.uint8)
+
+
+def _write_bnpc(engine, columns, col_int_ok, fusion_labels, fusion_bin, fusion_vaf4, barcodes_file, out_prefix, min_cells_per_mut, min_pos_cov):
+    """filter on the device, then the three files: header, the device's rows, the fusion rows (:27: by the column's dtype in Binary, floats in VAF)"""
+    n_rows, n_cols = engine.cellgeno_filter(min_cells_per_mut, min_pos_cov, col_int_ok)
+    f = engine.cellgeno_filter_fetch()
+    kept = np.nonzero(f["col_keep"])[0]
+    assert len(kept) == n_cols and int(f["row_keep"].sum()) == n_rows
+    names = [columns[i] for i in kept]
+    header = "\t".join([""] + names) if names else '""'                                # (to_csv quotes the lone empty field of a frame without columns)
+    for name, slot in (("BinaryMatrix", engine.TABLE_BNPC_BIN), ("VAFMatrix", engine.TABLE_BNPC_VAF)):
+        path = out_prefix + "." + name + ".tsv"
+        with open(path, "w") as out:
+            out.write(header + "\n")
+        engine.format_table(slot)
+        engine.append_table(slot, path)
+        engine.free_table(slot)
+        with open(path, "a") as out:
+            for label, b, v in zip(fusion_labels, fusion_bin, fusion_vaf4):
+                if name == "BinaryMatrix":
+                    cells = ["" if b[i] == 3 else str(int(b[i])) + ("" if f["col_int"][i] else ".0") for i in kept]
+                else:
+                    cells = ["" if v[i] < 0 else repr(int(v[i]) / 10000.0) for i in kept]
+                out.write("\t".join([label] + cells) + "\n")
+    write_bnpc_barcodes(barcodes_file, names, out_prefix + ".Barcodes.tsv")
+    return n_rows + len(fusion_labels), n_cols
+
+
+def format_bnpc_input(engine, columns: Sequence[str], fusions: Sequence[Tuple[str, str]], barcodes_file: str, out_prefix: str,
+                      min_cells_per_mut: int = 5, min_pos_cov: int = 3, *, float_cells: bool = False, fusion_order: Optional[Sequence[str]] = None):
+    """BnpC's input from the state cell_genotype_matrices leaves resident (cells, mat_order, col_src): <out_prefix>.BinaryMatrix.tsv,
+    .VAFMatrix.tsv and .Barcodes.tsv as FormatInputBnpC.py writes them from that run's matrices, without reading those back.  columns,
+    fusions, float_cells: as cell_genotype_matrices made them; fusion_order: the fusion names in the matrices' row order (default: the
+    pairs' order).  Returns (rows written, columns kept)."""
+    pairs = set(fusions)
+    names = list(fusion_order) if fusion_order is not None else list(dict.fromkeys(f for f, _ in fusions))
+    carried = np.array([[1 if (f, c) in pairs else 3 for c in columns] for f in names], np.uint8).reshape(len(names), len(columns))
+    return _write_bnpc(engine, list(columns), bnpc_col_int_ok(columns, fusions, float_cells), names, carried, np.where(carried == 1, 10000, -1),
+                       barcodes_file, out_prefix, min_cells_per_mut, min_pos_cov)
+
+
+def format_bnpc_input_files(engine, bin_path: str, vaf_path: str, barcodes_path: str, out_prefix: str, min_cells_per_mut: int = 5, min_pos_cov: int = 3):
+    """The file-in form: the two matrices parsed, their SNV rows made resident (cellgeno_load_cells + cellgeno_set_text), then as above.
+    A file the device form does not state goes to format_bnpc_input_host.  Returns (rows written, columns kept, "device" or "host")."""
+    try:
+        columns, labels, bin_, vaf4, f_labels, f_bin, f_vaf4, int_ok = read_bnpc_matrices(bin_path, vaf_path)
+    except HandBack:
+        return format_bnpc_input_host(bin_path, vaf_path, barcodes_path, out_prefix, min_cells_per_mut, min_pos_cov) + ("host",)
+    n, m = len(labels), len(columns)
+    engine.cellgeno_load_cells(bin_.reshape(n, m), vaf4.reshape(n, m))
+    engine.cellgeno_set_text([""] * n, [""] * n, labels, columns, [""] * m, [], list(range(n)), list(range(m)), False)
+    return _write_bnpc(engine, columns, int_ok, f_labels, f_bin, f_vaf4, barcodes_path, out_prefix, min_cells_per_mut, min_pos_cov) + ("device",)

@@ -262,7 +262,9 @@ def single_cell_genotype(argv=None):
 def cell_genotype_matrices(argv=None):
     """SingleCellGenotype.py --bam --infile --ref --meta --fusions [FILE] --outfile PREFIX [--alt_flag --nprocs --bin --min_bq --min_mq --tissue
     --tmp_dir --alpha2 --beta2 --pvalue --chrM_contaminant]  (scripts/CellClustering/SingleCellGenotype.py:381-400).  Writes
-    PREFIX.SingleCellGenotype.tsv and PREFIX.{Dp,Alt,VAF,Binary}Matrix.tsv.  --ref is accepted and not needed (:127,140)."""
+    PREFIX.SingleCellGenotype.tsv and PREFIX.{Dp,Alt,VAF,Binary}Matrix.tsv.  --ref is accepted and not needed (:127,140).
+    With --bnpc_outfile PREFIX2 [--min_cells_per_mut --min_pos_cov --bnpc_barcodes FILE (default: --meta)] the process also writes rule
+    FormatInputBnpC's three files from the cells while they are resident (cellclust.format_bnpc_input)."""
     from . import cellclust
     ap = argparse.ArgumentParser(description="SNVs / fusions observed in every cell and the cell-by-variant matrices, on the GPU")
     ap.add_argument("--bam", required=True); ap.add_argument("--infile", required=True); ap.add_argument("--ref", required=True)
@@ -273,6 +275,8 @@ def cell_genotype_matrices(argv=None):
     ap.add_argument("--alpha2", type=float, default=0.2474528917555431); ap.add_argument("--beta2", type=float, default=162.03696139428595)
     ap.add_argument("--pvalue", type=float, default=0.01); ap.add_argument("--chrM_contaminant", default="True")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--bnpc_outfile", nargs="?", const="", default=""); ap.add_argument("--bnpc_barcodes", default=None)
+    ap.add_argument("--min_cells_per_mut", type=int, default=5); ap.add_argument("--min_pos_cov", type=int, default=3)
     _add_htslib_flag(ap)
     a = ap.parse_args(argv)
     _apply_htslib_flag(a)
@@ -288,9 +292,27 @@ def cell_genotype_matrices(argv=None):
         eng.load_reads(dec.records)
         try:
             cellclust.cell_genotype_matrices(eng, a.infile, table, dec.contig_names, a.outfile, a.fusions or None, alt_flag=a.alt_flag, window=a.bin,
-                                             min_bq=a.min_bq, min_mq=a.min_mq, alpha2=a.alpha2, beta2=a.beta2, pvalue=a.pvalue, chrm_contaminant=a.chrM_contaminant)
+                                             min_bq=a.min_bq, min_mq=a.min_mq, alpha2=a.alpha2, beta2=a.beta2, pvalue=a.pvalue, chrm_contaminant=a.chrM_contaminant,
+                                             bnpc_prefix=a.bnpc_outfile, bnpc_barcodes=a.bnpc_barcodes or a.meta, min_cells_per_mut=a.min_cells_per_mut,
+                                             min_pos_cov=a.min_pos_cov)
         except cellclust.NoTargets as e:
             raise SystemExit(str(e))
+
+
+def format_input_bnpc(argv=None):
+    """FormatInputBnpC.py --bin --vaf --barcodes [--min_cells_per_mut 5 --min_pos_cov 3 --outfile PREFIX]
+    (scripts/CellClustering/FormatInputBnpC.py:37-45).  Writes PREFIX.BinaryMatrix.tsv, PREFIX.VAFMatrix.tsv and PREFIX.Barcodes.tsv."""
+    from . import cellclust
+    ap = argparse.ArgumentParser(description="Filter the cell-by-variant matrices into BnpC's input, on the GPU")
+    ap.add_argument("--bin", required=True); ap.add_argument("--vaf", required=True); ap.add_argument("--barcodes", required=True)
+    ap.add_argument("--min_cells_per_mut", type=int, default=5); ap.add_argument("--min_pos_cov", type=int, default=3)
+    ap.add_argument("--outfile", default="Matrix.tsv"); ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    print("Outfile prefix: ", a.outfile, "\n")
+    if os.path.dirname(a.outfile):
+        os.makedirs(os.path.dirname(a.outfile), exist_ok=True)
+    with Engine(a.device) as eng:
+        cellclust.format_bnpc_input_files(eng, a.bin, a.vaf, a.barcodes, a.outfile, a.min_cells_per_mut, a.min_pos_cov)
 
 
 def celltype_reannotation(argv=None):

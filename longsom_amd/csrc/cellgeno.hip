@@ -9,6 +9,12 @@
 // where they lie.  The orders (long table: windows by chromosome text; matrices: natsorted INDEX; columns: sorted CB) and every string a
 // row prints are the host's (longsom_amd/cellclust.py), uploaded once: the device prints n_sites x n_cb rows and four matrices from them.
 // The text is printed twice, as in tables.hip: lengths, a scan, then the bytes.
+//
+// Replaces, of workflow/scripts/CellClustering/FormatInputBnpC.py (rule FormatInputBnpC, rules/CellClustering.smk:105-133),
+//   the read with 3 and "." as NA             :7-8     the resident bin (3) and vaf4 (-1) already say it
+//   the row filter, the column filter         :16,19   k_bnpc_row_count, k_bnpc_col_count, k_bnpc_col_flags, two hipcub selects
+//   loc / concat / to_csv of both matrices    :21-34   k_cell_matrix over the kept rows and columns (kinds M_BNPC_BIN, M_BNPC_VAF)
+// The fusion rows (:11-13,27) and Barcodes.tsv (:9,26,30,35) are the host's (longsom_amd/cellclust.py).
 #include "lsg_ctx.h"
 #include "bb_tail.h"
 #include "text_sink.h"
@@ -68,6 +74,56 @@ __global__ __launch_bounds__(256) void k_cell_tally(const uint8_t* status, int64
     n_cov[cb] = cov; n_pass[cb] = pass;
 }
 
+// FormatInputBnpC.py:16 - bin.replace(0, nan).count(axis = 1) > min_cells_per_mut: per row of mat_order the cells equal to 1 (3 is NA,
+// a column no barcode stands behind is NA).  A wave per row, its lanes along the columns: with col_src ascending, as the sorted columns
+// of a sample's sorted barcodes are, a wave reads 64 neighbouring bytes of the row at a time.
+__global__ __launch_bounds__(256) void k_bnpc_row_count(const uint8_t* bin, const int32_t* mat_order, const int32_t* col_src, int64_t n_mat, int32_t n_cols,
+                                                        int32_t n_cb, int32_t min_mut, int32_t* row_mut, uint8_t* row_keep) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= n_mat) return;
+    const uint8_t* row = bin + (int64_t)mat_order[r] * n_cb;
+    int cnt = 0;
+    for (int col = lane; col < n_cols; col += 64) {
+        const int src = col_src[col];
+        if (src >= 0) cnt += row[src] == 1;
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, 64);
+    if (lane == 0) { row_mut[r] = cnt; row_keep[r] = (uint8_t)(cnt > min_mut); }
+}
+// :19 - bin.count() > min_pos_cov over the rows :16 kept, and the same count over all rows (a column with an NA anywhere was read as
+// float64, :7).  A lane per column, so that neighbours read neighbouring bytes of a row; the rows are split over the workgroups of
+// blockIdx.y, `share` rows each, and a workgroup adds its two sums with ONE atomic per column: integer sums do not depend on the order
+// they arrive in, a wave's 64 adds go to 256 contiguous bytes, and a second pass would need a slab of workgroups x columns partial
+// sums for what is two words per column.  cov_kept / cov_all are zeroed by the caller.
+__global__ __launch_bounds__(256) void k_bnpc_col_count(const uint8_t* bin, const int32_t* mat_order, const int32_t* col_src, const uint8_t* row_keep, int64_t n_mat,
+                                                        int32_t n_cols, int32_t n_cb, int64_t share, int32_t* cov_kept, int32_t* cov_all) {
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= n_cols) return;
+    const int src = col_src[col];
+    if (src < 0) return;                                             // nobody behind the column: it counts 0
+    const int64_t r0 = (int64_t)blockIdx.y * share, r1 = r0 + share < n_mat ? r0 + share : n_mat;
+    int kept = 0, all = 0;
+    for (int64_t r = r0; r < r1; ++r) {
+        const int covered = bin[(int64_t)mat_order[r] * n_cb + src] != 3;
+        all += covered; kept += covered & row_keep[r];
+    }
+    if (all) atomicAdd(cov_all + col, all);
+    if (kept) atomicAdd(cov_kept + col, kept);
+}
+__global__ __launch_bounds__(256) void k_bnpc_col_flags(const int32_t* cov_kept, const int32_t* cov_all, const uint8_t* col_ok, int32_t n_cols, int32_t n_mat,
+                                                        int32_t min_cov, uint8_t* col_keep, uint8_t* col_int) {
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    if (col >= n_cols) return;
+    col_keep[col] = (uint8_t)(cov_kept[col] > min_cov);
+    col_int[col] = (uint8_t)(col_ok[col] != 0 && cov_all[col] == n_mat);
+}
+// lsg_cellgeno_load_cells: the verdict a parsed Binary cell stands for
+__global__ __launch_bounds__(256) void k_cells_status(const uint8_t* bin, int64_t n_cells, uint8_t* status) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cells; i += (int64_t)gridDim.x * blockDim.x)
+        status[i] = (uint8_t)(bin[i] == 3 ? LSG_CELL_NOCOVERAGE : bin[i] == 1 ? LSG_CELL_PASS : LSG_CELL_NOALT);
+}
+
 struct CellArgs {
     const uint32_t* dp; const uint32_t* alt; const int32_t* vaf4; const int32_t* p4; const uint8_t* status; const uint8_t* bin;
     int32_t n_cb, n_cols, float_cells, kind;
@@ -75,6 +131,7 @@ struct CellArgs {
     const uint32_t* head_off; const uint32_t* index_off; const uint32_t* label_off; const uint32_t* cb_off; const uint32_t* ct_off;
     const int32_t* order; int64_t n;                  // the sites in the table's order; n = rows of the table (long: sites x n_cb)
     const int32_t* col_src;
+    const int32_t* col_sel; const uint8_t* col_int;   // the BnpC tables: the kept columns (n_cols of them) and which print as integers; else null
     uint32_t* len; const uint64_t* off; char* text;
 };
 
@@ -122,7 +179,7 @@ __global__ __launch_bounds__(256) void k_cell_row_put(CellArgs a) {
     long_row(s, a, i);
 }
 
-enum { M_DP = 0, M_ALT, M_VAF, M_BIN };
+enum { M_DP = 0, M_ALT, M_VAF, M_BIN, M_BNPC_BIN, M_BNPC_VAF };
 // one cell of a matrix, with the tab before it: the value of (site, barcode of the column), nothing for a column no barcode of the
 // sample stands behind (a barcode of the fusion file alone); float_cells: pandas prints the integer matrices of a pivot with gaps as floats
 template <class S> __device__ __forceinline__ void mat_cell(S& s, const CellArgs& a, int64_t site, int col) {
@@ -130,6 +187,17 @@ template <class S> __device__ __forceinline__ void mat_cell(S& s, const CellArgs
     const int src = a.col_src[col];
     if (src < 0) return;
     const int64_t cell = site * a.n_cb + src;
+    if (a.kind == M_BNPC_BIN) {                                      // FormatInputBnpC.py:33 - NA empty, the value as its column's dtype prints it
+        const int b = a.bin[cell];
+        if (b == 3) return;
+        s.ch((char)('0' + b));
+        if (!a.col_int[col]) LIT(s, ".0");
+        return;
+    }
+    if (a.kind == M_BNPC_VAF) {                                      // :34 - a float column: NA empty
+        if (a.vaf4[cell] >= 0) put_p4(s, a.vaf4[cell]);
+        return;
+    }
     if (a.kind == M_VAF) {                                           // the long table's own string
         if (a.status[cell] == LSG_CELL_NOCOVERAGE) s.ch('.'); else put_p4(s, a.vaf4[cell]);
         return;
@@ -150,13 +218,14 @@ template <bool PUT> __global__ __launch_bounds__(256) void k_cell_matrix(CellArg
     if (PUT) for (uint32_t q = threadIdx.x; q < lab; q += blockDim.x) out[q] = a.label[l0 + q];
     uint32_t base = lab;
     for (int c0 = 0; c0 < a.n_cols; c0 += 256) {
-        const int col = c0 + (int)threadIdx.x;
+        const bool in = c0 + (int)threadIdx.x < a.n_cols;
+        const int col = !in ? 0 : a.col_sel ? a.col_sel[c0 + (int)threadIdx.x] : c0 + (int)threadIdx.x;
         LenSink ls;
-        if (col < a.n_cols) mat_cell(ls, a, site, col);
+        if (in) mat_cell(ls, a, site, col);
         uint32_t excl, total;
         Scan(tmp).ExclusiveSum(ls.n, excl, total);
         __syncthreads();
-        if (PUT && col < a.n_cols) { PutSink ps{out + base + excl}; mat_cell(ps, a, site, col); }
+        if (PUT && in) { PutSink ps{out + base + excl}; mat_cell(ps, a, site, col); }
         base += total;
     }
     if (threadIdx.x == 0) { if (PUT) out[base] = '\n'; else a.len[r] = base + 1; }
@@ -186,7 +255,7 @@ int classify(lsg_ctx* c, const char* who, int64_t n_sites, int32_t n_cb, const u
     }
     hipLaunchKernelGGL(k_cell_tally, dim3((unsigned)((n_cb + 255) / 256)), dim3(256), 0, st, g.status.as<uint8_t>(), n_sites, n_cb, g.n_cov.as<int64_t>(), g.n_pass.as<int64_t>());
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { set_error("%s: kernel failed", who); return -1; }
-    g.n_sites = n_sites; g.n_cb = n_cb; g.valid = true;
+    g.n_sites = n_sites; g.n_cb = n_cb; g.valid = true; g.cells_only = false;
     return 0;
 }
 
@@ -201,7 +270,7 @@ int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_dep
                        const uint8_t* is_chrm, int64_t n_groups, const int64_t* group_off, double alpha2, double beta2, double pvalue) {
     const char* who = "lsg_cellgeno_count";
     CellGeno& g = c->cg;
-    g.valid = g.text_valid = false;
+    g.valid = g.text_valid = g.filt_valid = false;
     for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
     if (int rc = check_tail_params(who, alpha2, beta2, pvalue)) return rc;
     if (c->n_contigs <= 0) { set_error("%s: no contigs set", who); return -2; }
@@ -224,7 +293,7 @@ int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_dep
 int run_cellgeno_load_counts(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint32_t* dp, const uint32_t* alt, const uint8_t* is_chrm, double alpha2, double beta2, double pvalue) {
     const char* who = "lsg_cellgeno_load_counts";
     CellGeno& g = c->cg;
-    g.valid = g.text_valid = false;
+    g.valid = g.text_valid = g.filt_valid = false;
     for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
     if (int rc = check_tail_params(who, alpha2, beta2, pvalue)) return rc;
     if ((double)n_sites * (double)n_cb >= 2147483648.0) { set_error("%s: %lld sites x %d barcodes", who, (long long)n_sites, n_cb); return -2; }
@@ -240,6 +309,7 @@ int run_cellgeno_load_counts(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const ui
 int run_cellgeno_fetch(lsg_ctx* c, uint32_t* dp, uint32_t* alt, int32_t* vaf4, int32_t* p4, uint8_t* status, uint8_t* bin, int64_t* n_covered, int64_t* n_pass) {
     CellGeno& g = c->cg;
     if (!g.valid) { set_error("lsg_cellgeno_fetch: nothing classified (lsg_cellgeno_count first)"); return -2; }
+    if (g.cells_only && (dp || alt || p4)) { set_error("lsg_cellgeno_fetch: the cells were loaded by lsg_cellgeno_load_cells: there are no dp, alt or p4"); return -2; }
     const size_t cells = (size_t)g.n_sites * (size_t)g.n_cb;
     auto get = [&](void* dst, const DevBuf& src, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess; };
     LSG_HIP(get(dp, g.dp, cells * 4)); LSG_HIP(get(alt, g.alt, cells * 4)); LSG_HIP(get(vaf4, g.vaf4, cells * 4)); LSG_HIP(get(p4, g.p4, cells * 4));
@@ -252,7 +322,7 @@ int run_cellgeno_fetch(lsg_ctx* c, uint32_t* dp, uint32_t* alt, int32_t* vaf4, i
 int run_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* t) {
     const char* who = "lsg_cellgeno_set_text";
     CellGeno& g = c->cg;
-    g.text_valid = false;
+    g.text_valid = g.filt_valid = false;
     for (int q = LSG_TABLE_CELL_LONG; q < LSG_TABLE_SLOTS; ++q) c->tab_bytes[q] = -1;
     if (!g.valid) { set_error("%s: nothing classified (lsg_cellgeno_count first)", who); return -2; }
     const int64_t S = g.n_sites; const int32_t B = g.n_cb;
@@ -287,17 +357,126 @@ int run_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* t) {
     return 0;
 }
 
+int run_cellgeno_load_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint8_t* bin, const int32_t* vaf4) {
+    const char* who = "lsg_cellgeno_load_cells";
+    CellGeno& g = c->cg;
+    g.valid = g.text_valid = g.filt_valid = false;
+    for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
+    if ((double)n_sites * (double)n_cb >= 2147483648.0) { set_error("%s: %lld sites x %d barcodes", who, (long long)n_sites, n_cb); return -2; }
+    const int64_t cells = n_sites * (int64_t)n_cb;
+    for (int64_t i = 0; i < cells; ++i) {
+        if (bin[i] != 0 && bin[i] != 1 && bin[i] != 3) { set_error("%s: bin[%lld] = %d is not 0, 1 or 3", who, (long long)i, (int)bin[i]); return -2; }
+        if (vaf4[i] < -1) { set_error("%s: vaf4[%lld] = %d", who, (long long)i, vaf4[i]); return -2; }
+    }
+    const size_t room = (size_t)(cells > 0 ? cells : 1);
+    if (g.bin.reserve(room) || g.status.reserve(room) || g.vaf4.reserve(room * 4) || g.n_cov.reserve((size_t)n_cb * 8) || g.n_pass.reserve((size_t)n_cb * 8)) return -1;
+    hipStream_t st = c->stream;
+    if (cells > 0) {
+        LSG_HIP(hipMemcpyAsync(g.bin.p, bin, (size_t)cells, hipMemcpyHostToDevice, st));
+        LSG_HIP(hipMemcpyAsync(g.vaf4.p, vaf4, (size_t)cells * 4, hipMemcpyHostToDevice, st));
+        unsigned blocks = (unsigned)((cells + 255) / 256); if (blocks > (unsigned)(c->n_cus * 32)) blocks = (unsigned)(c->n_cus * 32);
+        hipLaunchKernelGGL(k_cells_status, dim3(blocks), dim3(256), 0, st, g.bin.as<uint8_t>(), cells, g.status.as<uint8_t>());
+    }
+    hipLaunchKernelGGL(k_cell_tally, dim3((unsigned)((n_cb + 255) / 256)), dim3(256), 0, st, g.status.as<uint8_t>(), n_sites, n_cb, g.n_cov.as<int64_t>(), g.n_pass.as<int64_t>());
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { set_error("%s: kernel failed", who); return -1; }
+    g.n_sites = n_sites; g.n_cb = n_cb; g.valid = true; g.cells_only = true;
+    return 0;
+}
+
+int run_cellgeno_filter(lsg_ctx* c, int32_t min_mut, int32_t min_cov, const uint8_t* col_int_ok, int64_t* n_rows_kept, int32_t* n_cols_kept) {
+    const char* who = "lsg_cellgeno_filter";
+    if (n_rows_kept) *n_rows_kept = 0;
+    if (n_cols_kept) *n_cols_kept = 0;
+    CellGeno& g = c->cg;
+    g.filt_valid = false;
+    c->tab_bytes[LSG_TABLE_BNPC_BIN] = c->tab_bytes[LSG_TABLE_BNPC_VAF] = -1;
+    if (!g.valid || !g.text_valid) { set_error("%s: needs the cells (lsg_cellgeno_count, _load_counts or _load_cells) and lsg_cellgeno_set_text first", who); return -2; }
+    const int64_t R = g.n_mat; const int32_t N = g.n_cols;            // (every mat_order and col_src entry was checked by lsg_cellgeno_set_text)
+    if (N > 0 && !col_int_ok) { set_error("%s: bad arguments", who); return -2; }
+    size_t at = 0;
+    auto place = [&](size_t bytes) { const size_t here = at; at = align_up(at + bytes, 256); return here; };
+    g.f_row_mut_at = place((size_t)R * 4); g.f_cov_kept_at = place((size_t)N * 4); g.f_cov_all_at = place((size_t)N * 4);      // (the two counts adjacent: one memset)
+    g.f_rows_at = place((size_t)R * 4); g.f_cols_at = place((size_t)N * 4); g.f_nsel_at = place(8);
+    g.f_row_keep_at = place((size_t)R); g.f_col_keep_at = place((size_t)N); g.f_col_int_at = place((size_t)N); g.f_col_ok_at = place((size_t)N);
+    if (g.filt.reserve(at + 256)) return -1;
+    hipStream_t st = c->stream;
+    char* f = g.filt.as<char>();
+    const char* tx = g.text.as<char>();
+    const int32_t* mat_order = reinterpret_cast<const int32_t*>(tx + g.mat_order_at);
+    const int32_t* col_src = reinterpret_cast<const int32_t*>(tx + g.col_src_at);
+    int32_t* row_mut = reinterpret_cast<int32_t*>(f + g.f_row_mut_at);
+    int32_t* cov_kept = reinterpret_cast<int32_t*>(f + g.f_cov_kept_at); int32_t* cov_all = reinterpret_cast<int32_t*>(f + g.f_cov_all_at);
+    int32_t* rows = reinterpret_cast<int32_t*>(f + g.f_rows_at); int32_t* cols = reinterpret_cast<int32_t*>(f + g.f_cols_at);
+    int32_t* nsel = reinterpret_cast<int32_t*>(f + g.f_nsel_at);
+    uint8_t* row_keep = reinterpret_cast<uint8_t*>(f + g.f_row_keep_at); uint8_t* col_keep = reinterpret_cast<uint8_t*>(f + g.f_col_keep_at);
+    uint8_t* col_int = reinterpret_cast<uint8_t*>(f + g.f_col_int_at); uint8_t* col_ok = reinterpret_cast<uint8_t*>(f + g.f_col_ok_at);
+    if (N > 0) LSG_HIP(hipMemsetAsync(cov_kept, 0, g.f_rows_at - g.f_cov_kept_at, st));
+    LSG_HIP(hipMemsetAsync(nsel, 0, 8, st));
+    if (N > 0) LSG_HIP(hipMemcpyAsync(col_ok, col_int_ok, (size_t)N, hipMemcpyHostToDevice, st));
+    if (R > 0) hipLaunchKernelGGL(k_bnpc_row_count, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, g.bin.as<uint8_t>(), mat_order, col_src, R, N, g.n_cb, min_mut, row_mut, row_keep);
+    if (R > 0 && N > 0) {
+        const int64_t share = (R + 32767) / 32768 > 128 ? (R + 32767) / 32768 : 128;      // rows per workgroup: 128, more only to keep gridDim.y small
+        hipLaunchKernelGGL(k_bnpc_col_count, dim3((unsigned)((N + 255) / 256), (unsigned)((R + share - 1) / share)), dim3(256), 0, st, g.bin.as<uint8_t>(), mat_order, col_src,
+                           row_keep, R, N, g.n_cb, share, cov_kept, cov_all);
+    }
+    if (N > 0) hipLaunchKernelGGL(k_bnpc_col_flags, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, cov_kept, cov_all, col_ok, N, (int32_t)R, min_cov, col_keep, col_int);
+    LSG_HIP(hipGetLastError());
+    // the kept rows (as sites) and the kept columns, compacted in input order
+    if (R > 0) {
+        size_t tb = 0;
+        LSG_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, mat_order, row_keep, rows, nsel, (int)R, st));
+        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
+        tb = c->d_cub_tmp.cap;
+        LSG_HIP(hipcub::DeviceSelect::Flagged(c->d_cub_tmp.p, tb, mat_order, row_keep, rows, nsel, (int)R, st));
+    }
+    if (N > 0) {
+        hipcub::CountingInputIterator<int32_t> iota(0);
+        size_t tb = 0;
+        LSG_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, iota, col_keep, cols, nsel + 1, (int)N, st));
+        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
+        tb = c->d_cub_tmp.cap;
+        LSG_HIP(hipcub::DeviceSelect::Flagged(c->d_cub_tmp.p, tb, iota, col_keep, cols, nsel + 1, (int)N, st));
+    }
+    LSG_HIP(hipMemcpyAsync(c->h_pin, nsel, 8, hipMemcpyDeviceToHost, st));
+    LSG_HIP(hipStreamSynchronize(st));
+    int32_t got[2];
+    memcpy(got, c->h_pin, 8);
+    if (got[0] < 0 || got[0] > R || got[1] < 0 || got[1] > N) { set_error("%s: the selects kept %d of %lld rows, %d of %d columns", who, got[0], (long long)R, got[1], N); return -1; }
+    g.n_rows_kept = got[0]; g.n_cols_kept = got[1]; g.filt_valid = true;
+    if (n_rows_kept) *n_rows_kept = got[0];
+    if (n_cols_kept) *n_cols_kept = got[1];
+    return 0;
+}
+
+int run_cellgeno_filter_fetch(lsg_ctx* c, uint8_t* row_keep, uint8_t* col_keep, int32_t* row_mut, int32_t* col_cov_kept, int32_t* col_cov_all, uint8_t* col_int) {
+    CellGeno& g = c->cg;
+    if (!g.filt_valid) { set_error("lsg_cellgeno_filter_fetch: nothing filtered (lsg_cellgeno_filter first)"); return -2; }
+    const char* f = g.filt.as<char>();
+    auto get = [&](void* dst, size_t where, size_t bytes) { return dst && bytes ? hipMemcpyAsync(dst, f + where, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess; };
+    const size_t R = (size_t)g.n_mat, N = (size_t)g.n_cols;
+    LSG_HIP(get(row_keep, g.f_row_keep_at, R)); LSG_HIP(get(col_keep, g.f_col_keep_at, N)); LSG_HIP(get(row_mut, g.f_row_mut_at, R * 4));
+    LSG_HIP(get(col_cov_kept, g.f_cov_kept_at, N * 4)); LSG_HIP(get(col_cov_all, g.f_cov_all_at, N * 4)); LSG_HIP(get(col_int, g.f_col_int_at, N));
+    LSG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     if (n_bytes) *n_bytes = 0;
     CellGeno& g = c->cg;
     if (!g.valid || !g.text_valid) { set_error("lsg_format_table: table %d needs lsg_cellgeno_count and lsg_cellgeno_set_text first", table); return -2; }
+    if (g.cells_only && (table == LSG_TABLE_CELL_LONG || table == LSG_TABLE_CELL_DP || table == LSG_TABLE_CELL_ALT)) {
+        set_error("lsg_format_table: table %d needs counts, and the cells were loaded by lsg_cellgeno_load_cells", table); return -2;
+    }
+    const bool is_bnpc = table == LSG_TABLE_BNPC_BIN || table == LSG_TABLE_BNPC_VAF;
+    if (is_bnpc && !g.filt_valid) { set_error("lsg_format_table: table %d needs lsg_cellgeno_filter first", table); return -2; }
     hipStream_t st = c->stream;
     const bool is_long = table == LSG_TABLE_CELL_LONG;
     const char* tx = g.text.as<char>();
     CellArgs a{};
     a.dp = g.dp.as<uint32_t>(); a.alt = g.alt.as<uint32_t>(); a.vaf4 = g.vaf4.as<int32_t>(); a.p4 = g.p4.as<int32_t>(); a.status = g.status.as<uint8_t>(); a.bin = g.bin.as<uint8_t>();
     a.n_cb = g.n_cb; a.n_cols = g.n_cols; a.float_cells = g.float_cells;
-    a.kind = table == LSG_TABLE_CELL_DP ? M_DP : table == LSG_TABLE_CELL_ALT ? M_ALT : table == LSG_TABLE_CELL_VAF ? M_VAF : M_BIN;
+    a.kind = table == LSG_TABLE_CELL_DP ? M_DP : table == LSG_TABLE_CELL_ALT ? M_ALT : table == LSG_TABLE_CELL_VAF ? M_VAF : table == LSG_TABLE_BNPC_BIN ? M_BNPC_BIN :
+             table == LSG_TABLE_BNPC_VAF ? M_BNPC_VAF : M_BIN;
     a.head = tx + g.head_at; a.index = tx + g.index_at; a.label = tx + g.label_at; a.cb = tx + g.cb_at; a.ct = tx + g.ct_at;
     a.head_off = reinterpret_cast<const uint32_t*>(tx + g.head_off_at); a.index_off = reinterpret_cast<const uint32_t*>(tx + g.index_off_at);
     a.label_off = reinterpret_cast<const uint32_t*>(tx + g.label_off_at); a.cb_off = reinterpret_cast<const uint32_t*>(tx + g.cb_off_at);
@@ -305,6 +484,12 @@ int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     a.order = reinterpret_cast<const int32_t*>(tx + (is_long ? g.long_order_at : g.mat_order_at));
     a.col_src = reinterpret_cast<const int32_t*>(tx + g.col_src_at);
     a.n = is_long ? g.n_long * (int64_t)g.n_cb : g.n_mat;
+    if (is_bnpc) {                                                   // the kept rows over the kept columns, both in input order (FormatInputBnpC.py:21-27)
+        const char* f = g.filt.as<char>();
+        a.order = reinterpret_cast<const int32_t*>(f + g.f_rows_at); a.n = g.n_rows_kept;
+        a.col_sel = reinterpret_cast<const int32_t*>(f + g.f_cols_at); a.n_cols = g.n_cols_kept;
+        a.col_int = reinterpret_cast<const uint8_t*>(f + g.f_col_int_at);
+    }
     c->tab_bytes[table] = -1;
     if (a.n == 0) { c->tab_bytes[table] = 0; return 0; }
     // scratch: len[n + 1] | off[n + 1]

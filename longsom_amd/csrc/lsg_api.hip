@@ -29,6 +29,9 @@ int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_dep
 int run_cellgeno_load_counts(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint32_t* dp, const uint32_t* alt, const uint8_t* is_chrm, double alpha2, double beta2, double pvalue);
 int run_cellgeno_fetch(lsg_ctx* c, uint32_t* dp, uint32_t* alt, int32_t* vaf4, int32_t* p4, uint8_t* status, uint8_t* bin, int64_t* n_covered, int64_t* n_pass);
 int run_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* t);
+int run_cellgeno_filter(lsg_ctx* c, int32_t min_cells_per_mut, int32_t min_pos_cov, const uint8_t* col_int_ok, int64_t* n_rows_kept, int32_t* n_cols_kept);
+int run_cellgeno_filter_fetch(lsg_ctx* c, uint8_t* row_keep, uint8_t* col_keep, int32_t* row_mut, int32_t* col_cov_kept, int32_t* col_cov_all, uint8_t* col_int);
+int run_cellgeno_load_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint8_t* bin, const int32_t* vaf4);
 int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes);
 int run_sf4(lsg_ctx* c, int64_t items, const uint32_t* k, const uint32_t* n, double al, double be, int32_t* out, double* raw);
 
@@ -546,6 +549,21 @@ int lsg_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* text) {
     if (!c || !text) { set_error("lsg_cellgeno_set_text: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
     return run_cellgeno_set_text(c, text);
+}
+int lsg_cellgeno_filter(lsg_ctx* c, int32_t min_cells_per_mut, int32_t min_pos_cov, const uint8_t* col_int_ok, int64_t* n_rows_kept, int32_t* n_cols_kept) {
+    if (!c) { set_error("lsg_cellgeno_filter: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_cellgeno_filter(c, min_cells_per_mut, min_pos_cov, col_int_ok, n_rows_kept, n_cols_kept);
+}
+int lsg_cellgeno_filter_fetch(lsg_ctx* c, uint8_t* row_keep, uint8_t* col_keep, int32_t* row_mut, int32_t* col_cov_kept, int32_t* col_cov_all, uint8_t* col_int) {
+    if (!c) { set_error("lsg_cellgeno_filter_fetch: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_cellgeno_filter_fetch(c, row_keep, col_keep, row_mut, col_cov_kept, col_cov_all, col_int);
+}
+int lsg_cellgeno_load_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint8_t* bin, const int32_t* vaf4) {
+    if (!c || n_sites < 0 || n_cb <= 0 || (n_sites > 0 && (!bin || !vaf4))) { set_error("lsg_cellgeno_load_cells: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_cellgeno_load_cells(c, n_sites, n_cb, bin, vaf4);
 }
 
 int lsg_betabinom_sf4(lsg_ctx* c, int64_t n_items, const uint32_t* k, const uint32_t* n, double alpha, double beta, int32_t* out_p4) {

@@ -60,12 +60,17 @@ struct PosSet { DevBuf keys; int64_t n = 0; };
 // cellgeno.hip: what lsg_cellgeno_count / lsg_cellgeno_load_counts leave resident ([n_sites][n_cb] per cell, per barcode the two
 // tallies) and what lsg_cellgeno_set_text uploaded (one buffer; the *_at fields are byte offsets into it)
 struct CellGeno {
-    DevBuf keys, alt_sym, is_chrm, dp, alt, vaf4, p4, status, bin, n_cov, n_pass, text, scratch;
+    DevBuf keys, alt_sym, is_chrm, dp, alt, vaf4, p4, status, bin, n_cov, n_pass, text, scratch, filt;
     int64_t n_sites = 0; int32_t n_cb = 0; bool valid = false;
+    bool cells_only = false;              // lsg_cellgeno_load_cells: bin / vaf4 / status alone are resident, no counts and no tails
     bool text_valid = false; int64_t n_long = 0, n_mat = 0; int32_t n_cols = 0, float_cells = 0;
     size_t head_off_at = 0, index_off_at = 0, label_off_at = 0, cb_off_at = 0, ct_off_at = 0, long_order_at = 0, mat_order_at = 0, col_src_at = 0,
            head_at = 0, index_at = 0, label_at = 0, cb_at = 0, ct_at = 0;
-    void release() { for (DevBuf* b : {&keys, &alt_sym, &is_chrm, &dp, &alt, &vaf4, &p4, &status, &bin, &n_cov, &n_pass, &text, &scratch}) b->release(); valid = text_valid = false; }
+    // lsg_cellgeno_filter (FormatInputBnpC.py:11-19) over mat_order x col_src: one buffer, the f_*_at fields are byte offsets into it
+    bool filt_valid = false; int64_t n_rows_kept = 0; int32_t n_cols_kept = 0;
+    size_t f_row_mut_at = 0, f_cov_kept_at = 0, f_cov_all_at = 0, f_rows_at = 0, f_cols_at = 0, f_nsel_at = 0, f_row_keep_at = 0, f_col_keep_at = 0,
+           f_col_int_at = 0, f_col_ok_at = 0;
+    void release() { for (DevBuf* b : {&keys, &alt_sym, &is_chrm, &dp, &alt, &vaf4, &p4, &status, &bin, &n_cov, &n_pass, &text, &scratch, &filt}) b->release(); valid = text_valid = filt_valid = false; }
 };
 
 // workspace buffers (lsg_ctx::ws)

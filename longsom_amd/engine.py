@@ -452,6 +452,7 @@ class Engine:
     # ---- the tables' text, printed on the device (include/longsom_hip.h: enum lsg_table) ----
     TABLE_COUNTS, TABLE_MERGED, TABLE_STEP1, TABLE_STEP1_KEPT, TABLE_STEP2, TABLE_STEP3_ROWS = 0, 4, 5, 6, 7, 8
     TABLE_CELL_LONG, TABLE_CELL_DP, TABLE_CELL_ALT, TABLE_CELL_VAF, TABLE_CELL_BIN = 9, 10, 11, 12, 13
+    TABLE_BNPC_BIN, TABLE_BNPC_VAF = 14, 15
 
     def set_table_names(self, contig_names, celltype_names) -> None:
         """Names the rows print (contigs in set_contigs order, cell types in index order)."""
@@ -552,7 +553,7 @@ class Engine:
         assert len(site_keys) == len(alt_sym) == len(is_chrm)
         _lib.check(self._lib.lsg_cellgeno_count(self._h, C.byref(params), int(max_depth), len(site_keys), _ptr(site_keys), _ptr(alt_sym), _ptr(is_chrm),
                                                 max(len(group_off) - 1, 0), _ptr(group_off), float(alpha2), float(beta2), float(pvalue)), "lsg_cellgeno_count")
-        self._cell_shape = (len(site_keys), self.n_cb)
+        self._cell_shape = (len(site_keys), self.n_cb); self._cells_only = False; self._filter_shape = self._mat_shape = None
 
     def cellgeno_load_counts(self, dp, alt, is_chrm, alpha2: float = 0.2474528917555431, beta2: float = 162.03696139428595, pvalue: float = 0.01) -> None:
         """The same verdicts for Dp / Alt tables [n_sites, n_cb] the caller brings instead of a count."""
@@ -561,7 +562,40 @@ class Engine:
         assert dp.ndim == 2 and dp.shape == alt.shape and len(is_chrm) == dp.shape[0]
         _lib.check(self._lib.lsg_cellgeno_load_counts(self._h, dp.shape[0], dp.shape[1], _ptr(dp), _ptr(alt), _ptr(is_chrm), float(alpha2), float(beta2), float(pvalue)),
                    "lsg_cellgeno_load_counts")
-        self._cell_shape = dp.shape
+        self._cell_shape = dp.shape; self._cells_only = False; self._filter_shape = self._mat_shape = None
+
+    def cellgeno_load_cells(self, bin, vaf4) -> None:
+        """bin [n_sites, n_cb] in {0, 1, 3} and vaf4 (VAF * 1e4, -1 for NA) parsed from matrix files, made resident as the verdicts of a
+        count would be (lsg_cellgeno_load_cells): for cellgeno_set_text + cellgeno_filter.  There are no counts behind them: the long
+        table, the Dp / Alt matrices and dp / alt / p4 of cellgeno_fetch are refused."""
+        bin = np.ascontiguousarray(bin, dtype=np.uint8); vaf4 = np.ascontiguousarray(vaf4, dtype=np.int32)
+        assert bin.ndim == 2 and bin.shape == vaf4.shape
+        _lib.check(self._lib.lsg_cellgeno_load_cells(self._h, bin.shape[0], bin.shape[1], _ptr(bin), _ptr(vaf4)), "lsg_cellgeno_load_cells")
+        self._cell_shape = bin.shape; self._cells_only = True; self._filter_shape = self._mat_shape = None
+
+    def cellgeno_filter(self, min_cells_per_mut: int, min_pos_cov: int, col_int_ok):
+        """FormatInputBnpC.py's two filters over the rows of mat_order and the columns of col_src (lsg_cellgeno_filter); col_int_ok: per
+        column, whether nothing on the host's side makes it a float column.  Returns (rows kept, columns kept);
+        format_table(TABLE_BNPC_BIN / TABLE_BNPC_VAF) print them."""
+        ok = np.ascontiguousarray(col_int_ok, dtype=np.uint8)
+        shape = getattr(self, "_mat_shape", None)
+        if shape is not None and len(ok) != shape[1]:                                   # (the library reads one flag per column of col_src)
+            raise ValueError("cellgeno_filter: %d flags for %d columns" % (len(ok), shape[1]))
+        n_rows, n_cols = C.c_int64(0), C.c_int32(0)
+        _lib.check(self._lib.lsg_cellgeno_filter(self._h, int(min_cells_per_mut), int(min_pos_cov), _ptr(ok), C.byref(n_rows), C.byref(n_cols)), "lsg_cellgeno_filter")
+        self._filter_shape = (self._mat_shape[0], len(ok))
+        return int(n_rows.value), int(n_cols.value)
+
+    def cellgeno_filter_fetch(self) -> dict:
+        """row_keep, row_mut per row of mat_order; col_keep, col_cov_kept, col_cov_all, col_int per column, of the last cellgeno_filter"""
+        shape = getattr(self, "_filter_shape", None)
+        if shape is None:
+            raise _lib.LsgError("cellgeno_filter_fetch: nothing filtered (cellgeno_filter first)")
+        out = dict(row_keep=np.zeros(shape[0], np.uint8), col_keep=np.zeros(shape[1], np.uint8), row_mut=np.zeros(shape[0], np.int32),
+                   col_cov_kept=np.zeros(shape[1], np.int32), col_cov_all=np.zeros(shape[1], np.int32), col_int=np.zeros(shape[1], np.uint8))
+        _lib.check(self._lib.lsg_cellgeno_filter_fetch(self._h, *[_ptr(out[k]) for k in ("row_keep", "col_keep", "row_mut", "col_cov_kept", "col_cov_all", "col_int")]),
+                   "lsg_cellgeno_filter_fetch")
+        return out
 
     def cellgeno_fetch(self, cells: bool = True) -> dict:
         """dp, alt, vaf4, p4, status, bin [n_sites, n_cb] (cells=False: not these) and n_covered, n_pass [n_cb] of the last cellgeno_count /
@@ -573,6 +607,9 @@ class Engine:
         if cells:
             out.update(dp=np.zeros(shape, np.uint32), alt=np.zeros(shape, np.uint32), vaf4=np.zeros(shape, np.int32), p4=np.zeros(shape, np.int32),
                        status=np.zeros(shape, np.uint8), bin=np.zeros(shape, np.uint8))
+            if getattr(self, "_cells_only", False):                                    # cellgeno_load_cells: no counts, no tails
+                for k in ("dp", "alt", "p4"):
+                    del out[k]
         _lib.check(self._lib.lsg_cellgeno_fetch(self._h, *[_ptr(out.get(k)) for k in ("dp", "alt", "vaf4", "p4", "status", "bin", "n_covered", "n_pass")]), "lsg_cellgeno_fetch")
         return out
 
@@ -594,7 +631,9 @@ class Engine:
             setattr(t, name, b); setattr(t, name + "_off", off.ctypes.data)
         t.n_long, t.long_order, t.n_mat, t.mat_order = len(lo), lo.ctypes.data, len(mo), mo.ctypes.data
         t.n_cols, t.float_cells, t.col_src = len(cs), 1 if float_cells else 0, cs.ctypes.data
+        self._filter_shape = self._mat_shape = None
         _lib.check(self._lib.lsg_cellgeno_set_text(self._h, C.byref(t)), "lsg_cellgeno_set_text")
+        self._mat_shape = (len(mo), len(cs))
 
     def betabinom_sf4(self, k, n, alpha: float, beta: float) -> np.ndarray:
         """round(betabinom.sf(k - 0.001, n, alpha, beta), 4) * 1e4 as int32, evaluated on the device."""

@@ -1,10 +1,19 @@
-### MI355X replacement of rule SingleCellGenotype of LongSom's workflow/rules/CellClustering.smk (same INPUT and OUTPUT files, same flags).
+### MI355X replacement of rules SingleCellGenotype and FormatInputBnpC of LongSom's workflow/rules/CellClustering.smk (same INPUT and OUTPUT
+### files, same flags).
 #
-# The reference states the rule twice (PoN run or not): the two differ only in where alpha2 / beta2 come from - the panel's
-# BetaBinEstimates.txt or config['SNVCalling']['BaseCellCalling'] - and that is the one conditional here.  FormatInputBnpC and
-# BnpC_clustering read the matrices this rule writes and stay the reference's.
+# The reference states SingleCellGenotype twice (PoN run or not): the two differ only in where alpha2 / beta2 come from - the panel's
+# BetaBinEstimates.txt or config['SNVCalling']['BaseCellCalling'] - and that is the one conditional here.  FormatInputBnpC filters the
+# Binary and VAF matrices into BnpC's input; with Run.fuse_bnpc_input: True rule SingleCellGenotype writes that input in its own process,
+# from the cells while they are resident, and FormatInputBnpC has nothing left to do (the rule order below gives the files to the fused
+# rule).  BnpC_clustering reads BnpC_input/ and is the one rule of the chain that stays the reference's.
 
 GPU_SCRIPTS = str(workflow.basedir) + "/scripts_gpu"
+FUSE_BNPC = config['Run'].get('fuse_bnpc_input', False)
+BNPC_INPUT = dict(bnpc_bin="CellClustering/BnpC_input/{id}.BinaryMatrix.tsv",
+                  bnpc_vaf="CellClustering/BnpC_input/{id}.VAFMatrix.tsv",
+                  bnpc_barcodes="CellClustering/BnpC_input/{id}.Barcodes.tsv") if FUSE_BNPC else {}
+
+ruleorder: SingleCellGenotype > FormatInputBnpC
 
 rule SingleCellGenotype:
     input:
@@ -20,7 +29,8 @@ rule SingleCellGenotype:
         alt="CellClustering/SingleCellGenotype/{id}.AltMatrix.tsv",
         vaf="CellClustering/SingleCellGenotype/{id}.VAFMatrix.tsv",
         bin="CellClustering/SingleCellGenotype/{id}.BinaryMatrix.tsv",
-        tmp=temp(directory("CellClustering/SingleCellGenotype/{id}/"))
+        tmp=temp(directory("CellClustering/SingleCellGenotype/{id}/")),
+        **BNPC_INPUT
     params:
         script=GPU_SCRIPTS+"/CellClustering/SingleCellGenotype.py",
         alt_flag=config['CellClust']['SingleCellGenotype']['alt_flag'],
@@ -31,6 +41,10 @@ rule SingleCellGenotype:
         chrm_conta=config['SNVCalling']['BaseCellCalling']['chrM_contaminant'],
         # Run.htslib_legacy_del_merge: True counts CIGAR 1D2D's first deleted column as 'D' (pysam over htslib <= 1.10); default: htslib >= 1.11
         htslib="--htslib_legacy_del_merge" if config['Run'].get('htslib_legacy_del_merge', False) else "",
+        # the fused form: a prefix, or nothing (a bare --bnpc_outfile: no BnpC input is written)
+        bnpc_outfile=lambda w: ("CellClustering/BnpC_input/" + w.id) if FUSE_BNPC else "",
+        min_cells=config['CellClust']['FormatInput']['min_cells_per_mut'],
+        min_cov=config['CellClust']['FormatInput']['min_pos_cov'],
     resources:
         gpu=1
     log:
@@ -53,5 +67,38 @@ rule SingleCellGenotype:
         --beta2 {params.beta2} \
         --alt_flag {params.alt_flag} \
         --chrM_contaminant {params.chrm_conta} \
+        --min_cells_per_mut {params.min_cells} \
+        --min_pos_cov {params.min_cov} \
+        --bnpc_outfile {params.bnpc_outfile} \
         --tmp_dir {output.tmp} {params.htslib}
+        """
+
+rule FormatInputBnpC:
+    input:
+        bin="CellClustering/SingleCellGenotype/{id}.BinaryMatrix.tsv",
+        vaf="CellClustering/SingleCellGenotype/{id}.VAFMatrix.tsv",
+        barcodes="CellTypeReannotation/ReannotatedCellTypes/{id}.tsv",
+    output:
+        bin="CellClustering/BnpC_input/{id}.BinaryMatrix.tsv",
+        vaf="CellClustering/BnpC_input/{id}.VAFMatrix.tsv",
+        barcodes="CellClustering/BnpC_input/{id}.Barcodes.tsv",
+    params:
+        script=GPU_SCRIPTS+"/CellClustering/FormatInputBnpC.py",
+        min_cells=config['CellClust']['FormatInput']['min_cells_per_mut'],
+        min_cov=config['CellClust']['FormatInput']['min_pos_cov'],
+    resources:
+        gpu=1
+    log:
+        "logs/FormatInputBnpC/{id}.log",
+    benchmark:
+        "benchmarks/FormatInputBnpC/{id}.benchmark.txt"
+    shell:
+        r"""
+        python {params.script} \
+        --bin {input.bin} \
+        --vaf {input.vaf} \
+        --barcodes {input.barcodes} \
+        --min_pos_cov {params.min_cov} \
+        --min_cells_per_mut {params.min_cells} \
+        --outfile CellClustering/BnpC_input/{wildcards.id}
         """
