@@ -5,7 +5,7 @@
 //
 // This is the device half of reading a BAM (the reference reads BAMs through pysam / htslib's bgzf + zlib,
 // BaseCellCounter.py:190-191, SplitBamCellTypes.py:51-65).  The same source is compiled for the host by tests/native/test_inflate.cpp,
-// which checks it byte for byte against zlib's inflate on random, compressible, stored, fixed-code and corrupted streams.
+// which checks it byte for byte against zlib's inflate on random, compressible, stored, fixed-code, spliced and corrupted streams.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>

@@ -19,6 +19,7 @@
 //   lsg_load_reads on the device arrays: the tile store (store.hip)
 #include "lsg_ctx.h"
 #include "inflate_core.h"
+#include "crc_core.h"
 #include "cbtable_host.h"
 #include <hipcub/hipcub.hpp>
 #include <chrono>
@@ -48,17 +49,9 @@ __global__ __launch_bounds__(64) void k_inflate(const uint8_t* comp, const IngBl
     }
 }
 
-// CRC32 (IEEE 802.3, reflected: zlib's crc32) of every block's uncompressed bytes against the block's trailer.  One WAVE per block: lane i
-// takes the 1 KB chunk i of the block's <= 64 KB (bytewise table in LDS, 16 bytes per load), the 64 chunk CRCs are combined as zlib's
-// crc32_combine does - CRC is linear over GF(2): crc0(A || B) = shift(crc0(A), |B|) ^ crc0(B) with crc0 the register started at 0 and
-// shift(v, n) = v run through n zero bytes, done as a product with the precomputed 32 x 32 bit matrices of 2^k zero bytes (zero_ops) -
-// and the initial and final complement are put back: crc32(M) = crc0(M) ^ shift(0xffffffff, |M|) ^ 0xffffffff.
-struct CrcTables { uint32_t byte_tab[256]; uint32_t zero_ops[17][32]; };      // zero_ops[k][j]: where bit j of the register goes under 2^k zero bytes
-__device__ __forceinline__ uint32_t crc_shift(const uint32_t (*ops)[32], uint32_t v, uint32_t n_bytes) {
-    for (int k = 0; n_bytes; ++k, n_bytes >>= 1)
-        if (n_bytes & 1u) { uint32_t r = 0; for (int j = 0; j < 32; ++j) r ^= (v >> j) & 1u ? ops[k][j] : 0u; v = r; }
-    return v;
-}
+// CRC32 of every block's uncompressed bytes against the block's trailer.  One WAVE per block: lane i takes the 1 KB chunk i of the
+// block's <= 64 KB, the 64 chunk CRCs are combined as zlib's crc32_combine does (crc_core.h has the arithmetic and its derivation)
+using lsc::CrcTables; using lsc::crc_shift;
 __global__ __launch_bounds__(256) void k_block_crc(const uint8_t* ubuf, const IngBlk* blk, uint32_t n_blk, const CrcTables* tabs, uint32_t* status) {
     __shared__ uint32_t tab[256];
     __shared__ uint32_t ops[17][32];
@@ -69,24 +62,9 @@ __global__ __launch_bounds__(256) void k_block_crc(const uint8_t* ubuf, const In
     for (uint32_t b = blockIdx.x * 4u + (threadIdx.x >> 6); b < n_blk; b += gridDim.x * 4u) {
         const IngBlk d = blk[b];
         if (!d.usize) continue;
-        const uint32_t lo = lane * 1024u, hi = lo + 1024u < d.usize ? lo + 1024u : d.usize;
+        const uint32_t lo = lane * lsc::CHUNK, hi = lo + lsc::CHUNK < d.usize ? lo + lsc::CHUNK : d.usize;
         uint32_t c = 0;
-        if (lo < d.usize) {
-            const uint8_t* p = ubuf + d.uoff;
-            uint32_t i = lo;
-            for (; i < hi && ((d.uoff + i) & 15u); ++i) c = tab[(c ^ p[i]) & 0xffu] ^ (c >> 8);
-            for (; i + 16 <= hi; i += 16) {
-                const uint4 q = *reinterpret_cast<const uint4*>(p + i);
-                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    c ^= w[k];
-                    c = tab[c & 0xffu] ^ (c >> 8); c = tab[c & 0xffu] ^ (c >> 8); c = tab[c & 0xffu] ^ (c >> 8); c = tab[c & 0xffu] ^ (c >> 8);
-                }
-            }
-            for (; i < hi; ++i) c = tab[(c ^ p[i]) & 0xffu] ^ (c >> 8);
-            c = crc_shift(ops, c, d.usize - hi);                      // ... through the bytes of the block behind this chunk
-        }
+        if (lo < d.usize) c = crc_shift(ops, lsc::crc_chunk(tab, ubuf + d.uoff, d.uoff, lo, hi), d.usize - hi);      // ... through the bytes of the block behind this chunk
         for (int o = 32; o > 0; o >>= 1) c ^= (uint32_t)__shfl_xor((int)c, o);
         if (lane == 0) {
             const uint32_t crc = c ^ crc_shift(ops, 0xffffffffu, d.usize) ^ 0xffffffffu;
@@ -94,13 +72,6 @@ __global__ __launch_bounds__(256) void k_block_crc(const uint8_t* ubuf, const In
         }
     }
 }
-static void make_crc_tables(CrcTables& t) {
-    for (uint32_t i = 0; i < 256; ++i) { uint32_t c = i; for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1; t.byte_tab[i] = c; }
-    for (int j = 0; j < 32; ++j) { uint32_t v = 1u << j; v = t.byte_tab[v & 0xffu] ^ (v >> 8); t.zero_ops[0][j] = v; }      // one zero byte
-    for (int k = 1; k < 17; ++k)                                        // the operator of 2^k zero bytes = the one of 2^(k-1) applied twice
-        for (int j = 0; j < 32; ++j) { const uint32_t v = t.zero_ops[k - 1][j]; uint32_t r = 0; for (int b = 0; b < 32; ++b) r ^= (v >> b) & 1u ? t.zero_ops[k - 1][b] : 0u; t.zero_ops[k][j] = r; }
-}
-
 // (One WAVE per block — uniform decode, a 32 KB LDS ring for the output, match copies spread over the lanes — was built and measured
 // this round: 0.8-1.3 s per GB of BAM against 0.17 s for the lane form above.  A DEFLATE symbol is a serial dependency chain of ~100
 // scalar-like operations; a wave that runs one chain uses a 64th of the vector unit.  DESIGN.md §8.)
@@ -374,7 +345,7 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     d_comp.release();
     if (!getenv("LSG_NO_BGZF_CRC")) {                     // every block's CRC32 against its trailer (k_block_crc)
         static CrcTables h_tabs; static bool h_tabs_made = false;
-        if (!h_tabs_made) { make_crc_tables(h_tabs); h_tabs_made = true; }
+        if (!h_tabs_made) { lsc::make_crc_tables(h_tabs); h_tabs_made = true; }
         DevBuf d_tabs;
         if (d_tabs.reserve(sizeof(CrcTables))) return done_ev(-1);
         ING_HIP(hipMemcpyAsync(d_tabs.p, &h_tabs, sizeof(CrcTables), hipMemcpyHostToDevice, st));

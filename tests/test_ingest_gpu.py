@@ -112,27 +112,10 @@ def test_damaged_files_are_errors(engine, tmp_path):
     assert engine.reads_shape()[0] == 1333
 
 
-@pytest.mark.parametrize("source", ["rand", "synth"])
-@pytest.mark.parametrize("world", [2, 5])
-def test_slices_of_an_indexed_bam_add_up_to_the_whole(engine, tmp_path, source, world):
-    """lsg_load_bam_range over the slices regions.BaiPlan cuts from the .bai's linear index: every region's rows are the whole file's
-    rows inside the region, SplitBam's counters and the per-barcode tallies add up to the whole file's — on the reference-pinned sample
-    (records straddle its blocks: a slice starts INSIDE a block, its last record is cut) and on an htslib-like 20 k-read BAM"""
-    import shutil
-    from longsom_amd import regions, tsvio
-    bam = str(tmp_path / "a.bam")
-    if source == "rand":
-        shutil.copy(os.path.join(G, "pileup.rand.bam"), bam)
-        bc = hostio.read_barcodes(os.path.join(G, "pileup.rand.barcodes.tsv"))
-        barcodes, celltype_of = bc.barcodes, bc.celltype_of
-        _, seqs = tsvio.read_fasta(os.path.join(G, "pileup.rand.fa"))
-        refs = [np.frombuffer(bytes(x), dtype=np.uint8) for x in seqs]
-    else:
-        m = synth.named("C1", n_reads=20000, n_genes=50, n_cb=80, snp_mod=150)
-        hostio.synth_bam(m, bam, str(tmp_path / "ref.fa"))
-        barcodes, celltype_of = hostio.synth_barcodes(m), m.celltype_of
-        _, seqs = tsvio.read_fasta(str(tmp_path / "ref.fa"))
-        refs = [np.frombuffer(bytes(x), dtype=np.uint8) for x in seqs]
+def slices_add_up(engine, bam, barcodes, celltype_of, refs, world):
+    """the whole file's load against its `world` slices (regions.BaiPlan over the file's own .bai): the slices' count rows, concatenated,
+    are the whole file's; SplitBam's counters and the per-barcode tallies add up"""
+    from longsom_amd import regions
     names, lens, first = hostio.bam_header(bam)
     engine.set_contigs(lens)
     for t, r in enumerate(refs):
@@ -165,6 +148,30 @@ def test_slices_of_an_indexed_bam_add_up_to_the_whole(engine, tmp_path, source, 
     for ct in range(2):
         for j in range(3):
             np.testing.assert_array_equal(np.concatenate([x[j] for x in parts[ct]]), whole[ct][j])
+
+
+@pytest.mark.parametrize("source", ["rand", "synth"])
+@pytest.mark.parametrize("world", [2, 5])
+def test_slices_of_an_indexed_bam_add_up_to_the_whole(engine, tmp_path, source, world):
+    """lsg_load_bam_range over the slices regions.BaiPlan cuts from the .bai's linear index: every region's rows are the whole file's
+    rows inside the region, SplitBam's counters and the per-barcode tallies add up to the whole file's — on the reference-pinned sample
+    (records straddle its blocks: a slice starts INSIDE a block, its last record is cut) and on an htslib-like 20 k-read BAM"""
+    import shutil
+    from longsom_amd import tsvio
+    bam = str(tmp_path / "a.bam")
+    if source == "rand":
+        shutil.copy(os.path.join(G, "pileup.rand.bam"), bam)
+        bc = hostio.read_barcodes(os.path.join(G, "pileup.rand.barcodes.tsv"))
+        barcodes, celltype_of = bc.barcodes, bc.celltype_of
+        _, seqs = tsvio.read_fasta(os.path.join(G, "pileup.rand.fa"))
+        refs = [np.frombuffer(bytes(x), dtype=np.uint8) for x in seqs]
+    else:
+        m = synth.named("C1", n_reads=20000, n_genes=50, n_cb=80, snp_mod=150)
+        hostio.synth_bam(m, bam, str(tmp_path / "ref.fa"))
+        barcodes, celltype_of = hostio.synth_barcodes(m), m.celltype_of
+        _, seqs = tsvio.read_fasta(str(tmp_path / "ref.fa"))
+        refs = [np.frombuffer(bytes(x), dtype=np.uint8) for x in seqs]
+    slices_add_up(engine, bam, barcodes, celltype_of, refs, world)
 
 
 def test_the_whole_device_ingest_path_at_scale(engine, tmp_path):
