@@ -489,6 +489,38 @@ int lsg_cellgeno_filter_fetch(lsg_ctx* ctx, uint8_t* row_keep, uint8_t* col_keep
  * no counts and no tails: LSG_TABLE_CELL_LONG, _DP and _ALT and the dp / alt / p4 of lsg_cellgeno_fetch are refused until the next count. */
 int lsg_cellgeno_load_cells(lsg_ctx* ctx, int64_t n_sites, int32_t n_cb, const uint8_t* bin, const int32_t* vaf4);
 
+/* ---- BnpC's posterior estimate (CellClustering/libs/utils.py:90-245; rule BnpC_clustering, rules/CellClustering.smk:135-176) ----------
+ * The deterministic half of BnpC: from the chains' posterior samples to one clustering and its genotypes.  The sampler (libs/CRP.py,
+ * libs/MCMC.py) stays the caller's and feeds it.  Nothing else need be resident: no reads, contigs or barcodes.
+ * lsg_bnpc_load_samples makes the samples resident: the chains concatenated after burn-in (_concat_chain_results, :206-223).
+ *   assign [n_samples][n_cells]   cell i's cluster label in sample s, any integer in [0, n_cells); kept as 16 bits
+ *   params [n_samples][k_max][n_muts]   row r = the parameters of the r-th smallest label present in the sample, zero beyond the sample's
+ *            cluster count (Chain.update_results, MCMC.py:260-282).  May be NULL: lsg_bnpc_mean_params is then refused.
+ * Refused with a message: n_cells < 2 or > 65535, n_samples < 1, a label outside [0, n_cells).  A second load replaces the first.
+ * lsg_bnpc_codist counts, for every pair i < j in pdist's condensed order (0,1), (0,2), .., (n-2,n-1), the samples in which the two
+ * cells' labels differ: get_dist (:90-97) before its division by n_samples.  The counts stay resident; lsg_bnpc_fetch_dist copies the
+ * n (n - 1) / 2 of them out.
+ * lsg_bnpc_mpear makes one pass over them for n_cuts candidate clusterings labels [n_cuts][n_cells] (values in [0, n_cells)):
+ *   same_pairs[k] = the pairs whose two labels in cut k are equal          (_calc_MPEAR's I.sum(), :134-136)
+ *   same_sim[k]   = the sum of n_samples - D over those pairs              (n_samples x (I * pi).sum(), :138)
+ *   *dist_sum     = the sum of D over all pairs                            (pi.sum() = (pairs x n_samples - dist_sum) / n_samples, :137)
+ * exact integers, whatever the order they were added in; the caller forms the score (:140-143) from them in fp64.
+ * lsg_bnpc_mean_params is get_mean_hierarchy_assignment (:149-189) for a final assignment final_assign [n_cells]; its clusters are the
+ * n_clusters distinct values, ascending.  Per cluster c and sample s: "same" = all of c's cells carry one label L (:157-162; always for a
+ * one-cell cluster), "no others" = L occurs in no cell outside c (:164-167), rel = the distinct labels of the sample smaller than L (the row
+ * :178-180 pick).  The samples used are those with both, if any, else those with "same" (:170-175): params[c][m] = the sum of
+ * params[s][rel][m], widened to double and added in ascending sample order, divided by their number n_used[c].  Where no sample has
+ * "same" (:183-189): the sum over all samples and all of c's cells of the row of the cell's label, divided by n_samples x cells.
+ *   params [n_clusters][n_muts] doubles; branch[c] = 0 both criteria, 1 the first only, 2 neither, 3 a one-cell cluster; branch and
+ *   n_used may be NULL.
+ * lsg_bnpc_unload frees all of it. */
+int lsg_bnpc_load_samples(lsg_ctx* ctx, int64_t n_samples, int32_t n_cells, const int32_t* assign, int32_t k_max, int32_t n_muts, const float* params);
+int lsg_bnpc_codist(lsg_ctx* ctx);
+int lsg_bnpc_fetch_dist(lsg_ctx* ctx, uint32_t* dist, int64_t capacity);
+int lsg_bnpc_mpear(lsg_ctx* ctx, int32_t n_cuts, const int32_t* labels, uint64_t* same_pairs, uint64_t* same_sim, uint64_t* dist_sum);
+int lsg_bnpc_mean_params(lsg_ctx* ctx, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used);
+int lsg_bnpc_unload(lsg_ctx* ctx);
+
 /* ---- measurement helpers --------------------------------------------------------------------*/
 /* Statistics of the last lsg_pileup_count: admitted reads / segments / events (events that passed
  * read admission, before the base-quality gate), tile entries, non-empty units, deep units. */

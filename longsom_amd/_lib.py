@@ -177,6 +177,12 @@ SIGNATURES = {
     "lsg_cellgeno_filter": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsg_cellgeno_filter_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsg_cellgeno_load_cells": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lsg_bnpc_load_samples": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "lsg_bnpc_codist": (C.c_int, [C.c_void_p]),
+    "lsg_bnpc_fetch_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "lsg_bnpc_mpear": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_bnpc_mean_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_bnpc_unload": (C.c_int, [C.c_void_p]),
     "lsg_betabinom_sf4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "lsg_betabinom_sf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "lsg_max_live_reads": (C.c_int64, [C.c_void_p]),

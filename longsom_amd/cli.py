@@ -5,6 +5,7 @@ import argparse
 import glob
 import json
 import os
+import sys
 import time
 
 from . import calling, hostio, pipeline, tsvio
@@ -313,6 +314,164 @@ def format_input_bnpc(argv=None):
         os.makedirs(os.path.dirname(a.outfile), exist_ok=True)
     with Engine(a.device) as eng:
         cellclust.format_bnpc_input_files(eng, a.bin, a.vaf, a.barcodes, a.outfile, a.min_cells_per_mut, a.min_pos_cov)
+
+
+def _bnpc_parser():
+    """the flags of scripts/CellClustering/run_BnpC.py:13-205, and three of this script's own"""
+    def ratio(lo_open, hi_open, lo=0.0, hi=1.0):
+        def check(val):
+            val = float(val)
+            if (val <= lo if lo_open else val < lo) or (val >= hi if hi_open else val > hi):
+                raise argparse.ArgumentTypeError("Invalid value: %s. Values need to be %s %s x %s %s" % (val, lo, "<" if lo_open else "<=", "<" if hi_open else "<=", hi))
+            return val
+        return check
+    check_ratio, check_percent, check_psrf = ratio(True, True), ratio(False, False), ratio(False, False, 1.0, 1.5)
+    ap = argparse.ArgumentParser(prog="BnpC", usage="python3 run_BnpC.py <DATA> [options]",
+                                 description="BnpC clustering: the reference's sampler, the posterior estimate on the GPU")
+    ap.add_argument("--version", action="version", version="0.2.1")
+    ap.add_argument("input", nargs="?", help="the cells' matrix: BnpC_input/<id>.BinaryMatrix.tsv (required)")
+    ap.add_argument("-t", "--transpose", action="store_false")
+    ap.add_argument("--debug", action="store_true", default=False)
+    ap.add_argument("--barcodes", type=str)
+    ap.add_argument("--mut_order", type=str, nargs="?", const="", default="")
+    m = ap.add_argument_group("model")
+    m.add_argument("-FN", "--falseNegative", type=float, default=-1)
+    m.add_argument("-FP", "--falsePositive", type=float, default=-1)
+    m.add_argument("-FN_m", "--falseNegative_mean", type=check_ratio, default=0.2)
+    m.add_argument("-FN_sd", "--falseNegative_std", type=check_ratio, default=0.1)
+    m.add_argument("-FP_m", "--falsePositive_mean", type=check_ratio, default=0.01)
+    m.add_argument("-FP_sd", "--falsePositive_std", type=check_ratio, default=0.01)
+    m.add_argument("-ap", "--DPa_prior", type=float, nargs=2, default=[-1, -1])
+    m.add_argument("-pp", "--param_prior", type=float, nargs=2, default=[.25, .25])
+    m.add_argument("-fa", "--fixed_assignment", type=str, default="")
+    c = ap.add_argument_group("MCMC")
+    c.add_argument("-n", "--chains", type=int, default=1)
+    c.add_argument("-s", "--steps", type=int, default=5000)
+    c.add_argument("-r", "--runtime", type=int, default=-1)
+    c.add_argument("-ls", "--lugsail", type=check_psrf, default=-1)
+    c.add_argument("-b", "--burn_in", type=check_percent, default=0.33)
+    c.add_argument("-cup", "--conc_update_prob", type=check_percent, default=0.25)
+    c.add_argument("-eup", "--error_update_prob", type=check_percent, default=0.25)
+    c.add_argument("-smp", "--split_merge_prob", type=check_percent, default=0.33)
+    c.add_argument("-sms", "--split_merge_steps", type=int, default=3)
+    c.add_argument("-smr", "--split_merge_ratios", type=check_percent, nargs=2, default=[0.75, 0.25])
+    c.add_argument("-e", "--estimator", type=str, default="posterior", nargs="+", choices=["posterior", "ML", "MAP"])
+    c.add_argument("-sc", "--single_chains", action="store_true", default=False)
+    c.add_argument("--seed", type=int, default=-1)
+    o = ap.add_argument_group("output")
+    o.add_argument("-o", "--output", type=str, default="")
+    o.add_argument("-v", "--verbosity", type=int, default=1, choices=[0, 1, 2])
+    o.add_argument("-np", "--no_plots", action="store_true", default=False)
+    o.add_argument("-tr", "--tree", type=str, default="")
+    o.add_argument("-tc", "--true_clusters", type=str, default="")
+    o.add_argument("-td", "--true_data", type=str, default="")
+    g = ap.add_argument_group("this script's own")
+    g.add_argument("--bnpc_libs", default="", help="the vendored BnpC's libs/ directory (default: ../../scripts/CellClustering/libs of the checkout this script lies in)")
+    g.add_argument("--save_chains", default="", help="write the chains to this .npz")
+    g.add_argument("--chains_npz", default="", help="estimate from chains saved by --save_chains: no sampler is run")
+    g.add_argument("--host_estimate", action="store_true", help="the numpy twin of the estimate, for a machine without a GPU")
+    g.add_argument("--device", type=int, default=0)
+    return ap
+
+
+def run_bnpc(argv=None):
+    """run_BnpC.py: the chains come from the vendored BnpC's sampler (libs/MCMC.py, run as the reference runs it) or from --chains_npz; the
+    posterior estimate is made on the device (longsom_amd.bnpc); assignment.txt, errors.txt and genotypes_*.tsv are written here; args.txt,
+    the PSRF, -e ML|MAP, the summaries and the plots are left to the checkout's own functions."""
+    from datetime import datetime
+    from . import bnpc
+    ap = _bnpc_parser()
+    a = ap.parse_args(argv)
+    if a.input is None:
+        ap.error("the following arguments are required: input")
+    script_dir = os.path.dirname(os.path.abspath(sys.argv[0]))          # the shim's place in the checkout it was dropped into
+    if isinstance(a.estimator, str):
+        a.estimator = [a.estimator]
+    if a.single_chains:
+        sys.exit("run_BnpC.py: -sc/--single_chains is not supported here: the posterior estimate is made once, over all chains")
+    point = [e for e in a.estimator if e != "posterior"]
+    if a.chains_npz and point:
+        sys.exit("run_BnpC.py: -e %s needs the sampler's run: it cannot be combined with --chains_npz" % " ".join(point))
+    libs_dir = a.bnpc_libs or os.path.join(script_dir, "..", "..", "scripts", "CellClustering", "libs")
+    have_libs = os.path.isfile(os.path.join(libs_dir, "MCMC.py"))
+    if not have_libs and not (a.chains_npz and a.no_plots):
+        sys.exit("run_BnpC.py: no vendored BnpC at %s (--bnpc_libs DIR): the sampler and the plots are the checkout's; only --chains_npz with --no_plots runs without one" % libs_dir)
+    io = ut = None
+    if have_libs:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(libs_dir)))
+        import libs.dpmmIO as io
+        import libs.utils as ut
+    if io is not None:
+        io.process_sim_folder(a, suffix="")
+    data, names = bnpc.load_data(a.input, transpose=a.transpose)
+    assert data.size > 0, f"Could not read data from file: {a.input}"
+    a.time = [datetime.now()]
+    if a.chains_npz:
+        results = bnpc.load_chains(a.chains_npz)
+    else:
+        from libs.MCMC import MCMC
+        if a.falsePositive > 0 and a.falseNegative > 0:                      # run_BnpC.py:261-296
+            a.error_update_prob = 0
+            import libs.CRP as CRP
+            model = CRP.CRP(data, DP_alpha=a.DPa_prior, param_beta=a.param_prior, FN_error=a.falseNegative, FP_error=a.falsePositive)
+        else:
+            import libs.CRP_learning_errors as CRP
+            model = CRP.CRP_errors_learning(data, DP_alpha=a.DPa_prior, param_beta=a.param_prior, FP_mean=a.falsePositive_mean, FP_sd=a.falsePositive_std,
+                                            FN_mean=a.falseNegative_mean, FN_sd=a.falseNegative_std)
+        run_var, run_str = io._get_mcmc_termination(a)
+        mcmc = MCMC(model, sm_prob=a.split_merge_prob, dpa_prob=a.conc_update_prob, error_prob=a.error_update_prob, sm_ratios=a.split_merge_ratios, sm_steps=a.split_merge_steps)
+        if a.verbosity > 0:
+            print(model); print(mcmc); print(f"Run MCMC with ({a.chains} chains {run_str}):")
+        if a.debug:
+            a.chains = 1
+        mcmc.run(run_var, a.seed, a.chains, a.verbosity, a.fixed_assignment, a.debug)
+        a.chain_seeds = mcmc.get_seeds()
+        results = mcmc.get_results()
+    a.time.append(datetime.now())
+    if a.save_chains:
+        bnpc.save_chains(a.save_chains, results)
+
+    # dpmmIO._infer_results (:199-225) with the posterior estimate taken from the device
+    if ut is not None:
+        a.PSRF = ut.get_lugsail_batch_means_est([(r["ML"], r["burn_in"]) for r in results])
+    a.steps = [r["ML"].size for r in results]
+    cat = bnpc.concat_chains(results)
+    inferred = {"mean": {}}
+    for est in a.estimator:
+        if est != "posterior":
+            inferred["mean"][est] = ut.get_latents_point(results, est, data, False)[0]
+        elif a.host_estimate:
+            inferred["mean"][est] = bnpc.posterior_estimate_host(cat["assignments"], cat["params"], data, cat["DP_alpha"], cat["FN"], cat["FP"])
+        else:
+            with Engine(a.device) as eng:
+                inferred["mean"][est] = bnpc.posterior_estimate(eng, cat["assignments"], cat["params"], data, cat["DP_alpha"], cat["FN"], cat["FP"])
+    out_dir = bnpc.out_dir_of(a.output, a.input, f"{a.time[0]:%Y%m%d_%H:%M:%S}")
+    if a.verbosity > 0 and io is not None and not a.chains_npz:
+        io.show_MCMC_summary(a, results)
+        io.show_assignments(inferred, names[0])
+        io.show_latents(inferred)
+    if a.verbosity > 0:
+        print(f"\nWriting output to: {out_dir}\n")
+    bnpc.save_errors(inferred, a.estimator, a.chains, out_dir)
+    bnpc.save_assignments(inferred, a.estimator, a.chains, out_dir)
+    bnpc.save_geno(inferred, out_dir, names[1])
+    if io is not None:
+        if a.true_clusters:
+            true_assign = io.load_txt(a.true_clusters)
+            io.save_v_measure(inferred, true_assign, out_dir)
+            io.save_ARI(inferred, true_assign, out_dir)
+        data_plot = data
+        if a.true_data:
+            data_plot = io.load_data(a.true_data, transpose=a.transpose)
+            io.save_hamming_dist(inferred, data_plot, out_dir)
+        if not a.no_plots:
+            io.save_geno_plots(a, inferred, data_plot, out_dir, names)          # the rule's declared output: genoCluster_posterior_mean_raw.pdf
+            if data.shape[0] < 300:
+                io.save_similarity(a, inferred, results, out_dir)
+        if not a.chains_npz:
+            for k in ("bnpc_libs", "save_chains", "chains_npz", "host_estimate", "device"):      # args.txt lists the reference's arguments
+                vars(a).pop(k)
+            io.save_config(a, out_dir)
 
 
 def celltype_reannotation(argv=None):

@@ -33,6 +33,12 @@ int run_cellgeno_filter(lsg_ctx* c, int32_t min_cells_per_mut, int32_t min_pos_c
 int run_cellgeno_filter_fetch(lsg_ctx* c, uint8_t* row_keep, uint8_t* col_keep, int32_t* row_mut, int32_t* col_cov_kept, int32_t* col_cov_all, uint8_t* col_int);
 int run_cellgeno_load_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint8_t* bin, const int32_t* vaf4);
 int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes);
+int run_bnpc_load(lsg_ctx* c, int64_t n_samples, int32_t n_cells, const int32_t* assign, int32_t k_max, int32_t n_muts, const float* params);
+int run_bnpc_codist(lsg_ctx* c);
+int run_bnpc_fetch_dist(lsg_ctx* c, uint32_t* out, int64_t capacity);
+int run_bnpc_mpear(lsg_ctx* c, int32_t n_cuts, const int32_t* labels, uint64_t* same_pairs, uint64_t* same_sim, uint64_t* dist_sum);
+int run_bnpc_mean_params(lsg_ctx* c, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used);
+int run_bnpc_unload(lsg_ctx* c);
 int run_sf4(lsg_ctx* c, int64_t items, const uint32_t* k, const uint32_t* n, double al, double be, int32_t* out, double* raw);
 
 // copy a host or device array into a grow-only device buffer of the handle (the caller's array is free again when the call returns)
@@ -106,6 +112,7 @@ void lsg_destroy(lsg_ctx* c) {
     for (auto& b : c->gen) b.release();
     (void)run_free_table(c, -1);
     c->cg.release();
+    c->bnpc.release();
     c->tab_names.release();
     for (auto& b : c->ws) b.release();
     for (auto& b : c->tm) b.release();
@@ -564,6 +571,42 @@ int lsg_cellgeno_load_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uin
     if (!c || n_sites < 0 || n_cb <= 0 || (n_sites > 0 && (!bin || !vaf4))) { set_error("lsg_cellgeno_load_cells: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
     return run_cellgeno_load_cells(c, n_sites, n_cb, bin, vaf4);
+}
+
+int lsg_bnpc_load_samples(lsg_ctx* c, int64_t n_samples, int32_t n_cells, const int32_t* assign, int32_t k_max, int32_t n_muts, const float* params) {
+    if (!c) { set_error("lsg_bnpc_load_samples: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_load(c, n_samples, n_cells, assign, k_max, n_muts, params);
+}
+
+int lsg_bnpc_codist(lsg_ctx* c) {
+    if (!c) { set_error("lsg_bnpc_codist: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_codist(c);
+}
+
+int lsg_bnpc_fetch_dist(lsg_ctx* c, uint32_t* dist, int64_t capacity) {
+    if (!c) { set_error("lsg_bnpc_fetch_dist: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_fetch_dist(c, dist, capacity);
+}
+
+int lsg_bnpc_mpear(lsg_ctx* c, int32_t n_cuts, const int32_t* labels, uint64_t* same_pairs, uint64_t* same_sim, uint64_t* dist_sum) {
+    if (!c) { set_error("lsg_bnpc_mpear: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_mpear(c, n_cuts, labels, same_pairs, same_sim, dist_sum);
+}
+
+int lsg_bnpc_mean_params(lsg_ctx* c, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used) {
+    if (!c) { set_error("lsg_bnpc_mean_params: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_mean_params(c, final_assign, n_clusters, params, branch, n_used);
+}
+
+int lsg_bnpc_unload(lsg_ctx* c) {
+    if (!c) { set_error("lsg_bnpc_unload: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_unload(c);
 }
 
 int lsg_betabinom_sf4(lsg_ctx* c, int64_t n_items, const uint32_t* k, const uint32_t* n, double alpha, double beta, int32_t* out_p4) {

@@ -73,6 +73,15 @@ struct CellGeno {
     void release() { for (DevBuf* b : {&keys, &alt_sym, &is_chrm, &dp, &alt, &vaf4, &p4, &status, &bin, &n_cov, &n_pass, &text, &scratch, &filt}) b->release(); valid = text_valid = filt_valid = false; }
 };
 
+// bnpc.hip: the posterior samples lsg_bnpc_load_samples made resident (labels as 16 bits, rows of `pitch` = n_cells rounded up to 64), the
+// pair distances of lsg_bnpc_codist and the scratch of the two calls that read them
+struct Bnpc {
+    DevBuf lab, raw, params, dist, cuts, sums, rank, flags, owner, cl16, idx, mean, part, ord2, small;
+    int64_t n_samples = 0; int32_t n_cells = 0, pitch = 0, k_max = 0, n_muts = 0;
+    bool valid = false, dist_valid = false, has_params = false;
+    void release() { for (DevBuf* b : {&lab, &raw, &params, &dist, &cuts, &sums, &rank, &flags, &owner, &cl16, &idx, &mean, &part, &ord2, &small}) b->release(); valid = dist_valid = has_params = false; }
+};
+
 // workspace buffers (lsg_ctx::ws)
 enum { WS_NE_NSLOT = 0, WS_NE_ACC, WS_NE_GEOM, WS_MULTI_LIST, WS_MACC, WS_EXPORT_K, WS_EXPORT_R,
        WS_EXPORT_C, WS_CALL_FLAGS, WS_CALL_SEL, WS_CALL_CANDS, WS_CALL_TASKS, WS_SEG_INFO };
@@ -228,6 +237,8 @@ struct lsg_ctx {
     int32_t tab_n_contigs = 0, tab_n_ct = 0; uint32_t tab_ct_off_at = 0, tab_order_at = 0, tab_ct_txt_at = 0, tab_contig_txt_at = 0;
 
     lsg::CellGeno cg;                     // cellgeno.hip: the per-cell verdicts of the last lsg_cellgeno_count and the strings their tables print
+
+    lsg::Bnpc bnpc;                       // bnpc.hip: the resident posterior samples and their pair distances
 
     lsg::PosSet posset[3];
     lsg::DevBuf syn[12];                  // synthetic-model tables + scan scratch (synth.hip)

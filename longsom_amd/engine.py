@@ -635,6 +635,59 @@ class Engine:
         _lib.check(self._lib.lsg_cellgeno_set_text(self._h, C.byref(t)), "lsg_cellgeno_set_text")
         self._mat_shape = (len(mo), len(cs))
 
+    # ---- BnpC's posterior estimate (CellClustering/libs/utils.py:90-245; csrc/bnpc.hip; longsom_amd/bnpc.py drives it) ----
+    def bnpc_load_samples(self, assignments, params=None) -> None:
+        """Posterior samples resident: assignments [S, N] (labels in [0, N)) and, for bnpc_mean_params, params [S, k_max, M] float32
+        (lsg_bnpc_load_samples).  A second load replaces the first."""
+        a = np.ascontiguousarray(assignments, dtype=np.int32)
+        if a.ndim != 2:
+            raise ValueError("bnpc_load_samples: assignments must be [samples, cells]")
+        p = None
+        if params is not None:
+            p = np.ascontiguousarray(params, dtype=np.float32)
+            if p.ndim != 3 or p.shape[0] != a.shape[0]:
+                raise ValueError("bnpc_load_samples: params must be [samples, clusters, mutations] with one row block per sample")
+        self._bnpc_shape = None
+        _lib.check(self._lib.lsg_bnpc_load_samples(self._h, a.shape[0], a.shape[1], a.ctypes.data_as(C.c_void_p), p.shape[1] if p is not None else 0,
+                                                   p.shape[2] if p is not None else 0, p.ctypes.data_as(C.c_void_p) if p is not None else None), "lsg_bnpc_load_samples")
+        self._bnpc_shape = (a.shape[0], a.shape[1], p.shape[2] if p is not None else 0)
+
+    def bnpc_codist(self, fetch: bool = True):
+        """D[pair] = the samples in which the pair's labels differ, pdist's condensed order, uint32 (lsg_bnpc_codist); stays resident for bnpc_mpear"""
+        _lib.check(self._lib.lsg_bnpc_codist(self._h), "lsg_bnpc_codist")
+        if not fetch:
+            return None
+        n = self._bnpc_shape[1]
+        out = np.zeros(n * (n - 1) // 2, np.uint32)
+        _lib.check(self._lib.lsg_bnpc_fetch_dist(self._h, out.ctypes.data_as(C.c_void_p), len(out)), "lsg_bnpc_fetch_dist")
+        return out
+
+    def bnpc_mpear(self, cuts):
+        """(same_pairs [n_cuts], same_sim [n_cuts], dist_sum) of candidate clusterings cuts [n_cuts, N] over the resident D (lsg_bnpc_mpear)"""
+        cuts = np.ascontiguousarray(cuts, dtype=np.int32)
+        shape = getattr(self, "_bnpc_shape", None)
+        if shape is not None and (cuts.ndim != 2 or cuts.shape[1] != shape[1]):
+            raise ValueError("bnpc_mpear: cuts must be [n_cuts, %d]" % shape[1])
+        k = cuts.shape[0] if cuts.ndim == 2 else 0
+        pairs = np.zeros(k, np.uint64); sim = np.zeros(k, np.uint64); dsum = C.c_uint64(0)
+        _lib.check(self._lib.lsg_bnpc_mpear(self._h, k, _ptr(cuts), _ptr(pairs), _ptr(sim), C.byref(dsum)), "lsg_bnpc_mpear")
+        return pairs, sim, int(dsum.value)
+
+    def bnpc_mean_params(self, final_assign):
+        """(params [C, M] float64, branch [C] uint8, n_used [C] int32) of a final assignment's clusters, its distinct values ascending (lsg_bnpc_mean_params)"""
+        fa = np.ascontiguousarray(final_assign, dtype=np.int32)
+        shape = getattr(self, "_bnpc_shape", None)
+        if shape is not None and fa.shape != (shape[1],):
+            raise ValueError("bnpc_mean_params: final_assign must be [%d]" % shape[1])
+        n_cl = len(np.unique(fa))
+        out = np.zeros((n_cl, shape[2] if shape else 0), np.float64); branch = np.zeros(n_cl, np.uint8); n_used = np.zeros(n_cl, np.int32)
+        _lib.check(self._lib.lsg_bnpc_mean_params(self._h, fa.ctypes.data_as(C.c_void_p), n_cl, out.ctypes.data_as(C.c_void_p), _ptr(branch), _ptr(n_used)), "lsg_bnpc_mean_params")
+        return out, branch, n_used
+
+    def bnpc_unload(self) -> None:
+        _lib.check(self._lib.lsg_bnpc_unload(self._h), "lsg_bnpc_unload")
+        self._bnpc_shape = None
+
     def betabinom_sf4(self, k, n, alpha: float, beta: float) -> np.ndarray:
         """round(betabinom.sf(k - 0.001, n, alpha, beta), 4) * 1e4 as int32, evaluated on the device."""
         k = np.ascontiguousarray(k, dtype=np.uint32); n = np.ascontiguousarray(n, dtype=np.uint32)

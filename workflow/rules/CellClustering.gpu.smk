@@ -1,11 +1,12 @@
-### MI355X replacement of rules SingleCellGenotype and FormatInputBnpC of LongSom's workflow/rules/CellClustering.smk (same INPUT and OUTPUT
-### files, same flags).
+### MI355X replacement of rules SingleCellGenotype, FormatInputBnpC and BnpC_clustering of LongSom's workflow/rules/CellClustering.smk (same
+### INPUT and OUTPUT files, same flags).
 #
 # The reference states SingleCellGenotype twice (PoN run or not): the two differ only in where alpha2 / beta2 come from - the panel's
 # BetaBinEstimates.txt or config['SNVCalling']['BaseCellCalling'] - and that is the one conditional here.  FormatInputBnpC filters the
 # Binary and VAF matrices into BnpC's input; with Run.fuse_bnpc_input: True rule SingleCellGenotype writes that input in its own process,
 # from the cells while they are resident, and FormatInputBnpC has nothing left to do (the rule order below gives the files to the fused
-# rule).  BnpC_clustering reads BnpC_input/ and is the one rule of the chain that stays the reference's.
+# rule).  BnpC_clustering reads BnpC_input/: its sampler is the vendored BnpC's of this checkout (scripts/CellClustering/libs), run as the
+# reference runs it; the posterior estimate over the chains' samples runs on the GPU.
 
 GPU_SCRIPTS = str(workflow.basedir) + "/scripts_gpu"
 FUSE_BNPC = config['Run'].get('fuse_bnpc_input', False)
@@ -101,4 +102,48 @@ rule FormatInputBnpC:
         --min_pos_cov {params.min_cov} \
         --min_cells_per_mut {params.min_cells} \
         --outfile CellClustering/BnpC_input/{wildcards.id}
+        """
+
+rule BnpC_clustering:
+    input:
+        bin="CellClustering/BnpC_input/{id}.BinaryMatrix.tsv",
+        vaf="CellClustering/BnpC_input/{id}.VAFMatrix.tsv",
+        barcodes="CellClustering/BnpC_input/{id}.Barcodes.tsv",
+    output:
+        pdf="CellClustering/BnpC_output/{id}/genoCluster_posterior_mean_raw.pdf"
+    params:
+        script=GPU_SCRIPTS+"/CellClustering/run_BnpC.py",
+        mcmc_steps = config['CellClust']['BnpC']['mcmc_steps'],
+        estimator = config['CellClust']['BnpC']['estimator'],
+        dpa = config['CellClust']['BnpC']['dpa'],
+        cup = config['CellClust']['BnpC']['cup'],
+        eup = config['CellClust']['BnpC']['eup'],
+        FP = config['CellClust']['BnpC']['FP'],
+        FN = config['CellClust']['BnpC']['FN'],
+        pp= config['CellClust']['BnpC']['pp'],
+    conda:
+        "../envs/BnpC.yaml"
+    threads: 16
+    resources:
+        mem_mb_per_cpu=1024,
+        gpu=1
+    log:
+        "logs/BnpC/{id}.log",
+    benchmark:
+        "benchmarks/BnpC/{id}.benchmark.txt"
+    shell:
+        r"""
+        python {params.script} \
+        {input.bin} \
+        -n {threads} \
+        -o CellClustering/BnpC_output/{wildcards.id} \
+        -s {params.mcmc_steps} \
+        -e {params.estimator} \
+        -cup {params.cup} \
+        -eup {params.eup} \
+        -FP {params.FP} \
+        -FN {params.FN} \
+        -pp {params.pp} \
+        -ap {params.dpa} \
+        --barcodes {input.barcodes}
         """
