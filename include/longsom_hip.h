@@ -521,6 +521,33 @@ int lsg_bnpc_mpear(lsg_ctx* ctx, int32_t n_cuts, const int32_t* labels, uint64_t
 int lsg_bnpc_mean_params(lsg_ctx* ctx, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used);
 int lsg_bnpc_unload(lsg_ctx* ctx);
 
+/* ---- BnpC's sampler (CellClustering/libs/CRP.py:17-410, libs/MCMC.py:200-388) for the model with fixed error rates -----------------------
+ * Gibbs assignment sweeps, the Escobar-West concentration update and the parameter Metropolis-Hastings, all chains of a run in every
+ * kernel; the split-merge move and the error-rate updates are not here.  The random stream (Philox4x32-10 keyed by the chain's seed), the
+ * variates and the order of a step are stated in longsom_amd/bnpc_sampler.py, whose numpy twin these calls are held to.
+ * lsg_bnpcs_create makes the data and the chains' buffers resident (a second create replaces the first):
+ *   one, zero [n_cells][ceil(n_muts / 64)]   the cells' masks: bit m % 64 of word m / 64 is set where the cell shows 1 resp. 0; neither: missing
+ *   cfg [10]   FN, FP, the parameter prior's p and q, DP_a_gamma's two numbers, the concentration update's probability, the new cluster's
+ *              two log terms (get_lpost_single_new_cluster: per 1 and per 0 of the cell), betaln(p, q)
+ *   seeds [n_chains]; n_steps: the run's steps (n_steps + 1 records, step 0 is the start); arena_rows: parameter rows of n_muts floats
+ *   per chain held between two fetches.  Refused: n_cells < 2 or > 65535 (the estimate keeps 16-bit labels).
+ * lsg_bnpcs_set_state / _get_state move one chain's state: labels [n_cells] in [0, n_cells), theta [n_cells][n_muts] float32 (row = cluster
+ * id, rows of free ids are not read) and the concentration.  They are how the start is loaded, and what a move made outside works on.
+ * lsg_bnpcs_run makes steps first_step .. first_step + n_steps - 1 (first_step must be the next step; step 0 only records) and records each:
+ * ML, the CRP prior's sum over the clusters, the beta prior's log density of their parameters, the cluster count, the concentration, the
+ * labels, and from step burn_in on the live clusters' parameter rows in ascending id into the arena.  When a step's rows do not fit the
+ * arena the call returns with *done = the steps recorded; lsg_bnpcs_fetch empties the arena and the next call goes on at that step.
+ * lsg_bnpcs_fetch copies out labels [n_chains][n_steps + 1][n_cells], scalars [n_chains][n_steps + 1][5] (in the order above), the arena
+ * [n_chains][arena_rows][n_muts] (per chain the first arena_used[chain] rows: the kept steps since the last fetch, one after the other) and
+ * errors [n_chains]: gamma variates that ran out of their 64 tries. */
+int lsg_bnpcs_create(lsg_ctx* ctx, int32_t n_cells, int32_t n_muts, int32_t n_chains, int32_t n_steps, const uint64_t* one, const uint64_t* zero, const double* cfg,
+                     const uint64_t* seeds, int64_t arena_rows);
+int lsg_bnpcs_set_state(lsg_ctx* ctx, int32_t chain, const int32_t* labels, const float* theta, double dp_alpha);
+int lsg_bnpcs_get_state(lsg_ctx* ctx, int32_t chain, int32_t* labels, float* theta, double* dp_alpha);
+int lsg_bnpcs_run(lsg_ctx* ctx, int32_t first_step, int32_t n_steps, int32_t burn_in, int32_t* done);
+int lsg_bnpcs_fetch(lsg_ctx* ctx, int32_t* labels, double* scalars, float* arena, int64_t* arena_used, int32_t* errors);
+int lsg_bnpcs_destroy(lsg_ctx* ctx);
+
 /* ---- measurement helpers --------------------------------------------------------------------*/
 /* Statistics of the last lsg_pileup_count: admitted reads / segments / events (events that passed
  * read admission, before the base-quality gate), tile entries, non-empty units, deep units. */

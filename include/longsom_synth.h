@@ -44,6 +44,19 @@ int lsg_get_reads_shape(lsg_ctx* ctx, int64_t* n_reads, int64_t* n_segs, int64_t
 int lsg_copy_reads_to_host(lsg_ctx* ctx, const lsg_reads* out);
 int lsg_copy_reference_to_host(lsg_ctx* ctx, int32_t tid, uint8_t* out);
 
+/* ---- the BnpC sampler's parts, one at a time (csrc/bnpc_sampler.hip; tests/test_bnpc_sampler_gpu.py) ---------------------------------
+ * lsg_bnpcs_test_stream: the Philox words [n][4] and the two doubles [n][2] of counters [n][4] under a key, as the kernels form them.
+ * lsg_bnpcs_test_variates: n variates with index i = 0 .. n-1 at step 0: kind 0 Beta(a, b) under purpose P_BIRTH, kind 1 the truncated
+ *   normal around a (float32) with sd b at the first double of purpose P_MH, kind 2 Gamma(a) under P_ALPHA; *errors: tries run out.
+ * The others work on the state lsg_bnpcs_set_state loaded: _test_counts copies out n1, n0 [n_cells][n_muts] of a chain; _test_ll makes the
+ * likelihood matrix and copies out ll [n_cells][*n_clusters] and the cluster ids of its columns; _test_move makes one sweep with its
+ * concentration update (what = 0) or one parameter move (what = 1) of every chain under the step number `step`, recording nothing. */
+int lsg_bnpcs_test_stream(lsg_ctx* ctx, uint64_t key, int64_t n, const uint32_t* counters, uint32_t* words, double* doubles);
+int lsg_bnpcs_test_variates(lsg_ctx* ctx, uint64_t key, int32_t kind, int64_t n, double a, double b, double* out, int32_t* errors);
+int lsg_bnpcs_test_counts(lsg_ctx* ctx, int32_t chain, uint32_t* n1, uint32_t* n0);
+int lsg_bnpcs_test_ll(lsg_ctx* ctx, int32_t chain, double* ll, int32_t* clusters, int32_t* n_clusters);
+int lsg_bnpcs_test_move(lsg_ctx* ctx, int32_t what, int32_t step);
+
 #ifdef __cplusplus
 }
 #endif

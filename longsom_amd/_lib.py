@@ -183,6 +183,17 @@ SIGNATURES = {
     "lsg_bnpc_mpear": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsg_bnpc_mean_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsg_bnpc_unload": (C.c_int, [C.c_void_p]),
+    "lsg_bnpcs_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "lsg_bnpcs_set_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double]),
+    "lsg_bnpcs_get_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_bnpcs_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "lsg_bnpcs_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_bnpcs_destroy": (C.c_int, [C.c_void_p]),
+    "lsg_bnpcs_test_stream": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_bnpcs_test_variates": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "lsg_bnpcs_test_counts": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lsg_bnpcs_test_ll": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_bnpcs_test_move": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "lsg_betabinom_sf4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "lsg_betabinom_sf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "lsg_max_live_reads": (C.c_int64, [C.c_void_p]),

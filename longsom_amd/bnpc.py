@@ -1,7 +1,7 @@
 """BnpC's posterior estimate (scripts/CellClustering/libs/utils.py:90-245) and the three files it ends in (libs/dpmmIO.py:464-521).
 
-BnpC has two halves.  The sampler (libs/CRP.py, libs/MCMC.py) is stochastic and serial over cells: it stays the reference's and feeds
-this module its chains.  The posterior estimate is deterministic: the co-clustering distance of every cell pair over every posterior
+BnpC has two halves.  The sampler (libs/CRP.py, libs/MCMC.py) is stochastic: the reference's own, or longsom_amd.bnpc_sampler's on the
+device, feeds this module its chains.  The posterior estimate is deterministic: the co-clustering distance of every cell pair over every posterior
 sample, a ward tree over it, the MPEAR score of every candidate cut, and the mean parameters of the chosen clusters.  The three passes
 over big index spaces run on the device (csrc/bnpc.hip, lsg_bnpc_*); scipy's linkage and cut_tree stay on the host, as in the reference.
 

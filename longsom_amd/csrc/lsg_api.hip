@@ -113,6 +113,7 @@ void lsg_destroy(lsg_ctx* c) {
     (void)run_free_table(c, -1);
     c->cg.release();
     c->bnpc.release();
+    c->bnpcs.release();
     c->tab_names.release();
     for (auto& b : c->ws) b.release();
     for (auto& b : c->tm) b.release();

@@ -82,6 +82,23 @@ struct Bnpc {
     void release() { for (DevBuf* b : {&lab, &raw, &params, &dist, &cuts, &sums, &rank, &flags, &owner, &cl16, &idx, &mean, &part, &ord2, &small}) b->release(); valid = dist_valid = has_params = false; }
 };
 
+// bnpc_sampler.hip: the sampler's resident state (lsg_bnpcs_create): per cell the masks and popcounts; per chain the labels, the slot
+// sizes, theta, the log tables, the likelihood matrix of the sweep, the counts, and the record buffers
+struct Bnpcs {
+    DevBuf one, zero, pop, seeds, lab, size, colof, live, nlive, hi, theta, L1, L0, LL, alpha, prow, n1, n0, rowml, rowb, order, keys, rec_lab, rec_sc, arena, err;
+    int32_t n_cells = 0, n_muts = 0, n_words = 0, n_chains = 0, steps1 = 0, k_max = 0, ll_pitch = 0, pending = -1, next_step = 0;
+    int64_t arena_rows = 0;
+    double cfg[10] = {};
+    bool valid = false, prepared = false;
+    std::vector<int32_t> h_k;             // clusters alive per chain, as of the last sweep
+    std::vector<int64_t> h_used;          // arena rows in use per chain
+    void release() {
+        for (DevBuf* b : {&one, &zero, &pop, &seeds, &lab, &size, &colof, &live, &nlive, &hi, &theta, &L1, &L0, &LL, &alpha, &prow, &n1, &n0, &rowml, &rowb, &order, &keys, &rec_lab, &rec_sc,
+                          &arena, &err}) b->release();
+        valid = prepared = false;
+    }
+};
+
 // workspace buffers (lsg_ctx::ws)
 enum { WS_NE_NSLOT = 0, WS_NE_ACC, WS_NE_GEOM, WS_MULTI_LIST, WS_MACC, WS_EXPORT_K, WS_EXPORT_R,
        WS_EXPORT_C, WS_CALL_FLAGS, WS_CALL_SEL, WS_CALL_CANDS, WS_CALL_TASKS, WS_SEG_INFO };
@@ -239,6 +256,7 @@ struct lsg_ctx {
     lsg::CellGeno cg;                     // cellgeno.hip: the per-cell verdicts of the last lsg_cellgeno_count and the strings their tables print
 
     lsg::Bnpc bnpc;                       // bnpc.hip: the resident posterior samples and their pair distances
+    lsg::Bnpcs bnpcs;                     // bnpc_sampler.hip: the sampler's chains
 
     lsg::PosSet posset[3];
     lsg::DevBuf syn[12];                  // synthetic-model tables + scan scratch (synth.hip)

@@ -688,6 +688,83 @@ class Engine:
         _lib.check(self._lib.lsg_bnpc_unload(self._h), "lsg_bnpc_unload")
         self._bnpc_shape = None
 
+    # ---- BnpC's sampler (CellClustering/libs/CRP.py, libs/MCMC.py; csrc/bnpc_sampler.hip; longsom_amd/bnpc_sampler.py drives it) ----
+    def bnpcs_create(self, model, seeds, steps: int, arena_rows: int) -> None:
+        """The data of a bnpc_sampler.Model and the buffers of len(seeds) chains of `steps` steps resident (lsg_bnpcs_create)"""
+        from scipy.special import betaln
+        one, zero = model.masks64()
+        cfg = np.array([model.FN, model.FP, model.p, model.q, model.g0, model.g1, model.dpa_prob,
+                        np.log(model.mix[1] * (1 - model.FN) + model.mix[0] * model.FP), np.log(model.mix[1] * model.FN + model.mix[0] * (1 - model.FP)),
+                        betaln(model.p, model.q)], np.float64)
+        sd = np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64)
+        self._bnpcs_shape = None
+        _lib.check(self._lib.lsg_bnpcs_create(self._h, model.N, model.M, len(sd), int(steps), _ptr(one), _ptr(zero), _ptr(cfg), _ptr(sd), int(arena_rows)), "lsg_bnpcs_create")
+        self._bnpcs_shape = (len(sd), int(steps) + 1, model.N, model.M, int(arena_rows))
+
+    def bnpcs_set_state(self, chain: int, labels, theta, alpha: float) -> None:
+        """one chain's labels [N], theta [N, M] float32 (row = cluster id) and concentration (lsg_bnpcs_set_state)"""
+        _, _, N, M, _ = self._bnpcs_shape
+        lab = np.ascontiguousarray(labels, dtype=np.int32); th = np.ascontiguousarray(theta, dtype=np.float32)
+        if lab.shape != (N,) or th.shape != (N, M):
+            raise ValueError("bnpcs_set_state: labels must be [%d] and theta [%d, %d]" % (N, N, M))
+        _lib.check(self._lib.lsg_bnpcs_set_state(self._h, int(chain), _ptr(lab), _ptr(th), float(alpha)), "lsg_bnpcs_set_state")
+
+    def bnpcs_get_state(self, chain: int):
+        """(labels [N] int32, theta [N, M] float32, alpha) of one chain (lsg_bnpcs_get_state)"""
+        _, _, N, M, _ = self._bnpcs_shape
+        lab = np.zeros(N, np.int32); th = np.zeros((N, M), np.float32); alpha = C.c_double(0)
+        _lib.check(self._lib.lsg_bnpcs_get_state(self._h, int(chain), _ptr(lab), _ptr(th), C.byref(alpha)), "lsg_bnpcs_get_state")
+        return lab, th, float(alpha.value)
+
+    def bnpcs_run(self, first_step: int, n_steps: int, burn_in: int) -> int:
+        """steps first_step .. first_step + n_steps - 1 of every chain; returns how many were recorded before the arena filled (lsg_bnpcs_run)"""
+        done = C.c_int32(0)
+        _lib.check(self._lib.lsg_bnpcs_run(self._h, int(first_step), int(n_steps), int(burn_in), C.byref(done)), "lsg_bnpcs_run")
+        return int(done.value)
+
+    def bnpcs_fetch(self):
+        """(labels [C, steps + 1, N], scalars [C, steps + 1, 5], arena [C, arena_rows, M]) so far; empties the arena (lsg_bnpcs_fetch)"""
+        Cn, S1, N, M, rows = self._bnpcs_shape
+        labels = np.zeros((Cn, S1, N), np.int32); scalars = np.zeros((Cn, S1, 5), np.float64); arena = np.zeros((Cn, rows, M), np.float32)
+        used = np.zeros(Cn, np.int64); self._bnpcs_errors = np.zeros(Cn, np.int32)
+        _lib.check(self._lib.lsg_bnpcs_fetch(self._h, _ptr(labels), _ptr(scalars), _ptr(arena), _ptr(used), _ptr(self._bnpcs_errors)), "lsg_bnpcs_fetch")
+        return labels, scalars, arena
+
+    def bnpcs_errors(self) -> np.ndarray:
+        """per chain, the gamma variates that ran out of tries, as of the last bnpcs_fetch"""
+        return self._bnpcs_errors
+
+    def bnpcs_destroy(self) -> None:
+        _lib.check(self._lib.lsg_bnpcs_destroy(self._h), "lsg_bnpcs_destroy")
+        self._bnpcs_shape = None
+
+    def bnpcs_test_stream(self, key: int, counters):
+        ctr = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 4)
+        words = np.zeros_like(ctr); dbl = np.zeros((len(ctr), 2), np.float64)
+        _lib.check(self._lib.lsg_bnpcs_test_stream(self._h, int(key), len(ctr), _ptr(ctr), _ptr(words), _ptr(dbl)), "lsg_bnpcs_test_stream")
+        return words, dbl
+
+    def bnpcs_test_variates(self, key: int, kind: int, n: int, a: float, b: float):
+        out = np.zeros(n, np.float64); err = C.c_int32(0)
+        _lib.check(self._lib.lsg_bnpcs_test_variates(self._h, int(key), int(kind), int(n), float(a), float(b), _ptr(out), C.byref(err)), "lsg_bnpcs_test_variates")
+        return out, int(err.value)
+
+    def bnpcs_test_counts(self, chain: int):
+        _, _, N, M, _ = self._bnpcs_shape
+        n1 = np.zeros((N, M), np.uint32); n0 = np.zeros((N, M), np.uint32)
+        _lib.check(self._lib.lsg_bnpcs_test_counts(self._h, int(chain), _ptr(n1), _ptr(n0)), "lsg_bnpcs_test_counts")
+        return n1, n0
+
+    def bnpcs_test_ll(self, chain: int):
+        _, _, N, M, _ = self._bnpcs_shape
+        ll = np.zeros((N, N), np.float64); ids = np.zeros(N, np.int32); k = C.c_int32(0)
+        _lib.check(self._lib.lsg_bnpcs_test_ll(self._h, int(chain), _ptr(ll), _ptr(ids), C.byref(k)), "lsg_bnpcs_test_ll")
+        K = int(k.value)
+        return ll.ravel()[:N * K].reshape(N, K).copy(), ids[:K].copy()
+
+    def bnpcs_test_move(self, what: int, step: int) -> None:
+        _lib.check(self._lib.lsg_bnpcs_test_move(self._h, int(what), int(step)), "lsg_bnpcs_test_move")
+
     def betabinom_sf4(self, k, n, alpha: float, beta: float) -> np.ndarray:
         """round(betabinom.sf(k - 0.001, n, alpha, beta), 4) * 1e4 as int32, evaluated on the device."""
         k = np.ascontiguousarray(k, dtype=np.uint32); n = np.ascontiguousarray(n, dtype=np.uint32)

@@ -6,7 +6,8 @@
 # Binary and VAF matrices into BnpC's input; with Run.fuse_bnpc_input: True rule SingleCellGenotype writes that input in its own process,
 # from the cells while they are resident, and FormatInputBnpC has nothing left to do (the rule order below gives the files to the fused
 # rule).  BnpC_clustering reads BnpC_input/: its sampler is the vendored BnpC's of this checkout (scripts/CellClustering/libs), run as the
-# reference runs it; the posterior estimate over the chains' samples runs on the GPU.
+# reference runs it; the posterior estimate over the chains' samples runs on the GPU.  With CellClust.BnpC.sampler: device the sampler
+# runs on the GPU too (all chains at once; Gibbs sweeps, the concentration update and the parameter moves, no split-merge move: -smp 0).
 
 GPU_SCRIPTS = str(workflow.basedir) + "/scripts_gpu"
 FUSE_BNPC = config['Run'].get('fuse_bnpc_input', False)
@@ -121,6 +122,7 @@ rule BnpC_clustering:
         FP = config['CellClust']['BnpC']['FP'],
         FN = config['CellClust']['BnpC']['FN'],
         pp= config['CellClust']['BnpC']['pp'],
+        sampler="--sampler device -smp 0" if config['CellClust']['BnpC'].get('sampler', 'reference') == 'device' else "",
     conda:
         "../envs/BnpC.yaml"
     threads: 16
@@ -144,6 +146,6 @@ rule BnpC_clustering:
         -FP {params.FP} \
         -FN {params.FN} \
         -pp {params.pp} \
-        -ap {params.dpa} \
+        -ap {params.dpa} {params.sampler} \
         --barcodes {input.barcodes}
         """
