@@ -521,9 +521,9 @@ int lsg_bnpc_mpear(lsg_ctx* ctx, int32_t n_cuts, const int32_t* labels, uint64_t
 int lsg_bnpc_mean_params(lsg_ctx* ctx, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used);
 int lsg_bnpc_unload(lsg_ctx* ctx);
 
-/* ---- BnpC's sampler (CellClustering/libs/CRP.py:17-410, libs/MCMC.py:200-388) for the model with fixed error rates -----------------------
- * Gibbs assignment sweeps, the Escobar-West concentration update and the parameter Metropolis-Hastings, all chains of a run in every
- * kernel; the split-merge move and the error-rate updates are not here.  The random stream (Philox4x32-10 keyed by the chain's seed), the
+/* ---- BnpC's sampler (CellClustering/libs/CRP.py:17-820, libs/MCMC.py:200-388) for the model with fixed error rates -----------------------
+ * Gibbs assignment sweeps, the split-merge move, the Escobar-West concentration update and the parameter Metropolis-Hastings, all chains
+ * of a run in every kernel; the error-rate updates are not here.  The random stream (Philox4x32-10 keyed by the chain's seed), the
  * variates and the order of a step are stated in longsom_amd/bnpc_sampler.py, whose numpy twin these calls are held to.
  * lsg_bnpcs_create makes the data and the chains' buffers resident (a second create replaces the first):
  *   one, zero [n_cells][ceil(n_muts / 64)]   the cells' masks: bit m % 64 of word m / 64 is set where the cell shows 1 resp. 0; neither: missing
@@ -539,13 +539,21 @@ int lsg_bnpc_unload(lsg_ctx* ctx);
  * arena the call returns with *done = the steps recorded; lsg_bnpcs_fetch empties the arena and the next call goes on at that step.
  * lsg_bnpcs_fetch copies out labels [n_chains][n_steps + 1][n_cells], scalars [n_chains][n_steps + 1][5] (in the order above), the arena
  * [n_chains][arena_rows][n_muts] (per chain the first arena_used[chain] rows: the kept steps since the last fetch, one after the other) and
- * errors [n_chains]: gamma variates that ran out of their 64 tries. */
+ * errors [n_chains]: gamma variates that ran out of their 64 tries.
+ * lsg_bnpcs_set_split_merge, called after lsg_bnpcs_create (without it the probability is 0 and no step is a move): every chain takes the
+ * non-conjugate split-merge move (CRP.py:417-820) in place of the sweep with probability prob per step, a split with ratio_split and a merge
+ * with ratio_merge where both are possible, after `scans` restricted Gibbs scans (run_BnpC.py's -smp, -smr, -sms).  Refused: prob outside
+ * [0, 1], ratios that are not positive or do not sum to 1, scans < 0 or > 2^20.
+ * lsg_bnpcs_fetch_moves copies out moves [n_chains][n_steps + 1]: what each step so far did: 0 a sweep (and step 0), 1 / 2 a split declined /
+ * accepted, 3 / 4 a merge declined / accepted. */
 int lsg_bnpcs_create(lsg_ctx* ctx, int32_t n_cells, int32_t n_muts, int32_t n_chains, int32_t n_steps, const uint64_t* one, const uint64_t* zero, const double* cfg,
                      const uint64_t* seeds, int64_t arena_rows);
 int lsg_bnpcs_set_state(lsg_ctx* ctx, int32_t chain, const int32_t* labels, const float* theta, double dp_alpha);
 int lsg_bnpcs_get_state(lsg_ctx* ctx, int32_t chain, int32_t* labels, float* theta, double* dp_alpha);
 int lsg_bnpcs_run(lsg_ctx* ctx, int32_t first_step, int32_t n_steps, int32_t burn_in, int32_t* done);
 int lsg_bnpcs_fetch(lsg_ctx* ctx, int32_t* labels, double* scalars, float* arena, int64_t* arena_used, int32_t* errors);
+int lsg_bnpcs_set_split_merge(lsg_ctx* ctx, double prob, double ratio_split, double ratio_merge, int32_t scans);
+int lsg_bnpcs_fetch_moves(lsg_ctx* ctx, int8_t* moves);
 int lsg_bnpcs_destroy(lsg_ctx* ctx);
 
 /* ---- measurement helpers --------------------------------------------------------------------*/

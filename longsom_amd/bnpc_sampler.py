@@ -1,6 +1,6 @@
 """BnpC's sampler (scripts/CellClustering/libs/CRP.py:17-410, libs/MCMC.py:200-388) for the model with fixed error rates: Gibbs assignment
-sweeps, the Escobar-West concentration update and the parameter Metropolis-Hastings, all chains of a run at once.  The split-merge move,
-the error-rate updates, --fixed_assignment, --runtime and --lugsail are not here.
+sweeps, the non-conjugate split-merge move (CRP.py:417-820), the Escobar-West concentration update and the parameter Metropolis-Hastings,
+all chains of a run at once.  The error-rate updates, --fixed_assignment, --runtime and --lugsail are not here.
 
 run_chains        the sampler on the device (csrc/bnpc_sampler.hip, lsg_bnpcs_*)
 run_chains_host   its twin in numpy: what the CPU tests hold to the reference's goldens, and the GPU tests compare the device against
@@ -18,7 +18,8 @@ THE STREAM.  The sampler does not reproduce numpy's Mersenne stream; it has its 
               seed (low word, high word); the counter is (index, step, purpose | sub << 8, attempt).
   Double      from the words (w0, w1) of a block: ((w1 << 32 | w0) >> 12) + 0.5, times 2^-52: 52 drawn bits and the half unit make the
               53-bit mantissa, so the value is exact and never 0 or 1.  (w2, w3) give the block's second double the same way.
-  Purposes    see P_* below.  `sub` carries a cell or a cluster id (< 65536).
+  Purposes    see P_* below.  `sub` carries a cell or a cluster id (< 65536); under the P_SM* purposes a scan number t (0 .. sm_steps, below
+              2^22) or a row r (0 = the i side, 1 = the j side, 2 = the merged cluster), and where both are needed 4 t + r: 24 bits hold it.
 THE VARIATES.
   Permutation   of the cells: ascending by (the 64-bit draw w1 << 32 | w0 of block (cell, step, P_PERM, 0), cell).
   Categorical   numpy's choice(p=...) rule: cdf = running sum of p, divided by its last element; the first slot whose cdf exceeds u wins.
@@ -31,7 +32,9 @@ THE VARIATES.
                 if v > 0 and ln u3 < x^2 / 2 + d - d v + d ln v; the value is d v, times u4^(1 / a) if a < 1.  After 64 refusals the
                 value is a (the mean) and an error is counted.
   Beta(a, b)    x / (x + y) of Gamma(a) under purpose P and Gamma(b) under purpose P + 1; 0.5 if both are 0.
-THE STEP (Chain.do_step, MCMC.py:320-337, with sm_prob = 0), step s >= 1:
+THE STEP (Chain.do_step, MCMC.py:320-337), step s >= 1.  (u0, u1) = the doubles of block (0, s, P_SM, 0): if u0 < sm_prob the step makes the
+split-merge move below in place of the sweep (with sm_prob = 0 no step does, and no draw of any other purpose moves); alpha, move and
+record follow either one.
   sweep   update_assignments_Gibbs (CRP.py:254-288) over the permuted cells.  A cell leaves its cluster; the log posterior of every live
           cluster (ll + log size - log(N - 1 + alpha)) and of a new one (get_lpost_single_new_cluster, :230-234) are normalised by
           _normalize_log_probs (:89-100, with its clip at log EPSILON) and one is drawn.  A new cluster takes the smallest free id
@@ -45,6 +48,43 @@ THE STEP (Chain.do_step, MCMC.py:320-337, with sm_prob = 0), step s >= 1:
           normal at u; it is declined iff ln v >= A.
   record  Chain.update_results (MCMC.py:242-282): ML, MAP, DP_alpha, FN, FP, the labels; from the first step after burn-in the theta rows
           of the live clusters in ascending id.
+THE SPLIT-MERGE MOVE (update_assignments_split_merge, do_split_move, do_merge_move, run_rg_nc and what they call, CRP.py:417-820).
+  Blocks of (0, s, P_SM, a): a = 0 (u0, u1) above; a = 1 (c0, c1) choose the clusters; a = 2 (a0, a1) choose the anchors; a = 3 its first
+  double v decides the move.  With K live clusters: K = 1 forces a split, K = N a merge, else a split iff u1 < r0 / (r0 + r1) (choice(p=ratios)).
+  split   the cluster: the first of the clusters with at least two cells, ascending, whose running share of their sizes exceeds c0.  The
+          anchors: with n cells in it, ascending, i the floor(a0 n)-th and j the floor(a1 (n - 1))-th of the others.  size_data:
+          log(size / N) - log size - log(size - 1), with the UNRESTRICTED size / N although one-cell clusters cannot be chosen (:454-456).
+  merge   the clusters: i the first live one whose running share of the inverse sizes exceeds c0, j the same with c1 over the others.  The
+          anchors: the floor(a0 n_i)-th cell of i, the floor(a1 n_j)-th of j.  size_data: log p_i + log p_j - log n_i - log n_j (:505-507).
+  S       the other cells of the move in ascending id; n = |S| + 2.
+  launch  _rg_init_split runs for BOTH moves, so a merge does not start from the original partition either: a cell of S goes to j iff
+          ll_j > ll_i, its likelihood under "parameters" that are the anchor's own data with mix[0] for a missing entry.  Such a theta is
+          0, 1 or mix[0]: six log constants times popcounts of mask intersections, added in the order (anchor 1, 0, missing) x (cell 1, 0).
+          The rows r = 0, 1, 2 (the i side with i, the j side with j, all cells): theta[m] ~ Beta(p + n1, q + n0) of the row's cells' counts,
+          block (m, s, P_SM_BETA | r << 8, .), clipped, float32.
+  scan t  (t = 0 .. sm_steps - 1) _rg_scan_assign if S is not empty: the likelihoods of all cells of S under rows 0 and 1 are taken ONCE;
+          the cells are walked in the order of ascending (64-bit draw of block (cell, s, P_SM_PERM | t << 8, 0), cell); the walked cell leaves,
+          n_j = 1 + the others on the j side, n_i = n - n_j - 1, log_post = ll + log_CRP_prior([n_i, n_j], n, alpha) with the move's n and
+          not N, normalised by _normalize_log (not _normalize_log_probs: no clip; its FloatingPointError fallback is [0, log EPSILON]), and
+          choice([0, 1], p=exp(.)) with u the first double of block (cell, s, P_SM_CHOICE | t << 8, 0).  Then MH_cluster_params on rows 0 and 1
+          with their cells' counts after the walk, and on row 2: (u, v) of block (m, s, P_SM_MH | (4 t + r) << 8, 0), sd by w0 % 3 of attempt 1.
+  split   scan t = sm_steps of rows 0, 1 with trans_prob: the walk returns the sum of the chosen log probabilities (0 if S is empty);
+          MH_cluster_params(trans_prob=True) clips A at 0 and a declined entry contributes log(-expm1(A)).  Then _get_log_A(parameters[the
+          cluster], row 2, clip=True) summed, with fresh sds (w0 % 3 of block (m, s, P_SM_SD | 2 << 8, 0)).  A = (that - the scan's) +
+          _get_lprior_ratio_split + _get_ll_ratio + _get_ltrans_prob_size_ratio_split, added in this order.  Refused when S is not empty
+          and all of it ended on one side (np.unique(.).size == 1; an empty S has size 0 and is not refused); else accepted iff ln v < A.
+          An accepted split leaves row 0 to the cluster and gives the j side the smallest free id with row 1.
+  merge   scan t = sm_steps of row 2 with trans_prob.  _rg_get_split_prob: fresh sds for rows 0, 1 (P_SM_SD | r << 8); _get_log_A(parameters
+          [cluster of the anchor], row r, clip=True) whose forward bounds are (0 - theta) / sd and (1 - theta) / sd, NOT TMIN / TMAX (the
+          reverse bounds are), over the LAUNCH state's members of the side, not the original cluster's; then the walk in S's own order with
+          the original clusters' parameters, which overwrites the assignment with the original one as it goes.  A = (that - the scan's) +
+          _get_lprior_ratio_merge + _get_ll_ratio + _get_ltrans_prob_size_ratio_merge in this order; the second and third read the (now
+          original) assignment together with the launch state's rows 0, 1.  log(|S| - 1) raises under MCMC.py:20's np.seterr for |S| of 0
+          or 1, and the term falls back to -log N.  Accepted iff ln v < A: the cluster of i takes row 2 and the cells of j's.
+  Where this differs from the reference in distribution only (never in the target): the cluster to split is drawn once from the clusters
+  with two cells or more (the re-draw loop's own distribution); the anchors are a uniform ordered pair of distinct cells (what the
+  acceptance ratio's - log n - log(n - 1) assumes; the reference's two swaps, :448-450, do not give it when obs_j_idx == 0); S is listed
+  in ascending id; the merge pair is two sequential draws without replacement; the permutation is a rank by Philox keys.
 The start (CRP.init(mode='random'), :139-148, :176-180): label i = floor(N u) of block (i, 0, P_INIT_LABEL, 0), compacted to 0 .. K-1 in
 ascending order; theta[k][m] = clip(u) of block (m, 0, P_INIT_THETA | k << 8, 0); alpha = the mean of scipy's gamma(*DP_a_gamma), whose
 second number is a `loc`: g0 + g1, so a negative -ap gives (sqrt N, 1) and a start at sqrt N + 1.
@@ -61,6 +101,9 @@ GAMMA_TRIES = 64
 MAX_CELLS = 65535                                 # the estimate keeps 16-bit labels
 
 P_PERM, P_CHOICE, P_BIRTH, P_BIRTH_B, P_DPA, P_ETA, P_ETA_B, P_ALPHA, P_MH, P_INIT_LABEL, P_INIT_THETA = range(1, 12)
+P_SM, P_SM_PERM, P_SM_CHOICE, P_SM_BETA, P_SM_BETA_B, P_SM_MH, P_SM_SD = range(12, 19)
+SM_SWEEP, SM_SPLIT_DECLINED, SM_SPLIT_ACCEPTED, SM_MERGE_DECLINED, SM_MERGE_ACCEPTED = range(5)      # the codes of sm_moves
+MAX_SM_STEPS = 1 << 20
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
@@ -164,9 +207,13 @@ def truncnorm_variate(u, old32, sd):
     return (np.asarray(old32, dtype=np.float64) + sd * ndtri(pa + u * (pb - pa))).astype(np.float32)
 
 
-def truncnorm_logpdf(x32, loc32, sd):
-    """log density at x of the normal(loc, sd) truncated to [TMIN, TMAX]"""
-    pa, pb = truncnorm_mass(loc32, sd)
+def truncnorm_logpdf(x32, loc32, sd, lo32=None, hi32=None):
+    """log density at x of the normal(loc, sd) truncated to [TMIN, TMAX], or to [lo, hi] where given"""
+    if lo32 is None:
+        pa, pb = truncnorm_mass(loc32, sd)
+    else:
+        from scipy.special import ndtr
+        pa, pb = ndtr(_f32diff(np.float32(lo32), loc32) / sd), ndtr(_f32diff(np.float32(hi32), loc32) / sd)
     z = (np.asarray(x32, dtype=np.float32) - np.asarray(loc32, dtype=np.float32)).astype(np.float64) / sd
     return -0.5 * z * z - 0.5 * np.log(2.0 * np.pi) - np.log(sd) - np.log(pb - pa)
 
@@ -347,16 +394,20 @@ def counts(model, st):
     return n1, n0
 
 
-def log_A(model, new32, old32, n1, n0, sd, terms=False):
-    """_get_log_A (:347-383) with clip False from the cluster's counts"""
+def log_A(model, new32, old32, n1, n0, sd, terms=False, clip=False, unit_bounds=False):
+    """_get_log_A (:347-383) from the cluster's counts.  unit_bounds: the forward density's bounds are (0 - old) / sd and (1 - old) / sd, as
+    _rg_get_split_prob (:779-780) passes them; the reverse bounds stay TMIN / TMAX"""
     nL1, nL0 = log_tables(new32, model.FN, model.FP)
     oL1, oL0 = log_tables(old32, model.FN, model.FP)
     new_ll, old_ll = n1 * nL1 + n0 * nL0, n1 * oL1 + n0 * oL0
     new_prior = old_prior = 0
     if not model.uniform:
         new_prior, old_prior = beta_logpdf(new32, model.p, model.q), beta_logpdf(old32, model.p, model.q)
-    new_p, old_p = truncnorm_logpdf(new32, old32, sd), truncnorm_logpdf(old32, new32, sd)
+    new_p = truncnorm_logpdf(new32, old32, sd, 0.0, 1.0) if unit_bounds else truncnorm_logpdf(new32, old32, sd)
+    old_p = truncnorm_logpdf(old32, new32, sd)
     A = new_ll + new_prior - old_ll - old_prior + old_p - new_p
+    if clip:
+        A = np.minimum(A, 0.0)
     if terms:
         mag = np.abs(n1 * nL1) + np.abs(n0 * nL0) + np.abs(n1 * oL1) + np.abs(n0 * oL0) + np.abs(new_prior) + np.abs(old_prior) + np.abs(old_p) + np.abs(new_p)
         return A, mag
@@ -378,6 +429,333 @@ def parameter_move(model, st, seed, step, margin=None):
     if margin is not None:
         margin.see((lv - A) / np.maximum(1.0, np.abs(A)))
     st.theta[live] = np.where(lv >= A, old, new)
+
+
+# ---- the split-merge move (CRP.py:417-820).  The functions take their draws as arguments: the run feeds them the Philox stream, the
+# CPU tests the reference's own replayed draws. --------------------------------------------------------------------------------------
+def anchor_logs(model):
+    """the six values log(theta B_FN(x) + (1 - theta) B_FP(x)) can take when theta is an anchor's data with mix[0] for a missing entry
+    (_rg_init_split, :557-560): [anchor 1, 0, missing][cell 1, 0]"""
+    FN, FP, m0 = model.FN, model.FP, model.mix[0]
+    return np.log(np.array([[1 - FN, FN], [FP, 1 - FP], [m0 * (1 - FN) + (1 - m0) * FP, m0 * FN + (1 - m0) * (1 - FP)]]))
+
+
+def sm_anchor_ll(model, S, anchor):
+    """_calc_ll(data[S], nan_to_num(data[anchor], nan=mix[0])): popcounts of mask intersections times the six constants, added in a fixed order"""
+    S = np.asarray(S, dtype=np.int64)
+    consts = anchor_logs(model)
+    sides = (model.one[anchor], model.zero[anchor], ~(model.one[anchor] | model.zero[anchor]))
+    ll = np.zeros(len(S)); mag = np.zeros(len(S)); cnt = np.zeros((len(S), 6), np.int64)
+    for a, mask in enumerate(sides):
+        for x, cells in enumerate((model.one, model.zero)):
+            n = (cells[S] & mask).sum(axis=1)
+            cnt[:, 2 * a + x] = n
+            ll = ll + n * consts[a, x]
+            mag = mag + n * abs(consts[a, x])
+    return ll, mag, cnt
+
+
+def sm_launch_assign(model, i, j, S, margin=None):
+    """_rg_init_split's assignment (:551-561): 1 where the j anchor's data explain the cell better"""
+    ll_i, mag_i, cnt_i = sm_anchor_ll(model, S, i)
+    ll_j, mag_j, cnt_j = sm_anchor_ll(model, S, j)
+    if margin is not None:
+        differ = (cnt_i != cnt_j).any(axis=1)                         # equal counts give equal sums wherever they are added
+        margin.see(((ll_j - ll_i) / np.maximum(1.0, mag_i + mag_j))[differ])
+    return np.where(ll_j > ll_i, 1, 0).astype(np.int64)
+
+
+def sm_row_counts(model, i, j, S, assign):
+    """n1, n0 [3][M] of the rows' cells: S where assign is 0 and i, S where it is 1 and j, all of them"""
+    S = np.asarray(S, dtype=np.int64)
+    n1 = np.zeros((3, model.M), np.int64); n0 = np.zeros((3, model.M), np.int64)
+    for r, cells in enumerate((np.append(S[assign == 0], i), np.append(S[assign == 1], j))):
+        n1[r], n0[r] = model.one[cells].sum(axis=0), model.zero[cells].sum(axis=0)
+    n1[2], n0[2] = n1[0] + n1[1], n0[0] + n0[1]
+    return n1, n0
+
+
+def sm_cell_ll(model, S, rows32):
+    """_rg_get_ll (:635-638): [|S|][2], and the sums of the terms' magnitudes"""
+    S = np.asarray(S, dtype=np.int64)
+    L1, L0 = log_tables(rows32, model.FN, model.FP)
+    return model.one_f[S] @ L1.T + model.zero_f[S] @ L0.T, model.one_f[S] @ np.abs(L1).T + model.zero_f[S] @ np.abs(L0).T
+
+
+def normalize_log(probs):
+    """_normalize_log (:104-116)"""
+    max_i = int(np.argmax(probs))
+    try:
+        with np.errstate(divide="raise", over="ignore", under="ignore", invalid="raise"):
+            return probs - probs[max_i] - np.log1p(np.sum(np.exp(np.delete(probs, max_i) - probs[max_i])))
+    except FloatingPointError:
+        return np.array([0, LOG_EPSILON]) if probs[0] > probs[1] else np.array([LOG_EPSILON, 0])
+
+
+def sm_scan_assign(ll, assign, n, alpha, order, us=None, fixed=None, margin=None):
+    """_rg_scan_assign (:609-632) with trans_prob over `order` (positions in S) with the uniforms us [|S|]; with `fixed` the walk of
+    _rg_get_split_prob (:803-818), which assigns fixed[.] instead of drawing.  `assign` is changed in place.  Returns (the sum of the chosen
+    log probabilities, the sum of their magnitudes)."""
+    lden = np.log(n - 1 + alpha)
+    prob = np.zeros(len(assign))
+    on_j = int(assign.sum())
+    for s in order:
+        others = on_j - int(assign[s])
+        n_j = others + 1                                              # nansum(rg_assignment) + 2 with -1 in the cell's place
+        n_i = n - n_j - 1
+        lp = normalize_log(ll[s] + (np.log(np.array([n_i, n_j], dtype=np.float64)) - lden))
+        if fixed is None:
+            p = np.exp(lp)
+            cdf = np.cumsum(p)
+            cdf /= cdf[-1]
+            new = 0 if cdf[0] > us[s] else 1
+            if margin is not None:
+                margin.see(cdf[0] - us[s])
+        else:
+            new = int(fixed[s])
+        assign[s] = new
+        on_j = others + new
+        prob[s] = lp[new]
+    return float(prob.sum()), float(np.abs(prob).sum())
+
+
+def sm_param_move(model, old32, new32, n1, n0, sd, lv, margin=None):
+    """MH_cluster_params(trans_prob=True) (:314-342) of one row after its proposal: A clipped at 0, declined iff ln v >= A, a declined
+    entry contributes log(-expm1(A)).  Returns (the row, the sum, the sum of magnitudes: an entry's own and those of A's terms, which a
+    declined entry's log(-expm1(.)) passes on times its slope 1 / expm1(-A))."""
+    A, mag = log_A(model, new32, old32, n1, n0, sd, terms=True)
+    A = np.minimum(A, 0.0)
+    decline = lv >= A
+    if margin is not None:
+        margin.see((lv - A) / np.maximum(1.0, np.abs(A)))
+    with np.errstate(all="ignore"):
+        T = np.where(decline, np.log(-np.expm1(np.where(decline, A, -1.0))), A)
+        slope = np.where(decline, 1.0 / np.expm1(-np.where(decline, A, -1.0)), 1.0)
+    return np.where(decline, old32, new32).astype(np.float32), float(T.sum()), float((np.abs(T) + mag * np.maximum(1.0, slope)).sum())
+
+
+def sm_lprior_ratio(model, move, n, n_j, alpha, rows32, theta_orig):
+    """_get_lprior_ratio_split (:695-713) / _merge (:736-754): rows32 are rows 0, 1 for a split and row 2 for a merge; theta_orig the
+    parameters of the original cluster(s)"""
+    from scipy.special import gammaln
+    n_i = n - n_j
+    sign = 1.0 if move == "split" else -1.0
+    r = sign * (np.log(alpha) - gammaln(n))
+    if n_i > 0:
+        r += sign * gammaln(n_j)
+    if n_j > 0:
+        r += sign * gammaln(n_i)
+    mag = abs(np.log(alpha)) + abs(gammaln(n)) + abs(gammaln(n_j)) + abs(gammaln(n_i))
+    if not model.uniform:
+        a, b = beta_logpdf(rows32, model.p, model.q), beta_logpdf(theta_orig, model.p, model.q)
+        r += float(np.sum(a)) - float(np.sum(b))
+        mag += float(np.abs(a).sum() + np.abs(b).sum())
+    return float(r), float(mag)
+
+
+def sm_ll_ratio(model, move, n1, n0, rows32):
+    """_get_ll_ratio (:716-733) from the three rows' counts"""
+    L1, L0 = log_tables(rows32, model.FN, model.FP)
+    t = n1 * L1 + n0 * L0
+    ll = t.sum(axis=1)
+    r = ll[0] + ll[1] - ll[2] if move == "split" else ll[2] - ll[0] - ll[1]
+    return float(r), float(np.abs(t).sum())
+
+
+def sm_size_ratio_split(ltrans_prob_size, other_sizes, n, n_j):
+    """_get_ltrans_prob_size_ratio_split (:757-764)"""
+    n_i = n - n_j
+    norm = np.sum(1 / np.append(np.asarray(other_sizes, dtype=np.float64), [n_i, n_j]))
+    return float(np.log(1 / n_i / norm) + np.log(1 / n_j / norm) - ltrans_prob_size)
+
+
+def sm_size_ratio_merge(size_data, N, n_S):
+    """_get_ltrans_prob_size_ratio_merge (:767-774): log(|S| - 1) raises for |S| of 0 or 1 and the term falls back"""
+    rev = -np.log(N) - np.log(n_S - 1) if n_S > 1 else -np.log(N)
+    return float(rev - size_data)
+
+
+def sm_split_size_data(sizes, live, cl):
+    """do_split_move's ltrans_prob_size (:454-456): the unrestricted share of the cluster"""
+    size = int(sizes[cl])
+    return float(np.log(size / float(sizes[live].sum())) - np.log(size) - np.log(size - 1))
+
+
+def sm_merge_size_data(sizes, live, cl_i, cl_j):
+    """do_merge_move's cluster_size_data (:505-507); the inverse sizes are added in the order of the ids"""
+    inv = 1 / sizes[live].astype(np.float64)
+    total = np.cumsum(inv)[-1]
+    return float((np.log(1 / float(sizes[cl_i]) / total) + np.log(1 / float(sizes[cl_j]) / total)) - (np.log(float(sizes[cl_i])) + np.log(float(sizes[cl_j]))))
+
+
+def sm_choose_split(sizes, live, c0):
+    """the cluster to split: the first of those with two cells or more whose running share of their sizes exceeds c0"""
+    cand = live[sizes[live] >= 2]
+    cdf = np.cumsum(sizes[cand]).astype(np.float64) / float(sizes[cand].sum())
+    return int(cand[min(int(np.searchsorted(cdf, c0, side="right")), len(cand) - 1)])
+
+
+def sm_choose_merge(sizes, live, c0, c1):
+    """the clusters to merge: two sequential draws without replacement from the inverse sizes"""
+    inv = 1 / sizes[live].astype(np.float64)
+    cdf = np.cumsum(inv)
+    ji = min(int(np.searchsorted(cdf / cdf[-1], c0, side="right")), len(live) - 1)
+    rest = np.delete(np.arange(len(live)), ji)
+    cdf2 = np.cumsum(inv[rest])
+    jj = int(rest[min(int(np.searchsorted(cdf2 / cdf2[-1], c1, side="right")), len(rest) - 1)])
+    return int(live[ji]), int(live[jj])
+
+
+def sm_apply(st, move, cl_i, cl_j, j, S, assign, rows32):
+    """an accepted move on the state (:465-477, :513-520): rows32 are rows 0, 1 for a split (cl_j the free id) and row 2 for a merge"""
+    if move == "split":
+        st.theta[cl_i], st.theta[cl_j] = rows32[0], rows32[1]
+        st.labels[np.append(np.asarray(S, dtype=np.int64)[np.asarray(assign) == 1], j)] = cl_j
+    else:
+        st.theta[cl_i] = rows32
+        st.labels[st.labels == cl_j] = cl_i
+    st.sizes[:] = np.bincount(st.labels, minlength=len(st.labels))
+
+
+def _sm_mh_draws(seed, step, M, scan, row):
+    m = np.arange(M)
+    sub = 4 * scan + row
+    u, v = doubles(seed, m, step, P_SM_MH, 0, sub)
+    w = philox(seed, m, step, np.uint64(P_SM_MH) | (np.uint64(sub) << np.uint64(8)), 1)
+    return u, np.log(v), PROPOSAL_SD[w[0] % np.uint32(3)]
+
+
+def _sm_fresh_sd(seed, step, M, row):
+    w = philox(seed, np.arange(M), step, np.uint64(P_SM_SD) | (np.uint64(row) << np.uint64(8)), 0)
+    return PROPOSAL_SD[w[0] % np.uint32(3)]
+
+
+def split_merge_move(model, st, seed, step, ratios=(0.75, 0.25), scans=3, margin=None):
+    """update_assignments_split_merge (:417-431) on the state, under the stream.  Returns the outcome: code (as in sm_moves), clusters
+    (i, j: for a split j is the smallest free id), anchors, A, terms [4], mags [4] (the sums of magnitudes behind the terms), counts [4]
+    (their numbers of terms), lv (ln v), errors."""
+    N, M = model.N, model.M
+    live = st.live()
+    K = len(live)
+    _, u_kind = doubles(seed, 0, step, P_SM, 0)
+    c0, c1 = doubles(seed, 0, step, P_SM, 1)
+    a0, a1 = doubles(seed, 0, step, P_SM, 2)
+    v, _ = doubles(seed, 0, step, P_SM, 3)
+    lv = float(np.log(v))
+    if K == 1:
+        split = True
+    elif K == N:
+        split = False
+    else:
+        edge = ratios[0] / (ratios[0] + ratios[1])
+        split = bool(u_kind < edge)
+        if margin is not None:
+            margin.see(float(u_kind) - edge)
+    if split:
+        cl_i = sm_choose_split(st.sizes, live, float(c0))
+        size_data = sm_split_size_data(st.sizes, live, cl_i)
+        cl_j = int(np.nonzero(st.sizes == 0)[0][0])                   # get_empty_cluster, should the split be accepted
+        cells = np.nonzero(st.labels == cl_i)[0]
+        n = len(cells)
+        ii = min(int(float(a0) * n), n - 1)
+        jj = min(int(float(a1) * (n - 1)), n - 2)
+        jj += jj >= ii
+        i, j = int(cells[ii]), int(cells[jj])
+        orig_rows = st.theta[[cl_i]]
+    else:
+        cl_i, cl_j = sm_choose_merge(st.sizes, live, float(c0), float(c1))
+        size_data = sm_merge_size_data(st.sizes, live, cl_i, cl_j)
+        cells_i, cells_j = np.nonzero(st.labels == cl_i)[0], np.nonzero(st.labels == cl_j)[0]
+        i = int(cells_i[min(int(float(a0) * len(cells_i)), len(cells_i) - 1)])
+        j = int(cells_j[min(int(float(a1) * len(cells_j)), len(cells_j) - 1)])
+        cells = np.sort(np.concatenate([cells_i, cells_j]))
+        n = len(cells)
+        orig_rows = st.theta[[cl_i, cl_j]]
+    S = cells[(cells != i) & (cells != j)]
+    n_S = len(S)
+    # run_rg_nc (:527-544): the launch state
+    assign = sm_launch_assign(model, i, j, S, margin)
+    n1, n0 = sm_row_counts(model, i, j, S, assign)
+    b, errors = beta_variate(seed, model.p + n1, model.q + n0, np.arange(M)[None, :], step, P_SM_BETA, np.arange(3)[:, None], margin)
+    rows = np.clip(b, TMIN, TMAX).astype(np.float32)
+
+    def scan_assign(t):
+        if n_S == 0:
+            return 0.0, 0.0                                           # _rg_scan_split (:571-572)
+        w = philox(seed, S, step, np.uint64(P_SM_PERM) | (np.uint64(t) << np.uint64(8)), 0)
+        order = np.lexsort((S, w[1].astype(np.uint64) << _S32 | w[0].astype(np.uint64)))
+        us, _ = doubles(seed, S, step, P_SM_CHOICE, 0, t)
+        ll, _ = sm_cell_ll(model, S, rows[:2])
+        return sm_scan_assign(ll, assign, n, st.alpha, order, us, None, margin)
+
+    def move_row(t, r, n1, n0):
+        u, lvs, sd = _sm_mh_draws(seed, step, M, t, r)
+        rows[r], total, mag = sm_param_move(model, rows[r], truncnorm_variate(u, rows[r], sd), n1[r], n0[r], sd, lvs, margin)
+        return total, mag
+
+    for t in range(scans):
+        scan_assign(t)
+        n1, n0 = sm_row_counts(model, i, j, S, assign)
+        for r in range(3):
+            move_row(t, r, n1, n0)
+    terms, mags, counts = np.zeros(4), np.zeros(4), np.zeros(4, np.int64)
+    per_row = 2 * n * M + 6 * M                                       # what one row's M values of A are sums of, at most
+    if split:
+        # _do_rg_split_MH (:641-653), _get_trans_prob_ratio_split (:668-682)
+        prob_cl, mag_cl = scan_assign(scans)
+        n1, n0 = sm_row_counts(model, i, j, S, assign)
+        (p0, m0), (p1, m1) = move_row(scans, 0, n1, n0), move_row(scans, 1, n1, n0)
+        GS_split = prob_cl + (p0 + p1)
+        sd = _sm_fresh_sd(seed, step, M, 2)
+        A_rev, mag_rev = log_A(model, orig_rows[0], rows[2], n1[2], n0[2], sd, terms=True, clip=True)
+        terms[0], mags[0], counts[0] = float(A_rev.sum()) - GS_split, mag_cl + m0 + m1 + float(mag_rev.sum()), n_S + 3 * per_row
+        n_j = int(assign.sum()) + 1
+        terms[1], mags[1] = sm_lprior_ratio(model, "split", n, n_j, st.alpha, rows[:2], orig_rows)
+        terms[2], mags[2] = sm_ll_ratio(model, "split", n1, n0, rows)
+        terms[3] = sm_size_ratio_split(size_data, np.delete(st.sizes[live], np.searchsorted(live, cl_i)), n, n_j)
+        refused = n_S > 0 and len(np.unique(assign)) == 1
+    else:
+        # _do_rg_merge_MH (:656-665), _get_trans_prob_ratio_merge (:685-692), _rg_get_split_prob (:777-820)
+        GS_merge, mag_m = move_row(scans, 2, n1, n0)
+        GS_split, mag_s = 0.0, 0.0
+        for r in range(2):
+            sd = _sm_fresh_sd(seed, step, M, r)
+            A_r, mag_r = log_A(model, orig_rows[r], rows[r], n1[r], n0[r], sd, terms=True, clip=True, unit_bounds=True)
+            GS_split += float(A_r.sum()); mag_s += float(mag_r.sum())
+        original = (st.labels[S] == cl_j).astype(np.int64)
+        if n_S:
+            ll, _ = sm_cell_ll(model, S, orig_rows)
+            pa, mag_a = sm_scan_assign(ll, assign, n, st.alpha, np.arange(n_S), None, original, None)
+            GS_split += pa; mag_s += mag_a
+        terms[0], mags[0], counts[0] = GS_split - GS_merge, mag_m + mag_s, n_S + 3 * per_row
+        n1, n0 = sm_row_counts(model, i, j, S, assign)                # the original clusters' cells by now
+        n_j = int(assign.sum()) + 1
+        terms[1], mags[1] = sm_lprior_ratio(model, "merge", n, n_j, st.alpha, rows[2], orig_rows)
+        terms[2], mags[2] = sm_ll_ratio(model, "merge", n1, n0, rows)
+        terms[3] = sm_size_ratio_merge(size_data, N, n_S)
+        refused = False
+    counts[1], counts[2], counts[3] = 4 + 3 * M, 6 * M, 8
+    mags[3] = abs(terms[3]) + 4 * np.log(N) + abs(size_data)
+    A = ((terms[0] + terms[1]) + terms[2]) + terms[3]
+    accept = not refused and lv < A
+    if split:
+        code = SM_SPLIT_ACCEPTED if accept else SM_SPLIT_DECLINED
+    else:
+        code = SM_MERGE_ACCEPTED if accept else SM_MERGE_DECLINED
+    if accept:
+        sm_apply(st, "split" if split else "merge", cl_i, cl_j, j, S, assign, rows[:2] if split else rows[2])
+    return {"code": code, "clusters": (cl_i, cl_j), "anchors": (i, j), "A": float(A), "terms": terms, "mags": mags, "counts": counts, "lv": lv,
+            "refused": bool(refused), "errors": int(errors)}
+
+
+def sm_bound_of_A(out):
+    """the bound on |A - A'| between two evaluations of the move's acceptance ratio: (n + 4) 2^-52 sum |term| per term"""
+    return float(np.sum((out["counts"] + 4) * 2.0 ** -52 * out["mags"]))
+
+
+def takes_split_merge(seed, step, sm_prob):
+    """Chain.do_step's first draw (MCMC.py:322)"""
+    return bool(sm_prob > 0 and float(doubles(seed, 0, step, P_SM, 0)[0]) < sm_prob)
 
 
 def likelihood(model, labels, theta_rows):
@@ -409,7 +787,8 @@ def alpha_logpdf(model, alpha):
 def _empty_result(model, steps, burn_in):
     n = steps + 1
     return {"ML": np.zeros(n), "MAP": np.zeros(n), "DP_alpha": np.zeros(n), "FN": np.full(n, model.FN), "FP": np.full(n, model.FP),
-            "assignments": np.zeros((n, model.N), dtype=int), "burn_in": burn_in, "_crp": np.zeros(n), "_beta": np.zeros(n), "_rows": []}
+            "assignments": np.zeros((n, model.N), dtype=int), "burn_in": burn_in, "_crp": np.zeros(n), "_beta": np.zeros(n), "_rows": [],
+            "sm_moves": np.zeros(n, np.int8)}
 
 
 def _finish_result(model, r):
@@ -424,14 +803,19 @@ def _finish_result(model, r):
     return r
 
 
-def _check_run(steps, burn_in):
+def _check_run(steps, burn_in, sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3):
     if steps < 1 or not 0 <= burn_in <= steps:
         raise ValueError("steps must be at least 1 and burn_in within [0, steps], got %d and %d" % (steps, burn_in))
+    if not 0 <= sm_prob <= 1 or len(sm_ratios) != 2 or min(sm_ratios) <= 0 or abs(sum(sm_ratios) - 1) > 1e-9 or not 0 <= sm_steps <= MAX_SM_STEPS:
+        raise ValueError("sm_prob must lie in [0, 1], sm_ratios be two positive numbers that sum to 1 and sm_steps be in [0, %d], got %r, %r and %r"
+                         % (MAX_SM_STEPS, sm_prob, tuple(sm_ratios), sm_steps))
 
 
-def run_chains_host(data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None):
-    """The whole sampler in numpy.  seeds: one 64-bit seed per chain.  states: start there instead of at the random initialisation."""
-    _check_run(steps, burn_in)
+def run_chains_host(data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None,
+                    sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3):
+    """The whole sampler in numpy.  seeds: one 64-bit seed per chain.  states: start there instead of at the random initialisation.
+    sm_prob, sm_ratios, sm_steps: run_BnpC.py's -smp, -smr, -sms; the result's sm_moves [steps + 1] says what each step did."""
+    _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps)
     model = Model(data, FN, FP, pp, dpa, dpa_prob, error_prior)
     out = []
     for c, seed in enumerate(seeds):
@@ -440,7 +824,12 @@ def run_chains_host(data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1)
         errors = 0
         for s in range(steps + 1):
             if s:
-                errors += gibbs_sweep(model, st, seed, s)
+                if takes_split_merge(seed, s, sm_prob):
+                    move = split_merge_move(model, st, seed, s, sm_ratios, sm_steps)
+                    errors += move["errors"]
+                    r["sm_moves"][s] = move["code"]
+                else:
+                    errors += gibbs_sweep(model, st, seed, s)
                 errors += alpha_update(model, st, seed, s)
                 parameter_move(model, st, seed, s)
             live = st.live()
@@ -455,16 +844,19 @@ def run_chains_host(data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1)
     return out
 
 
-def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None, arena_rows=0):
+def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None, arena_rows=0,
+               sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3):
     """The same on the device, all chains in every kernel.  arena_rows: the parameter rows per chain the device holds between two fetches
     (0: enough for 64 kept steps of 64 clusters, at least N rows); a full arena only costs a fetch."""
-    _check_run(steps, burn_in)
+    _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps)
     model = Model(data, FN, FP, pp, dpa, dpa_prob, error_prior)
     seeds = [int(s) for s in seeds]
     start = [initial_state(model, s) for s in seeds] if states is None else states
     arena_rows = int(arena_rows) or max(model.N, 4096)
     engine.bnpcs_create(model, seeds, steps, arena_rows)
     try:
+        if sm_prob > 0:
+            engine.bnpcs_set_split_merge(sm_prob, sm_ratios[0], sm_ratios[1], sm_steps)
         for c, st in enumerate(start):
             engine.bnpcs_set_state(c, st.labels, st.theta, st.alpha)
         rows = [[] for _ in seeds]
@@ -480,6 +872,7 @@ def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, 
                     at += k
             done += n
         errors = engine.bnpcs_errors()
+        moves = engine.bnpcs_fetch_moves() if sm_prob > 0 else None
         out = []
         for c in range(len(seeds)):
             r = _empty_result(model, steps, burn_in)
@@ -489,6 +882,8 @@ def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, 
             r["assignments"] = labels[c].astype(int)
             r["_rows"] = rows[c]
             r["variate_errors"] = int(errors[c])
+            if moves is not None:
+                r["sm_moves"] = moves[c].copy()
             out.append(_finish_result(model, r))
         return out
     finally:

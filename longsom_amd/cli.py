@@ -371,28 +371,30 @@ def _bnpc_parser():
     g.add_argument("--chains_npz", default="", help="estimate from chains saved by --save_chains: no sampler is run")
     g.add_argument("--host_estimate", action="store_true", help="the numpy twin of the estimate, for a machine without a GPU")
     g.add_argument("--device", type=int, default=0)
-    g.add_argument("--sampler", choices=["reference", "device"], default="reference",
-                   help="device: Gibbs sweeps, the concentration update and the parameter moves on the GPU, all chains at once (needs -smp 0)")
+    g.add_argument("--sampler", choices=["reference", "device", "device-sm"], default="reference",
+                   help="device: Gibbs sweeps, the concentration update and the parameter moves on the GPU, all chains at once (needs -smp 0); "
+                        "device-sm: the same with the split-merge move, -smp / -sms / -smr honoured (-smp 0 equals device)")
     return ap
 
 
 def _device_sampler_refusals(a):
-    """what longsom_amd.bnpc_sampler does not do, each named by its flag"""
-    if a.split_merge_prob != 0:
+    """what longsom_amd.bnpc_sampler does not do, each named by its flag; --sampler device and device-sm share all but the first"""
+    if a.sampler == "device" and a.split_merge_prob != 0:
         sys.exit("run_BnpC.py: --sampler device has no split-merge move: -smp/--split_merge_prob %g is not supported, run it with -smp 0" % a.split_merge_prob)
+    who = "--sampler %s" % a.sampler
     if not (a.falsePositive > 0 and a.falseNegative > 0) and a.error_update_prob != 0:
-        sys.exit("run_BnpC.py: --sampler device keeps the error rates fixed: -eup/--error_update_prob %g is not supported, run it with -eup 0 (or give -FP and -FN)"
-                 % a.error_update_prob)
+        sys.exit("run_BnpC.py: %s keeps the error rates fixed: -eup/--error_update_prob %g is not supported, run it with -eup 0 (or give -FP and -FN)"
+                 % (who, a.error_update_prob))
     if a.fixed_assignment:
-        sys.exit("run_BnpC.py: --sampler device does not support -fa/--fixed_assignment")
+        sys.exit("run_BnpC.py: %s does not support -fa/--fixed_assignment" % who)
     if a.runtime > 0:
-        sys.exit("run_BnpC.py: --sampler device does not support -r/--runtime: give the steps with -s")
+        sys.exit("run_BnpC.py: %s does not support -r/--runtime: give the steps with -s" % who)
     if a.lugsail > 0:
-        sys.exit("run_BnpC.py: --sampler device does not support -ls/--lugsail: give the steps with -s")
+        sys.exit("run_BnpC.py: %s does not support -ls/--lugsail: give the steps with -s" % who)
 
 
 def _device_chains(a, data):
-    """the chains of --sampler device: the model of run_BnpC.py:261-296 with its error rates fixed (the given ones, or the priors' means
+    """the chains of --sampler device / device-sm: the model of run_BnpC.py:261-296 with its error rates fixed (the given ones, or the priors' means
     with the priors' own terms in MAP), the seeds drawn as MCMC.run draws them"""
     from scipy.stats import truncnorm
     from . import bnpc_sampler
@@ -406,12 +408,13 @@ def _device_chains(a, data):
         print(f"Run MCMC on the device ({a.chains} chains for {a.steps} steps, FN {FN} FP {FP}):")
     with Engine(a.device) as eng:
         return bnpc_sampler.run_chains(eng, data, [int(s) for s in a.chain_seeds], a.steps, int(a.steps * a.burn_in), FN, FP, pp=a.param_prior, dpa=a.DPa_prior,
-                                       dpa_prob=a.conc_update_prob, error_prior=error_prior)
+                                       dpa_prob=a.conc_update_prob, error_prior=error_prior, sm_prob=a.split_merge_prob if a.sampler == "device-sm" else 0.0,
+                                       sm_ratios=tuple(a.split_merge_ratios), sm_steps=a.split_merge_steps)
 
 
 def run_bnpc(argv=None):
     """run_BnpC.py: the chains come from the vendored BnpC's sampler (libs/MCMC.py, run as the reference runs it), from --sampler device
-    (longsom_amd.bnpc_sampler: no split-merge move, fixed error rates) or from --chains_npz; the
+    or device-sm (longsom_amd.bnpc_sampler: fixed error rates; device-sm with the split-merge move) or from --chains_npz; the
     posterior estimate is made on the device (longsom_amd.bnpc); assignment.txt, errors.txt and genotypes_*.tsv are written here; args.txt,
     the PSRF, -e ML|MAP, the summaries and the plots are left to the checkout's own functions."""
     from datetime import datetime
@@ -425,17 +428,18 @@ def run_bnpc(argv=None):
         a.estimator = [a.estimator]
     if a.single_chains:
         sys.exit("run_BnpC.py: -sc/--single_chains is not supported here: the posterior estimate is made once, over all chains")
-    if a.sampler == "device" and not a.chains_npz:
+    on_device = a.sampler in ("device", "device-sm")
+    if on_device and not a.chains_npz:
         _device_sampler_refusals(a)
     point = [e for e in a.estimator if e != "posterior"]
     if a.chains_npz and point:
         sys.exit("run_BnpC.py: -e %s needs the sampler's run: it cannot be combined with --chains_npz" % " ".join(point))
     libs_dir = a.bnpc_libs or os.path.join(script_dir, "..", "..", "scripts", "CellClustering", "libs")
     have_libs = os.path.isfile(os.path.join(libs_dir, "MCMC.py"))
-    own_chains = a.chains_npz or a.sampler == "device"
+    own_chains = a.chains_npz or on_device
     if not have_libs and not (own_chains and a.no_plots and not point):
         sys.exit("run_BnpC.py: no vendored BnpC at %s (--bnpc_libs DIR): the reference's sampler, -e ML|MAP and the plots are the checkout's; only --chains_npz or "
-                 "--sampler device, with --no_plots, run without one" % libs_dir)
+                 "--sampler device / device-sm, with --no_plots, run without one" % libs_dir)
     io = ut = None
     if have_libs:
         sys.path.insert(0, os.path.dirname(os.path.abspath(libs_dir)))
@@ -448,7 +452,7 @@ def run_bnpc(argv=None):
     a.time = [datetime.now()]
     if a.chains_npz:
         results = bnpc.load_chains(a.chains_npz)
-    elif a.sampler == "device":
+    elif on_device:
         if a.debug:
             a.chains = 1
         results = _device_chains(a, data)

@@ -1,5 +1,6 @@
-// BnpC's sampler for the model with fixed error rates (CellClustering/libs/CRP.py:17-410, libs/MCMC.py:200-388): Gibbs assignment sweeps,
-// the Escobar-West concentration update and the parameter Metropolis-Hastings, every chain of a run in every kernel.  The stream, the
+// BnpC's sampler for the model with fixed error rates (CellClustering/libs/CRP.py:17-820, libs/MCMC.py:200-388): Gibbs assignment sweeps,
+// the non-conjugate split-merge move, the Escobar-West concentration update and the parameter Metropolis-Hastings, every chain of a run in
+// every kernel.  The stream, the
 // variates and the order of a step are defined in longsom_amd/bnpc_sampler.py's docstring; its numpy twin is what these kernels are held
 // to.  See include/longsom_hip.h, lsg_bnpcs_*.  Everything is fp64 except theta.
 #include "lsg_ctx.h"
@@ -11,7 +12,10 @@ namespace lsg {
 constexpr double S_TMIN = 1e-5, S_TMAX = 1 - 1e-5;
 constexpr double S_EPS = 1e-15;                       // np.finfo(np.float64).resolution
 constexpr int S_TRIES = 64;                           // Marsaglia-Tsang tries before the mean is written and an error counted
-enum { P_PERM = 1, P_CHOICE, P_BIRTH, P_BIRTH_B, P_DPA, P_ETA, P_ETA_B, P_ALPHA, P_MH, P_INIT_LABEL, P_INIT_THETA };
+enum { P_PERM = 1, P_CHOICE, P_BIRTH, P_BIRTH_B, P_DPA, P_ETA, P_ETA_B, P_ALPHA, P_MH, P_INIT_LABEL, P_INIT_THETA,
+       P_SM, P_SM_PERM, P_SM_CHOICE, P_SM_BETA, P_SM_BETA_B, P_SM_MH, P_SM_SD };
+constexpr int SM_OUT = 12;                            // doubles of a move's outcome: code, the clusters, the anchors, A, its four terms, ln v, |S|
+constexpr int SM_MAX_SCANS = 1 << 20;                 // 4 scan + row must fit the 24 bits of `sub`
 constexpr int LT = 16;                                // k_bnpcs_ll: cells x columns per workgroup
 constexpr int REC = 5;                                // doubles recorded per chain and step: ML, the CRP prior sum, the beta prior sum, live clusters, alpha
 
@@ -29,6 +33,16 @@ struct SDev {
     double *L1, *L0, *LL, *alpha, *prow, *rowml, *rowb, *rec_sc;
     uint32_t *n1, *n0;
     uint64_t* keys;
+    // the split-merge move: a step takes it with probability sm_prob, a split with sm_edge = r0 / (r0 + r1); sm_anchor: the six logs of
+    // _rg_init_split's likelihood, [anchor 1, 0, missing][cell 1, 0].  Per chain: sm_i 5 N (the cells of cluster i, of cluster j, S, the
+    // assignment of S, the walk's picks), sm_d 6 N + 6 M + SM_OUT (ll [N][2], u [N], the same in walk order, the rows' L1 / L0, the outcome),
+    // sm_c 6 M (the rows' n1 / n0), sm_t 3 M (the rows), rec_sm steps1 (the codes of sm_moves)
+    double sm_prob, sm_edge, sm_anchor[6];
+    int32_t sm_scans;
+    int32_t *sm_i, *rec_sm;
+    double* sm_d;
+    uint32_t* sm_c;
+    float* sm_t;
 };
 
 // ---- the stream ----------------------------------------------------------------------------------------------------------------
@@ -85,6 +99,13 @@ __device__ inline float truncnorm_variate(double u, float old, double sd) {
 
 __device__ inline double truncnorm_logpdf(float x, float loc, double sd) {
     const double pa = normcdf(f32diff((float)S_TMIN, loc) / sd), pb = normcdf(f32diff((float)S_TMAX, loc) / sd);
+    const double z = (double)(x - loc) / sd;
+    return -0.5 * z * z - 0.5 * log(2.0 * M_PI) - log(sd) - log(pb - pa);
+}
+
+// the same density truncated to [lo, hi]: _rg_get_split_prob passes (0 - theta) / sd and (1 - theta) / sd (CRP.py:779-780)
+__device__ inline double truncnorm_logpdf_in(float x, float loc, double sd, float lo, float hi) {
+    const double pa = normcdf(f32diff(lo, loc) / sd), pb = normcdf(f32diff(hi, loc) / sd);
     const double z = (double)(x - loc) / sd;
     return -0.5 * z * z - 0.5 * log(2.0 * M_PI) - log(sd) - log(pb - pa);
 }
@@ -250,17 +271,46 @@ __device__ inline double ll_direct(const SDev& d, int c, int cell, int k) {
     return acc;
 }
 
+// ---- the concentration update (update_DP_alpha, :386-410) that follows a chain's sweep or its split-merge move: the whole workgroup calls it
+// once the chain's sizes are final
+__device__ void alpha_update(const SDev& d, int c, uint32_t step, const int32_t* size, double alpha, double* shd) {
+    const int t = threadIdx.x, N = d.N;
+    const uint64_t key = d.seeds[c];
+    const int chn = (N + 255) / 256;
+    double kk = 0.0;
+    for (int k = min(t * chn, N); k < min(t * chn + chn, N); ++k) kk += size[k] > 0;
+    kk = block_sum(kk, shd);
+    if (t == 0) {
+        double u0, u1;
+        doubles(key, 0, step, P_DPA, 0, u0, u1);
+        if (u0 < d.dpa_prob) {
+            const double eta = beta_variate(key, 0, step, P_ETA, alpha + 1.0, (double)N, d.err + c);
+            const double scale = d.g1 - log(eta);
+            const double w = (d.g0 + kk - 1.0) / ((double)N * scale);
+            const double pi_eta = w / (1.0 + w);
+            const double g = gamma_variate(key, 0, step, P_ALPHA, u1 < pi_eta ? d.g0 + kk : d.g0 + kk - 1.0, d.err + c);
+            d.alpha[c] = fmax(1.0 + S_EPS, g * scale);
+        }
+    }
+}
+
 // ---- the sweep: one workgroup per chain walks the permuted cells (update_assignments_Gibbs, CRP.py:254-288), then the concentration
 // update (update_DP_alpha, :386-410).  No workgroup waits for another.  A lane owns a run of cluster ids, so the running sum of the
 // probabilities keeps the ids' order.  A cluster alive at the sweep's start reads its column of LL; one born in the sweep, or an id that
-// emptied and was issued again, has colof = -1 and is evaluated from its own tables (the stale-column rule).
-__global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step) {
+// emptied and was issued again, has colof = -1 and is evaluated from its own tables (the stale-column rule).  With `decide` a chain whose
+// step is a split-merge move (Chain.do_step, MCMC.py:322) leaves here at once: k_bnpcs_sm moves it and makes its concentration update.
+__global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step, int decide) {
     __shared__ double shd[4];
     __shared__ int shi[4];
     __shared__ double pref[4];
     __shared__ int s_pick;
     const int c = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6, N = d.N;
     const uint64_t key = d.seeds[c];
+    if (decide) {
+        double u0, u1;
+        doubles(key, 0, step, P_SM, 0, u0, u1);
+        if (u0 < d.sm_prob) return;
+    }
     int32_t* lab = d.lab + (size_t)c * N; int32_t* size = d.size + (size_t)c * N; int32_t* colof = d.colof + (size_t)c * N;
     const int32_t* order = d.order + (size_t)c * N;
     double* prow = d.prow + (size_t)c * (N + 1);
@@ -339,23 +389,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step) {
         } else if (t == 0) { size[pick] += 1; lab[cell] = pick; }
     }
     __syncthreads();
-    // the concentration update
-    const int chn = (N + 255) / 256;
-    double kk = 0.0;
-    for (int k = min(t * chn, N); k < min(t * chn + chn, N); ++k) kk += size[k] > 0;
-    kk = block_sum(kk, shd);
-    if (t == 0) {
-        double u0, u1;
-        doubles(key, 0, step, P_DPA, 0, u0, u1);
-        if (u0 < d.dpa_prob) {
-            const double eta = beta_variate(key, 0, step, P_ETA, alpha + 1.0, (double)N, d.err + c);
-            const double scale = d.g1 - log(eta);
-            const double w = (d.g0 + kk - 1.0) / ((double)N * scale);
-            const double pi_eta = w / (1.0 + w);
-            const double g = gamma_variate(key, 0, step, P_ALPHA, u1 < pi_eta ? d.g0 + kk : d.g0 + kk - 1.0, d.err + c);
-            d.alpha[c] = fmax(1.0 + S_EPS, g * scale);
-        }
-    }
+    alpha_update(d, c, step, size, alpha, shd);
 }
 
 // ---- the parameter move (MH_cluster_params / _get_log_A, :314-383): a lane per (mutation, live cluster, chain) ------------------------------
@@ -383,6 +417,392 @@ __global__ __launch_bounds__(64) void k_bnpcs_mh(SDev d, uint32_t step) {
     const double new_p = truncnorm_logpdf(nw, old, sd), old_p = truncnorm_logpdf(old, nw, sd);
     const double A = new_ll + new_prior - old_ll - old_prior + old_p - new_p;
     if (log(v) < A) d.theta[at] = nw;
+}
+
+// ---- the split-merge move (update_assignments_split_merge and what it calls, CRP.py:417-820; the stream and the order of the draws are in
+// longsom_amd/bnpc_sampler.py's docstring).  One workgroup per chain, as the sweep: no workgroup waits for another and every loop is bounded.
+// The lanes share the compaction of the move's cells, the launch assignment, the rows' counts, Beta draws and tables, the parameter moves,
+// the cells' likelihoods and every sum of the acceptance ratio (block_sum: a fixed order); only the assignment walk is serial, over
+// records laid out in walk order.  The rows' tables stay in global memory: they are read once per scan, the dense part does not bound a step.
+struct SmBuf {
+    int32_t *A, *B, *S, *asg, *pick;
+    double *ll, *u, *wll, *wu, *L1, *L0, *out;
+    uint32_t *n1, *n0;
+    float* th;
+};
+
+__device__ inline SmBuf sm_buf(const SDev& d, int c) {
+    const size_t N = d.N, M = d.M;
+    SmBuf b;
+    int32_t* pi = d.sm_i + (size_t)c * 5 * N;
+    b.A = pi; b.B = pi + N; b.S = pi + 2 * N; b.asg = pi + 3 * N; b.pick = pi + 4 * N;
+    double* pd = d.sm_d + (size_t)c * (6 * N + 6 * M + SM_OUT);
+    b.ll = pd; b.u = pd + 2 * N; b.wll = pd + 3 * N; b.wu = pd + 5 * N; b.L1 = pd + 6 * N; b.L0 = b.L1 + 3 * M; b.out = b.L0 + 3 * M;
+    b.n1 = d.sm_c + (size_t)c * 6 * M; b.n0 = b.n1 + 3 * M;
+    b.th = d.sm_t + (size_t)c * 3 * M;
+    return b;
+}
+
+// the cells labelled a or b, without the cells xi and xj, in ascending id into out; every lane gets their number.  cnt: 256 ints of LDS
+__device__ int sm_compact(const int32_t* lab, int N, int a, int b, int xi, int xj, int32_t* out, int* cnt) {
+    const int t = threadIdx.x, ch = (N + 255) / 256, k0 = min(t * ch, N), k1 = min(k0 + ch, N);
+    int n = 0;
+    for (int k = k0; k < k1; ++k) { const int l = lab[k]; n += (l == a || l == b) && k != xi && k != xj; }
+    __syncthreads();
+    cnt[t] = n;
+    __syncthreads();
+    int at = 0, total = 0;
+    for (int j = 0; j < 256; ++j) { const int v = cnt[j]; total += v; if (j < t) at += v; }
+    for (int k = k0; k < k1; ++k) { const int l = lab[k]; if ((l == a || l == b) && k != xi && k != xj) out[at++] = k; }
+    __syncthreads();
+    return total;
+}
+
+// _rg_init_split's likelihood of a cell under an anchor's data as parameters (:557-560): popcounts times the six constants, in their order
+__device__ inline double sm_anchor_ll(const SDev& d, int cell, int anchor) {
+    int n[6] = {0, 0, 0, 0, 0, 0};
+    for (int w = 0; w < d.W; ++w) {
+        const uint64_t co = d.one[(size_t)cell * d.W + w], cz = d.zero[(size_t)cell * d.W + w];
+        const uint64_t ao = d.one[(size_t)anchor * d.W + w], az = d.zero[(size_t)anchor * d.W + w], am = ~(ao | az);
+        n[0] += __popcll(co & ao); n[1] += __popcll(cz & ao); n[2] += __popcll(co & az); n[3] += __popcll(cz & az); n[4] += __popcll(co & am); n[5] += __popcll(cz & am);
+    }
+    double ll = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ll = ll + (double)n[k] * d.sm_anchor[k];
+    return ll;
+}
+
+// n1 / n0 of rows 0 and 1 from the assignment of S and the two anchors, and row 2 as their sum
+__device__ void sm_count(const SDev& d, const SmBuf& b, int nS, int ai, int aj) {
+    const int M = d.M;
+    for (int e = threadIdx.x; e < 2 * M; e += 256) { b.n1[e] = 0; b.n0[e] = 0; }
+    __syncthreads();
+    for (int s = threadIdx.x; s < nS + 2; s += 256) {
+        const int cell = s < nS ? b.S[s] : s == nS ? ai : aj, r = s < nS ? b.asg[s] : s - nS;
+        for (int w = 0; w < d.W; ++w) {
+            uint64_t o = d.one[(size_t)cell * d.W + w], z = d.zero[(size_t)cell * d.W + w];
+            while (o) { atomicAdd(&b.n1[r * M + w * 64 + __ffsll((unsigned long long)o) - 1], 1u); o &= o - 1; }
+            while (z) { atomicAdd(&b.n0[r * M + w * 64 + __ffsll((unsigned long long)z) - 1], 1u); z &= z - 1; }
+        }
+    }
+    __syncthreads();
+    for (int m = threadIdx.x; m < M; m += 256) { b.n1[2 * M + m] = b.n1[m] + b.n1[M + m]; b.n0[2 * M + m] = b.n0[m] + b.n0[M + m]; }
+    __syncthreads();
+}
+
+__device__ void sm_tables(const SDev& d, const SmBuf& b, int r0, int r1) {
+    for (int e = r0 * d.M + threadIdx.x; e < r1 * d.M; e += 256) { double l1, l0; log_terms(d, b.th[e], l1, l0); b.L1[e] = l1; b.L0[e] = l0; }
+    __syncthreads();
+}
+
+__device__ inline double sm_sd(uint64_t key, uint32_t m, uint32_t step, uint32_t purpose, uint32_t attempt) {
+    uint32_t w[4];
+    philox4x32(key, m, step, purpose, attempt, w);
+    const uint32_t pick = w[0] % 3u;
+    return pick == 0 ? 0.1 : pick == 1 ? 0.25 : 0.5;
+}
+
+// _get_log_A with clip (:347-383) of one entry; unit: the forward density's bounds are 0 and 1
+__device__ inline double sm_log_A(const SDev& d, float nw, float old, double n1, double n0, double sd, bool unit) {
+    double nl1, nl0, ol1, ol0;
+    log_terms(d, nw, nl1, nl0);
+    log_terms(d, old, ol1, ol0);
+    const double new_ll = n1 * nl1 + n0 * nl0, old_ll = n1 * ol1 + n0 * ol0;
+    const double new_prior = d.uniform ? 0.0 : beta_logpdf(d, nw), old_prior = d.uniform ? 0.0 : beta_logpdf(d, old);
+    const double new_p = unit ? truncnorm_logpdf_in(nw, old, sd, 0.0f, 1.0f) : truncnorm_logpdf(nw, old, sd), old_p = truncnorm_logpdf(old, nw, sd);
+    return fmin(new_ll + new_prior - old_ll - old_prior + old_p - new_p, 0.0);
+}
+
+// MH_cluster_params(trans_prob=True) (:314-342) of rows r0 .. r1-1 at scan `scan`, a lane per (row, mutation); sums[r] gets the row's
+// transition probability in every lane, and the moved rows' tables are made again
+__device__ void sm_move_rows(const SDev& d, const SmBuf& b, uint64_t key, uint32_t step, int scan, int r0, int r1, double* sums, double* shd) {
+    const int M = d.M;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int e = r0 * M + threadIdx.x; e < r1 * M; e += 256) {
+        const int r = e / M, m = e - r * M;
+        const uint32_t pw = (uint32_t)P_SM_MH | ((uint32_t)(4 * scan + r) << 8);
+        double u, v;
+        doubles(key, (uint32_t)m, step, pw, 0, u, v);
+        const double sd = sm_sd(key, (uint32_t)m, step, pw, 1);
+        const float old = b.th[e];
+        const float nw = truncnorm_variate(u, old, sd);
+        const double A = sm_log_A(d, nw, old, (double)b.n1[e], (double)b.n0[e], sd, false);
+        double share;
+        if (log(v) < A) { b.th[e] = nw; share = A; }
+        else share = log(-expm1(A));
+        if (r == 0) a0 += share; else if (r == 1) a1 += share; else a2 += share;
+    }
+    sums[0] = block_sum(a0, shd); sums[1] = block_sum(a1, shd); sums[2] = block_sum(a2, shd);
+    sm_tables(d, b, r0, r1);
+}
+
+// a masked sum of a cell over one row's tables
+__device__ inline double sm_row_ll(const SDev& d, int cell, const double* l1, const double* l0) {
+    double acc = 0.0;
+    for (int w = 0; w < d.W; ++w) {
+        uint64_t o = d.one[(size_t)cell * d.W + w], z = d.zero[(size_t)cell * d.W + w];
+        while (o) { acc += l1[w * 64 + __ffsll((unsigned long long)o) - 1]; o &= o - 1; }
+        while (z) { acc += l0[w * 64 + __ffsll((unsigned long long)z) - 1]; z &= z - 1; }
+    }
+    return acc;
+}
+
+// _rg_scan_assign (:609-632) with its transition probability; with clj >= 0 the in-order walk of _rg_get_split_prob (:803-818), which
+// assigns the original cluster instead of drawing.  The likelihoods of all cells of S under the two rows (la / lb: their L1, L0) are
+// taken once; the walk's records are laid out in walk order, lane 0 walks them, the lanes scatter its picks.  Every lane gets the sum.
+__device__ double sm_scan(const SDev& d, const SmBuf& b, int c, uint64_t key, uint32_t step, int scan, int nS, double alpha, const double* l1a, const double* l0a,
+                          const double* l1b, const double* l0b, int clj, uint64_t* tile, double* s_out) {
+    const int t = threadIdx.x;
+    uint64_t* keys = d.keys + (size_t)c * d.N;
+    int32_t* pos = d.order + (size_t)c * d.N;
+    const int32_t* lab = d.lab + (size_t)c * d.N;
+    for (int s = t; s < nS; s += 256) {
+        const int cell = b.S[s];
+        b.ll[2 * s] = sm_row_ll(d, cell, l1a, l0a); b.ll[2 * s + 1] = sm_row_ll(d, cell, l1b, l0b);
+        if (clj < 0) {
+            uint32_t w[4];
+            philox4x32(key, (uint32_t)cell, step, (uint32_t)P_SM_PERM | ((uint32_t)scan << 8), 0, w);
+            keys[s] = ((uint64_t)w[1] << 32) | w[0];
+            double u, u_unused;
+            doubles(key, (uint32_t)cell, step, (uint32_t)P_SM_CHOICE | ((uint32_t)scan << 8), 0, u, u_unused);
+            b.u[s] = u;
+        }
+    }
+    __syncthreads();
+    for (int base = 0; base < nS; base += 256) {
+        const int s = base + t;
+        int rank = s;
+        if (clj < 0) {
+            // the rank of the cell's key among the keys of S: ties go by the position in S, which is the order of the ids
+            const uint64_t mine = s < nS ? keys[s] : 0;
+            rank = 0;
+            for (int j0 = 0; j0 < nS; j0 += 256) {
+                __syncthreads();
+                tile[t] = j0 + t < nS ? keys[j0 + t] : ~0ull;
+                __syncthreads();
+                const int n = min(256, nS - j0);
+                for (int j = 0; j < n; ++j) rank += (tile[j] < mine) || (tile[j] == mine && j0 + j < s);
+            }
+        }
+        if (s < nS) {
+            pos[rank] = s;
+            b.wll[2 * rank] = b.ll[2 * s]; b.wll[2 * rank + 1] = b.ll[2 * s + 1];
+            b.wu[rank] = clj < 0 ? b.u[s] : 0.0;
+            b.pick[rank] = clj < 0 ? b.asg[s] : (b.asg[s] | ((lab[b.S[s]] == clj ? 1 : 0) << 1));      // bit 0: where it is, bit 1: where it goes
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        const int nn = nS + 2;
+        const double lden = log((double)(nn - 1) + alpha);
+        int on_j = 0;
+        for (int r = 0; r < nS; ++r) on_j += b.pick[r] & 1;
+        double prob = 0.0;
+        for (int r = 0; r < nS; ++r) {
+            const int was = b.pick[r];
+            const int others = on_j - (was & 1), n_j = others + 1, n_i = nn - n_j - 1;
+            const double lp0 = b.wll[2 * r] + (log((double)n_i) - lden), lp1 = b.wll[2 * r + 1] + (log((double)n_j) - lden);
+            // _normalize_log (:104-116): the tables are finite, so its FloatingPointError branch is never met
+            double o0, o1;
+            if (lp0 >= lp1) { const double z = log1p(exp(lp1 - lp0)); o0 = 0.0 - z; o1 = (lp1 - lp0) - z; }
+            else { const double z = log1p(exp(lp0 - lp1)); o0 = (lp0 - lp1) - z; o1 = 0.0 - z; }
+            int nw;
+            if (clj < 0) { const double p0 = exp(o0), p1 = exp(o1); nw = p0 / (p0 + p1) > b.wu[r] ? 0 : 1; }
+            else nw = was >> 1;
+            b.pick[r] = nw;
+            on_j = others + nw;
+            prob += nw ? o1 : o0;
+        }
+        *s_out = prob;
+    }
+    __syncthreads();
+    for (int r = t; r < nS; r += 256) b.asg[pos[r]] = b.pick[r];
+    __syncthreads();
+    return *s_out;
+}
+
+// sum over a row's mutations of n1 L1 + n0 L0: the likelihood of the row's cells under the row
+__device__ double sm_ll_of_row(const SDev& d, const SmBuf& b, int r, double* shd) {
+    double acc = 0.0;
+    for (int m = threadIdx.x; m < d.M; m += 256) { const int e = r * d.M + m; acc += (double)b.n1[e] * b.L1[e] + (double)b.n0[e] * b.L0[e]; }
+    return block_sum(acc, shd);
+}
+
+__global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int force) {
+    __shared__ double shd[4];
+    __shared__ int shi[4];
+    __shared__ int cnt[256];
+    __shared__ uint64_t tile[256];
+    __shared__ int s_int[5];
+    __shared__ double s_dbl[2];
+    const int c = blockIdx.x, t = threadIdx.x, N = d.N, M = d.M;
+    const uint64_t key = d.seeds[c];
+    double u0, u_kind;
+    doubles(key, 0, step, P_SM, 0, u0, u_kind);
+    if (!force && !(u0 < d.sm_prob)) return;                       // this chain's step is a sweep: k_bnpcs_scan has made it
+    int32_t* lab = d.lab + (size_t)c * N; int32_t* size = d.size + (size_t)c * N;
+    const int32_t* live = d.live + (size_t)c * N;
+    const int K = d.nlive[c];
+    const SmBuf b = sm_buf(d, c);
+    const double alpha = d.alpha[c];
+    // get_empty_cluster: the smallest free id (N if there is none: then every cluster has one cell and the move is a merge)
+    int fr = N;
+    { const int ch = (N + 255) / 256; for (int k = min(t * ch, N); k < min(t * ch + ch, N); ++k) if (size[k] == 0) { fr = k; break; } }
+    const int free_id = block_min_int(fr, shi);
+    if (t == 0) {
+        double c0, c1;
+        doubles(key, 0, step, P_SM, 1, c0, c1);
+        const bool split = K == 1 ? true : K == N ? false : u_kind < d.sm_edge;
+        int cli = -1, clj = -1;
+        double size_data;
+        if (split) {
+            // once from the clusters of two cells or more: the re-draw loop's own distribution (:441-445)
+            long long tot = 0, cum = 0;
+            for (int j = 0; j < K; ++j) { const int sz = size[live[j]]; if (sz >= 2) tot += sz; }
+            for (int j = 0; j < K; ++j) { const int sz = size[live[j]]; if (sz >= 2) { cum += sz; cli = live[j]; if ((double)cum / (double)tot > c0) break; } }
+            const double sz = (double)size[cli];
+            size_data = log(sz / (double)N) - log(sz) - log(sz - 1.0);                   // the unrestricted share (:454-456)
+        } else {
+            double tot = 0.0, cum = 0.0;
+            for (int j = 0; j < K; ++j) tot += 1.0 / (double)size[live[j]];
+            int ji = 0, jj = 0;
+            for (int j = 0; j < K; ++j) { cum += 1.0 / (double)size[live[j]]; ji = j; if (cum / tot > c0) break; }
+            double tot2 = 0.0;
+            for (int j = 0; j < K; ++j) if (j != ji) tot2 += 1.0 / (double)size[live[j]];
+            cum = 0.0;
+            for (int j = 0; j < K; ++j) if (j != ji) { cum += 1.0 / (double)size[live[j]]; jj = j; if (cum / tot2 > c1) break; }
+            cli = live[ji]; clj = live[jj];
+            const double si = (double)size[cli], sj = (double)size[clj];
+            size_data = (log(1.0 / si / tot) + log(1.0 / sj / tot)) - (log(si) + log(sj));           // :505-507
+        }
+        s_int[0] = split; s_int[1] = cli; s_int[2] = clj; s_dbl[0] = size_data;
+    }
+    __syncthreads();
+    const bool split = s_int[0] != 0;
+    const int cli = s_int[1], clj = split ? free_id : s_int[2];
+    const double size_data = s_dbl[0];
+    const int nA = sm_compact(lab, N, cli, cli, -1, -1, b.A, cnt);
+    const int nB = split ? 0 : sm_compact(lab, N, clj, clj, -1, -1, b.B, cnt);
+    if (t == 0) {
+        double a0, a1;
+        doubles(key, 0, step, P_SM, 2, a0, a1);
+        const int ii = min((int)(a0 * (double)nA), nA - 1);
+        int aj;
+        if (split) { int jj = min((int)(a1 * (double)(nA - 1)), nA - 2); jj += jj >= ii; aj = b.A[jj]; }
+        else aj = b.B[min((int)(a1 * (double)nB), nB - 1)];
+        s_int[3] = b.A[ii]; s_int[4] = aj;
+    }
+    __syncthreads();
+    const int ai = s_int[3], aj = s_int[4];
+    const int nS = sm_compact(lab, N, cli, split ? cli : clj, ai, aj, b.S, cnt);
+    const int nn = nS + 2, scans = d.sm_scans;
+    // run_rg_nc (:527-544): the launch state
+    for (int s = t; s < nS; s += 256) { const int cell = b.S[s]; b.asg[s] = sm_anchor_ll(d, cell, aj) > sm_anchor_ll(d, cell, ai) ? 1 : 0; }
+    __syncthreads();
+    sm_count(d, b, nS, ai, aj);
+    for (int e = t; e < 3 * M; e += 256) {
+        const int r = e / M, m = e - r * M;
+        const double x = beta_variate(key, (uint32_t)m, step, (uint32_t)P_SM_BETA | ((uint32_t)r << 8), d.p + (double)b.n1[e], d.q + (double)b.n0[e], d.err + c);
+        b.th[e] = (float)fmin(fmax(x, S_TMIN), S_TMAX);
+    }
+    __syncthreads();
+    sm_tables(d, b, 0, 3);
+    double sums[3];
+    for (int sc = 0; sc < scans; ++sc) {
+        if (nS > 0) {
+            sm_scan(d, b, c, key, step, sc, nS, alpha, b.L1, b.L0, b.L1 + M, b.L0 + M, -1, tile, &s_dbl[1]);
+            sm_count(d, b, nS, ai, aj);
+        }
+        sm_move_rows(d, b, key, step, sc, 0, 3, sums, shd);
+    }
+    const float* th_i = d.theta + ((size_t)c * N + cli) * M;
+    const float* th_j = d.theta + ((size_t)c * N + (split ? cli : clj)) * M;
+    double t1, t2, t3, t4;
+    int on_j;
+    if (split) {
+        // _do_rg_split_MH (:641-653), _get_trans_prob_ratio_split (:668-682)
+        double prob_cl = 0.0;
+        if (nS > 0) {
+            prob_cl = sm_scan(d, b, c, key, step, scans, nS, alpha, b.L1, b.L0, b.L1 + M, b.L0 + M, -1, tile, &s_dbl[1]);
+            sm_count(d, b, nS, ai, aj);
+        }
+        sm_move_rows(d, b, key, step, scans, 0, 2, sums, shd);
+        const double gs_split = prob_cl + (sums[0] + sums[1]);
+        double rev = 0.0, pa = 0.0, pb = 0.0, cj = 0.0, inv = 0.0;
+        for (int m = t; m < M; m += 256) {
+            const int e = 2 * M + m;
+            rev += sm_log_A(d, th_i[m], b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | (2u << 8), 0), false);
+            if (!d.uniform) { pa += beta_logpdf(d, b.th[m]) + beta_logpdf(d, b.th[M + m]); pb += beta_logpdf(d, th_i[m]); }
+        }
+        for (int s = t; s < nS; s += 256) cj += b.asg[s];
+        for (int j = t; j < K; j += 256) if (live[j] != cli) inv += 1.0 / (double)size[live[j]];
+        rev = block_sum(rev, shd); pa = block_sum(pa, shd); pb = block_sum(pb, shd); cj = block_sum(cj, shd); inv = block_sum(inv, shd);
+        on_j = (int)cj;
+        const double n_j = (double)(on_j + 1), n_i = (double)nn - n_j;
+        t1 = rev - gs_split;
+        t2 = (log(alpha) - lgamma((double)nn)) + lgamma(n_j);        // :702-706
+        t2 += lgamma(n_i);
+        if (!d.uniform) t2 += pa - pb;
+        const double ll0 = sm_ll_of_row(d, b, 0, shd), ll1 = sm_ll_of_row(d, b, 1, shd), ll2 = sm_ll_of_row(d, b, 2, shd);
+        t3 = ll0 + ll1 - ll2;
+        const double norm = inv + 1.0 / n_i + 1.0 / n_j;             // :762-764
+        t4 = log(1.0 / n_i / norm) + log(1.0 / n_j / norm) - size_data;
+    } else {
+        // _do_rg_merge_MH (:656-665), _get_trans_prob_ratio_merge (:685-692), _rg_get_split_prob (:777-820)
+        sm_move_rows(d, b, key, step, scans, 2, 3, sums, shd);
+        const double gs_merge = sums[2];
+        double par = 0.0, pa = 0.0, pb = 0.0, cj = 0.0;
+        for (int e = t; e < 2 * M; e += 256) {
+            const int r = e / M, m = e - r * M;
+            const float orig = r == 0 ? th_i[m] : th_j[m];
+            par += sm_log_A(d, orig, b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | ((uint32_t)r << 8), 0), true);
+            if (!d.uniform) pb += beta_logpdf(d, orig);
+        }
+        if (!d.uniform) for (int m = t; m < M; m += 256) pa += beta_logpdf(d, b.th[2 * M + m]);
+        par = block_sum(par, shd); pa = block_sum(pa, shd); pb = block_sum(pb, shd);
+        double prob_assign = 0.0;
+        if (nS > 0) {
+            const double* L1 = d.L1 + (size_t)c * N * M; const double* L0 = d.L0 + (size_t)c * N * M;
+            prob_assign = sm_scan(d, b, c, key, step, scans, nS, alpha, L1 + (size_t)cli * M, L0 + (size_t)cli * M, L1 + (size_t)clj * M, L0 + (size_t)clj * M, clj, tile, &s_dbl[1]);
+            sm_count(d, b, nS, ai, aj);                              // the assignment is the original one by now (:817)
+        }
+        for (int s = t; s < nS; s += 256) cj += b.asg[s];
+        cj = block_sum(cj, shd);
+        on_j = (int)cj;
+        const double n_j = (double)(on_j + 1), n_i = (double)nn - n_j;
+        t1 = (par + prob_assign) - gs_merge;
+        t2 = -(log(alpha) - lgamma((double)nn)) - lgamma(n_j);       // :743-747
+        t2 -= lgamma(n_i);
+        if (!d.uniform) t2 += pa - pb;
+        const double ll0 = sm_ll_of_row(d, b, 0, shd), ll1 = sm_ll_of_row(d, b, 1, shd), ll2 = sm_ll_of_row(d, b, 2, shd);
+        t3 = ll2 - ll0 - ll1;
+        // log(|S| - 1) raises for |S| of 0 or 1 under the reference's np.seterr, and the term falls back (:769-773)
+        t4 = (nS > 1 ? -log((double)N) - log((double)(nS - 1)) : -log((double)N)) - size_data;
+    }
+    const double A = ((t1 + t2) + t3) + t4;
+    double v, v_unused;
+    doubles(key, 0, step, P_SM, 3, v, v_unused);
+    const bool refused = split && nS > 0 && (on_j == 0 || on_j == nS);   // np.unique(rg_assignment).size == 1 (:647)
+    const bool accept = !refused && log(v) < A;
+    const int code = split ? (accept ? 2 : 1) : (accept ? 4 : 3);
+    if (accept) {
+        if (split) {
+            for (int m = t; m < M; m += 256) { d.theta[((size_t)c * N + cli) * M + m] = b.th[m]; d.theta[((size_t)c * N + clj) * M + m] = b.th[M + m]; }
+            for (int s = t; s < nS; s += 256) if (b.asg[s]) lab[b.S[s]] = clj;
+            if (t == 0) { lab[aj] = clj; size[clj] = on_j + 1; size[cli] -= on_j + 1; }
+        } else {
+            for (int m = t; m < M; m += 256) d.theta[((size_t)c * N + cli) * M + m] = b.th[2 * M + m];
+            for (int s = t; s < nS; s += 256) if (b.asg[s]) lab[b.S[s]] = cli;
+            if (t == 0) { lab[aj] = cli; size[cli] += size[clj]; size[clj] = 0; }
+        }
+    }
+    if (t == 0) {
+        b.out[0] = (double)code; b.out[1] = (double)cli; b.out[2] = (double)clj; b.out[3] = (double)ai; b.out[4] = (double)aj; b.out[5] = A;
+        b.out[6] = t1; b.out[7] = t2; b.out[8] = t3; b.out[9] = t4; b.out[10] = log(v); b.out[11] = (double)nS;
+        if ((int)step < d.steps1) d.rec_sm[(size_t)c * d.steps1 + step] = code;
+    }
+    __syncthreads();
+    alpha_update(d, c, step, size, alpha, shd);
 }
 
 // ---- record (Chain.update_results, MCMC.py:242-282): ML, the two prior sums, the labels, and after burn-in the live clusters' parameters
@@ -453,6 +873,9 @@ static SDev dev_of(const Bnpcs& b) {
     d.L1 = b.L1.as<double>(); d.L0 = b.L0.as<double>(); d.LL = b.LL.as<double>(); d.alpha = b.alpha.as<double>(); d.prow = b.prow.as<double>();
     d.rowml = b.rowml.as<double>(); d.rowb = b.rowb.as<double>(); d.rec_sc = b.rec_sc.as<double>();
     d.n1 = b.n1.as<uint32_t>(); d.n0 = b.n0.as<uint32_t>(); d.keys = b.keys.as<uint64_t>();
+    d.sm_prob = b.sm_prob; d.sm_edge = b.sm_ratio[0] / (b.sm_ratio[0] + b.sm_ratio[1]); d.sm_scans = b.sm_scans;
+    std::copy(b.sm_anchor, b.sm_anchor + 6, d.sm_anchor);
+    d.sm_i = b.sm_i.as<int32_t>(); d.rec_sm = b.rec_sm.as<int32_t>(); d.sm_d = b.sm_d.as<double>(); d.sm_c = b.sm_c.as<uint32_t>(); d.sm_t = b.sm_t.as<float>();
     return d;
 }
 
@@ -494,7 +917,8 @@ static int prepare(lsg_ctx* c, const char* who) {
     return 0;
 }
 
-static int launch_sweep(lsg_ctx* c, uint32_t step) {
+// decide: each chain draws whether this step is a sweep or a split-merge move; else every chain sweeps
+static int launch_sweep(lsg_ctx* c, uint32_t step, int decide) {
     Bnpcs& b = c->bnpcs;
     b.ll_pitch = std::max(b.k_max, 1);
     if (b.LL.reserve((size_t)b.n_chains * b.n_cells * b.ll_pitch * 8)) return -1;
@@ -502,7 +926,14 @@ static int launch_sweep(lsg_ctx* c, uint32_t step) {
     hipLaunchKernelGGL(k_bnpcs_ll, dim3((b.ll_pitch + LT - 1) / LT, (b.n_cells + LT - 1) / LT, b.n_chains), dim3(256), 0, c->stream, d);
     hipLaunchKernelGGL(k_bnpcs_keys, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, d, step);
     hipLaunchKernelGGL(k_bnpcs_perm, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, d);
-    hipLaunchKernelGGL(k_bnpcs_scan, dim3(b.n_chains), dim3(256), 0, c->stream, d, step);
+    hipLaunchKernelGGL(k_bnpcs_scan, dim3(b.n_chains), dim3(256), 0, c->stream, d, step, decide);
+    return 0;
+}
+
+// the split-merge move of the chains whose step is one (force: of every chain)
+static int launch_sm(lsg_ctx* c, uint32_t step, int force) {
+    Bnpcs& b = c->bnpcs;
+    hipLaunchKernelGGL(k_bnpcs_sm, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), step, force);
     return 0;
 }
 
@@ -533,7 +964,9 @@ int lsg_bnpcs_create(lsg_ctx* c, int32_t n_cells, int32_t n_muts, int32_t n_chai
         b.colof.reserve(C * N * 4) || b.live.reserve(C * N * 4) || b.nlive.reserve(C * 4) || b.hi.reserve(C * 4) || b.theta.reserve(C * N * M * 4) || b.L1.reserve(C * N * M * 8) ||
         b.L0.reserve(C * N * M * 8) || b.alpha.reserve(C * 8) || b.prow.reserve(C * (N + 1) * 8) || b.n1.reserve(C * N * M * 4) || b.n0.reserve(C * N * M * 4) ||
         b.rowml.reserve(C * N * 8) || b.rowb.reserve(C * N * 8) || b.order.reserve(C * N * 4) || b.keys.reserve(C * N * 8) || b.rec_lab.reserve(C * S1 * N * 4) ||
-        b.rec_sc.reserve(C * S1 * REC * 8) || b.arena.reserve(C * (size_t)arena_rows * M * 4) || b.err.reserve(C * 4 + 8 * C + 8)) return -1;
+        b.rec_sc.reserve(C * S1 * REC * 8) || b.arena.reserve(C * (size_t)arena_rows * M * 4) || b.err.reserve(C * 4 + 8 * C + 8) ||
+        b.sm_i.reserve(C * 5 * N * 4) || b.sm_d.reserve(C * (6 * N + 6 * M + SM_OUT) * 8) || b.sm_c.reserve(C * 6 * M * 4) || b.sm_t.reserve(C * 3 * M * 4) ||
+        b.rec_sm.reserve(C * S1 * 4)) return -1;
     std::vector<int32_t> pop(2 * N);
     const uint64_t tail = M % 64 ? ((1ull << (M % 64)) - 1) : ~0ull;
     for (size_t i = 0; i < N; ++i) {
@@ -557,10 +990,21 @@ int lsg_bnpcs_create(lsg_ctx* c, int32_t n_cells, int32_t n_muts, int32_t n_chai
     LSG_HIP(hipMemsetAsync(b.err.p, 0, C * 4 + 8 * C, st));
     LSG_HIP(hipMemsetAsync(b.rec_lab.p, 0, C * S1 * N * 4, st));
     LSG_HIP(hipMemsetAsync(b.rec_sc.p, 0, C * S1 * REC * 8, st));
+    LSG_HIP(hipMemsetAsync(b.rec_sm.p, 0, C * S1 * 4, st));
+    LSG_HIP(hipMemsetAsync(b.sm_d.p, 0, C * (6 * N + 6 * M + SM_OUT) * 8, st));
     LSG_HIP(hipStreamSynchronize(st));
     b.n_cells = n_cells; b.n_muts = n_muts; b.n_words = (int32_t)W; b.n_chains = n_chains; b.steps1 = (int32_t)S1; b.arena_rows = arena_rows;
     b.k_max = 0; b.ll_pitch = 1; b.pending = -1; b.next_step = 0;
     std::copy(cfg, cfg + 10, b.cfg);
+    b.sm_prob = 0.0; b.sm_ratio[0] = 0.75; b.sm_ratio[1] = 0.25; b.sm_scans = 3;
+    {
+        // _beta_mix_const[0] (CRP.py:42-44) and the six values a likelihood term takes under an anchor's data as parameters (:557-560)
+        const double p = cfg[2], q = cfg[3], FN = cfg[0], FP = cfg[1];
+        const double m0 = std::tgamma(p) * std::tgamma(q + 1) / std::tgamma(p + q + 1), m1 = std::tgamma(p + 1) * std::tgamma(q) / std::tgamma(p + q + 1);
+        const double mix0 = m0 / (m0 + m1);
+        const double v[6] = {1 - FN, FN, FP, 1 - FP, mix0 * (1 - FN) + (1 - mix0) * FP, mix0 * FN + (1 - mix0) * (1 - FP)};
+        for (int k = 0; k < 6; ++k) b.sm_anchor[k] = std::log(v[k]);
+    }
     b.h_k.assign(C, 0); b.h_used.assign(C, 0);
     b.valid = true;
     return 0;
@@ -620,7 +1064,8 @@ int lsg_bnpcs_run(lsg_ctx* c, int32_t first_step, int32_t n_steps, int32_t burn_
     int64_t* d_used = reinterpret_cast<int64_t*>(b.err.as<int32_t>() + b.n_chains + (b.n_chains & 1));
     for (int32_t s = first_step; s < first_step + n_steps; ++s) {
         if (s > 0 && b.pending != s) {
-            if (int rc = launch_sweep(c, (uint32_t)s)) return rc;
+            if (int rc = launch_sweep(c, (uint32_t)s, b.sm_prob > 0)) return rc;
+            if (b.sm_prob > 0) if (int rc = launch_sm(c, (uint32_t)s, 0)) return rc;
             if (fetch_live(c, who)) return -1;
             if (int rc = launch_counts_tables(c)) return rc;
             if (int rc = launch_mh(c, (uint32_t)s)) return rc;
@@ -658,6 +1103,31 @@ int lsg_bnpcs_fetch(lsg_ctx* c, int32_t* labels, double* scalars, float* arena, 
     LSG_HIP(hipMemcpyAsync(errors, b.err.p, C * 4, hipMemcpyDeviceToHost, st));
     if (sync_check(c, who)) return -1;
     for (size_t k = 0; k < C; ++k) { arena_used[k] = b.h_used[k]; b.h_used[k] = 0; }
+    return 0;
+}
+
+int lsg_bnpcs_set_split_merge(lsg_ctx* c, double prob, double ratio_split, double ratio_merge, int32_t scans) {
+    const char* who = "lsg_bnpcs_set_split_merge";
+    if (int rc = need(c, who)) return rc;
+    if (!(prob >= 0 && prob <= 1) || !(ratio_split > 0) || !(ratio_merge > 0) || !(std::fabs(ratio_split + ratio_merge - 1) <= 1e-9) || scans < 0 || scans > SM_MAX_SCANS) {
+        set_error("%s: the probability must lie in [0, 1], the ratios be positive and sum to 1 and the scans be in [0, %d], got %g, %g, %g and %d", who, SM_MAX_SCANS, prob,
+                  ratio_split, ratio_merge, scans);
+        return -2;
+    }
+    Bnpcs& b = c->bnpcs;
+    b.sm_prob = prob; b.sm_ratio[0] = ratio_split; b.sm_ratio[1] = ratio_merge; b.sm_scans = scans;
+    return 0;
+}
+
+int lsg_bnpcs_fetch_moves(lsg_ctx* c, int8_t* moves) {
+    const char* who = "lsg_bnpcs_fetch_moves";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (!moves) { set_error("%s: bad arguments", who); return -2; }
+    std::vector<int32_t> codes((size_t)b.n_chains * b.steps1);
+    LSG_HIP(hipMemcpyAsync(codes.data(), b.rec_sm.p, codes.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    if (sync_check(c, who)) return -1;
+    for (size_t k = 0; k < codes.size(); ++k) moves[k] = (int8_t)codes[k];
     return 0;
 }
 
@@ -734,15 +1204,26 @@ int lsg_bnpcs_test_move(lsg_ctx* c, int32_t what, int32_t step) {
     const char* who = "lsg_bnpcs_test_move";
     if (int rc = need(c, who)) return rc;
     Bnpcs& b = c->bnpcs;
-    if (what < 0 || what > 1 || step < 0) { set_error("%s: bad arguments", who); return -2; }
+    if (what < 0 || what > 2 || step < 0) { set_error("%s: bad arguments", who); return -2; }
     if (int rc = prepare(c, who)) return rc;
-    if (what == 0) {
-        if (int rc = launch_sweep(c, (uint32_t)step)) return rc;
+    if (what == 0 || what == 2) {
+        if (what == 0) { if (int rc = launch_sweep(c, (uint32_t)step, 0)) return rc; }
+        else if (int rc = launch_sm(c, (uint32_t)step, 1)) return rc;
         if (fetch_live(c, who)) return -1;
         if (int rc = launch_counts_tables(c)) return rc;
     } else {
         if (int rc = launch_mh(c, (uint32_t)step)) return rc;
         hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, dev_of(b));
     }
+    return sync_check(c, who);
+}
+
+int lsg_bnpcs_test_move_outcome(lsg_ctx* c, int32_t chain, double* outcome) {
+    const char* who = "lsg_bnpcs_test_move_outcome";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (chain < 0 || chain >= b.n_chains || !outcome) { set_error("%s: bad arguments", who); return -2; }
+    const size_t per = 6 * (size_t)b.n_cells + 6 * (size_t)b.n_muts + SM_OUT;
+    LSG_HIP(hipMemcpyAsync(outcome, b.sm_d.as<double>() + (chain + 1) * per - SM_OUT, SM_OUT * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_check(c, who);
 }

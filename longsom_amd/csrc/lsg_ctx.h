@@ -86,6 +86,9 @@ struct Bnpc {
 // sizes, theta, the log tables, the likelihood matrix of the sweep, the counts, and the record buffers
 struct Bnpcs {
     DevBuf one, zero, pop, seeds, lab, size, colof, live, nlive, hi, theta, L1, L0, LL, alpha, prow, n1, n0, rowml, rowb, order, keys, rec_lab, rec_sc, arena, err;
+    DevBuf sm_i, sm_d, sm_c, sm_t, rec_sm;                          // the split-merge move's scratch and its record (SDev in bnpc_sampler.hip)
+    double sm_prob = 0.0, sm_ratio[2] = {0.75, 0.25}, sm_anchor[6] = {};
+    int32_t sm_scans = 3;
     int32_t n_cells = 0, n_muts = 0, n_words = 0, n_chains = 0, steps1 = 0, k_max = 0, ll_pitch = 0, pending = -1, next_step = 0;
     int64_t arena_rows = 0;
     double cfg[10] = {};
@@ -94,7 +97,7 @@ struct Bnpcs {
     std::vector<int64_t> h_used;          // arena rows in use per chain
     void release() {
         for (DevBuf* b : {&one, &zero, &pop, &seeds, &lab, &size, &colof, &live, &nlive, &hi, &theta, &L1, &L0, &LL, &alpha, &prow, &n1, &n0, &rowml, &rowb, &order, &keys, &rec_lab, &rec_sc,
-                          &arena, &err}) b->release();
+                          &arena, &err, &sm_i, &sm_d, &sm_c, &sm_t, &rec_sm}) b->release();
         valid = prepared = false;
     }
 };

@@ -730,6 +730,17 @@ class Engine:
         _lib.check(self._lib.lsg_bnpcs_fetch(self._h, _ptr(labels), _ptr(scalars), _ptr(arena), _ptr(used), _ptr(self._bnpcs_errors)), "lsg_bnpcs_fetch")
         return labels, scalars, arena
 
+    def bnpcs_set_split_merge(self, prob: float, ratio_split: float, ratio_merge: float, scans: int) -> None:
+        """every chain takes the split-merge move with this probability per step (lsg_bnpcs_set_split_merge); after bnpcs_create"""
+        _lib.check(self._lib.lsg_bnpcs_set_split_merge(self._h, float(prob), float(ratio_split), float(ratio_merge), int(scans)), "lsg_bnpcs_set_split_merge")
+
+    def bnpcs_fetch_moves(self) -> np.ndarray:
+        """[C, steps + 1] int8: 0 a sweep, 1 / 2 a split declined / accepted, 3 / 4 a merge declined / accepted (lsg_bnpcs_fetch_moves)"""
+        Cn, S1, _, _, _ = self._bnpcs_shape
+        moves = np.zeros((Cn, S1), np.int8)
+        _lib.check(self._lib.lsg_bnpcs_fetch_moves(self._h, _ptr(moves)), "lsg_bnpcs_fetch_moves")
+        return moves
+
     def bnpcs_errors(self) -> np.ndarray:
         """per chain, the gamma variates that ran out of tries, as of the last bnpcs_fetch"""
         return self._bnpcs_errors
@@ -764,6 +775,13 @@ class Engine:
 
     def bnpcs_test_move(self, what: int, step: int) -> None:
         _lib.check(self._lib.lsg_bnpcs_test_move(self._h, int(what), int(step)), "lsg_bnpcs_test_move")
+
+    def bnpcs_test_move_outcome(self, chain: int) -> dict:
+        """a chain's last split-merge move (what = 2): code, clusters, anchors, A, terms [4], lv, n_S (lsg_bnpcs_test_move_outcome)"""
+        o = np.zeros(12, np.float64)
+        _lib.check(self._lib.lsg_bnpcs_test_move_outcome(self._h, int(chain), _ptr(o)), "lsg_bnpcs_test_move_outcome")
+        return {"code": int(o[0]), "clusters": (int(o[1]), int(o[2])), "anchors": (int(o[3]), int(o[4])), "A": float(o[5]), "terms": o[6:10].copy(), "lv": float(o[10]),
+                "n_S": int(o[11])}
 
     def betabinom_sf4(self, k, n, alpha: float, beta: float) -> np.ndarray:
         """round(betabinom.sf(k - 0.001, n, alpha, beta), 4) * 1e4 as int32, evaluated on the device."""

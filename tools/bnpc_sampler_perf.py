@@ -3,7 +3,9 @@
 own calls, so that the first steps and the late steps can be timed apart).
 
   device      seconds per step over the first 10 steps from the random start, and over 100 steps after step 200
-  --reference DIR   also time the reference's sampler (libs/CRP.py, libs/MCMC.py of the LongSom checkout DIR, with sm_prob = 0) at the same
+  --sm_prob P --sm_steps S   with the split-merge move in a share P of the steps, S restricted scans each (run_BnpC.py's -smp, -sms; the
+              ratios stay 0.75 / 0.25); the result then counts the moves of each kind over all chains and steps
+  --reference DIR   also time the reference's sampler (libs/CRP.py, libs/MCMC.py of the LongSom checkout DIR, with the same --sm_prob) at the same
               shape on this host, one process per chain: its first 10 steps from its random start, and 10 steps from the planted partition
               (the state a chain is in after a few hundred steps), per step
 Prints one JSON line.  For a per-kernel split run it under `rocprofv3 --kernel-trace --stats -- python tools/bnpc_sampler_perf.py --late_only`.
@@ -33,7 +35,7 @@ def planted(N, M, K, seed=1):
     return data, truth
 
 
-def device(data, chains, late_only):
+def device(data, chains, late_only, sm_prob=0.0, sm_steps=3):
     from longsom_amd import bnpc_sampler as bs
     from longsom_amd.engine import Engine
     model = bs.Model(data, 0.1, 0.01)
@@ -42,6 +44,8 @@ def device(data, chains, late_only):
     out = {}
     with Engine(0) as e:
         e.bnpcs_create(model, seeds, steps, 1 << 15)
+        if sm_prob > 0:
+            e.bnpcs_set_split_merge(sm_prob, 0.75, 0.25, sm_steps)
         for c, s in enumerate(seeds):
             st = bs.initial_state(model, s)
             e.bnpcs_set_state(c, st.labels, st.theta, st.alpha)
@@ -59,12 +63,16 @@ def device(data, chains, late_only):
         out["late100_s_per_step"] = (time.perf_counter() - t) / 100
         _, scalars, _ = e.bnpcs_fetch()
         out["clusters_at_10_200_300"] = [float(np.mean(scalars[:, s, 3])) for s in (10, 200, 300)]
+        if sm_prob > 0:
+            seen = np.bincount(e.bnpcs_fetch_moves().ravel(), minlength=5)
+            out["moves"] = {"sweeps": int(seen[0]) - chains, "splits_declined": int(seen[1]), "splits_accepted": int(seen[2]), "merges_declined": int(seen[3]),
+                            "merges_accepted": int(seen[4])}
         e.bnpcs_destroy()
     return out
 
 
 def _reference_chain(args):
-    ref, data, seed, assign = args
+    ref, data, seed, assign, sm_prob, sm_steps = args
     from make_bnpc_estimate_goldens import stand_ins
     stand_ins()
     sys.path.insert(0, os.path.join(ref, "workflow", "scripts", "CellClustering"))
@@ -73,20 +81,20 @@ def _reference_chain(args):
     np.random.seed(seed)
     model = CRP.CRP(data, DP_alpha=[-1, -1], param_beta=[1, 1], FN_error=0.1, FP_error=0.01)
     model.init(assign=assign)
-    mcmc = MCMC(model, sm_prob=0, dpa_prob=0.5, error_prob=0)
+    mcmc = MCMC(model, sm_prob=sm_prob, dpa_prob=0.5, error_prob=0, sm_ratios=[0.75, 0.25], sm_steps=sm_steps)
     chain = Chain_steps(model, 1, 10, 5, mcmc.params, 0, False)
     t = time.perf_counter()
     chain.run()
     return (time.perf_counter() - t) / 10
 
 
-def reference(ref, data, truth, chains):
+def reference(ref, data, truth, chains, sm_prob=0.0, sm_steps=3):
     import multiprocessing as mp
     out = {}
     with mp.Pool(chains) as pool:
         for name, assign in (("first10_s_per_step", None), ("planted10_s_per_step", [int(x) for x in truth])):
             t = time.perf_counter()
-            per = pool.map(_reference_chain, [(ref, data, s, assign) for s in range(1, chains + 1)])
+            per = pool.map(_reference_chain, [(ref, data, s, assign, sm_prob, sm_steps) for s in range(1, chains + 1)])
             out[name] = (time.perf_counter() - t) / 10                # the chains run side by side: wall time per step of the run
             out[name + "_one_chain"] = float(np.mean(per))
     return out
@@ -97,14 +105,16 @@ def main():
     ap.add_argument("--cells", type=int, default=2000); ap.add_argument("--muts", type=int, default=200); ap.add_argument("--clusters", type=int, default=10)
     ap.add_argument("--chains", type=int, default=16)
     ap.add_argument("--reference", default="", help="root of a LongSom checkout: time its sampler too")
+    ap.add_argument("--sm_prob", type=float, default=0.0); ap.add_argument("--sm_steps", type=int, default=3)
     ap.add_argument("--no_device", action="store_true"); ap.add_argument("--late_only", action="store_true", help="50 steps only: what a profiler should see")
     a = ap.parse_args()
     data, truth = planted(a.cells, a.muts, a.clusters)
     out = {"cells": a.cells, "muts": a.muts, "clusters": a.clusters, "chains": a.chains, "cpus": os.cpu_count()}
     if not a.no_device:
-        out["device"] = device(data, a.chains, a.late_only)
+        out["sm_prob"], out["sm_steps"] = a.sm_prob, a.sm_steps
+        out["device"] = device(data, a.chains, a.late_only, a.sm_prob, a.sm_steps)
     if a.reference:
-        out["reference"] = reference(a.reference, data, truth, a.chains)
+        out["reference"] = reference(a.reference, data, truth, a.chains, a.sm_prob, a.sm_steps)
     print(json.dumps(out))
 
 

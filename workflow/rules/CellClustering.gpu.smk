@@ -6,8 +6,10 @@
 # Binary and VAF matrices into BnpC's input; with Run.fuse_bnpc_input: True rule SingleCellGenotype writes that input in its own process,
 # from the cells while they are resident, and FormatInputBnpC has nothing left to do (the rule order below gives the files to the fused
 # rule).  BnpC_clustering reads BnpC_input/: its sampler is the vendored BnpC's of this checkout (scripts/CellClustering/libs), run as the
-# reference runs it; the posterior estimate over the chains' samples runs on the GPU.  With CellClust.BnpC.sampler: device the sampler
-# runs on the GPU too (all chains at once; Gibbs sweeps, the concentration update and the parameter moves, no split-merge move: -smp 0).
+# reference runs it; the posterior estimate over the chains' samples runs on the GPU.  With CellClust.BnpC.sampler: device-sm the sampler
+# runs on the GPU too, all chains at once, with the reference's own settings: Gibbs sweeps, the split-merge move in a third of the steps
+# (--sampler device-sm, no -smp passed, so run_BnpC.py's defaults -smp 0.33 -sms 3 -smr 0.75 0.25 apply as in the reference's rule), the
+# parameter moves, fixed error rates.  CellClust.BnpC.sampler: device is the same without the split-merge move (--sampler device -smp 0).
 
 GPU_SCRIPTS = str(workflow.basedir) + "/scripts_gpu"
 FUSE_BNPC = config['Run'].get('fuse_bnpc_input', False)
@@ -122,7 +124,7 @@ rule BnpC_clustering:
         FP = config['CellClust']['BnpC']['FP'],
         FN = config['CellClust']['BnpC']['FN'],
         pp= config['CellClust']['BnpC']['pp'],
-        sampler="--sampler device -smp 0" if config['CellClust']['BnpC'].get('sampler', 'reference') == 'device' else "",
+        sampler={'device': "--sampler device -smp 0", 'device-sm': "--sampler device-sm"}.get(config['CellClust']['BnpC'].get('sampler', 'reference'), ""),
     conda:
         "../envs/BnpC.yaml"
     threads: 16
