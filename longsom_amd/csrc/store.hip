@@ -243,19 +243,45 @@ constexpr int BIN_SUPER = 16;          // batches per dequeue
 constexpr int BIN_MAXI = 32;           // items per chunk
 constexpr uint32_t BIN_FILL = BIN_H * 5 / 8;
 
+// a wave's sum / maximum in its LAST lane, by data-parallel primitives (six dependent lane shuffles through the LDS crossbar cost an
+// item of the scatter as much as its hash operations)
+template <class OP>
+__device__ __forceinline__ uint32_t wave_reduce_last(uint32_t v, OP op) {
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));      // row_shr:1
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));      // row_shr:2
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));      // row_shr:4
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));      // row_shr:8: lane 15 of every row holds the row's
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));     // row_bcast:15 into rows 1 and 3
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));     // row_bcast:31 into rows 2 and 3
+    return v;
+}
 struct BinSeg { uint32_t key, tb, t0, rd; int32_t st, ln, ntile; int64_t evoff, b1; };      // ntile: ENTRIES of the segment = tiles it touches + window edges that cut it inside a tile; b1: the first window edge after its start
 
-__device__ __forceinline__ BinSeg bin_load(const BuildArgs& a, int64_t s) {
-    BinSeg g; g.key = KEY_INVALID; g.tb = 0; g.t0 = 0; g.rd = 0; g.b1 = 0; g.st = 0; g.ln = 0; g.ntile = 0; g.evoff = 0;
-    // (all five loads at once, whatever the segment's admission says: a segment past the end reads the last one)
+// What a segment's five arrays hold, as loaded.  The scatter waits for memory, not for bandwidth (71 % of its wave-cycles in a wait,
+// 2.4 TB/s), so the loads (bin_fetch) are issued ONE ITEM AHEAD of the arithmetic that uses them (bin_make): the next batch's lines
+// travel while this batch's entries go through the hash.
+struct BinRaw { uint2 info; int32_t st, ln; int64_t evoff; uint32_t rd; };
+// (all five loads at once, whatever the segment's admission says and with no branch around any of them: a segment past the end reads
+// the last one, and bin_make does not look at it)
+__device__ __forceinline__ BinRaw bin_fetch(const BuildArgs& a, int64_t s) {
     const int64_t si = s < a.n_segs ? s : a.n_segs - 1;
-    const uint2 info = a.seg_info[si];
-    const int64_t st = a.seg_start[si], ln = a.seg_len[si], evoff = a.seg_ev_off[si];
-    const uint32_t rd = a.seg_read[si];
+    BinRaw w;
+    w.info = a.seg_info[si]; w.st = a.seg_start[si]; w.ln = a.seg_len[si]; w.evoff = a.seg_ev_off[si]; w.rd = a.seg_read[si];
+    return w;
+}
+// (FULL: pass B, which writes the entries, needs all five; pass A counts them from three, and the compiler drops the other two loads.
+// What is needed is asked for HERE, admitted segment or not: left to their first use inside a branch, the waits for these loads would
+// stand on one path only and come back, stricter, at the top of the item loops - behind the stores they are meant to overtake.)
+template <bool FULL>
+__device__ __forceinline__ BinSeg bin_make(const BuildArgs& a, int64_t s, const BinRaw& w) {
+    BinSeg g; g.key = KEY_INVALID; g.tb = 0; g.t0 = 0; g.rd = 0; g.b1 = 0; g.st = 0; g.ln = 0; g.ntile = 0; g.evoff = 0;
+    if (FULL) asm volatile("" :: "v"(w.info.x), "v"(w.info.y), "v"(w.st), "v"(w.ln), "v"(w.evoff), "v"(w.rd));
+    else asm volatile("" :: "v"(w.info.x), "v"(w.info.y), "v"(w.st), "v"(w.ln));
+    const uint2 info = w.info;
     const int bs = 6 + a.wsh;                            // positions per bin: 1 << bs (a contig's first tile is even: its bins are its positions >> bs)
     if (s < a.n_segs && info.x != KEY_INVALID) {
         g.key = info.x; g.tb = info.y >> a.wsh;
-        g.st = (int32_t)st; g.ln = (int32_t)ln; g.evoff = evoff; g.rd = rd;
+        g.st = w.st; g.ln = w.ln; g.evoff = w.evoff; g.rd = w.rd;
         g.t0 = g.tb + ((uint32_t)g.st >> bs);
         g.ntile = (int)(((uint32_t)(g.st + g.ln - 1) >> bs) - ((uint32_t)g.st >> bs)) + 1;
         g.b1 = win_edge_after(g.st, a.window);
@@ -303,11 +329,13 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(BuildArgs a) {
         // every workgroup's first item is its own index: no storm of same-address atomics at launch
         if (t == 0) s_super = first ? blockIdx.x : (uint32_t)atomicAdd(a.qhead, 1ull) + gridDim.x;
         __syncthreads();
-        const int64_t sup = s_super;
+        // (what every thread reads from the same LDS word goes through readfirstlane: the item loops then branch on scalars)
+        const int64_t sup = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_super);
         if (sup >= n_super) break;
         const int64_t b0 = sup * BIN_SUPER;
         const int64_t b1 = b0 + BIN_SUPER < n_batches ? b0 + BIN_SUPER : n_batches;
         int64_t cb = b0; int cr = 0;                 // next item: round cr of batch cb
+        BinRaw nx = bin_fetch(a, cb * BIN_THREADS + t);      // always the loads of the batch that is made next, issued an item before
         while (cb < b1) {
             // ---- pass A: accumulate items in the hash
             if (t < BIN_MAXI) { s_newb[t] = 0; s_maxb[t] = 0; }
@@ -316,37 +344,52 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(BuildArgs a) {
             int64_t b = cb; int r = cr;
             bool stop = false;
             while (!stop && b < b1) {
-                const BinSeg g = bin_load(a, b * BIN_THREADS + t);
+                const BinSeg g = bin_make<false>(a, b * BIN_THREADS + t, nx);
+                // batch b + 1 travels during batch b's hash work (the super's last batch: its own lines again, nobody looks at them; a
+                // batch past n_segs: the clamped index).  If the chunk stops before it, it is fetched again where the next chunk starts.
+                nx = bin_fetch(a, (b + 1 < b1 ? b + 1 : b) * BIN_THREADS + t);
                 const int ni_first = ni;
-                int wmax = g.ntile;
-                for (int o = 32; o > 0; o >>= 1) { int v = __shfl_down(wmax, o); wmax = v > wmax ? v : wmax; }
-                if (lane == 0 && wmax) atomicMax(&s_maxb[ni_first], wmax);
+                const int wmax = (int)wave_reduce_last((uint32_t)g.ntile, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
+                if (lane == 63 && wmax) atomicMax(&s_maxb[ni_first], wmax);
                 int R = -1;
                 for (;;) {
                     uint32_t newc = 0;
+                    // the thread's (up to) eight entries of the item side by side, not one dependent compare-and-swap -> add chain after
+                    // the other: their tiles and slots first, then every first probe, and only then a look at what came back
+                    uint32_t x[BIN_TPR], h[BIN_TPR], prev[BIN_TPR];        // (x = KEY_INVALID: no such entry; never a tile)
 #pragma unroll
                     for (int j = 0; j < BIN_TPR; ++j) {
                         const int k = r * BIN_TPR + j;
+                        x[j] = KEY_INVALID; h[j] = 0; prev[j] = 0;
                         if (k < g.ntile) {
                             uint32_t trel; int32_t lo_, hi_;
                             bin_piece(g, a.window, 6 + a.wsh, k, trel, lo_, hi_);
-                            const uint32_t x = g.t0 + trel;
-                            uint32_t h = (x * 2654435761u) >> HSHIFT;
-                            while (true) {
-                                uint32_t prev = atomicCAS(&hkey[h], KEY_INVALID, x);
-                                if (prev == KEY_INVALID) { ++newc; break; }
-                                if (prev == x) break;
-                                h = (h + 1) & (BIN_H - 1);
-                            }
-                            atomicAdd(&hcnt[h], 1u);
+                            x[j] = g.t0 + trel;
+                            h[j] = (x[j] * 2654435761u) >> HSHIFT;
                         }
                     }
-                    for (int o = 32; o > 0; o >>= 1) newc += __shfl_down(newc, o);
-                    if (lane == 0 && newc) atomicAdd(&s_newb[ni], newc);
+#pragma unroll
+                    for (int j = 0; j < BIN_TPR; ++j)
+                        if (x[j] != KEY_INVALID) prev[j] = atomicCAS(&hkey[h[j]], KEY_INVALID, x[j]);
+#pragma unroll
+                    for (int j = 0; j < BIN_TPR; ++j)
+                        if (x[j] != KEY_INVALID) {
+                            uint32_t hh = h[j], p = prev[j];
+                            if (p == KEY_INVALID) ++newc;
+                            else
+                                while (p != x[j]) {                   // a collision: on along the probe sequence as before
+                                    hh = (hh + 1) & (BIN_H - 1);
+                                    p = atomicCAS(&hkey[hh], KEY_INVALID, x[j]);
+                                    if (p == KEY_INVALID) { ++newc; break; }
+                                }
+                            atomicAdd(&hcnt[hh], 1u);
+                        }
+                    newc = wave_reduce_last(newc, [](uint32_t x, uint32_t y) { return x + y; });
+                    if (lane == 63 && newc) atomicAdd(&s_newb[ni], newc);
                     if (t == 0) { s_ib[ni] = (uint32_t)(b - b0); s_ir[ni] = (uint32_t)r; }
                     __syncthreads();
-                    if (R < 0) R = (s_maxb[ni_first] + BIN_TPR - 1) / BIN_TPR;
-                    tot += s_newb[ni];
+                    if (R < 0) R = __builtin_amdgcn_readfirstlane((s_maxb[ni_first] + BIN_TPR - 1) / BIN_TPR);
+                    tot += (uint32_t)__builtin_amdgcn_readfirstlane((int)s_newb[ni]);
                     ++ni; ++r;
                     if (r >= R) { ++b; r = 0; }
                     if (ni >= BIN_MAXI || tot + BIN_THREADS * BIN_TPR > BIN_FILL) { stop = true; break; }
@@ -354,27 +397,56 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(BuildArgs a) {
                 }
             }
             // ---- one global atomic per distinct tile of the chunk
+            nx = bin_fetch(a, cb * BIN_THREADS + t);                       // pass B's first item, beside the claims
             for (int i = t; i < BIN_H; i += BIN_THREADS) {
                 const uint32_t cnt = hcnt[i];
                 if (cnt) hcnt[i] = atomicAdd(&a.cursor[hkey[i]], cnt);       // first place of this workgroup's range in the tile's region
             }
             __syncthreads();
             {
-                // ---- pass B: replay the items, write the entries
+                // ---- pass B: replay the items, write the entries.  The chunk's items are the rounds of CONSECUTIVE batches; rounds of one
+                // batch keep its registers.  The next batch's loads were issued an item ago; they are turned into its registers
+                // (bin_make) and the loads of the batch after it are issued BEFORE this item's stores go out: loads and stores share one
+                // counter, so a wait for loads issued behind stores is a wait for those stores as well.  Behind the chunk's last batch
+                // comes the batch the next chunk's pass A starts with.
+                const uint32_t ibl = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_ib[ni - 1]);       // the chunk's last batch
+                const int64_t b_next = b < b1 ? b : b1 - 1;
+                uint32_t ib = (uint32_t)(cb - b0);
+                BinSeg g = bin_make<true>(a, cb * BIN_THREADS + t, nx);
+                nx = bin_fetch(a, (ib < ibl ? b0 + ib + 1 : b_next) * BIN_THREADS + t);
                 for (int it = 0; it < ni; ++it) {
-                    const int64_t bb = b0 + s_ib[it];
-                    const int rr = (int)s_ir[it];
-                    const BinSeg g = bin_load(a, bb * BIN_THREADS + t);
+                    const int rr = __builtin_amdgcn_readfirstlane((int)s_ir[it]);
+                    const uint32_t nb = it + 1 < ni ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s_ib[it + 1]) : ib;
+                    // the eight look-ups together, then the eight adds that return the places, then the eight stores
+                    uint32_t x_[BIN_TPR], h_[BIN_TPR], hk_[BIN_TPR], pos_[BIN_TPR]; int32_t lo_[BIN_TPR], hi_[BIN_TPR];      // (x_ = KEY_INVALID: no such entry)
 #pragma unroll
                     for (int j = 0; j < BIN_TPR; ++j) {
                         const int k = rr * BIN_TPR + j;
+                        x_[j] = KEY_INVALID; h_[j] = 0; hk_[j] = KEY_INVALID; pos_[j] = 0; lo_[j] = 0; hi_[j] = 0;
                         if (k < g.ntile) {
-                            uint32_t trel; int32_t lo, hi;
-                            bin_piece(g, a.window, 6 + a.wsh, k, trel, lo, hi);
-                            const uint32_t x = g.t0 + trel;
-                            uint32_t h = (x * 2654435761u) >> HSHIFT;
-                            while (hkey[h] != x) h = (h + 1) & (BIN_H - 1);
-                            const uint32_t pos = atomicAdd(&hcnt[h], 1u);
+                            uint32_t trel;
+                            bin_piece(g, a.window, 6 + a.wsh, k, trel, lo_[j], hi_[j]);
+                            x_[j] = g.t0 + trel;
+                            h_[j] = (x_[j] * 2654435761u) >> HSHIFT;
+                            hk_[j] = hkey[h_[j]];
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < BIN_TPR; ++j)
+                        if (x_[j] != KEY_INVALID) {
+                            while (hk_[j] != x_[j]) { h_[j] = (h_[j] + 1) & (BIN_H - 1); hk_[j] = hkey[h_[j]]; }
+                            pos_[j] = atomicAdd(&hcnt[h_[j]], 1u);
+                        }
+                    BinSeg gn = g;
+                    if (nb != ib) {                                   // (nb = ib + 1)
+                        gn = bin_make<true>(a, (b0 + nb) * BIN_THREADS + t, nx);
+                        nx = bin_fetch(a, (nb < ibl ? b0 + nb + 1 : b_next) * BIN_THREADS + t);
+                    }
+#pragma unroll
+                    for (int j = 0; j < BIN_TPR; ++j) {
+                        if (x_[j] != KEY_INVALID) {
+                            const uint32_t x = x_[j]; const int32_t lo = lo_[j], hi = hi_[j];
+                            const uint32_t pos = pos_[j];
                             const int32_t tstart = (int32_t)((x - g.tb) << (6 + a.wsh));
                             // the entry lies in the window that STARTS inside its tile: an edge in (tstart, lo].  Edges the segment crosses are
                             // known (b1, b1 + W, ...); a segment that starts behind its tile's edge finds it one window before b1
@@ -390,6 +462,7 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin(BuildArgs a) {
                             else a.key[pos] = key | ((uint64_t)flags << 32);      // keys alone (build_store, keys_only): the two flags a count needs above the source field, bits 62 and 63
                         }
                     }
+                    g = gn; ib = nb;
                 }
                 __syncthreads();
                 for (int i = t; i < BIN_H; i += BIN_THREADS)
