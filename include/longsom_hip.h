@@ -521,9 +521,9 @@ int lsg_bnpc_mpear(lsg_ctx* ctx, int32_t n_cuts, const int32_t* labels, uint64_t
 int lsg_bnpc_mean_params(lsg_ctx* ctx, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used);
 int lsg_bnpc_unload(lsg_ctx* ctx);
 
-/* ---- BnpC's sampler (CellClustering/libs/CRP.py:17-820, libs/MCMC.py:200-388) for the model with fixed error rates -----------------------
- * Gibbs assignment sweeps, the split-merge move, the Escobar-West concentration update and the parameter Metropolis-Hastings, all chains
- * of a run in every kernel; the error-rate updates are not here.  The random stream (Philox4x32-10 keyed by the chain's seed), the
+/* ---- BnpC's sampler (CellClustering/libs/CRP.py:17-820, libs/CRP_learning_errors.py, libs/MCMC.py:200-388) ------------------------------
+ * Gibbs assignment sweeps, the split-merge move, the Escobar-West concentration update, the parameter Metropolis-Hastings and the
+ * error-rate updates, all chains of a run in every kernel.  The random stream (Philox4x32-10 keyed by the chain's seed), the
  * variates and the order of a step are stated in longsom_amd/bnpc_sampler.py, whose numpy twin these calls are held to.
  * lsg_bnpcs_create makes the data and the chains' buffers resident (a second create replaces the first):
  *   one, zero [n_cells][ceil(n_muts / 64)]   the cells' masks: bit m % 64 of word m / 64 is set where the cell shows 1 resp. 0; neither: missing
@@ -545,7 +545,20 @@ int lsg_bnpc_unload(lsg_ctx* ctx);
  * with ratio_merge where both are possible, after `scans` restricted Gibbs scans (run_BnpC.py's -smp, -smr, -sms).  Refused: prob outside
  * [0, 1], ratios that are not positive or do not sum to 1, scans < 0 or > 2^20.
  * lsg_bnpcs_fetch_moves copies out moves [n_chains][n_steps + 1]: what each step so far did: 0 a sweep (and step 0), 1 / 2 a split declined /
- * accepted, 3 / 4 a merge declined / accepted. */
+ * accepted, 3 / 4 a merge declined / accepted.
+ * lsg_bnpcs_set_error_learning, called after lsg_bnpcs_create (without it the rates stay cfg's): every chain has error rates of its own,
+ * which start at the priors' means fp_mean, fn_mean (CRP_errors_learning.__init__, CRP_learning_errors.py:18-32), and after a step's
+ * parameter move makes with probability prob a Metropolis-Hastings update of FP and then of FN (update_error_rates / MH_error_rates,
+ * :52-111; Chain.do_step, MCMC.py:339-342; run_BnpC.py's -eup, -FP_m, -FP_sd, -FN_m, -FN_sd).  Refused: prob outside [0, 1], a mean or an
+ * sd outside (0, 1).
+ * lsg_bnpcs_set_error_rates loads one chain's rates (the model's FP and FN, CRP.py:36-37), for states written as data.  Refused: a rate
+ * outside (0, 1).
+ * lsg_bnpcs_fetch_error_rates copies out rates [n_chains][n_steps + 1][2]: FP and FN as each step so far recorded them
+ * (Chain.update_results, MCMC.py:256-257), and counts [n_chains][4]: the FP moves accepted and declined, the FN moves accepted and
+ * declined (Chain.MH_counter[3], [4], MCMC.py:340-342).
+ * lsg_bnpcs_set_fixed_assignment: with on != 0 a step makes neither the sweep, nor the split-merge move, nor the concentration update
+ * (Chain.do_step with fix_assign, MCMC.py:321-333): the labels stay the loaded ones; the parameter move, the error update and the record
+ * run as always. */
 int lsg_bnpcs_create(lsg_ctx* ctx, int32_t n_cells, int32_t n_muts, int32_t n_chains, int32_t n_steps, const uint64_t* one, const uint64_t* zero, const double* cfg,
                      const uint64_t* seeds, int64_t arena_rows);
 int lsg_bnpcs_set_state(lsg_ctx* ctx, int32_t chain, const int32_t* labels, const float* theta, double dp_alpha);
@@ -554,6 +567,10 @@ int lsg_bnpcs_run(lsg_ctx* ctx, int32_t first_step, int32_t n_steps, int32_t bur
 int lsg_bnpcs_fetch(lsg_ctx* ctx, int32_t* labels, double* scalars, float* arena, int64_t* arena_used, int32_t* errors);
 int lsg_bnpcs_set_split_merge(lsg_ctx* ctx, double prob, double ratio_split, double ratio_merge, int32_t scans);
 int lsg_bnpcs_fetch_moves(lsg_ctx* ctx, int8_t* moves);
+int lsg_bnpcs_set_error_learning(lsg_ctx* ctx, double prob, double fp_mean, double fp_sd, double fn_mean, double fn_sd);
+int lsg_bnpcs_set_error_rates(lsg_ctx* ctx, int32_t chain, double fp, double fn);
+int lsg_bnpcs_fetch_error_rates(lsg_ctx* ctx, double* rates, int32_t* counts);
+int lsg_bnpcs_set_fixed_assignment(lsg_ctx* ctx, int32_t on);
 int lsg_bnpcs_destroy(lsg_ctx* ctx);
 
 /* ---- measurement helpers --------------------------------------------------------------------*/

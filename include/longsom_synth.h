@@ -50,16 +50,21 @@ int lsg_copy_reference_to_host(lsg_ctx* ctx, int32_t tid, uint8_t* out);
  *   normal around a (float32) with sd b at the first double of purpose P_MH, kind 2 Gamma(a) under P_ALPHA; *errors: tries run out.
  * The others work on the state lsg_bnpcs_set_state loaded: _test_counts copies out n1, n0 [n_cells][n_muts] of a chain; _test_ll makes the
  * likelihood matrix and copies out ll [n_cells][*n_clusters] and the cluster ids of its columns; _test_move makes one sweep with its
- * concentration update (what = 0), one parameter move (what = 1) or one split-merge move with its concentration update (what = 2: every
- * chain takes it, whatever its deciding draw says) of every chain under the step number `step`, recording nothing.
+ * concentration update (what = 0), one parameter move (what = 1), one split-merge move with its concentration update (what = 2: every
+ * chain takes it, whatever its deciding draw says) or one error-rate update (what = 3: a chain makes it where its deciding draw says so
+ * under lsg_bnpcs_set_error_learning's probability) of every chain under the step number `step`, recording nothing.
  * lsg_bnpcs_test_move_outcome: a chain's last split-merge move, outcome [12]: the code as in lsg_bnpcs_fetch_moves, the two cluster ids (a
- * split: the cluster and the smallest free id), the two anchors, A, its four terms in the order they are added, ln v, |S|. */
+ * split: the cluster and the smallest free id), the two anchors, A, its four terms in the order they are added, ln v, |S|.
+ * lsg_bnpcs_test_error_outcome: a chain's last error-rate update (what = 3), outcome [21]: 1 if the deciding draw said update, else 0; then
+ * for FP and for FN ten numbers: the index of the proposal's sd, the proposed rate, new_ll, old_ll, new_prior - old_prior, new_p_target,
+ * old_p_target, A, ln v, the decision (1 accepted, 0 declined, -1 declined because rounding put the proposal at <= 0 or >= 1). */
 int lsg_bnpcs_test_stream(lsg_ctx* ctx, uint64_t key, int64_t n, const uint32_t* counters, uint32_t* words, double* doubles);
 int lsg_bnpcs_test_variates(lsg_ctx* ctx, uint64_t key, int32_t kind, int64_t n, double a, double b, double* out, int32_t* errors);
 int lsg_bnpcs_test_counts(lsg_ctx* ctx, int32_t chain, uint32_t* n1, uint32_t* n0);
 int lsg_bnpcs_test_ll(lsg_ctx* ctx, int32_t chain, double* ll, int32_t* clusters, int32_t* n_clusters);
 int lsg_bnpcs_test_move(lsg_ctx* ctx, int32_t what, int32_t step);
 int lsg_bnpcs_test_move_outcome(lsg_ctx* ctx, int32_t chain, double* outcome);
+int lsg_bnpcs_test_error_outcome(lsg_ctx* ctx, int32_t chain, double* outcome);
 
 #ifdef __cplusplus
 }

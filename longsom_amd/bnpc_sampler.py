@@ -1,6 +1,7 @@
-"""BnpC's sampler (scripts/CellClustering/libs/CRP.py:17-410, libs/MCMC.py:200-388) for the model with fixed error rates: Gibbs assignment
-sweeps, the non-conjugate split-merge move (CRP.py:417-820), the Escobar-West concentration update and the parameter Metropolis-Hastings,
-all chains of a run at once.  The error-rate updates, --fixed_assignment, --runtime and --lugsail are not here.
+"""BnpC's sampler (scripts/CellClustering/libs/CRP.py:17-410, libs/CRP_learning_errors.py, libs/MCMC.py:200-388): Gibbs assignment
+sweeps, the non-conjugate split-merge move (CRP.py:417-820), the Escobar-West concentration update, the parameter Metropolis-Hastings
+and the Metropolis-Hastings updates of the error rates, all chains of a run at once; --fixed_assignment is a start state and a flag.
+--runtime, --lugsail and --single_chains are not here.
 
 run_chains        the sampler on the device (csrc/bnpc_sampler.hip, lsg_bnpcs_*)
 run_chains_host   its twin in numpy: what the CPU tests hold to the reference's goldens, and the GPU tests compare the device against
@@ -85,6 +86,33 @@ THE SPLIT-MERGE MOVE (update_assignments_split_merge, do_split_move, do_merge_mo
   with two cells or more (the re-draw loop's own distribution); the anchors are a uniform ordered pair of distinct cells (what the
   acceptance ratio's - log n - log(n - 1) assumes; the reference's two swaps, :448-450, do not give it when obs_j_idx == 0); S is listed
   in ascending id; the merge pair is two sequential draws without replacement; the permutation is a rank by Philox keys.
+THE ERROR-RATE UPDATE (CRP_errors_learning.update_error_rates / MH_error_rates, CRP_learning_errors.py:52-111; Chain.do_step, MCMC.py:339-342).
+  State     per chain FP, FN (doubles).  They start at the prior means; the priors are truncnorm((0 - m) / sd, (1 - m) / sd, m, sd) for
+            (FP_mean, FP_sd) and (FN_mean, FN_sd); the proposal sds of a rate are (0.5 sd, sd, 1.5 sd) of ITS prior sd (:26, :32).
+  When      after the parameter move and before the record (MCMC.py:335-342), only when learning is on.  (u0, _) = the doubles of block
+            (0, s, P_ERR, 0): if u0 < error_prob, the FP move and then the FN move, which sees the FP move's result (:52-55).
+  A move    of rate e under purpose P_e (P_ERR_FP, P_ERR_FN): (u, v) = the doubles of block (0, s, P_e, 0); std = sds[w0 % 3] with w0 of block
+            (0, s, P_e, 1); a = (0 - old) / std, b = (1 - old) / std, all in double; new = old + std ndtri(ndtr(a) + u (ndtr(b) - ndtr(a))).
+            new_p_target: the log density of new under the normal(old, std) truncated to [0, 1]; old_p_target: that of old under the
+            normal(new, std) truncated to [0, 1]; both, and the prior's log density, in the form -z^2 / 2 - log(2 pi) / 2 - log std -
+            log(ndtr(b) - ndtr(a)).  A = new_ll + new_prior - old_ll - old_prior + old_p_target - new_p_target, added in this order (:106);
+            accepted iff ln v < A.
+  ll        get_ll_full_error(FP, FN) (:58-63) is the nansum over cells x mutations of log(par (1 - FN)^d FN^(1 - d) + (1 - par)(1 - FP)^(1 - d)
+            FP^d): L1 for d = 1, L0 for d = 0 of log_tables, so it equals sum_k sum_m n1[k][m] L1'[k][m] + n0[k][m] L0'[k][m] over the live
+            clusters with the tables taken under the trial rates: K x M terms from the counts.  old_ll is the likelihood under the current
+            rates; after an accepted FP move it is that move's new_ll.
+  After     an accepted move the chain's derived constants change (1 - FN, 1 - FP, the new cluster's two log terms, the six anchor logs) and
+            its L1 / L0: the next sweep, split-merge move and parameter move of THAT chain read the new ones.
+  record    FN[s], FP[s] per step (MCMC.py:256-257); MAP[s] gains FP_prior.logpdf(FP[s]) + FN_prior.logpdf(FN[s]) (get_lprior_full, :47-49),
+            added on the host over all steps at once with scipy, as the concentration's term.  error_moves: FP accepted, declined, FN
+            accepted, declined.
+  Where this differs from the reference in distribution only: a `new` that rounding put at <= 0 or >= 1 is declined and counted in
+  variate_errors (the reference would raise there under MCMC.py:20's np.seterr).
+A FIXED ASSIGNMENT (CRP.init(assign=...), :121-128, :169-175; Chain.do_step with fix_assign, MCMC.py:321-333).  The labels are the file's, read
+as dpmmIO.load_txt reads them (:101-112) and compacted to 0 .. K-1 in ascending order; theta[k][m] = clip(Beta(p + n1[k][m], q + n0[k][m])),
+float32, of block (m, 0, P_INIT_ASSIGN | k << 8, .).  A step makes neither the sweep, nor the split-merge move, nor the concentration
+update, and consumes no draw of theirs: only the parameter move and the error update run.  All chains start from the same labels and
+differ by their seeds.
 The start (CRP.init(mode='random'), :139-148, :176-180): label i = floor(N u) of block (i, 0, P_INIT_LABEL, 0), compacted to 0 .. K-1 in
 ascending order; theta[k][m] = clip(u) of block (m, 0, P_INIT_THETA | k << 8, 0); alpha = the mean of scipy's gamma(*DP_a_gamma), whose
 second number is a `loc`: g0 + g1, so a negative -ap gives (sqrt N, 1) and a start at sqrt N + 1.
@@ -102,6 +130,8 @@ MAX_CELLS = 65535                                 # the estimate keeps 16-bit la
 
 P_PERM, P_CHOICE, P_BIRTH, P_BIRTH_B, P_DPA, P_ETA, P_ETA_B, P_ALPHA, P_MH, P_INIT_LABEL, P_INIT_THETA = range(1, 12)
 P_SM, P_SM_PERM, P_SM_CHOICE, P_SM_BETA, P_SM_BETA_B, P_SM_MH, P_SM_SD = range(12, 19)
+P_ERR, P_ERR_FP, P_ERR_FN, P_INIT_ASSIGN, P_INIT_ASSIGN_B = range(19, 24)
+ERROR_SD_FACTORS = (0.5, 1.0, 1.5)                # CRP_learning_errors.py:26,32
 SM_SWEEP, SM_SPLIT_DECLINED, SM_SPLIT_ACCEPTED, SM_MERGE_DECLINED, SM_MERGE_ACCEPTED = range(5)      # the codes of sm_moves
 MAX_SM_STEPS = 1 << 20
 
@@ -250,7 +280,7 @@ def beta_logpdf(x32, p, q):
 class Model:
     """the fixed part of a run: the data as masks and the constants"""
 
-    def __init__(self, data, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None):
+    def __init__(self, data, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, error_prob=0.0, error_priors=None):
         data = np.asarray(data, dtype=np.float64)
         if data.ndim != 2 or data.shape[0] < 2 or data.shape[1] < 1:
             raise ValueError("the sampler needs a cells x mutations matrix of at least 2 x 1, got %r" % (data.shape,))
@@ -270,6 +300,18 @@ class Model:
         self.dpa_prob = float(dpa_prob)
         self.error_prior = 0.0 if error_prior is None else float(error_prior)      # the error rates' own prior terms in MAP (CRP_learning_errors.py:47-49)
         self.one_f, self.zero_f = self.one.astype(np.float64), self.zero.astype(np.float64)
+        # the error-rate update: its probability and (FP_mean, FP_sd, FN_mean, FN_sd); a chain whose rates move works on a copy (of_chain)
+        self.error_prob = float(error_prob)
+        self.error_priors = None if error_priors is None else tuple(float(x) for x in error_priors)
+        self.learning = self.error_priors is not None and self.error_prob > 0
+
+    def of_chain(self, FP=None, FN=None):
+        """the model of one chain: the same data, rates of its own (error_update writes them)"""
+        import copy
+        m = copy.copy(self)
+        if FP is not None:
+            m.FP, m.FN = float(FP), float(FN)
+        return m
 
     def new_cluster_ll(self):
         """get_lpost_single_new_cluster (:230-234) without CRP_prior[-1]: two popcounts times two logs"""
@@ -287,12 +329,14 @@ class Model:
 
 
 class State:
-    """one chain: labels [N], sizes [N] (0 = a free id), theta [N][M] float32 (row = cluster id), alpha"""
+    """one chain: labels [N], sizes [N] (0 = a free id), theta [N][M] float32 (row = cluster id), alpha, and the error rates FP, FN
+    (None: the model's)"""
 
-    def __init__(self, labels, theta, alpha):
+    def __init__(self, labels, theta, alpha, FP=None, FN=None):
         self.labels = np.array(labels, dtype=np.int64)
         self.theta = np.array(theta, dtype=np.float32)
         self.alpha = float(alpha)
+        self.FP, self.FN = (None, None) if FP is None else (float(FP), float(FN))
         self.sizes = np.bincount(self.labels, minlength=len(self.labels)).astype(np.int64)
 
     def live(self):
@@ -309,6 +353,31 @@ def initial_state(model, seed):
     ut, _ = doubles(seed, np.arange(M)[None, :], 0, P_INIT_THETA, 0, np.arange(K)[:, None])
     theta[:K] = np.clip(ut, TMIN, TMAX).astype(np.float32)
     return State(labels, theta, model.alpha0)
+
+
+def load_assignment(path):
+    """dpmmIO.load_txt (:101-112): the first row's 'Assignment' of a tab-separated table, or a file of numbers separated by blanks"""
+    import pandas as pd
+    try:
+        x = pd.read_csv(path, sep="\t", index_col=False).at[0, "Assignment"].split(" ")
+    except (ValueError, KeyError, AttributeError):
+        with open(path) as f:
+            x = f.read().split(" ")
+    return [int(v) for v in x]
+
+
+def assigned_state(model, seed, assign):
+    """CRP.init(assign=...) (:121-128) with _init_cl_params('assign') (:169-175)"""
+    assign = np.asarray(assign)
+    if assign.ndim != 1 or len(assign) != model.N:
+        raise ValueError("the fixed assignment has %d labels, the data have %d cells" % (assign.size, model.N))
+    labels = np.unique(assign, return_inverse=True)[1].reshape(-1)
+    K = int(labels.max()) + 1
+    st = State(labels, np.zeros((model.N, model.M), np.float32), model.alpha0)
+    n1, n0 = counts(model, st)
+    b, _ = beta_variate(seed, model.p + n1[:K], model.q + n0[:K], np.arange(model.M)[None, :], 0, P_INIT_ASSIGN, np.arange(K)[:, None])
+    st.theta[:K] = np.clip(b, TMIN, TMAX).astype(np.float32)
+    return st
 
 
 def crp_prior(sizes, N, alpha):
@@ -758,6 +827,92 @@ def takes_split_merge(seed, step, sm_prob):
     return bool(sm_prob > 0 and float(doubles(seed, 0, step, P_SM, 0)[0]) < sm_prob)
 
 
+# ---- the error-rate update (CRP_learning_errors.py:47-111) ----------------------------------------------------------------------------
+def unit_truncnorm_logpdf(x, loc, sd):
+    """log density at x of the normal(loc, sd) truncated to [0, 1], all in double"""
+    from scipy.special import ndtr
+    pa, pb = ndtr((0.0 - loc) / sd), ndtr((1.0 - loc) / sd)
+    z = (np.asarray(x, dtype=np.float64) - loc) / sd
+    return -0.5 * z * z - 0.5 * np.log(2.0 * np.pi) - np.log(sd) - np.log(pb - pa)
+
+
+def error_ll(model, st, FP, FN):
+    """get_ll_full_error (:58-63) from the counts of the live clusters: (the sum, the sum of the terms' magnitudes)"""
+    live = st.live()
+    n1, n0 = counts(model, st)
+    L1, L0 = log_tables(st.theta[live], FN, FP)
+    terms = np.concatenate([(n1[live] * L1).ravel(), (n0[live] * L0).ravel()])
+    return float(terms.sum()), float(np.abs(terms).sum())
+
+
+def error_log_A(model, st, rate, new, sd):
+    """the terms of MH_error_rates' A (:86-106) for the proposal `new` of `rate` ('FP' or 'FN') made with the proposal sd `sd`, from the
+    state's current rates"""
+    e = 0 if rate == "FP" else 1
+    FP, FN = (model.FP, model.FN) if st.FP is None else (st.FP, st.FN)
+    old = (FP, FN)[e]
+    mean, psd = model.error_priors[2 * e], model.error_priors[2 * e + 1]
+    new_ll, new_mag = error_ll(model, st, new if e == 0 else FP, FN if e == 0 else new)
+    old_ll, old_mag = error_ll(model, st, FP, FN)
+    new_prior, old_prior = float(unit_truncnorm_logpdf(new, mean, psd)), float(unit_truncnorm_logpdf(old, mean, psd))
+    new_p, old_p = float(unit_truncnorm_logpdf(new, old, sd)), float(unit_truncnorm_logpdf(old, new, sd))
+    A = new_ll + new_prior - old_ll - old_prior + old_p - new_p
+    return {"new": float(new), "old": float(old), "new_ll": new_ll, "old_ll": old_ll, "ll_mag": (new_mag, old_mag), "new_prior": new_prior, "old_prior": old_prior,
+            "prior": new_prior - old_prior, "new_p": new_p, "old_p": old_p, "A": float(A)}
+
+
+def error_bound_of_A(model, out):
+    """the bound on |A - A'| between two evaluations of A: (n + 4) 2^-52 sum |term| for each likelihood (n: the observed entries), and a few
+    ulp of the six scalar terms, each of which is itself a sum of four"""
+    n_obs = int(model.pop1.sum() + model.pop0.sum())
+    scalars = abs(out["new_prior"]) + abs(out["old_prior"]) + abs(out["new_p"]) + abs(out["old_p"])
+    return float((n_obs + 4) * 2.0 ** -52 * (out["ll_mag"][0] + out["ll_mag"][1]) + 64 * 2.0 ** -52 * (scalars + 40.0))
+
+
+def error_update(model, st, seed, step, margin=None):
+    """Chain.do_step's draw (MCMC.py:339) and update_error_rates (:52-55) on the state; the model is the chain's own (Model.of_chain): its
+    rates follow the state's.  Returns None where the draw says no update, else {'FP': ..., 'FN': ...}: error_log_A's terms with pick (the
+    sd's index), lv (ln v) and code (1 accepted, 0 declined, -1 declined because rounding put the proposal on an end).  margin sees the
+    draw's distance from error_prob."""
+    from scipy.special import ndtr, ndtri
+    if st.FP is None:
+        st.FP, st.FN = model.FP, model.FN
+    u0, _ = doubles(seed, 0, step, P_ERR)
+    if margin is not None:
+        margin.see(float(u0) - model.error_prob)
+    if not float(u0) < model.error_prob:
+        return None
+    out = {}
+    for e, (rate, purpose) in enumerate((("FP", P_ERR_FP), ("FN", P_ERR_FN))):
+        u, v = doubles(seed, 0, step, purpose)
+        pick = int(philox(seed, 0, step, purpose, 1)[0] % np.uint32(3))
+        psd = model.error_priors[2 * e + 1]
+        sd = (psd * 0.5, psd, psd * 1.5)[pick]
+        old = (st.FP, st.FN)[e]
+        pa, pb = ndtr((0.0 - old) / sd), ndtr((1.0 - old) / sd)
+        new = float(old + sd * ndtri(pa + float(u) * (pb - pa)))
+        inside = 0.0 < new < 1.0
+        o = error_log_A(model, st, rate, new if inside else old, sd)
+        o.update(new=new, pick=pick, lv=float(np.log(v)))
+        accept = inside and o["lv"] < o["A"]
+        o["code"] = 1 if accept else 0 if inside else -1
+        if accept:
+            if e == 0:
+                st.FP = new
+            else:
+                st.FN = new
+            model.FP, model.FN = st.FP, st.FN
+        out[rate] = o
+    return out
+
+
+def error_prior_logpdf(model, FP, FN):
+    """FP_prior.logpdf(FP) + FN_prior.logpdf(FN) (get_lprior_full, CRP_learning_errors.py:47-49) with scipy, over arrays"""
+    from scipy.stats import truncnorm
+    fm, fs, nm, ns = model.error_priors
+    return truncnorm((0 - fm) / fs, (1 - fm) / fs, fm, fs).logpdf(np.asarray(FP, dtype=np.float64)) + truncnorm((0 - nm) / ns, (1 - nm) / ns, nm, ns).logpdf(np.asarray(FN, dtype=np.float64))
+
+
 def likelihood(model, labels, theta_rows):
     """get_ll_full (:237-238) from the counts: theta_rows [K][M] are the rows of the K distinct labels, ascending"""
     ids, inv = np.unique(labels, return_inverse=True)
@@ -788,12 +943,14 @@ def _empty_result(model, steps, burn_in):
     n = steps + 1
     return {"ML": np.zeros(n), "MAP": np.zeros(n), "DP_alpha": np.zeros(n), "FN": np.full(n, model.FN), "FP": np.full(n, model.FP),
             "assignments": np.zeros((n, model.N), dtype=int), "burn_in": burn_in, "_crp": np.zeros(n), "_beta": np.zeros(n), "_rows": [],
-            "sm_moves": np.zeros(n, np.int8)}
+            "sm_moves": np.zeros(n, np.int8), "error_moves": np.zeros(4, np.int64)}
 
 
 def _finish_result(model, r):
-    """MAP from its parts (the scalar prior logpdf with scipy, over all steps at once) and the parameter blocks padded to one cluster count"""
-    r["MAP"] = r["ML"] + alpha_logpdf(model, r["DP_alpha"]) + r.pop("_crp") + r.pop("_beta") + model.error_prior
+    """MAP from its parts (the scalar prior logpdfs with scipy, over all steps at once) and the parameter blocks padded to one cluster count.
+    The error rates' own terms: the priors' log densities at the recorded rates where they are learned, else the run's one number."""
+    error_prior = error_prior_logpdf(model, r["FP"], r["FN"]) if model.learning else model.error_prior
+    r["MAP"] = r["ML"] + alpha_logpdf(model, r["DP_alpha"]) + r.pop("_crp") + r.pop("_beta") + error_prior
     rows = r.pop("_rows")
     k_max = max(b.shape[0] for b in rows)
     params = np.zeros((len(rows), k_max, model.M), np.float32)
@@ -811,54 +968,95 @@ def _check_run(steps, burn_in, sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3):
                          % (MAX_SM_STEPS, sm_prob, tuple(sm_ratios), sm_steps))
 
 
+def _error_model(data, FN, FP, pp, dpa, dpa_prob, error_prior, error_prob, error_priors):
+    """the run's model; where the error rates are learned (error_prob > 0) the four numbers of their priors are needed, and the rates start
+    at the priors' means, which FP and FN must then be"""
+    if not 0 <= error_prob <= 1:
+        raise ValueError("error_prob must lie in [0, 1], got %r" % (error_prob,))
+    if error_prob > 0:
+        if error_priors is None or len(error_priors) != 4 or not all(0 < float(x) < 1 for x in error_priors):
+            raise ValueError("error_prob %g needs error_priors = (FP_mean, FP_sd, FN_mean, FN_sd), each inside (0, 1), got %r" % (error_prob, error_priors))
+        if float(FP) != float(error_priors[0]) or float(FN) != float(error_priors[2]):
+            raise ValueError("the learned error rates start at their priors' means: FP %r and FN %r were given, the means are %r and %r"
+                             % (FP, FN, error_priors[0], error_priors[2]))
+    return Model(data, FN, FP, pp, dpa, dpa_prob, error_prior, error_prob, error_priors if error_prob > 0 else None)
+
+
+def _start_states(model, seeds, states, fixed_assignment):
+    if fixed_assignment is not None:
+        if states is not None:
+            raise ValueError("give either states or fixed_assignment")
+        return [assigned_state(model, s, fixed_assignment) for s in seeds]
+    return [initial_state(model, s) for s in seeds] if states is None else states
+
+
 def run_chains_host(data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None,
-                    sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3):
+                    sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3, error_prob=0.0, error_priors=None, fixed_assignment=None):
     """The whole sampler in numpy.  seeds: one 64-bit seed per chain.  states: start there instead of at the random initialisation.
-    sm_prob, sm_ratios, sm_steps: run_BnpC.py's -smp, -smr, -sms; the result's sm_moves [steps + 1] says what each step did."""
+    sm_prob, sm_ratios, sm_steps: run_BnpC.py's -smp, -smr, -sms; the result's sm_moves [steps + 1] says what each step did.
+    error_prob, error_priors: -eup and (-FP_m, -FP_sd, -FN_m, -FN_sd): the result's FP / FN are then the rates of each step and error_moves
+    the moves' counts (FP accepted, declined, FN accepted, declined).  fixed_assignment: -fa's labels [N]; the steps keep them."""
     _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps)
-    model = Model(data, FN, FP, pp, dpa, dpa_prob, error_prior)
+    shared = _error_model(data, FN, FP, pp, dpa, dpa_prob, error_prior, error_prob, error_priors)
+    fixed = fixed_assignment is not None
     out = []
-    for c, seed in enumerate(seeds):
-        st = initial_state(model, seed) if states is None else State(states[c].labels, states[c].theta, states[c].alpha)
+    for c, start in enumerate(_start_states(shared, seeds, states, fixed_assignment)):
+        seed = seeds[c]
+        st = State(start.labels, start.theta, start.alpha, start.FP, start.FN)
+        model = shared.of_chain(st.FP, st.FN)
         r = _empty_result(model, steps, burn_in)
         errors = 0
         for s in range(steps + 1):
             if s:
-                if takes_split_merge(seed, s, sm_prob):
-                    move = split_merge_move(model, st, seed, s, sm_ratios, sm_steps)
-                    errors += move["errors"]
-                    r["sm_moves"][s] = move["code"]
-                else:
-                    errors += gibbs_sweep(model, st, seed, s)
-                errors += alpha_update(model, st, seed, s)
+                if not fixed:
+                    if takes_split_merge(seed, s, sm_prob):
+                        move = split_merge_move(model, st, seed, s, sm_ratios, sm_steps)
+                        errors += move["errors"]
+                        r["sm_moves"][s] = move["code"]
+                    else:
+                        errors += gibbs_sweep(model, st, seed, s)
+                    errors += alpha_update(model, st, seed, s)
                 parameter_move(model, st, seed, s)
+                if model.learning:
+                    move = error_update(model, st, seed, s)
+                    if move is not None:
+                        for e, rate in enumerate(("FP", "FN")):
+                            r["error_moves"][2 * e + (0 if move[rate]["code"] == 1 else 1)] += 1
+                            errors += move[rate]["code"] == -1
             live = st.live()
             r["ML"][s] = likelihood(model, st.labels, st.theta[live])[0]
             r["_crp"][s], r["_beta"][s] = prior_parts(model, st)
             r["DP_alpha"][s] = st.alpha
+            r["FP"][s], r["FN"][s] = model.FP, model.FN
             r["assignments"][s] = st.labels
             if s >= burn_in:
                 r["_rows"].append(st.theta[live].copy())
-        r["variate_errors"] = errors
+        r["variate_errors"] = int(errors)
         out.append(_finish_result(model, r))
     return out
 
 
 def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None, arena_rows=0,
-               sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3):
+               sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3, error_prob=0.0, error_priors=None, fixed_assignment=None):
     """The same on the device, all chains in every kernel.  arena_rows: the parameter rows per chain the device holds between two fetches
     (0: enough for 64 kept steps of 64 clusters, at least N rows); a full arena only costs a fetch."""
     _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps)
-    model = Model(data, FN, FP, pp, dpa, dpa_prob, error_prior)
+    model = _error_model(data, FN, FP, pp, dpa, dpa_prob, error_prior, error_prob, error_priors)
     seeds = [int(s) for s in seeds]
-    start = [initial_state(model, s) for s in seeds] if states is None else states
+    start = _start_states(model, seeds, states, fixed_assignment)
     arena_rows = int(arena_rows) or max(model.N, 4096)
     engine.bnpcs_create(model, seeds, steps, arena_rows)
     try:
         if sm_prob > 0:
             engine.bnpcs_set_split_merge(sm_prob, sm_ratios[0], sm_ratios[1], sm_steps)
+        if model.learning:
+            engine.bnpcs_set_error_learning(model.error_prob, *model.error_priors)
+        if fixed_assignment is not None:
+            engine.bnpcs_set_fixed_assignment(True)
         for c, st in enumerate(start):
             engine.bnpcs_set_state(c, st.labels, st.theta, st.alpha)
+            if st.FP is not None:
+                engine.bnpcs_set_error_rates(c, st.FP, st.FN)
         rows = [[] for _ in seeds]
         done = 0
         while done < steps + 1:
@@ -873,6 +1071,7 @@ def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, 
             done += n
         errors = engine.bnpcs_errors()
         moves = engine.bnpcs_fetch_moves() if sm_prob > 0 else None
+        rates, rate_moves = engine.bnpcs_fetch_error_rates() if model.learning or any(st.FP is not None for st in start) else (None, None)
         out = []
         for c in range(len(seeds)):
             r = _empty_result(model, steps, burn_in)
@@ -884,6 +1083,8 @@ def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, 
             r["variate_errors"] = int(errors[c])
             if moves is not None:
                 r["sm_moves"] = moves[c].copy()
+            if rates is not None:
+                r["FP"], r["FN"], r["error_moves"] = rates[c, :, 0].copy(), rates[c, :, 1].copy(), rate_moves[c].astype(np.int64)
             out.append(_finish_result(model, r))
         return out
     finally:

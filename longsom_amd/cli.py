@@ -371,21 +371,23 @@ def _bnpc_parser():
     g.add_argument("--chains_npz", default="", help="estimate from chains saved by --save_chains: no sampler is run")
     g.add_argument("--host_estimate", action="store_true", help="the numpy twin of the estimate, for a machine without a GPU")
     g.add_argument("--device", type=int, default=0)
-    g.add_argument("--sampler", choices=["reference", "device", "device-sm"], default="reference",
+    g.add_argument("--sampler", choices=["reference", "device", "device-sm", "device-errors"], default="reference",
                    help="device: Gibbs sweeps, the concentration update and the parameter moves on the GPU, all chains at once (needs -smp 0); "
-                        "device-sm: the same with the split-merge move, -smp / -sms / -smr honoured (-smp 0 equals device)")
+                        "device-sm: the same with the split-merge move, -smp / -sms / -smr honoured (-smp 0 equals device); "
+                        "device-errors: device-sm with the error rates learned (-eup, unless -FP and -FN are both given) and -fa honoured")
     return ap
 
 
 def _device_sampler_refusals(a):
-    """what longsom_amd.bnpc_sampler does not do, each named by its flag; --sampler device and device-sm share all but the first"""
+    """what longsom_amd.bnpc_sampler does not do, or a --sampler value does not ask of it, each named by its flag; --sampler device and
+    device-sm share all but the first, device-errors has only the last two"""
     if a.sampler == "device" and a.split_merge_prob != 0:
         sys.exit("run_BnpC.py: --sampler device has no split-merge move: -smp/--split_merge_prob %g is not supported, run it with -smp 0" % a.split_merge_prob)
     who = "--sampler %s" % a.sampler
-    if not (a.falsePositive > 0 and a.falseNegative > 0) and a.error_update_prob != 0:
+    if a.sampler != "device-errors" and not (a.falsePositive > 0 and a.falseNegative > 0) and a.error_update_prob != 0:
         sys.exit("run_BnpC.py: %s keeps the error rates fixed: -eup/--error_update_prob %g is not supported, run it with -eup 0 (or give -FP and -FN)"
                  % (who, a.error_update_prob))
-    if a.fixed_assignment:
+    if a.sampler != "device-errors" and a.fixed_assignment:
         sys.exit("run_BnpC.py: %s does not support -fa/--fixed_assignment" % who)
     if a.runtime > 0:
         sys.exit("run_BnpC.py: %s does not support -r/--runtime: give the steps with -s" % who)
@@ -394,27 +396,38 @@ def _device_sampler_refusals(a):
 
 
 def _device_chains(a, data):
-    """the chains of --sampler device / device-sm: the model of run_BnpC.py:261-296 with its error rates fixed (the given ones, or the priors' means
-    with the priors' own terms in MAP), the seeds drawn as MCMC.run draws them"""
+    """the chains of --sampler device / device-sm / device-errors: the model of run_BnpC.py:261-296, the seeds drawn as MCMC.run draws them.
+    device and device-sm keep the error rates fixed (the given ones, or the priors' means with the priors' own terms in MAP); device-errors
+    learns them with -eup unless both are given (run_BnpC.py:261-262), and starts from -fa's labels and keeps them where it is given."""
     from scipy.stats import truncnorm
     from . import bnpc_sampler
+    learn = {}
     if a.falsePositive > 0 and a.falseNegative > 0:
+        if a.sampler == "device-errors":
+            a.error_update_prob = 0
         FN, FP, error_prior = a.falseNegative, a.falsePositive, None
     else:
         FN, FP = a.falseNegative_mean, a.falsePositive_mean
         error_prior = sum(float(truncnorm((0 - m) / sd, (1 - m) / sd, m, sd).logpdf(m)) for m, sd in ((FP, a.falsePositive_std), (FN, a.falseNegative_std)))
+        if a.sampler == "device-errors" and a.error_update_prob > 0:
+            learn = dict(error_prob=a.error_update_prob, error_priors=(FP, a.falsePositive_std, FN, a.falseNegative_std))
+    if a.sampler == "device-errors" and a.fixed_assignment:
+        learn["fixed_assignment"] = bnpc_sampler.load_assignment(a.fixed_assignment)
+        if len(learn["fixed_assignment"]) != data.shape[0]:
+            sys.exit("run_BnpC.py: -fa/--fixed_assignment %s has %d labels, the data have %d cells" % (a.fixed_assignment, len(learn["fixed_assignment"]), data.shape[0]))
     a.chain_seeds = bnpc_sampler.chain_seeds(a.seed, a.chains)
     if a.verbosity > 0:
-        print(f"Run MCMC on the device ({a.chains} chains for {a.steps} steps, FN {FN} FP {FP}):")
+        print(f"Run MCMC on the device ({a.chains} chains for {a.steps} steps, FN {FN} FP {FP}{', learned' if 'error_prob' in learn else ''}):")
     with Engine(a.device) as eng:
         return bnpc_sampler.run_chains(eng, data, [int(s) for s in a.chain_seeds], a.steps, int(a.steps * a.burn_in), FN, FP, pp=a.param_prior, dpa=a.DPa_prior,
-                                       dpa_prob=a.conc_update_prob, error_prior=error_prior, sm_prob=a.split_merge_prob if a.sampler == "device-sm" else 0.0,
-                                       sm_ratios=tuple(a.split_merge_ratios), sm_steps=a.split_merge_steps)
+                                       dpa_prob=a.conc_update_prob, error_prior=error_prior, sm_prob=a.split_merge_prob if a.sampler != "device" else 0.0,
+                                       sm_ratios=tuple(a.split_merge_ratios), sm_steps=a.split_merge_steps, **learn)
 
 
 def run_bnpc(argv=None):
     """run_BnpC.py: the chains come from the vendored BnpC's sampler (libs/MCMC.py, run as the reference runs it), from --sampler device
-    or device-sm (longsom_amd.bnpc_sampler: fixed error rates; device-sm with the split-merge move) or from --chains_npz; the
+    / device-sm / device-errors (longsom_amd.bnpc_sampler: device-sm with the split-merge move, device-errors also with learned error
+    rates and -fa) or from --chains_npz; the
     posterior estimate is made on the device (longsom_amd.bnpc); assignment.txt, errors.txt and genotypes_*.tsv are written here; args.txt,
     the PSRF, -e ML|MAP, the summaries and the plots are left to the checkout's own functions."""
     from datetime import datetime
@@ -428,7 +441,7 @@ def run_bnpc(argv=None):
         a.estimator = [a.estimator]
     if a.single_chains:
         sys.exit("run_BnpC.py: -sc/--single_chains is not supported here: the posterior estimate is made once, over all chains")
-    on_device = a.sampler in ("device", "device-sm")
+    on_device = a.sampler in ("device", "device-sm", "device-errors")
     if on_device and not a.chains_npz:
         _device_sampler_refusals(a)
     point = [e for e in a.estimator if e != "posterior"]
@@ -439,7 +452,7 @@ def run_bnpc(argv=None):
     own_chains = a.chains_npz or on_device
     if not have_libs and not (own_chains and a.no_plots and not point):
         sys.exit("run_BnpC.py: no vendored BnpC at %s (--bnpc_libs DIR): the reference's sampler, -e ML|MAP and the plots are the checkout's; only --chains_npz or "
-                 "--sampler device / device-sm, with --no_plots, run without one" % libs_dir)
+                 "--sampler device / device-sm / device-errors, with --no_plots, run without one" % libs_dir)
     io = ut = None
     if have_libs:
         sys.path.insert(0, os.path.dirname(os.path.abspath(libs_dir)))

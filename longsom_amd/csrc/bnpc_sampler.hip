@@ -1,6 +1,8 @@
-// BnpC's sampler for the model with fixed error rates (CellClustering/libs/CRP.py:17-820, libs/MCMC.py:200-388): Gibbs assignment sweeps,
-// the non-conjugate split-merge move, the Escobar-West concentration update and the parameter Metropolis-Hastings, every chain of a run in
-// every kernel.  The stream, the
+// BnpC's sampler (CellClustering/libs/CRP.py:17-820, libs/CRP_learning_errors.py, libs/MCMC.py:200-388): Gibbs assignment sweeps, the
+// non-conjugate split-merge move, the Escobar-West concentration update, the parameter Metropolis-Hastings and the Metropolis-Hastings
+// updates of the error rates, every chain of a run in every kernel.  A chain has error rates of its own (Rates): with the updates off
+// they are the run's for every chain, with them on they move between steps.  A run with a fixed assignment makes only the parameter move
+// and the error update.  The stream, the
 // variates and the order of a step are defined in longsom_amd/bnpc_sampler.py's docstring; its numpy twin is what these kernels are held
 // to.  See include/longsom_hip.h, lsg_bnpcs_*.  Everything is fp64 except theta.
 #include "lsg_ctx.h"
@@ -13,7 +15,8 @@ constexpr double S_TMIN = 1e-5, S_TMAX = 1 - 1e-5;
 constexpr double S_EPS = 1e-15;                       // np.finfo(np.float64).resolution
 constexpr int S_TRIES = 64;                           // Marsaglia-Tsang tries before the mean is written and an error counted
 enum { P_PERM = 1, P_CHOICE, P_BIRTH, P_BIRTH_B, P_DPA, P_ETA, P_ETA_B, P_ALPHA, P_MH, P_INIT_LABEL, P_INIT_THETA,
-       P_SM, P_SM_PERM, P_SM_CHOICE, P_SM_BETA, P_SM_BETA_B, P_SM_MH, P_SM_SD };
+       P_SM, P_SM_PERM, P_SM_CHOICE, P_SM_BETA, P_SM_BETA_B, P_SM_MH, P_SM_SD, P_ERR, P_ERR_FP, P_ERR_FN, P_INIT_ASSIGN, P_INIT_ASSIGN_B };
+constexpr int ERR_OUT = 21;                           // doubles of an error update's outcome: whether it was made, then ten per rate (lsg_bnpcs_test_error_outcome)
 constexpr int SM_OUT = 12;                            // doubles of a move's outcome: code, the clusters, the anchors, A, its four terms, ln v, |S|
 constexpr int SM_MAX_SCANS = 1 << 20;                 // 4 scan + row must fit the 24 bits of `sub`
 constexpr int LT = 16;                                // k_bnpcs_ll: cells x columns per workgroup
@@ -21,10 +24,29 @@ constexpr int REC = 5;                                // doubles recorded per ch
 
 // what every kernel reads: the shape, the constants and where the state lies.  Per chain c: lab, size, colof, live, prow at c * N (prow:
 // c * (N + 1)); theta, L1, L0, n1, n0 at c * N * M; LL at c * N * ll_pitch.
+// a chain's error rates and what follows from them: the new cluster's two log terms (get_lpost_single_new_cluster, CRP.py:230-234) and the
+// six logs of _rg_init_split's likelihood, [anchor 1, 0, missing][cell 1, 0]
+struct Rates {
+    double FP, FN, omFP, omFN, new1, new0, sm_anchor[6];
+};
+
+__host__ __device__ inline void rates_fill(Rates& r, double FP, double FN, double mix0, double mix1) {
+    r.FP = FP; r.FN = FN; r.omFP = 1 - FP; r.omFN = 1 - FN;
+    r.new1 = log(mix1 * (1 - FN) + mix0 * FP); r.new0 = log(mix1 * FN + mix0 * (1 - FP));
+    const double v[6] = {1 - FN, FN, FP, 1 - FP, mix0 * (1 - FN) + (1 - mix0) * FP, mix0 * FN + (1 - mix0) * (1 - FP)};
+    for (int k = 0; k < 6; ++k) r.sm_anchor[k] = log(v[k]);
+}
+
 struct SDev {
     int32_t N, M, W, C, steps1, ll_pitch;
     int64_t arena_rows;
-    double FN, FP, omFN, omFP, p, q, g0, g1, dpa_prob, new1, new0, betaln;
+    double p, q, g0, g1, dpa_prob, betaln, mix0, mix1;
+    // the error-rate update: a step makes it with probability err_prob; the priors' (mean, sd) of FP and of FN.  rates [chain]; rec_err
+    // [chain][steps1][2]: FP, FN per step; err_cnt [chain][4]: FP accepted, declined, FN accepted, declined; err_out [chain][ERR_OUT]
+    double err_prob, err_mean[2], err_sd[2];
+    Rates* rates;
+    double *rec_err, *err_out;
+    int32_t* err_cnt;
     int32_t uniform;
     const uint64_t *one, *zero, *seeds;
     const int32_t* pop;                               // [N][2]: ones, zeros
@@ -33,11 +55,10 @@ struct SDev {
     double *L1, *L0, *LL, *alpha, *prow, *rowml, *rowb, *rec_sc;
     uint32_t *n1, *n0;
     uint64_t* keys;
-    // the split-merge move: a step takes it with probability sm_prob, a split with sm_edge = r0 / (r0 + r1); sm_anchor: the six logs of
-    // _rg_init_split's likelihood, [anchor 1, 0, missing][cell 1, 0].  Per chain: sm_i 5 N (the cells of cluster i, of cluster j, S, the
+    // the split-merge move: a step takes it with probability sm_prob, a split with sm_edge = r0 / (r0 + r1).  Per chain: sm_i 5 N (the cells of cluster i, of cluster j, S, the
     // assignment of S, the walk's picks), sm_d 6 N + 6 M + SM_OUT (ll [N][2], u [N], the same in walk order, the rows' L1 / L0, the outcome),
     // sm_c 6 M (the rows' n1 / n0), sm_t 3 M (the rows), rec_sm steps1 (the codes of sm_moves)
-    double sm_prob, sm_edge, sm_anchor[6];
+    double sm_prob, sm_edge;
     int32_t sm_scans;
     int32_t *sm_i, *rec_sm;
     double* sm_d;
@@ -110,10 +131,11 @@ __device__ inline double truncnorm_logpdf_in(float x, float loc, double sd, floa
     return -0.5 * z * z - 0.5 * log(2.0 * M_PI) - log(sd) - log(pb - pa);
 }
 
-__device__ inline void log_terms(const SDev& d, float theta, double& l1, double& l0) {
+// under the rates of the chain (a kernel copies its chain's row of SDev::rates once)
+__device__ inline void log_terms(const Rates& r, float theta, double& l1, double& l0) {
     const double th = (double)theta, om = (double)(1.0f - theta);
-    l1 = log(th * d.omFN + om * d.FP);
-    l0 = log(th * d.FN + om * d.omFP);
+    l1 = log(th * r.omFN + om * r.FP);
+    l0 = log(th * r.FN + om * r.omFP);
 }
 
 __device__ inline double beta_logpdf(const SDev& d, float theta) {
@@ -168,12 +190,13 @@ __global__ __launch_bounds__(256) void k_bnpcs_counts(SDev d) {
 __global__ __launch_bounds__(64) void k_bnpcs_tables(SDev d) {
     const int c = blockIdx.y, k = blockIdx.x;
     const size_t row = (size_t)c * d.N + k;
+    const Rates er = d.rates[c];
     double ml = 0.0, bp = 0.0;
     if (d.size[row] > 0)
         for (int m = threadIdx.x; m < d.M; m += 64) {
             const float th = d.theta[row * d.M + m];
             double l1, l0;
-            log_terms(d, th, l1, l0);
+            log_terms(er, th, l1, l0);
             d.L1[row * d.M + m] = l1; d.L0[row * d.M + m] = l0;
             ml += (double)d.n1[row * d.M + m] * l1 + (double)d.n0[row * d.M + m] * l0;
             if (!d.uniform) bp += beta_logpdf(d, th);
@@ -315,6 +338,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step, int d
     const int32_t* order = d.order + (size_t)c * N;
     double* prow = d.prow + (size_t)c * (N + 1);
     const double alpha = d.alpha[c], lden = log((double)(N - 1) + alpha), lnew = log(alpha) - lden, log_eps = log(S_EPS);
+    const Rates er = d.rates[c];
     int hi = d.hi[c];
     for (int n = 0; n < N; ++n) {
         const int cell = order[n];
@@ -327,7 +351,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step, int d
         double mx = -INFINITY;
         for (int k = k0; k < k1; ++k) {
             double lp = -INFINITY;
-            if (k == hi) lp = ((double)d.pop[2 * cell] * d.new1 + (double)d.pop[2 * cell + 1] * d.new0) + lnew;
+            if (k == hi) lp = ((double)d.pop[2 * cell] * er.new1 + (double)d.pop[2 * cell + 1] * er.new0) + lnew;
             else {
                 const int sz = size[k];
                 if (sz > 0) {
@@ -381,7 +405,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step, int d
                 const double x = beta_variate(key, (uint32_t)m, step, (uint32_t)P_BIRTH | ((uint32_t)cell << 8), a1, b1, d.err + c);
                 const float th = (float)fmin(fmax(x, S_TMIN), S_TMAX);
                 double l1, l0;
-                log_terms(d, th, l1, l0);
+                log_terms(er, th, l1, l0);
                 d.theta[row * d.M + m] = th; d.L1[row * d.M + m] = l1; d.L0[row * d.M + m] = l0;
             }
             if (t == 0) { size[slot] = 1; colof[slot] = -1; lab[cell] = slot; }
@@ -409,9 +433,10 @@ __global__ __launch_bounds__(64) void k_bnpcs_mh(SDev d, uint32_t step) {
     const float old = d.theta[at];
     const float nw = truncnorm_variate(u, old, sd);
     const double n1 = (double)d.n1[at], n0 = (double)d.n0[at];
+    const Rates er = d.rates[c];
     double nl1, nl0, ol1, ol0;
-    log_terms(d, nw, nl1, nl0);
-    log_terms(d, old, ol1, ol0);
+    log_terms(er, nw, nl1, nl0);
+    log_terms(er, old, ol1, ol0);
     const double new_ll = n1 * nl1 + n0 * nl0, old_ll = n1 * ol1 + n0 * ol0;
     const double new_prior = d.uniform ? 0.0 : beta_logpdf(d, nw), old_prior = d.uniform ? 0.0 : beta_logpdf(d, old);
     const double new_p = truncnorm_logpdf(nw, old, sd), old_p = truncnorm_logpdf(old, nw, sd);
@@ -459,7 +484,7 @@ __device__ int sm_compact(const int32_t* lab, int N, int a, int b, int xi, int x
 }
 
 // _rg_init_split's likelihood of a cell under an anchor's data as parameters (:557-560): popcounts times the six constants, in their order
-__device__ inline double sm_anchor_ll(const SDev& d, int cell, int anchor) {
+__device__ inline double sm_anchor_ll(const SDev& d, const Rates& er, int cell, int anchor) {
     int n[6] = {0, 0, 0, 0, 0, 0};
     for (int w = 0; w < d.W; ++w) {
         const uint64_t co = d.one[(size_t)cell * d.W + w], cz = d.zero[(size_t)cell * d.W + w];
@@ -468,7 +493,7 @@ __device__ inline double sm_anchor_ll(const SDev& d, int cell, int anchor) {
     }
     double ll = 0.0;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) ll = ll + (double)n[k] * d.sm_anchor[k];
+    for (int k = 0; k < 6; ++k) ll = ll + (double)n[k] * er.sm_anchor[k];
     return ll;
 }
 
@@ -490,8 +515,8 @@ __device__ void sm_count(const SDev& d, const SmBuf& b, int nS, int ai, int aj) 
     __syncthreads();
 }
 
-__device__ void sm_tables(const SDev& d, const SmBuf& b, int r0, int r1) {
-    for (int e = r0 * d.M + threadIdx.x; e < r1 * d.M; e += 256) { double l1, l0; log_terms(d, b.th[e], l1, l0); b.L1[e] = l1; b.L0[e] = l0; }
+__device__ void sm_tables(const SDev& d, const Rates& er, const SmBuf& b, int r0, int r1) {
+    for (int e = r0 * d.M + threadIdx.x; e < r1 * d.M; e += 256) { double l1, l0; log_terms(er, b.th[e], l1, l0); b.L1[e] = l1; b.L0[e] = l0; }
     __syncthreads();
 }
 
@@ -503,10 +528,10 @@ __device__ inline double sm_sd(uint64_t key, uint32_t m, uint32_t step, uint32_t
 }
 
 // _get_log_A with clip (:347-383) of one entry; unit: the forward density's bounds are 0 and 1
-__device__ inline double sm_log_A(const SDev& d, float nw, float old, double n1, double n0, double sd, bool unit) {
+__device__ inline double sm_log_A(const SDev& d, const Rates& er, float nw, float old, double n1, double n0, double sd, bool unit) {
     double nl1, nl0, ol1, ol0;
-    log_terms(d, nw, nl1, nl0);
-    log_terms(d, old, ol1, ol0);
+    log_terms(er, nw, nl1, nl0);
+    log_terms(er, old, ol1, ol0);
     const double new_ll = n1 * nl1 + n0 * nl0, old_ll = n1 * ol1 + n0 * ol0;
     const double new_prior = d.uniform ? 0.0 : beta_logpdf(d, nw), old_prior = d.uniform ? 0.0 : beta_logpdf(d, old);
     const double new_p = unit ? truncnorm_logpdf_in(nw, old, sd, 0.0f, 1.0f) : truncnorm_logpdf(nw, old, sd), old_p = truncnorm_logpdf(old, nw, sd);
@@ -515,7 +540,7 @@ __device__ inline double sm_log_A(const SDev& d, float nw, float old, double n1,
 
 // MH_cluster_params(trans_prob=True) (:314-342) of rows r0 .. r1-1 at scan `scan`, a lane per (row, mutation); sums[r] gets the row's
 // transition probability in every lane, and the moved rows' tables are made again
-__device__ void sm_move_rows(const SDev& d, const SmBuf& b, uint64_t key, uint32_t step, int scan, int r0, int r1, double* sums, double* shd) {
+__device__ void sm_move_rows(const SDev& d, const Rates& er, const SmBuf& b, uint64_t key, uint32_t step, int scan, int r0, int r1, double* sums, double* shd) {
     const int M = d.M;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
     for (int e = r0 * M + threadIdx.x; e < r1 * M; e += 256) {
@@ -526,14 +551,14 @@ __device__ void sm_move_rows(const SDev& d, const SmBuf& b, uint64_t key, uint32
         const double sd = sm_sd(key, (uint32_t)m, step, pw, 1);
         const float old = b.th[e];
         const float nw = truncnorm_variate(u, old, sd);
-        const double A = sm_log_A(d, nw, old, (double)b.n1[e], (double)b.n0[e], sd, false);
+        const double A = sm_log_A(d, er, nw, old, (double)b.n1[e], (double)b.n0[e], sd, false);
         double share;
         if (log(v) < A) { b.th[e] = nw; share = A; }
         else share = log(-expm1(A));
         if (r == 0) a0 += share; else if (r == 1) a1 += share; else a2 += share;
     }
     sums[0] = block_sum(a0, shd); sums[1] = block_sum(a1, shd); sums[2] = block_sum(a2, shd);
-    sm_tables(d, b, r0, r1);
+    sm_tables(d, er, b, r0, r1);
 }
 
 // a masked sum of a cell over one row's tables
@@ -645,6 +670,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
     const int K = d.nlive[c];
     const SmBuf b = sm_buf(d, c);
     const double alpha = d.alpha[c];
+    const Rates er = d.rates[c];
     // get_empty_cluster: the smallest free id (N if there is none: then every cluster has one cell and the move is a merge)
     int fr = N;
     { const int ch = (N + 255) / 256; for (int k = min(t * ch, N); k < min(t * ch + ch, N); ++k) if (size[k] == 0) { fr = k; break; } }
@@ -697,7 +723,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
     const int nS = sm_compact(lab, N, cli, split ? cli : clj, ai, aj, b.S, cnt);
     const int nn = nS + 2, scans = d.sm_scans;
     // run_rg_nc (:527-544): the launch state
-    for (int s = t; s < nS; s += 256) { const int cell = b.S[s]; b.asg[s] = sm_anchor_ll(d, cell, aj) > sm_anchor_ll(d, cell, ai) ? 1 : 0; }
+    for (int s = t; s < nS; s += 256) { const int cell = b.S[s]; b.asg[s] = sm_anchor_ll(d, er, cell, aj) > sm_anchor_ll(d, er, cell, ai) ? 1 : 0; }
     __syncthreads();
     sm_count(d, b, nS, ai, aj);
     for (int e = t; e < 3 * M; e += 256) {
@@ -706,14 +732,14 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
         b.th[e] = (float)fmin(fmax(x, S_TMIN), S_TMAX);
     }
     __syncthreads();
-    sm_tables(d, b, 0, 3);
+    sm_tables(d, er, b, 0, 3);
     double sums[3];
     for (int sc = 0; sc < scans; ++sc) {
         if (nS > 0) {
             sm_scan(d, b, c, key, step, sc, nS, alpha, b.L1, b.L0, b.L1 + M, b.L0 + M, -1, tile, &s_dbl[1]);
             sm_count(d, b, nS, ai, aj);
         }
-        sm_move_rows(d, b, key, step, sc, 0, 3, sums, shd);
+        sm_move_rows(d, er, b, key, step, sc, 0, 3, sums, shd);
     }
     const float* th_i = d.theta + ((size_t)c * N + cli) * M;
     const float* th_j = d.theta + ((size_t)c * N + (split ? cli : clj)) * M;
@@ -726,12 +752,12 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
             prob_cl = sm_scan(d, b, c, key, step, scans, nS, alpha, b.L1, b.L0, b.L1 + M, b.L0 + M, -1, tile, &s_dbl[1]);
             sm_count(d, b, nS, ai, aj);
         }
-        sm_move_rows(d, b, key, step, scans, 0, 2, sums, shd);
+        sm_move_rows(d, er, b, key, step, scans, 0, 2, sums, shd);
         const double gs_split = prob_cl + (sums[0] + sums[1]);
         double rev = 0.0, pa = 0.0, pb = 0.0, cj = 0.0, inv = 0.0;
         for (int m = t; m < M; m += 256) {
             const int e = 2 * M + m;
-            rev += sm_log_A(d, th_i[m], b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | (2u << 8), 0), false);
+            rev += sm_log_A(d, er, th_i[m], b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | (2u << 8), 0), false);
             if (!d.uniform) { pa += beta_logpdf(d, b.th[m]) + beta_logpdf(d, b.th[M + m]); pb += beta_logpdf(d, th_i[m]); }
         }
         for (int s = t; s < nS; s += 256) cj += b.asg[s];
@@ -749,13 +775,13 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
         t4 = log(1.0 / n_i / norm) + log(1.0 / n_j / norm) - size_data;
     } else {
         // _do_rg_merge_MH (:656-665), _get_trans_prob_ratio_merge (:685-692), _rg_get_split_prob (:777-820)
-        sm_move_rows(d, b, key, step, scans, 2, 3, sums, shd);
+        sm_move_rows(d, er, b, key, step, scans, 2, 3, sums, shd);
         const double gs_merge = sums[2];
         double par = 0.0, pa = 0.0, pb = 0.0, cj = 0.0;
         for (int e = t; e < 2 * M; e += 256) {
             const int r = e / M, m = e - r * M;
             const float orig = r == 0 ? th_i[m] : th_j[m];
-            par += sm_log_A(d, orig, b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | ((uint32_t)r << 8), 0), true);
+            par += sm_log_A(d, er, orig, b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | ((uint32_t)r << 8), 0), true);
             if (!d.uniform) pb += beta_logpdf(d, orig);
         }
         if (!d.uniform) for (int m = t; m < M; m += 256) pa += beta_logpdf(d, b.th[2 * M + m]);
@@ -805,6 +831,80 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
     alpha_update(d, c, step, size, alpha, shd);
 }
 
+// ---- the error-rate update (update_error_rates / MH_error_rates, CRP_learning_errors.py:52-111; Chain.do_step, MCMC.py:339-342; the draws
+// are in longsom_amd/bnpc_sampler.py's docstring).  One workgroup per chain, after the parameter move and its tables: the FP move, then
+// the FN move, which sees the FP move's result.  get_ll_full_error (:58-63) under the trial rates is sum_k sum_m n1 L1' + n0 L0' over the live
+// clusters: the lanes stride over clusters x mutations, block_sum adds in a fixed order.  The scalar terms are the same in every lane.
+// An accepted move rewrites the chain's Rates; the host makes the tables again behind this kernel.
+__device__ inline double unit_truncnorm_logpdf(double x, double loc, double sd) {
+    const double pa = normcdf((0.0 - loc) / sd), pb = normcdf((1.0 - loc) / sd);
+    const double z = (x - loc) / sd;
+    return -0.5 * z * z - 0.5 * log(2.0 * M_PI) - log(sd) - log(pb - pa);
+}
+
+__device__ double err_ll(const SDev& d, int c, int K, double FP, double FN, double* shd) {
+    const int32_t* live = d.live + (size_t)c * d.N;
+    const double omFP = 1 - FP, omFN = 1 - FN;
+    double acc = 0.0;
+    for (int64_t e = threadIdx.x; e < (int64_t)K * d.M; e += 256) {
+        const int j = (int)(e / d.M), m = (int)(e - (int64_t)j * d.M);
+        const size_t at = ((size_t)c * d.N + live[j]) * d.M + m;
+        const float theta = d.theta[at];
+        const double th = (double)theta, om = (double)(1.0f - theta);
+        acc += (double)d.n1[at] * log(th * omFN + om * FP) + (double)d.n0[at] * log(th * FN + om * omFP);
+    }
+    return block_sum(acc, shd);
+}
+
+__global__ __launch_bounds__(256) void k_bnpcs_err(SDev d, uint32_t step) {
+    __shared__ double shd[4];
+    const int c = blockIdx.x, t = threadIdx.x, N = d.N, K = d.nlive[c];
+    const uint64_t key = d.seeds[c];
+    double* out = d.err_out + (size_t)c * ERR_OUT;
+    double u0, u_unused;
+    doubles(key, 0, step, P_ERR, 0, u0, u_unused);
+    if (!(u0 < d.err_prob)) { if (t == 0) out[0] = 0.0; return; }
+    const int32_t* live = d.live + (size_t)c * N;
+    double rate[2] = {d.rates[c].FP, d.rates[c].FN};
+    // the likelihood under the current rates: the sum of the tables' rows, as the record takes it
+    double old_ll = 0.0;
+    { const int ch = (K + 255) / 256; for (int j = min(t * ch, K); j < min(t * ch + ch, K); ++j) old_ll += d.rowml[(size_t)c * N + live[j]]; }
+    old_ll = block_sum(old_ll, shd);
+    bool moved = false;
+    for (int e = 0; e < 2; ++e) {
+        const uint32_t purpose = e == 0 ? P_ERR_FP : P_ERR_FN;
+        double u, v;
+        doubles(key, 0, step, purpose, 0, u, v);
+        uint32_t w[4];
+        philox4x32(key, 0, step, purpose, 1, w);
+        const uint32_t pick = w[0] % 3u;
+        const double psd = d.err_sd[e], sd = pick == 0 ? psd * 0.5 : pick == 1 ? psd : psd * 1.5;
+        const double old = rate[e];
+        const double pa = normcdf((0.0 - old) / sd), pb = normcdf((1.0 - old) / sd);
+        const double nw = old + sd * normcdfinv(pa + u * (pb - pa));
+        const bool inside = nw > 0.0 && nw < 1.0;                    // rounding can put it on an end: declined, and counted as a variate error
+        const double trial = inside ? nw : old;
+        const double new_ll = err_ll(d, c, K, e == 0 ? trial : rate[0], e == 0 ? rate[1] : trial, shd);
+        const double new_p = unit_truncnorm_logpdf(trial, old, sd), old_p = unit_truncnorm_logpdf(old, trial, sd);
+        const double new_prior = unit_truncnorm_logpdf(trial, d.err_mean[e], psd), old_prior = unit_truncnorm_logpdf(old, d.err_mean[e], psd);
+        const double A = new_ll + new_prior - old_ll - old_prior + old_p - new_p;
+        const double lv = log(v);
+        const bool accept = inside && lv < A;
+        if (t == 0) {
+            double* o = out + 1 + 10 * e;
+            o[0] = (double)pick; o[1] = nw; o[2] = new_ll; o[3] = old_ll; o[4] = new_prior - old_prior; o[5] = new_p; o[6] = old_p; o[7] = A; o[8] = lv;
+            o[9] = accept ? 1.0 : inside ? 0.0 : -1.0;
+            d.err_cnt[4 * c + 2 * e + (accept ? 0 : 1)] += 1;
+            if (!inside) atomicAdd(d.err + c, 1);
+        }
+        if (accept) { rate[e] = nw; old_ll = new_ll; moved = true; }
+    }
+    if (t == 0) {
+        out[0] = 1.0;
+        if (moved) rates_fill(d.rates[c], rate[0], rate[1], d.mix0, d.mix1);
+    }
+}
+
 // ---- record (Chain.update_results, MCMC.py:242-282): ML, the two prior sums, the labels, and after burn-in the live clusters' parameters
 // in ascending id into the arena.  A workgroup per chain. ------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_bnpcs_record(SDev d, int32_t step, int32_t keep, const int64_t* used) {
@@ -823,6 +923,8 @@ __global__ __launch_bounds__(256) void k_bnpcs_record(SDev d, int32_t step, int3
     if (t == 0) {
         double* r = d.rec_sc + ((size_t)c * d.steps1 + step) * REC;
         r[0] = ml; r[1] = crp; r[2] = bp; r[3] = (double)K; r[4] = alpha;
+        double* e = d.rec_err + ((size_t)c * d.steps1 + step) * 2;
+        e[0] = d.rates[c].FP; e[1] = d.rates[c].FN;
     }
     for (int i = t; i < N; i += 256) d.rec_lab[((size_t)c * d.steps1 + step) * N + i] = d.lab[(size_t)c * N + i];
     if (keep) {
@@ -863,9 +965,11 @@ static int sync_check(lsg_ctx* c, const char* who) {
 static SDev dev_of(const Bnpcs& b) {
     SDev d{};
     d.N = b.n_cells; d.M = b.n_muts; d.W = b.n_words; d.C = b.n_chains; d.steps1 = b.steps1; d.ll_pitch = b.ll_pitch; d.arena_rows = b.arena_rows;
-    d.FN = b.cfg[0]; d.FP = b.cfg[1]; d.omFN = 1 - b.cfg[0]; d.omFP = 1 - b.cfg[1]; d.p = b.cfg[2]; d.q = b.cfg[3]; d.g0 = b.cfg[4]; d.g1 = b.cfg[5]; d.dpa_prob = b.cfg[6];
+    d.p = b.cfg[2]; d.q = b.cfg[3]; d.g0 = b.cfg[4]; d.g1 = b.cfg[5]; d.dpa_prob = b.cfg[6];
     d.uniform = d.p == 1.0 && d.q == 1.0;
-    d.new1 = b.cfg[7]; d.new0 = b.cfg[8]; d.betaln = b.cfg[9];
+    d.betaln = b.cfg[9]; d.mix0 = b.mix[0]; d.mix1 = b.mix[1];
+    d.err_prob = b.err_prob; d.err_mean[0] = b.err_prior[0]; d.err_sd[0] = b.err_prior[1]; d.err_mean[1] = b.err_prior[2]; d.err_sd[1] = b.err_prior[3];
+    d.rates = b.rates.as<Rates>(); d.rec_err = b.rec_err.as<double>(); d.err_out = b.err_out.as<double>(); d.err_cnt = b.err_cnt.as<int32_t>();
     d.one = b.one.as<uint64_t>(); d.zero = b.zero.as<uint64_t>(); d.seeds = b.seeds.as<uint64_t>(); d.pop = b.pop.as<int32_t>();
     d.lab = b.lab.as<int32_t>(); d.size = b.size.as<int32_t>(); d.colof = b.colof.as<int32_t>(); d.live = b.live.as<int32_t>(); d.nlive = b.nlive.as<int32_t>();
     d.hi = b.hi.as<int32_t>(); d.order = b.order.as<int32_t>(); d.rec_lab = b.rec_lab.as<int32_t>(); d.err = b.err.as<int32_t>();
@@ -874,7 +978,6 @@ static SDev dev_of(const Bnpcs& b) {
     d.rowml = b.rowml.as<double>(); d.rowb = b.rowb.as<double>(); d.rec_sc = b.rec_sc.as<double>();
     d.n1 = b.n1.as<uint32_t>(); d.n0 = b.n0.as<uint32_t>(); d.keys = b.keys.as<uint64_t>();
     d.sm_prob = b.sm_prob; d.sm_edge = b.sm_ratio[0] / (b.sm_ratio[0] + b.sm_ratio[1]); d.sm_scans = b.sm_scans;
-    std::copy(b.sm_anchor, b.sm_anchor + 6, d.sm_anchor);
     d.sm_i = b.sm_i.as<int32_t>(); d.rec_sm = b.rec_sm.as<int32_t>(); d.sm_d = b.sm_d.as<double>(); d.sm_c = b.sm_c.as<uint32_t>(); d.sm_t = b.sm_t.as<float>();
     return d;
 }
@@ -943,6 +1046,15 @@ static int launch_mh(lsg_ctx* c, uint32_t step) {
     return 0;
 }
 
+// the error-rate update of the chains whose draw says so, behind the parameter move's tables; then the tables under the rates it left
+static int launch_err(lsg_ctx* c, uint32_t step) {
+    Bnpcs& b = c->bnpcs;
+    const SDev d = dev_of(b);
+    hipLaunchKernelGGL(k_bnpcs_err, dim3(b.n_chains), dim3(256), 0, c->stream, d, step);
+    hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, d);
+    return 0;
+}
+
 } // namespace lsg
 
 using namespace lsg;
@@ -966,7 +1078,8 @@ int lsg_bnpcs_create(lsg_ctx* c, int32_t n_cells, int32_t n_muts, int32_t n_chai
         b.rowml.reserve(C * N * 8) || b.rowb.reserve(C * N * 8) || b.order.reserve(C * N * 4) || b.keys.reserve(C * N * 8) || b.rec_lab.reserve(C * S1 * N * 4) ||
         b.rec_sc.reserve(C * S1 * REC * 8) || b.arena.reserve(C * (size_t)arena_rows * M * 4) || b.err.reserve(C * 4 + 8 * C + 8) ||
         b.sm_i.reserve(C * 5 * N * 4) || b.sm_d.reserve(C * (6 * N + 6 * M + SM_OUT) * 8) || b.sm_c.reserve(C * 6 * M * 4) || b.sm_t.reserve(C * 3 * M * 4) ||
-        b.rec_sm.reserve(C * S1 * 4)) return -1;
+        b.rec_sm.reserve(C * S1 * 4) || b.rates.reserve(C * sizeof(Rates)) || b.rec_err.reserve(C * S1 * 2 * 8) || b.err_cnt.reserve(C * 4 * 4) ||
+        b.err_out.reserve(C * ERR_OUT * 8)) return -1;
     std::vector<int32_t> pop(2 * N);
     const uint64_t tail = M % 64 ? ((1ull << (M % 64)) - 1) : ~0ull;
     for (size_t i = 0; i < N; ++i) {
@@ -992,19 +1105,27 @@ int lsg_bnpcs_create(lsg_ctx* c, int32_t n_cells, int32_t n_muts, int32_t n_chai
     LSG_HIP(hipMemsetAsync(b.rec_sc.p, 0, C * S1 * REC * 8, st));
     LSG_HIP(hipMemsetAsync(b.rec_sm.p, 0, C * S1 * 4, st));
     LSG_HIP(hipMemsetAsync(b.sm_d.p, 0, C * (6 * N + 6 * M + SM_OUT) * 8, st));
-    LSG_HIP(hipStreamSynchronize(st));
+    LSG_HIP(hipMemsetAsync(b.rec_err.p, 0, C * S1 * 2 * 8, st));
+    LSG_HIP(hipMemsetAsync(b.err_cnt.p, 0, C * 4 * 4, st));
+    LSG_HIP(hipMemsetAsync(b.err_out.p, 0, C * ERR_OUT * 8, st));
+    {
+        // every chain starts with cfg's rates: the new cluster's log terms as cfg gives them, _beta_mix_const (CRP.py:42-44) and the six
+        // values a likelihood term takes under an anchor's data as parameters (:557-560)
+        const double p = cfg[2], q = cfg[3];
+        const double m0 = std::tgamma(p) * std::tgamma(q + 1) / std::tgamma(p + q + 1), m1 = std::tgamma(p + 1) * std::tgamma(q) / std::tgamma(p + q + 1);
+        b.mix[0] = m0 / (m0 + m1); b.mix[1] = m1 / (m0 + m1);
+        Rates r;
+        rates_fill(r, cfg[1], cfg[0], b.mix[0], b.mix[1]);
+        r.new1 = cfg[7]; r.new0 = cfg[8];
+        const std::vector<Rates> all(C, r);
+        LSG_HIP(hipMemcpyAsync(b.rates.p, all.data(), C * sizeof(Rates), hipMemcpyHostToDevice, st));
+        LSG_HIP(hipStreamSynchronize(st));                         // (`all` is read by the copy until here)
+    }
     b.n_cells = n_cells; b.n_muts = n_muts; b.n_words = (int32_t)W; b.n_chains = n_chains; b.steps1 = (int32_t)S1; b.arena_rows = arena_rows;
     b.k_max = 0; b.ll_pitch = 1; b.pending = -1; b.next_step = 0;
     std::copy(cfg, cfg + 10, b.cfg);
     b.sm_prob = 0.0; b.sm_ratio[0] = 0.75; b.sm_ratio[1] = 0.25; b.sm_scans = 3;
-    {
-        // _beta_mix_const[0] (CRP.py:42-44) and the six values a likelihood term takes under an anchor's data as parameters (:557-560)
-        const double p = cfg[2], q = cfg[3], FN = cfg[0], FP = cfg[1];
-        const double m0 = std::tgamma(p) * std::tgamma(q + 1) / std::tgamma(p + q + 1), m1 = std::tgamma(p + 1) * std::tgamma(q) / std::tgamma(p + q + 1);
-        const double mix0 = m0 / (m0 + m1);
-        const double v[6] = {1 - FN, FN, FP, 1 - FP, mix0 * (1 - FN) + (1 - mix0) * FP, mix0 * FN + (1 - mix0) * (1 - FP)};
-        for (int k = 0; k < 6; ++k) b.sm_anchor[k] = std::log(v[k]);
-    }
+    b.err_prob = 0.0; b.learn = b.fixed_assign = false; std::fill(b.err_prior, b.err_prior + 4, 0.0);
     b.h_k.assign(C, 0); b.h_used.assign(C, 0);
     b.valid = true;
     return 0;
@@ -1064,12 +1185,15 @@ int lsg_bnpcs_run(lsg_ctx* c, int32_t first_step, int32_t n_steps, int32_t burn_
     int64_t* d_used = reinterpret_cast<int64_t*>(b.err.as<int32_t>() + b.n_chains + (b.n_chains & 1));
     for (int32_t s = first_step; s < first_step + n_steps; ++s) {
         if (s > 0 && b.pending != s) {
-            if (int rc = launch_sweep(c, (uint32_t)s, b.sm_prob > 0)) return rc;
-            if (b.sm_prob > 0) if (int rc = launch_sm(c, (uint32_t)s, 0)) return rc;
+            if (!b.fixed_assign) {
+                if (int rc = launch_sweep(c, (uint32_t)s, b.sm_prob > 0)) return rc;
+                if (b.sm_prob > 0) if (int rc = launch_sm(c, (uint32_t)s, 0)) return rc;
+            }
             if (fetch_live(c, who)) return -1;
             if (int rc = launch_counts_tables(c)) return rc;
             if (int rc = launch_mh(c, (uint32_t)s)) return rc;
             hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, dev_of(b));
+            if (b.learn) if (int rc = launch_err(c, (uint32_t)s)) return rc;
         }
         b.pending = s;
         const bool keep = s >= burn_in;
@@ -1128,6 +1252,57 @@ int lsg_bnpcs_fetch_moves(lsg_ctx* c, int8_t* moves) {
     LSG_HIP(hipMemcpyAsync(codes.data(), b.rec_sm.p, codes.size() * 4, hipMemcpyDeviceToHost, c->stream));
     if (sync_check(c, who)) return -1;
     for (size_t k = 0; k < codes.size(); ++k) moves[k] = (int8_t)codes[k];
+    return 0;
+}
+
+int lsg_bnpcs_set_error_learning(lsg_ctx* c, double prob, double fp_mean, double fp_sd, double fn_mean, double fn_sd) {
+    const char* who = "lsg_bnpcs_set_error_learning";
+    if (int rc = need(c, who)) return rc;
+    const double v[4] = {fp_mean, fp_sd, fn_mean, fn_sd};
+    bool ok = prob >= 0 && prob <= 1;
+    for (double x : v) ok = ok && x > 0 && x < 1;
+    if (!ok) {
+        set_error("%s: the probability must lie in [0, 1], the means and the sds inside (0, 1), got %g and FP (%g, %g), FN (%g, %g)", who, prob, fp_mean, fp_sd, fn_mean, fn_sd);
+        return -2;
+    }
+    Bnpcs& b = c->bnpcs;
+    Rates r;
+    rates_fill(r, fp_mean, fn_mean, b.mix[0], b.mix[1]);
+    const std::vector<Rates> all((size_t)b.n_chains, r);
+    LSG_HIP(hipMemcpyAsync(b.rates.p, all.data(), all.size() * sizeof(Rates), hipMemcpyHostToDevice, c->stream));
+    LSG_HIP(hipStreamSynchronize(c->stream));
+    b.err_prob = prob; std::copy(v, v + 4, b.err_prior); b.learn = true; b.prepared = false;
+    return 0;
+}
+
+int lsg_bnpcs_set_error_rates(lsg_ctx* c, int32_t chain, double fp, double fn) {
+    const char* who = "lsg_bnpcs_set_error_rates";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (chain < 0 || chain >= b.n_chains) { set_error("%s: bad arguments", who); return -2; }
+    if (!(fp > 0 && fp < 1 && fn > 0 && fn < 1)) { set_error("%s: the rates must lie inside (0, 1), got FP %g and FN %g", who, fp, fn); return -2; }
+    Rates r;
+    rates_fill(r, fp, fn, b.mix[0], b.mix[1]);
+    LSG_HIP(hipMemcpyAsync(b.rates.as<Rates>() + chain, &r, sizeof(Rates), hipMemcpyHostToDevice, c->stream));
+    LSG_HIP(hipStreamSynchronize(c->stream));
+    b.prepared = false;
+    return 0;
+}
+
+int lsg_bnpcs_fetch_error_rates(lsg_ctx* c, double* rates, int32_t* counts) {
+    const char* who = "lsg_bnpcs_fetch_error_rates";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (!rates || !counts) { set_error("%s: bad arguments", who); return -2; }
+    LSG_HIP(hipMemcpyAsync(rates, b.rec_err.p, (size_t)b.n_chains * b.steps1 * 2 * 8, hipMemcpyDeviceToHost, c->stream));
+    LSG_HIP(hipMemcpyAsync(counts, b.err_cnt.p, (size_t)b.n_chains * 4 * 4, hipMemcpyDeviceToHost, c->stream));
+    return sync_check(c, who);
+}
+
+int lsg_bnpcs_set_fixed_assignment(lsg_ctx* c, int32_t on) {
+    const char* who = "lsg_bnpcs_set_fixed_assignment";
+    if (int rc = need(c, who)) return rc;
+    c->bnpcs.fixed_assign = on != 0;
     return 0;
 }
 
@@ -1204,8 +1379,13 @@ int lsg_bnpcs_test_move(lsg_ctx* c, int32_t what, int32_t step) {
     const char* who = "lsg_bnpcs_test_move";
     if (int rc = need(c, who)) return rc;
     Bnpcs& b = c->bnpcs;
-    if (what < 0 || what > 2 || step < 0) { set_error("%s: bad arguments", who); return -2; }
+    if (what < 0 || what > 3 || step < 0) { set_error("%s: bad arguments", who); return -2; }
+    if (what == 3 && !b.learn) { set_error("%s: no error-rate update (lsg_bnpcs_set_error_learning first)", who); return -2; }
     if (int rc = prepare(c, who)) return rc;
+    if (what == 3) {
+        if (int rc = launch_err(c, (uint32_t)step)) return rc;
+        return sync_check(c, who);
+    }
     if (what == 0 || what == 2) {
         if (what == 0) { if (int rc = launch_sweep(c, (uint32_t)step, 0)) return rc; }
         else if (int rc = launch_sm(c, (uint32_t)step, 1)) return rc;
@@ -1225,5 +1405,14 @@ int lsg_bnpcs_test_move_outcome(lsg_ctx* c, int32_t chain, double* outcome) {
     if (chain < 0 || chain >= b.n_chains || !outcome) { set_error("%s: bad arguments", who); return -2; }
     const size_t per = 6 * (size_t)b.n_cells + 6 * (size_t)b.n_muts + SM_OUT;
     LSG_HIP(hipMemcpyAsync(outcome, b.sm_d.as<double>() + (chain + 1) * per - SM_OUT, SM_OUT * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync_check(c, who);
+}
+
+int lsg_bnpcs_test_error_outcome(lsg_ctx* c, int32_t chain, double* outcome) {
+    const char* who = "lsg_bnpcs_test_error_outcome";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (chain < 0 || chain >= b.n_chains || !outcome) { set_error("%s: bad arguments", who); return -2; }
+    LSG_HIP(hipMemcpyAsync(outcome, b.err_out.as<double>() + (size_t)chain * ERR_OUT, ERR_OUT * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_check(c, who);
 }

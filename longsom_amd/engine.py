@@ -741,6 +741,27 @@ class Engine:
         _lib.check(self._lib.lsg_bnpcs_fetch_moves(self._h, _ptr(moves)), "lsg_bnpcs_fetch_moves")
         return moves
 
+    def bnpcs_set_error_learning(self, prob: float, fp_mean: float, fp_sd: float, fn_mean: float, fn_sd: float) -> None:
+        """every chain gets error rates of its own, started at the priors' means, and updates them with this probability per step
+        (lsg_bnpcs_set_error_learning); after bnpcs_create"""
+        _lib.check(self._lib.lsg_bnpcs_set_error_learning(self._h, float(prob), float(fp_mean), float(fp_sd), float(fn_mean), float(fn_sd)), "lsg_bnpcs_set_error_learning")
+
+    def bnpcs_set_error_rates(self, chain: int, fp: float, fn: float) -> None:
+        """one chain's error rates (lsg_bnpcs_set_error_rates)"""
+        _lib.check(self._lib.lsg_bnpcs_set_error_rates(self._h, int(chain), float(fp), float(fn)), "lsg_bnpcs_set_error_rates")
+
+    def bnpcs_fetch_error_rates(self):
+        """(rates [C, steps + 1, 2]: FP, FN as each step recorded them; counts [C, 4]: FP accepted, declined, FN accepted, declined)
+        (lsg_bnpcs_fetch_error_rates)"""
+        Cn, S1, _, _, _ = self._bnpcs_shape
+        rates = np.zeros((Cn, S1, 2), np.float64); counts = np.zeros((Cn, 4), np.int32)
+        _lib.check(self._lib.lsg_bnpcs_fetch_error_rates(self._h, _ptr(rates), _ptr(counts)), "lsg_bnpcs_fetch_error_rates")
+        return rates, counts
+
+    def bnpcs_set_fixed_assignment(self, on: bool) -> None:
+        """the steps keep the loaded labels: no sweep, no split-merge move, no concentration update (lsg_bnpcs_set_fixed_assignment)"""
+        _lib.check(self._lib.lsg_bnpcs_set_fixed_assignment(self._h, 1 if on else 0), "lsg_bnpcs_set_fixed_assignment")
+
     def bnpcs_errors(self) -> np.ndarray:
         """per chain, the gamma variates that ran out of tries, as of the last bnpcs_fetch"""
         return self._bnpcs_errors
@@ -782,6 +803,17 @@ class Engine:
         _lib.check(self._lib.lsg_bnpcs_test_move_outcome(self._h, int(chain), _ptr(o)), "lsg_bnpcs_test_move_outcome")
         return {"code": int(o[0]), "clusters": (int(o[1]), int(o[2])), "anchors": (int(o[3]), int(o[4])), "A": float(o[5]), "terms": o[6:10].copy(), "lv": float(o[10]),
                 "n_S": int(o[11])}
+
+    def bnpcs_test_error_outcome(self, chain: int):
+        """a chain's last error-rate update (bnpcs_test_move(3, step)): None where its deciding draw said no update, else per rate a dict of
+        pick (the sd's index), new, new_ll, old_ll, prior (new - old), new_p, old_p, A, lv and code (1 accepted, 0 declined, -1 declined
+        because rounding put the proposal on an end) (lsg_bnpcs_test_error_outcome)"""
+        o = np.zeros(21, np.float64)
+        _lib.check(self._lib.lsg_bnpcs_test_error_outcome(self._h, int(chain), _ptr(o)), "lsg_bnpcs_test_error_outcome")
+        if not o[0]:
+            return None
+        names = ("pick", "new", "new_ll", "old_ll", "prior", "new_p", "old_p", "A", "lv", "code")
+        return {rate: {k: (int(v) if k in ("pick", "code") else float(v)) for k, v in zip(names, o[1 + 10 * e:11 + 10 * e])} for e, rate in enumerate(("FP", "FN"))}
 
     def betabinom_sf4(self, k, n, alpha: float, beta: float) -> np.ndarray:
         """round(betabinom.sf(k - 0.001, n, alpha, beta), 4) * 1e4 as int32, evaluated on the device."""

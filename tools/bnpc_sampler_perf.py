@@ -5,6 +5,8 @@ own calls, so that the first steps and the late steps can be timed apart).
   device      seconds per step over the first 10 steps from the random start, and over 100 steps after step 200
   --sm_prob P --sm_steps S   with the split-merge move in a share P of the steps, S restricted scans each (run_BnpC.py's -smp, -sms; the
               ratios stay 0.75 / 0.25); the result then counts the moves of each kind over all chains and steps
+  --eup P     with the error rates learned: the update in a share P of the steps (run_BnpC.py's -eup), priors FP (0.01, 0.01) and FN
+              (0.1, 0.1) around the rates the other runs keep fixed; the result then counts the moves of each rate over all chains
   --reference DIR   also time the reference's sampler (libs/CRP.py, libs/MCMC.py of the LongSom checkout DIR, with the same --sm_prob) at the same
               shape on this host, one process per chain: its first 10 steps from its random start, and 10 steps from the planted partition
               (the state a chain is in after a few hundred steps), per step
@@ -35,7 +37,7 @@ def planted(N, M, K, seed=1):
     return data, truth
 
 
-def device(data, chains, late_only, sm_prob=0.0, sm_steps=3):
+def device(data, chains, late_only, sm_prob=0.0, sm_steps=3, eup=0.0):
     from longsom_amd import bnpc_sampler as bs
     from longsom_amd.engine import Engine
     model = bs.Model(data, 0.1, 0.01)
@@ -46,6 +48,8 @@ def device(data, chains, late_only, sm_prob=0.0, sm_steps=3):
         e.bnpcs_create(model, seeds, steps, 1 << 15)
         if sm_prob > 0:
             e.bnpcs_set_split_merge(sm_prob, 0.75, 0.25, sm_steps)
+        if eup > 0:
+            e.bnpcs_set_error_learning(eup, 0.01, 0.01, 0.1, 0.1)
         for c, s in enumerate(seeds):
             st = bs.initial_state(model, s)
             e.bnpcs_set_state(c, st.labels, st.theta, st.alpha)
@@ -67,6 +71,10 @@ def device(data, chains, late_only, sm_prob=0.0, sm_steps=3):
             seen = np.bincount(e.bnpcs_fetch_moves().ravel(), minlength=5)
             out["moves"] = {"sweeps": int(seen[0]) - chains, "splits_declined": int(seen[1]), "splits_accepted": int(seen[2]), "merges_declined": int(seen[3]),
                             "merges_accepted": int(seen[4])}
+        if eup > 0:
+            rates, moves = e.bnpcs_fetch_error_rates()
+            out["error_moves"] = dict(zip(("FP_accepted", "FP_declined", "FN_accepted", "FN_declined"), (int(x) for x in moves.sum(axis=0))))
+            out["rates_at_300"] = {"FP": float(rates[:, 300, 0].mean()), "FN": float(rates[:, 300, 1].mean())}
         e.bnpcs_destroy()
     return out
 
@@ -106,13 +114,14 @@ def main():
     ap.add_argument("--chains", type=int, default=16)
     ap.add_argument("--reference", default="", help="root of a LongSom checkout: time its sampler too")
     ap.add_argument("--sm_prob", type=float, default=0.0); ap.add_argument("--sm_steps", type=int, default=3)
+    ap.add_argument("--eup", type=float, default=0.0, help="the share of the steps that update the error rates (device only)")
     ap.add_argument("--no_device", action="store_true"); ap.add_argument("--late_only", action="store_true", help="50 steps only: what a profiler should see")
     a = ap.parse_args()
     data, truth = planted(a.cells, a.muts, a.clusters)
     out = {"cells": a.cells, "muts": a.muts, "clusters": a.clusters, "chains": a.chains, "cpus": os.cpu_count()}
     if not a.no_device:
-        out["sm_prob"], out["sm_steps"] = a.sm_prob, a.sm_steps
-        out["device"] = device(data, a.chains, a.late_only, a.sm_prob, a.sm_steps)
+        out["sm_prob"], out["sm_steps"], out["eup"] = a.sm_prob, a.sm_steps, a.eup
+        out["device"] = device(data, a.chains, a.late_only, a.sm_prob, a.sm_steps, a.eup)
     if a.reference:
         out["reference"] = reference(a.reference, data, truth, a.chains, a.sm_prob, a.sm_steps)
     print(json.dumps(out))

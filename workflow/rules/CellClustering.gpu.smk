@@ -10,6 +10,8 @@
 # runs on the GPU too, all chains at once, with the reference's own settings: Gibbs sweeps, the split-merge move in a third of the steps
 # (--sampler device-sm, no -smp passed, so run_BnpC.py's defaults -smp 0.33 -sms 3 -smr 0.75 0.25 apply as in the reference's rule), the
 # parameter moves, fixed error rates.  CellClust.BnpC.sampler: device is the same without the split-merge move (--sampler device -smp 0).
+# CellClust.BnpC.sampler: device-errors is device-sm with the error rates learned (--sampler device-errors): the rule passes the config's
+# -eup, and any value of it runs on the GPU, where device and device-sm need eup: 0.
 
 GPU_SCRIPTS = str(workflow.basedir) + "/scripts_gpu"
 FUSE_BNPC = config['Run'].get('fuse_bnpc_input', False)
@@ -124,7 +126,7 @@ rule BnpC_clustering:
         FP = config['CellClust']['BnpC']['FP'],
         FN = config['CellClust']['BnpC']['FN'],
         pp= config['CellClust']['BnpC']['pp'],
-        sampler={'device': "--sampler device -smp 0", 'device-sm': "--sampler device-sm"}.get(config['CellClust']['BnpC'].get('sampler', 'reference'), ""),
+        sampler={'device': "--sampler device -smp 0", 'device-sm': "--sampler device-sm", 'device-errors': "--sampler device-errors"}.get(config['CellClust']['BnpC'].get('sampler', 'reference'), ""),
     conda:
         "../envs/BnpC.yaml"
     threads: 16
