@@ -558,7 +558,19 @@ int lsg_bnpc_unload(lsg_ctx* ctx);
  * declined (Chain.MH_counter[3], [4], MCMC.py:340-342).
  * lsg_bnpcs_set_fixed_assignment: with on != 0 a step makes neither the sweep, nor the split-merge move, nor the concentration update
  * (Chain.do_step with fix_assign, MCMC.py:321-333): the labels stay the loaded ones; the parameter move, the error update and the record
- * run as always. */
+ * run as always.
+ * lsg_bnpcs_extend makes room for add_steps more recorded steps: the run's n_steps grows by add_steps.  Every chain's state, the records
+ * made so far, the arena and its fill, the moves' and the rates' counts and the next step stay; the layouts of lsg_bnpcs_fetch, _fetch_moves
+ * and _fetch_error_rates hold for the new n_steps.  A chain's stream is a function of (seed, step, purpose), so an extended chain is the
+ * chain a create with the larger n_steps would have made.  Refused: before a create, add_steps < 1, and a step count that lsg_bnpcs_create
+ * would refuse for its size (the message names the steps it would reach); then, and when the device has no room, the run stays as it was.
+ * lsg_bnpcs_psrf: what the lugsail batch-means PSRF (utils.get_lugsail_batch_means_est, utils.py:427-467) needs of every chain's ML
+ * records first[chain] .. last - 1, stats [n_chains][5]: their number n, their mean, their sample variance (ddof 1), tau(b) and tau(b / 3)
+ * with b = int(n ** 0.5) and tau(b) = b / (a - 1) sum (batch mean - mean)^2 over the a = n / b whole batches of b (get_tau_lugsail,
+ * :464-467); both are 0 where n < 9.  The sums are of ML - ML[first], in two passes, in double.  Nothing but stats is moved to the host.
+ * Refused: last past the records made, first[chain] < 0 or > last. */
+int lsg_bnpcs_extend(lsg_ctx* ctx, int32_t add_steps);
+int lsg_bnpcs_psrf(lsg_ctx* ctx, const int32_t* first, int32_t last, double* stats);
 int lsg_bnpcs_create(lsg_ctx* ctx, int32_t n_cells, int32_t n_muts, int32_t n_chains, int32_t n_steps, const uint64_t* one, const uint64_t* zero, const double* cfg,
                      const uint64_t* seeds, int64_t arena_rows);
 int lsg_bnpcs_set_state(lsg_ctx* ctx, int32_t chain, const int32_t* labels, const float* theta, double dp_alpha);

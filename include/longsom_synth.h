@@ -57,7 +57,9 @@ int lsg_copy_reference_to_host(lsg_ctx* ctx, int32_t tid, uint8_t* out);
  * split: the cluster and the smallest free id), the two anchors, A, its four terms in the order they are added, ln v, |S|.
  * lsg_bnpcs_test_error_outcome: a chain's last error-rate update (what = 3), outcome [21]: 1 if the deciding draw said update, else 0; then
  * for FP and for FN ten numbers: the index of the proposal's sd, the proposed rate, new_ll, old_ll, new_prior - old_prior, new_p_target,
- * old_p_target, A, ln v, the decision (1 accepted, 0 declined, -1 declined because rounding put the proposal at <= 0 or >= 1). */
+ * old_p_target, A, ln v, the decision (1 accepted, 0 declined, -1 declined because rounding put the proposal at <= 0 or >= 1).
+ * lsg_bnpcs_test_set_ml: writes values [n] as the ML records first .. first + n - 1 of a chain, so that lsg_bnpcs_psrf can be held to given
+ * series; lsg_bnpcs_psrf then takes the records below first + n as made.  Refused: records past the room lsg_bnpcs_create / _extend made. */
 int lsg_bnpcs_test_stream(lsg_ctx* ctx, uint64_t key, int64_t n, const uint32_t* counters, uint32_t* words, double* doubles);
 int lsg_bnpcs_test_variates(lsg_ctx* ctx, uint64_t key, int32_t kind, int64_t n, double a, double b, double* out, int32_t* errors);
 int lsg_bnpcs_test_counts(lsg_ctx* ctx, int32_t chain, uint32_t* n1, uint32_t* n0);
@@ -65,6 +67,7 @@ int lsg_bnpcs_test_ll(lsg_ctx* ctx, int32_t chain, double* ll, int32_t* clusters
 int lsg_bnpcs_test_move(lsg_ctx* ctx, int32_t what, int32_t step);
 int lsg_bnpcs_test_move_outcome(lsg_ctx* ctx, int32_t chain, double* outcome);
 int lsg_bnpcs_test_error_outcome(lsg_ctx* ctx, int32_t chain, double* outcome);
+int lsg_bnpcs_test_set_ml(lsg_ctx* ctx, int32_t chain, int32_t first, int32_t n, const double* values);
 
 #ifdef __cplusplus
 }

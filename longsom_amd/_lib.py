@@ -194,6 +194,8 @@ SIGNATURES = {
     "lsg_bnpcs_set_error_rates": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double]),
     "lsg_bnpcs_fetch_error_rates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsg_bnpcs_set_fixed_assignment": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lsg_bnpcs_extend": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lsg_bnpcs_psrf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "lsg_bnpcs_destroy": (C.c_int, [C.c_void_p]),
     "lsg_bnpcs_test_stream": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsg_bnpcs_test_variates": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
@@ -202,6 +204,7 @@ SIGNATURES = {
     "lsg_bnpcs_test_move": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "lsg_bnpcs_test_move_outcome": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "lsg_bnpcs_test_error_outcome": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "lsg_bnpcs_test_set_ml": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "lsg_betabinom_sf4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "lsg_betabinom_sf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "lsg_max_live_reads": (C.c_int64, [C.c_void_p]),

@@ -1,7 +1,7 @@
 """BnpC's sampler (scripts/CellClustering/libs/CRP.py:17-410, libs/CRP_learning_errors.py, libs/MCMC.py:200-388): Gibbs assignment
 sweeps, the non-conjugate split-merge move (CRP.py:417-820), the Escobar-West concentration update, the parameter Metropolis-Hastings
-and the Metropolis-Hastings updates of the error rates, all chains of a run at once; --fixed_assignment is a start state and a flag.
---runtime, --lugsail and --single_chains are not here.
+and the Metropolis-Hastings updates of the error rates, all chains of a run at once; --fixed_assignment is a start state and a flag;
+--steps, --lugsail and --runtime are three stop rules over the same chains.  --single_chains is not here.
 
 run_chains        the sampler on the device (csrc/bnpc_sampler.hip, lsg_bnpcs_*)
 run_chains_host   its twin in numpy: what the CPU tests hold to the reference's goldens, and the GPU tests compare the device against
@@ -113,6 +113,20 @@ as dpmmIO.load_txt reads them (:101-112) and compacted to 0 .. K-1 in ascending 
 float32, of block (m, 0, P_INIT_ASSIGN | k << 8, .).  A step makes neither the sweep, nor the split-merge move, nor the concentration
 update, and consumes no draw of theirs: only the parameter move and the error update run.  All chains start from the same labels and
 differ by their seeds.
+THE STOP RULES (dpmmIO._get_mcmc_termination, dpmmIO.py:158-169; MCMC.run, MCMC.py:79-123).  A chain's draws are a function of (seed, step,
+purpose) alone, so a chain that is extended IS the longer chain: nothing below changes what any step does.
+  steps     `steps` steps, the first `burn_in` of which keep no parameters.
+  Lugsail   run_lugsail_chains (MCMC.py:138-177).  A first run of max(10, int(1 / (cutoff^2 - 1))) steps that keeps every step's parameters,
+            step 0 included; then, with steps_run the records so far: PSRF = get_lugsail_batch_means_est over ML[steps_run // 2:] of every
+            chain (utils.py:427-467; lugsail_psrf here, lsg_bnpcs_psrf on the device); (steps_run, PSRF) joins the result's "PSRF" list; at or
+            below the cutoff the run ends, else the chains go on for `extend` (200) steps.  At the end burn_in = steps_run // 2 + 1, params =
+            params[burn_in:] and "PSRF_cutoff" = cutoff.  An extension that is refused for room ends the run with an error.
+            Where this differs from the reference: MCMC.extend_chain (:180-188) re-seeds numpy with the chain's seed before every extension,
+            so its chains replay the random numbers of their start every 200 steps; these do not.
+  Runtime   Chain_time (MCMC.py:395-440).  Steps in batches; the clock is read before each batch; no batch starts after `end`; the first step
+            of the first batch that starts at or after `burn_in_end` is the first kept one, and step 0 never is; burn_in = the records minus
+            the kept ones.  Where this differs from the reference: the chains run in lockstep, so all have the same length (the reference's
+            run in processes of their own and end with different lengths), and the clock is read per batch, not per step.
 The start (CRP.init(mode='random'), :139-148, :176-180): label i = floor(N u) of block (i, 0, P_INIT_LABEL, 0), compacted to 0 .. K-1 in
 ascending order; theta[k][m] = clip(u) of block (m, 0, P_INIT_THETA | k << 8, 0); alpha = the mean of scipy's gamma(*DP_a_gamma), whose
 second number is a `loc`: g0 + g1, so a negative -ap gives (sqrt N, 1) and a start at sqrt N + 1.
@@ -960,8 +974,81 @@ def _finish_result(model, r):
     return r
 
 
-def _check_run(steps, burn_in, sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3):
-    if steps < 1 or not 0 <= burn_in <= steps:
+# ---- the stop rules: run_BnpC.py's -s, -ls and -r (dpmmIO._get_mcmc_termination, dpmmIO.py:158-169) ---------------------------------------
+_NEVER = 2 ** 31 - 1                                                  # the first kept step of a run that keeps none yet
+
+
+class Lugsail:
+    """--lugsail: run until the lugsail batch-means PSRF of the chains' ML, over the second half of their records, is at most `cutoff`
+    (MCMC.run, MCMC.py:85-90; run_lugsail_chains, :138-177).  The first run has max(10, int(1 / (cutoff^2 - 1))) steps; after every check
+    above the cutoff the chains go on for `extend` steps.  report(steps_run, psrf) is called at every check."""
+
+    def __init__(self, cutoff, extend=200, report=None):
+        cutoff, extend = float(cutoff), int(extend)
+        if not cutoff > 1:
+            raise ValueError("lugsail cutoff %r: it must be above 1 (the first run has int(1 / (cutoff^2 - 1)) steps, which 1 divides by zero)" % (cutoff,))
+        if extend < 1:
+            raise ValueError("lugsail extend must be at least 1, got %d" % extend)
+        self.cutoff, self.extend, self.report = cutoff, extend, report
+        self.first_steps = max(10, int(1 / (cutoff ** 2 - 1)))
+
+
+class Runtime:
+    """--runtime: steps in batches of `batch` until clock() passes `end`; the clock is read before each batch, no batch starts after `end`,
+    and the first step of the first batch that starts at or after `burn_in_end` is the first kept one (Chain_time, MCMC.py:395-440, which
+    reads the clock before each step).  clock() returns what compares with end and burn_in_end: datetimes, or numbers."""
+
+    def __init__(self, end, burn_in_end, clock, batch=50):
+        if int(batch) < 1:
+            raise ValueError("runtime batch must be at least 1, got %r" % (batch,))
+        self.end, self.burn_in_end, self.clock, self.batch = end, burn_in_end, clock, int(batch)
+
+
+def ml_stats(series, first, last=None):
+    """n, the mean, the sample variance (ddof 1), tau(b) and tau(b // 3) of series[first:last] (get_tau_lugsail, utils.py:464-467; b =
+    int(n ** 0.5)): what lsg_bnpcs_psrf returns per chain.  The sums are of x - x[first], in two passes."""
+    x = np.asarray(series, dtype=np.float64)[first:last]
+    n = x.size
+    if n < 1:
+        return np.zeros(5)
+    pivot = x[0]
+    x = x - pivot
+    mean = x.sum() / n
+    var = float(np.square(x - mean).sum() / (n - 1)) if n > 1 else 0.0
+    taus = [0.0, 0.0]
+    if n >= 9:
+        b = int(n ** 0.5)
+        for k, size in enumerate((b, b // 3)):
+            a = n // size
+            taus[k] = size / (a - 1) * float(np.square(x[:a * size].reshape(a, size).sum(axis=1) / size - mean).sum())
+    return np.array([n, pivot + mean, var, taus[0], taus[1]])
+
+
+def psrf_of_stats(stats):
+    """get_lugsail_batch_means_est (utils.py:427-461) from the chains' five statistics [C][5] (ml_stats, lsg_bnpcs_psrf): inf where a chain
+    has fewer than 9 values, and where the reference's FloatingPointError is (MCMC.py:20's np.seterr: a mean variance of 0, a negative
+    quotient under the root)"""
+    stats = np.asarray(stats, dtype=np.float64).reshape(-1, 5)
+    if (stats[:, 0] < 9).any():
+        return np.inf
+    T_L = np.mean(2 * stats[:, 3] - stats[:, 4])
+    s = np.mean(stats[:, 2])
+    n = np.round(np.mean(stats[:, 0]))
+    sigma_L = ((n - 1) * s + T_L) / n
+    if s == 0 or not sigma_L / s >= 0:
+        return np.inf
+    return float(np.sqrt(sigma_L / s))
+
+
+def lugsail_psrf(chains):
+    """utils.get_lugsail_batch_means_est of chains = [(series, burn_in), ...]"""
+    return psrf_of_stats([ml_stats(series, burn_in) for series, burn_in in chains])
+
+
+def _check_run(steps, burn_in, sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3, stop=None):
+    if stop is not None and not isinstance(stop, (Lugsail, Runtime)):
+        raise ValueError("stop must be None (steps and burn_in hold), a Lugsail or a Runtime, got %r" % (stop,))
+    if stop is None and (steps < 1 or not 0 <= burn_in <= steps):
         raise ValueError("steps must be at least 1 and burn_in within [0, steps], got %d and %d" % (steps, burn_in))
     if not 0 <= sm_prob <= 1 or len(sm_ratios) != 2 or min(sm_ratios) <= 0 or abs(sum(sm_ratios) - 1) > 1e-9 or not 0 <= sm_steps <= MAX_SM_STEPS:
         raise ValueError("sm_prob must lie in [0, 1], sm_ratios be two positive numbers that sum to 1 and sm_steps be in [0, %d], got %r, %r and %r"
@@ -991,102 +1078,226 @@ def _start_states(model, seeds, states, fixed_assignment):
 
 
 def run_chains_host(data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None,
-                    sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3, error_prob=0.0, error_priors=None, fixed_assignment=None):
+                    sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3, error_prob=0.0, error_priors=None, fixed_assignment=None, stop=None):
     """The whole sampler in numpy.  seeds: one 64-bit seed per chain.  states: start there instead of at the random initialisation.
+    stop: None (the run has `steps` steps, the first `burn_in` of which keep no parameters), a Lugsail or a Runtime, under which steps and
+    burn_in are not read (pass None): see THE STOP RULES above.
     sm_prob, sm_ratios, sm_steps: run_BnpC.py's -smp, -smr, -sms; the result's sm_moves [steps + 1] says what each step did.
     error_prob, error_priors: -eup and (-FP_m, -FP_sd, -FN_m, -FN_sd): the result's FP / FN are then the rates of each step and error_moves
     the moves' counts (FP accepted, declined, FN accepted, declined).  fixed_assignment: -fa's labels [N]; the steps keep them."""
-    _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps)
+    _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps, stop)
     shared = _error_model(data, FN, FP, pp, dpa, dpa_prob, error_prior, error_prob, error_priors)
-    fixed = fixed_assignment is not None
-    out = []
-    for c, start in enumerate(_start_states(shared, seeds, states, fixed_assignment)):
-        seed = seeds[c]
-        st = State(start.labels, start.theta, start.alpha, start.FP, start.FN)
-        model = shared.of_chain(st.FP, st.FN)
-        r = _empty_result(model, steps, burn_in)
-        errors = 0
-        for s in range(steps + 1):
-            if s:
-                if not fixed:
-                    if takes_split_merge(seed, s, sm_prob):
-                        move = split_merge_move(model, st, seed, s, sm_ratios, sm_steps)
-                        errors += move["errors"]
-                        r["sm_moves"][s] = move["code"]
-                    else:
-                        errors += gibbs_sweep(model, st, seed, s)
-                    errors += alpha_update(model, st, seed, s)
-                parameter_move(model, st, seed, s)
-                if model.learning:
-                    move = error_update(model, st, seed, s)
-                    if move is not None:
-                        for e, rate in enumerate(("FP", "FN")):
-                            r["error_moves"][2 * e + (0 if move[rate]["code"] == 1 else 1)] += 1
-                            errors += move[rate]["code"] == -1
-            live = st.live()
-            r["ML"][s] = likelihood(model, st.labels, st.theta[live])[0]
-            r["_crp"][s], r["_beta"][s] = prior_parts(model, st)
-            r["DP_alpha"][s] = st.alpha
-            r["FP"][s], r["FN"][s] = model.FP, model.FN
-            r["assignments"][s] = st.labels
-            if s >= burn_in:
-                r["_rows"].append(st.theta[live].copy())
-        r["variate_errors"] = int(errors)
-        out.append(_finish_result(model, r))
-    return out
+    run = _HostRun(shared, seeds, _start_states(shared, seeds, states, fixed_assignment), sm_prob, sm_ratios, sm_steps, fixed_assignment is not None)
+    return _drive(run, steps, burn_in, stop)
 
 
-def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None, arena_rows=0,
-               sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3, error_prob=0.0, error_priors=None, fixed_assignment=None):
-    """The same on the device, all chains in every kernel.  arena_rows: the parameter rows per chain the device holds between two fetches
-    (0: enough for 64 kept steps of 64 clusters, at least N rows); a full arena only costs a fetch."""
-    _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps)
-    model = _error_model(data, FN, FP, pp, dpa, dpa_prob, error_prior, error_prob, error_priors)
-    seeds = [int(s) for s in seeds]
-    start = _start_states(model, seeds, states, fixed_assignment)
-    arena_rows = int(arena_rows) or max(model.N, 4096)
-    engine.bnpcs_create(model, seeds, steps, arena_rows)
-    try:
+class _HostRun:
+    """the chains of run_chains_host under _drive: open(steps), advance(n, keep_from), stats(first), extend(add), results(burn_in)"""
+
+    def __init__(self, shared, seeds, start, sm_prob, sm_ratios, sm_steps, fixed):
+        self.sm, self.fixed, self.done = (sm_prob, sm_ratios, sm_steps), fixed, 0
+        self.chains = []
+        for seed, s0 in zip(seeds, start):
+            st = State(s0.labels, s0.theta, s0.alpha, s0.FP, s0.FN)
+            self.chains.append({"seed": seed, "st": st, "model": shared.of_chain(st.FP, st.FN), "errors": 0})
+
+    def open(self, steps):
+        for ch in self.chains:
+            ch["r"] = _empty_result(ch["model"], steps, 0)
+
+    def extend(self, add):
+        for ch in self.chains:
+            r, more = ch["r"], _empty_result(ch["model"], add - 1, 0)
+            for k in ("ML", "MAP", "DP_alpha", "FN", "FP", "assignments", "_crp", "_beta", "sm_moves"):
+                r[k] = np.concatenate([r[k], more[k]])
+
+    def advance(self, n, keep_from):
+        sm_prob, sm_ratios, sm_steps = self.sm
+        for ch in self.chains:
+            seed, st, model, r = ch["seed"], ch["st"], ch["model"], ch["r"]
+            errors = 0
+            for s in range(self.done, self.done + n):
+                if s:
+                    if not self.fixed:
+                        if takes_split_merge(seed, s, sm_prob):
+                            move = split_merge_move(model, st, seed, s, sm_ratios, sm_steps)
+                            errors += move["errors"]
+                            r["sm_moves"][s] = move["code"]
+                        else:
+                            errors += gibbs_sweep(model, st, seed, s)
+                        errors += alpha_update(model, st, seed, s)
+                    parameter_move(model, st, seed, s)
+                    if model.learning:
+                        move = error_update(model, st, seed, s)
+                        if move is not None:
+                            for e, rate in enumerate(("FP", "FN")):
+                                r["error_moves"][2 * e + (0 if move[rate]["code"] == 1 else 1)] += 1
+                                errors += move[rate]["code"] == -1
+                live = st.live()
+                r["ML"][s] = likelihood(model, st.labels, st.theta[live])[0]
+                r["_crp"][s], r["_beta"][s] = prior_parts(model, st)
+                r["DP_alpha"][s] = st.alpha
+                r["FP"][s], r["FN"][s] = model.FP, model.FN
+                r["assignments"][s] = st.labels
+                if s >= keep_from:
+                    r["_rows"].append(st.theta[live].copy())
+            ch["errors"] += int(errors)
+        self.done += n
+
+    def stats(self, first):
+        return np.array([ml_stats(ch["r"]["ML"], first, self.done) for ch in self.chains])
+
+    def results(self, burn_in):
+        out = []
+        for ch in self.chains:
+            r = ch["r"]
+            for k in ("ML", "MAP", "DP_alpha", "FN", "FP", "assignments", "_crp", "_beta", "sm_moves"):
+                r[k] = r[k][:self.done]
+            r["burn_in"], r["variate_errors"] = burn_in, ch["errors"]
+            out.append(_finish_result(ch["model"], r))
+        return out
+
+
+class _DeviceRun:
+    """the chains of run_chains under _drive.  The arena is emptied when it is full and at the end; a convergence check moves five numbers
+    per chain to the host (engine.bnpcs_psrf)."""
+
+    def __init__(self, engine, model, seeds, start, arena_rows, sm_prob, sm_ratios, sm_steps, fixed):
+        self.engine, self.model, self.seeds, self.start, self.arena_rows = engine, model, seeds, start, arena_rows
+        self.sm, self.fixed, self.done, self.taken, self.keep_from = (sm_prob, sm_ratios, sm_steps), fixed, 0, 0, _NEVER
+        self.rows = [[] for _ in seeds]
+
+    def open(self, steps):
+        engine, model = self.engine, self.model
+        sm_prob, sm_ratios, sm_steps = self.sm
+        engine.bnpcs_create(model, self.seeds, steps, self.arena_rows)
         if sm_prob > 0:
             engine.bnpcs_set_split_merge(sm_prob, sm_ratios[0], sm_ratios[1], sm_steps)
         if model.learning:
             engine.bnpcs_set_error_learning(model.error_prob, *model.error_priors)
-        if fixed_assignment is not None:
+        if self.fixed:
             engine.bnpcs_set_fixed_assignment(True)
-        for c, st in enumerate(start):
+        for c, st in enumerate(self.start):
             engine.bnpcs_set_state(c, st.labels, st.theta, st.alpha)
             if st.FP is not None:
                 engine.bnpcs_set_error_rates(c, st.FP, st.FN)
-        rows = [[] for _ in seeds]
-        done = 0
-        while done < steps + 1:
-            n = engine.bnpcs_run(done, steps + 1 - done, burn_in)
-            labels, scalars, arena = engine.bnpcs_fetch()
-            for c in range(len(seeds)):
-                at = 0
-                for s in range(max(done, burn_in), done + n):
-                    k = int(scalars[c, s, 3])
-                    rows[c].append(arena[c, at:at + k].copy())
-                    at += k
-            done += n
+
+    def extend(self, add):
+        self.engine.bnpcs_extend(add)
+
+    def advance(self, n, keep_from):
+        target = self.done + n
+        self.keep_from = keep_from
+        while self.done < target:
+            self.done += self.engine.bnpcs_run(self.done, target - self.done, keep_from)
+            if self.done < target:
+                self._take()                                          # the arena is full
+
+    def _take(self):
+        """the records so far, and the parameter rows of the steps kept since the arena was last emptied"""
+        labels, scalars, arena = self.engine.bnpcs_fetch()
+        for c in range(len(self.seeds)):
+            at = 0
+            for s in range(max(self.taken, self.keep_from), self.done):
+                k = int(scalars[c, s, 3])
+                self.rows[c].append(arena[c, at:at + k].copy())
+                at += k
+        self.taken = self.done
+        return labels, scalars
+
+    def stats(self, first):
+        return self.engine.bnpcs_psrf([first] * len(self.seeds), self.done)
+
+    def results(self, burn_in):
+        engine, model, n = self.engine, self.model, self.done
+        labels, scalars = self._take()
         errors = engine.bnpcs_errors()
-        moves = engine.bnpcs_fetch_moves() if sm_prob > 0 else None
-        rates, rate_moves = engine.bnpcs_fetch_error_rates() if model.learning or any(st.FP is not None for st in start) else (None, None)
+        moves = engine.bnpcs_fetch_moves() if self.sm[0] > 0 else None
+        rates, rate_moves = engine.bnpcs_fetch_error_rates() if model.learning or any(st.FP is not None for st in self.start) else (None, None)
         out = []
-        for c in range(len(seeds)):
-            r = _empty_result(model, steps, burn_in)
-            r["ML"], r["_crp"], r["_beta"], r["DP_alpha"] = scalars[c, :, 0].copy(), scalars[c, :, 1].copy(), scalars[c, :, 2].copy(), scalars[c, :, 4].copy()
+        for c in range(len(self.seeds)):
+            r = _empty_result(model, n - 1, burn_in)
+            r["ML"], r["_crp"], r["_beta"], r["DP_alpha"] = scalars[c, :n, 0].copy(), scalars[c, :n, 1].copy(), scalars[c, :n, 2].copy(), scalars[c, :n, 4].copy()
             if model.uniform:
                 r["_beta"][:] = 0.0
-            r["assignments"] = labels[c].astype(int)
-            r["_rows"] = rows[c]
+            r["assignments"] = labels[c, :n].astype(int)
+            r["_rows"] = self.rows[c]
             r["variate_errors"] = int(errors[c])
             if moves is not None:
-                r["sm_moves"] = moves[c].copy()
+                r["sm_moves"] = moves[c, :n].copy()
             if rates is not None:
-                r["FP"], r["FN"], r["error_moves"] = rates[c, :, 0].copy(), rates[c, :, 1].copy(), rate_moves[c].astype(np.int64)
+                r["FP"], r["FN"], r["error_moves"] = rates[c, :n, 0].copy(), rates[c, :n, 1].copy(), rate_moves[c].astype(np.int64)
             out.append(_finish_result(model, r))
         return out
+
+
+def _drive(run, steps, burn_in, stop):
+    """the three stop rules over a run (_HostRun, _DeviceRun)"""
+    if stop is None:
+        run.open(steps)
+        run.advance(steps + 1, burn_in)
+        return run.results(burn_in)
+    if isinstance(stop, Lugsail):
+        # MCMC.run (MCMC.py:85-90): the first run keeps every step's parameters; run_lugsail_chains (:138-177)
+        run.open(stop.first_steps)
+        run.advance(stop.first_steps + 1, 0)
+        checks = []
+        while True:
+            steps_run = run.done
+            psrf = psrf_of_stats(run.stats(steps_run // 2))
+            checks.append((steps_run, psrf))
+            if stop.report is not None:
+                stop.report(steps_run, psrf)
+            if psrf <= stop.cutoff:
+                break
+            try:
+                run.extend(stop.extend)
+            except (RuntimeError, MemoryError) as e:
+                raise RuntimeError("the chains have not converged and cannot go on: after %d steps the PSRF is %.5f, above the cutoff %g, and %d more "
+                                   "steps were refused: %s" % (steps_run, psrf, stop.cutoff, stop.extend, e)) from e
+            run.advance(stop.extend, 0)
+        burn_in = steps_run // 2 + 1
+        out = run.results(burn_in)
+        for r in out:
+            r["params"] = r["params"][burn_in:]
+            r["PSRF"], r["PSRF_cutoff"] = list(checks), stop.cutoff
+        return out
+    # Chain_time (MCMC.py:395-440), the chains in lockstep: the clock is read before each batch
+    room = stop.batch
+    run.open(room)
+    run.advance(1, _NEVER)                                            # step 0 is never kept (update_results(0), :404)
+    keep_from = _NEVER
+    while True:
+        now = stop.clock()
+        if now > stop.end:
+            break
+        if keep_from == _NEVER and not now < stop.burn_in_end:
+            keep_from = run.done
+        if run.done + stop.batch > room + 1:
+            add = max(stop.batch, room)                               # room doubles, so that the records are moved a logarithmic number of times
+            try:
+                run.extend(add)
+            except (RuntimeError, MemoryError):
+                add = run.done + stop.batch - room - 1
+                run.extend(add)
+            room += add
+        run.advance(stop.batch, keep_from)
+    if keep_from == _NEVER:
+        raise ValueError("the runtime ended before the burn-in did: no step of %d is kept, so there is nothing to estimate from" % (run.done - 1))
+    return run.results(keep_from)
+
+
+def run_chains(engine, data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1), dpa_prob=0.5, error_prior=None, states=None, arena_rows=0,
+               sm_prob=0.0, sm_ratios=(0.75, 0.25), sm_steps=3, error_prob=0.0, error_priors=None, fixed_assignment=None, stop=None):
+    """The same on the device, all chains in every kernel.  arena_rows: the parameter rows per chain the device holds between two fetches
+    (0: enough for 64 kept steps of 64 clusters, at least N rows); a full arena only costs a fetch."""
+    _check_run(steps, burn_in, sm_prob, sm_ratios, sm_steps, stop)
+    model = _error_model(data, FN, FP, pp, dpa, dpa_prob, error_prior, error_prob, error_priors)
+    seeds = [int(s) for s in seeds]
+    start = _start_states(model, seeds, states, fixed_assignment)
+    run = _DeviceRun(engine, model, seeds, start, int(arena_rows) or max(model.N, 4096), sm_prob, sm_ratios, sm_steps, fixed_assignment is not None)
+    try:
+        return _drive(run, steps, burn_in, stop)
     finally:
         engine.bnpcs_destroy()
 

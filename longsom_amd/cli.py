@@ -371,63 +371,86 @@ def _bnpc_parser():
     g.add_argument("--chains_npz", default="", help="estimate from chains saved by --save_chains: no sampler is run")
     g.add_argument("--host_estimate", action="store_true", help="the numpy twin of the estimate, for a machine without a GPU")
     g.add_argument("--device", type=int, default=0)
-    g.add_argument("--sampler", choices=["reference", "device", "device-sm", "device-errors"], default="reference",
+    g.add_argument("--sampler", choices=["reference", "device", "device-sm", "device-errors", "device-open"], default="reference",
                    help="device: Gibbs sweeps, the concentration update and the parameter moves on the GPU, all chains at once (needs -smp 0); "
                         "device-sm: the same with the split-merge move, -smp / -sms / -smr honoured (-smp 0 equals device); "
-                        "device-errors: device-sm with the error rates learned (-eup, unless -FP and -FN are both given) and -fa honoured")
+                        "device-errors: device-sm with the error rates learned (-eup, unless -FP and -FN are both given) and -fa honoured; "
+                        "device-open: device-errors with chains of open length: -ls runs until the PSRF is at most the cutoff, -r for a time (-r wins over -ls, both over -s)")
     return ap
 
 
 def _device_sampler_refusals(a):
     """what longsom_amd.bnpc_sampler does not do, or a --sampler value does not ask of it, each named by its flag; --sampler device and
-    device-sm share all but the first, device-errors has only the last two"""
+    device-sm share all but the first, device-errors has only the last two, device-open none of them (and -ls 1 of its own)"""
+    like_errors = a.sampler in ("device-errors", "device-open")
     if a.sampler == "device" and a.split_merge_prob != 0:
         sys.exit("run_BnpC.py: --sampler device has no split-merge move: -smp/--split_merge_prob %g is not supported, run it with -smp 0" % a.split_merge_prob)
     who = "--sampler %s" % a.sampler
-    if a.sampler != "device-errors" and not (a.falsePositive > 0 and a.falseNegative > 0) and a.error_update_prob != 0:
+    if not like_errors and not (a.falsePositive > 0 and a.falseNegative > 0) and a.error_update_prob != 0:
         sys.exit("run_BnpC.py: %s keeps the error rates fixed: -eup/--error_update_prob %g is not supported, run it with -eup 0 (or give -FP and -FN)"
                  % (who, a.error_update_prob))
-    if a.sampler != "device-errors" and a.fixed_assignment:
+    if not like_errors and a.fixed_assignment:
         sys.exit("run_BnpC.py: %s does not support -fa/--fixed_assignment" % who)
+    if a.sampler == "device-open":
+        if not a.runtime > 0 and a.lugsail == 1:
+            sys.exit("run_BnpC.py: -ls/--lugsail 1 is not supported: the first run has int(1 / (cutoff^2 - 1)) steps, give a cutoff above 1")
+        return
     if a.runtime > 0:
-        sys.exit("run_BnpC.py: %s does not support -r/--runtime: give the steps with -s" % who)
+        sys.exit("run_BnpC.py: %s does not support -r/--runtime: give the steps with -s, or run --sampler device-open" % who)
     if a.lugsail > 0:
-        sys.exit("run_BnpC.py: %s does not support -ls/--lugsail: give the steps with -s" % who)
+        sys.exit("run_BnpC.py: %s does not support -ls/--lugsail: give the steps with -s, or run --sampler device-open" % who)
+
+
+def _device_stop_rule(a, clock=None):
+    """--sampler device-open's stop rule from -r, -ls and -s as dpmmIO._get_mcmc_termination (dpmmIO.py:158-169) reads them: -r wins over
+    -ls, both over -s.  Returns (the rule: None for -s's steps, what the run is printed as).  a.time[0] is the run's start."""
+    from datetime import datetime, timedelta
+    from . import bnpc_sampler
+    if a.sampler != "device-open" or not (a.runtime > 0 or a.lugsail > 0):
+        return None, f"for {a.steps} steps"
+    if a.runtime > 0:
+        whole = timedelta(minutes=a.runtime)
+        return bnpc_sampler.Runtime(a.time[0] + whole, a.time[0] + a.burn_in * whole, clock or datetime.now), f"for {a.runtime} mins"
+    report = (lambda steps_run, psrf: print(f"\tPSRF at {steps_run}:\t{psrf:.5f}")) if a.verbosity > 1 else None
+    return bnpc_sampler.Lugsail(a.lugsail, report=report), f"until PSRF < {a.lugsail:.4f}"
 
 
 def _device_chains(a, data):
-    """the chains of --sampler device / device-sm / device-errors: the model of run_BnpC.py:261-296, the seeds drawn as MCMC.run draws them.
+    """the chains of --sampler device / device-sm / device-errors / device-open: the model of run_BnpC.py:261-296, the seeds drawn as MCMC.run draws them.
     device and device-sm keep the error rates fixed (the given ones, or the priors' means with the priors' own terms in MAP); device-errors
-    learns them with -eup unless both are given (run_BnpC.py:261-262), and starts from -fa's labels and keeps them where it is given."""
+    learns them with -eup unless both are given (run_BnpC.py:261-262), and starts from -fa's labels and keeps them where it is given;
+    device-open is device-errors under _device_stop_rule."""
     from scipy.stats import truncnorm
     from . import bnpc_sampler
     learn = {}
+    like_errors = a.sampler in ("device-errors", "device-open")
     if a.falsePositive > 0 and a.falseNegative > 0:
-        if a.sampler == "device-errors":
+        if like_errors:
             a.error_update_prob = 0
         FN, FP, error_prior = a.falseNegative, a.falsePositive, None
     else:
         FN, FP = a.falseNegative_mean, a.falsePositive_mean
         error_prior = sum(float(truncnorm((0 - m) / sd, (1 - m) / sd, m, sd).logpdf(m)) for m, sd in ((FP, a.falsePositive_std), (FN, a.falseNegative_std)))
-        if a.sampler == "device-errors" and a.error_update_prob > 0:
+        if like_errors and a.error_update_prob > 0:
             learn = dict(error_prob=a.error_update_prob, error_priors=(FP, a.falsePositive_std, FN, a.falseNegative_std))
-    if a.sampler == "device-errors" and a.fixed_assignment:
+    if like_errors and a.fixed_assignment:
         learn["fixed_assignment"] = bnpc_sampler.load_assignment(a.fixed_assignment)
         if len(learn["fixed_assignment"]) != data.shape[0]:
             sys.exit("run_BnpC.py: -fa/--fixed_assignment %s has %d labels, the data have %d cells" % (a.fixed_assignment, len(learn["fixed_assignment"]), data.shape[0]))
     a.chain_seeds = bnpc_sampler.chain_seeds(a.seed, a.chains)
+    stop, run_str = _device_stop_rule(a)
     if a.verbosity > 0:
-        print(f"Run MCMC on the device ({a.chains} chains for {a.steps} steps, FN {FN} FP {FP}{', learned' if 'error_prob' in learn else ''}):")
+        print(f"Run MCMC on the device ({a.chains} chains {run_str}, FN {FN} FP {FP}{', learned' if 'error_prob' in learn else ''}):")
     with Engine(a.device) as eng:
         return bnpc_sampler.run_chains(eng, data, [int(s) for s in a.chain_seeds], a.steps, int(a.steps * a.burn_in), FN, FP, pp=a.param_prior, dpa=a.DPa_prior,
                                        dpa_prob=a.conc_update_prob, error_prior=error_prior, sm_prob=a.split_merge_prob if a.sampler != "device" else 0.0,
-                                       sm_ratios=tuple(a.split_merge_ratios), sm_steps=a.split_merge_steps, **learn)
+                                       sm_ratios=tuple(a.split_merge_ratios), sm_steps=a.split_merge_steps, stop=stop, **learn)
 
 
 def run_bnpc(argv=None):
     """run_BnpC.py: the chains come from the vendored BnpC's sampler (libs/MCMC.py, run as the reference runs it), from --sampler device
-    / device-sm / device-errors (longsom_amd.bnpc_sampler: device-sm with the split-merge move, device-errors also with learned error
-    rates and -fa) or from --chains_npz; the
+    / device-sm / device-errors / device-open (longsom_amd.bnpc_sampler: device-sm with the split-merge move, device-errors also with learned
+    error rates and -fa, device-open also with -ls and -r) or from --chains_npz; the
     posterior estimate is made on the device (longsom_amd.bnpc); assignment.txt, errors.txt and genotypes_*.tsv are written here; args.txt,
     the PSRF, -e ML|MAP, the summaries and the plots are left to the checkout's own functions."""
     from datetime import datetime
@@ -441,7 +464,7 @@ def run_bnpc(argv=None):
         a.estimator = [a.estimator]
     if a.single_chains:
         sys.exit("run_BnpC.py: -sc/--single_chains is not supported here: the posterior estimate is made once, over all chains")
-    on_device = a.sampler in ("device", "device-sm", "device-errors")
+    on_device = a.sampler in ("device", "device-sm", "device-errors", "device-open")
     if on_device and not a.chains_npz:
         _device_sampler_refusals(a)
     point = [e for e in a.estimator if e != "posterior"]
@@ -495,6 +518,9 @@ def run_bnpc(argv=None):
     # dpmmIO._infer_results (:199-225) with the posterior estimate taken from the device
     if ut is not None:
         a.PSRF = ut.get_lugsail_batch_means_est([(r["ML"], r["burn_in"]) for r in results])
+    else:
+        from . import bnpc_sampler
+        a.PSRF = bnpc_sampler.lugsail_psrf([(r["ML"], r["burn_in"]) for r in results])
     a.steps = [r["ML"].size for r in results]
     cat = bnpc.concat_chains(results)
     inferred = {"mean": {}}

@@ -936,6 +936,58 @@ __global__ __launch_bounds__(256) void k_bnpcs_record(SDev d, int32_t step, int3
     }
 }
 
+// ---- lsg_bnpcs_extend: the records [chain][steps1][rec] moved to rows of a larger steps1.  rec, old_row and new_row in 32-bit words
+// (every record is a whole number of them); only the `used` words of a row that hold records made so far are moved. -----------------------
+__global__ __launch_bounds__(256) void k_bnpcs_restride(uint32_t* dst, const uint32_t* src, size_t old_row, size_t new_row, size_t used, int32_t C) {
+    for (int c = blockIdx.y; c < C; c += gridDim.y) {
+        const uint32_t* s = src + (size_t)c * old_row;
+        uint32_t* o = dst + (size_t)c * new_row;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < used; i += (size_t)gridDim.x * 256) o[i] = s[i];
+    }
+}
+
+// ---- lsg_bnpcs_psrf: what the lugsail batch-means PSRF (utils.get_lugsail_batch_means_est, utils.py:427-467) needs of a chain's ML
+// records first .. last - 1: n, the mean, the sample variance, tau(b) and tau(b // 3), tau(b) = b / (a - 1) sum (batch mean - mean)^2
+// over the a = n / b whole batches.  All sums are of x - x[first] (the ML is about -1e4 with a spread of a few units), in two passes: the
+// mean first, then the deviations.  A workgroup per chain; a wave sums a batch.  par [chain][3]: first, b, b // 3; out [chain][5]. -------
+__device__ inline double psrf_tau(const double* x, double pivot, double mean, int32_t n, int32_t b, double* shd) {
+    const int t = threadIdx.x, lane = t & 63, a = n / b;
+    double acc = 0.0;
+    for (int j = t >> 6; j < a; j += 4) {
+        double s = 0.0;
+        for (int i = lane; i < b; i += 64) s += x[((size_t)j * b + i) * REC] - pivot;
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const double dev = s / (double)b - mean;
+        if (lane == 0) acc += dev * dev;
+    }
+    return (double)b / (double)(a - 1) * block_sum(acc, shd);
+}
+
+__global__ __launch_bounds__(256) void k_bnpcs_psrf(SDev d, const int32_t* par, int32_t last, double* out) {
+    __shared__ double shd[4];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const int32_t first = par[3 * c], b = par[3 * c + 1], b3 = par[3 * c + 2], n = last - first;
+    double* o = out + 5 * (size_t)c;
+    if (n < 1) {                                                      // no record is read
+        if (t < 5) o[t] = 0.0;
+        return;
+    }
+    const double* x = d.rec_sc + ((size_t)c * d.steps1 + first) * REC;      // x[i * REC]: the ML of step first + i
+    const double pivot = x[0];
+    double s = 0.0;
+    for (int i = t; i < n; i += 256) s += x[(size_t)i * REC] - pivot;
+    const double mean = block_sum(s, shd) / (double)n;
+    double q = 0.0;
+    for (int i = t; i < n; i += 256) { const double e = (x[(size_t)i * REC] - pivot) - mean; q += e * e; }
+    q = block_sum(q, shd);
+    const bool whole = n >= 9 && b >= 3 && b3 >= 1;                   // fewer than 9 values: b // 3 is 0 and the estimate is inf (utils.py:435)
+    const double tau = whole ? psrf_tau(x, pivot, mean, n, b, shd) : 0.0;
+    const double tau3 = whole ? psrf_tau(x, pivot, mean, n, b3, shd) : 0.0;
+    if (t == 0) {
+        o[0] = (double)n; o[1] = pivot + mean; o[2] = n > 1 ? q / (double)(n - 1) : 0.0; o[3] = tau; o[4] = tau3;
+    }
+}
+
 // ---- test support: the stream and the variates as the kernels see them -----------------------------------------------------------------
 __global__ void k_bnpcs_test_stream(uint64_t key, int64_t n, const uint32_t* ctr, uint32_t* words, double* dbl) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1122,7 +1174,7 @@ int lsg_bnpcs_create(lsg_ctx* c, int32_t n_cells, int32_t n_muts, int32_t n_chai
         LSG_HIP(hipStreamSynchronize(st));                         // (`all` is read by the copy until here)
     }
     b.n_cells = n_cells; b.n_muts = n_muts; b.n_words = (int32_t)W; b.n_chains = n_chains; b.steps1 = (int32_t)S1; b.arena_rows = arena_rows;
-    b.k_max = 0; b.ll_pitch = 1; b.pending = -1; b.next_step = 0;
+    b.k_max = 0; b.ll_pitch = 1; b.pending = -1; b.next_step = 0; b.test_ml_end = 0;
     std::copy(cfg, cfg + 10, b.cfg);
     b.sm_prob = 0.0; b.sm_ratio[0] = 0.75; b.sm_ratio[1] = 0.25; b.sm_scans = 3;
     b.err_prob = 0.0; b.learn = b.fixed_assign = false; std::fill(b.err_prior, b.err_prior + 4, 0.0);
@@ -1306,6 +1358,71 @@ int lsg_bnpcs_set_fixed_assignment(lsg_ctx* c, int32_t on) {
     return 0;
 }
 
+int lsg_bnpcs_extend(lsg_ctx* c, int32_t add_steps) {
+    const char* who = "lsg_bnpcs_extend";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (add_steps < 1) { set_error("%s: %d steps to add (at least 1)", who, add_steps); return -2; }
+    const size_t N = b.n_cells, M = b.n_muts, C = b.n_chains, old1 = b.steps1, S1 = old1 + (size_t)add_steps;
+    const double bytes = (double)C * N * M * (4 + 8 + 8 + 4 + 4) + (double)C * S1 * N * 4 + (double)C * b.arena_rows * M * 4;
+    if (S1 > (size_t)INT32_MAX) { set_error("%s: %zu steps are more than a run can number", who, S1 - 1); return -2; }
+    if (bytes > 64e9) {
+        set_error("%s: %d chains x %d cells x %d mutations x %zu steps would need %.0f GB of state", who, b.n_chains, b.n_cells, b.n_muts, S1 - 1, bytes / 1e9);
+        return -2;
+    }
+    // the four records, each [chain][steps1][words]: new buffers first, so that a refused allocation leaves the run as it was
+    DevBuf* rec[4] = {&b.rec_lab, &b.rec_sc, &b.rec_sm, &b.rec_err};
+    const size_t words[4] = {N, (size_t)REC * 2, 1, 4};
+    DevBuf grown[4];
+    for (int k = 0; k < 4; ++k)
+        if (grown[k].reserve(C * S1 * words[k] * 4)) { for (DevBuf& g : grown) g.release(); return -1; }
+    hipStream_t st = c->stream;
+    // a step that waits for room in the arena (pending) has made its move and written its code of rec_sm, though nothing else of its record
+    const int32_t made = std::max(std::max(b.next_step, b.pending + 1), b.test_ml_end);
+    for (int k = 0; k < 4; ++k) {
+        const size_t used = (size_t)made * words[k];
+        hipError_t e = hipMemsetAsync(grown[k].p, 0, C * S1 * words[k] * 4, st);
+        if (e == hipSuccess && used) {
+            const unsigned gx = (unsigned)std::min<size_t>((used + 255) / 256, 4096), gy = (unsigned)std::min<size_t>(C, 65535);
+            hipLaunchKernelGGL(k_bnpcs_restride, dim3(gx, gy), dim3(256), 0, st, grown[k].as<uint32_t>(), rec[k]->as<uint32_t>(), old1 * words[k], S1 * words[k], used, (int32_t)C);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(st);
+            for (DevBuf& g : grown) g.release();
+            set_error("%s: moving the records failed: %s", who, hipGetErrorString(e));
+            return -1;
+        }
+    }
+    if (sync_check(c, who)) { for (DevBuf& g : grown) g.release(); return -1; }
+    for (int k = 0; k < 4; ++k) { rec[k]->release(); *rec[k] = grown[k]; }
+    b.steps1 = (int32_t)S1;
+    return 0;
+}
+
+int lsg_bnpcs_psrf(lsg_ctx* c, const int32_t* first, int32_t last, double* stats) {
+    const char* who = "lsg_bnpcs_psrf";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (!first || !stats) { set_error("%s: bad arguments", who); return -2; }
+    const int32_t made = std::max(b.next_step, b.test_ml_end);
+    if (last < 0 || last > made) { set_error("%s: records up to %d asked, %d are made", who, last, made); return -2; }
+    const size_t C = b.n_chains;
+    std::vector<int32_t> par(3 * C);
+    for (size_t k = 0; k < C; ++k) {
+        if (first[k] < 0 || first[k] > last) { set_error("%s: chain %zu: records %d .. %d asked", who, k, first[k], last - 1); return -2; }
+        const int32_t bsz = (int32_t)std::pow((double)(last - first[k]), 0.5);      // int(n ** 0.5), as utils.py:439 forms it
+        par[3 * k] = first[k]; par[3 * k + 1] = bsz; par[3 * k + 2] = bsz / 3;
+    }
+    const size_t out_at = (3 * C * 4 + 7) / 8 * 8;
+    if (b.psrf.reserve(out_at + C * 5 * 8)) return -1;
+    double* d_out = reinterpret_cast<double*>(b.psrf.as<char>() + out_at);
+    LSG_HIP(hipMemcpyAsync(b.psrf.p, par.data(), 3 * C * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_bnpcs_psrf, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), b.psrf.as<int32_t>(), last, d_out);
+    LSG_HIP(hipMemcpyAsync(stats, d_out, C * 5 * 8, hipMemcpyDeviceToHost, c->stream));
+    return sync_check(c, who);                                        // (`par` is read by the copy until here)
+}
+
 int lsg_bnpcs_destroy(lsg_ctx* c) {
     if (!c) { set_error("lsg_bnpcs_destroy: NULL handle"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
@@ -1415,4 +1532,17 @@ int lsg_bnpcs_test_error_outcome(lsg_ctx* c, int32_t chain, double* outcome) {
     if (chain < 0 || chain >= b.n_chains || !outcome) { set_error("%s: bad arguments", who); return -2; }
     LSG_HIP(hipMemcpyAsync(outcome, b.err_out.as<double>() + (size_t)chain * ERR_OUT, ERR_OUT * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_check(c, who);
+}
+
+int lsg_bnpcs_test_set_ml(lsg_ctx* c, int32_t chain, int32_t first, int32_t n, const double* values) {
+    const char* who = "lsg_bnpcs_test_set_ml";
+    if (int rc = need(c, who)) return rc;
+    Bnpcs& b = c->bnpcs;
+    if (chain < 0 || chain >= b.n_chains || first < 0 || n < 1 || !values) { set_error("%s: bad arguments", who); return -2; }
+    if ((int64_t)first + n > b.steps1) { set_error("%s: records %d .. %lld asked, there is room for %d", who, first, (long long)first + n - 1, b.steps1); return -2; }
+    double* dst = b.rec_sc.as<double>() + ((size_t)chain * b.steps1 + first) * REC;
+    LSG_HIP(hipMemcpy2DAsync(dst, REC * 8, values, 8, 8, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (sync_check(c, who)) return -1;
+    b.test_ml_end = std::max(b.test_ml_end, first + n);
+    return 0;
 }

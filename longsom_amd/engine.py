@@ -766,6 +766,28 @@ class Engine:
         """per chain, the gamma variates that ran out of tries, as of the last bnpcs_fetch"""
         return self._bnpcs_errors
 
+    def bnpcs_extend(self, add_steps: int) -> None:
+        """room for add_steps more recorded steps; the chains, their records, the arena and the next step stay (lsg_bnpcs_extend)"""
+        _lib.check(self._lib.lsg_bnpcs_extend(self._h, int(add_steps)), "lsg_bnpcs_extend")
+        Cn, S1, N, M, rows = self._bnpcs_shape
+        self._bnpcs_shape = (Cn, S1 + int(add_steps), N, M, rows)
+
+    def bnpcs_psrf(self, first, last: int) -> np.ndarray:
+        """[C, 5] float64: n, the mean, the sample variance, tau(b), tau(b // 3) of every chain's ML records first[c] .. last - 1, computed
+        on the device; nothing else comes to the host (lsg_bnpcs_psrf; bnpc_sampler.psrf_of_stats makes the PSRF of them)"""
+        Cn = self._bnpcs_shape[0]
+        fs = np.ascontiguousarray(first, dtype=np.int32)
+        if fs.shape != (Cn,):
+            raise ValueError("bnpcs_psrf: first must be [%d]" % Cn)
+        stats = np.zeros((Cn, 5), np.float64)
+        _lib.check(self._lib.lsg_bnpcs_psrf(self._h, _ptr(fs), int(last), _ptr(stats)), "lsg_bnpcs_psrf")
+        return stats
+
+    def bnpcs_test_set_ml(self, chain: int, first: int, values) -> None:
+        """values as the chain's ML records first .. first + len(values) - 1 (lsg_bnpcs_test_set_ml)"""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        _lib.check(self._lib.lsg_bnpcs_test_set_ml(self._h, int(chain), int(first), len(v), _ptr(v)), "lsg_bnpcs_test_set_ml")
+
     def bnpcs_destroy(self) -> None:
         _lib.check(self._lib.lsg_bnpcs_destroy(self._h), "lsg_bnpcs_destroy")
         self._bnpcs_shape = None

@@ -10,6 +10,9 @@ own calls, so that the first steps and the late steps can be timed apart).
   --reference DIR   also time the reference's sampler (libs/CRP.py, libs/MCMC.py of the LongSom checkout DIR, with the same --sm_prob) at the same
               shape on this host, one process per chain: its first 10 steps from its random start, and 10 steps from the planted partition
               (the state a chain is in after a few hundred steps), per step
+  --lugsail   what the lugsail rule adds to a run (run_chains' Lugsail stop rule): one PSRF check (lsg_bnpcs_psrf over the second half of the
+              records) and one 200-step extension (lsg_bnpcs_extend, which moves the records to their new rows), at 1 000 and at 10 000
+              recorded steps; the records are marked as made through the test hook, no step is run.  Seconds, the median of 5 checks
 Prints one JSON line.  For a per-kernel split run it under `rocprofv3 --kernel-trace --stats -- python tools/bnpc_sampler_perf.py --late_only`.
 """
 import argparse
@@ -79,6 +82,31 @@ def device(data, chains, late_only, sm_prob=0.0, sm_steps=3, eup=0.0):
     return out
 
 
+def lugsail(data, chains):
+    from longsom_amd import bnpc_sampler as bs
+    from longsom_amd.engine import Engine
+    model = bs.Model(data, 0.1, 0.01)
+    rng = np.random.default_rng(1)
+    out = {}
+    with Engine(0) as e:
+        for records in (1000, 10000):
+            e.bnpcs_create(model, list(range(1, chains + 1)), records - 1, 1 << 15)
+            for c in range(chains):
+                e.bnpcs_test_set_ml(c, 0, -1e4 + 3 * rng.standard_normal(records))
+            e.bnpcs_psrf([records // 2] * chains, records)
+            checks = []
+            for _ in range(5):
+                t = time.perf_counter()
+                stats = e.bnpcs_psrf([records // 2] * chains, records)
+                checks.append(time.perf_counter() - t)
+            t = time.perf_counter()
+            e.bnpcs_extend(200)
+            out["at_%d" % records] = {"psrf_check_s": float(np.median(checks)), "extend_200_s": time.perf_counter() - t, "psrf": bs.psrf_of_stats(stats),
+                                      "label_records_gb": chains * records * model.N * 4 / 1e9}
+            e.bnpcs_destroy()
+    return out
+
+
 def _reference_chain(args):
     ref, data, seed, assign, sm_prob, sm_steps = args
     from make_bnpc_estimate_goldens import stand_ins
@@ -116,9 +144,14 @@ def main():
     ap.add_argument("--sm_prob", type=float, default=0.0); ap.add_argument("--sm_steps", type=int, default=3)
     ap.add_argument("--eup", type=float, default=0.0, help="the share of the steps that update the error rates (device only)")
     ap.add_argument("--no_device", action="store_true"); ap.add_argument("--late_only", action="store_true", help="50 steps only: what a profiler should see")
+    ap.add_argument("--lugsail", action="store_true", help="time a PSRF check and a 200-step extension at 1 000 and 10 000 recorded steps, and nothing else")
     a = ap.parse_args()
     data, truth = planted(a.cells, a.muts, a.clusters)
     out = {"cells": a.cells, "muts": a.muts, "clusters": a.clusters, "chains": a.chains, "cpus": os.cpu_count()}
+    if a.lugsail:
+        out["lugsail"] = lugsail(data, a.chains)
+        print(json.dumps(out))
+        return
     if not a.no_device:
         out["sm_prob"], out["sm_steps"], out["eup"] = a.sm_prob, a.sm_steps, a.eup
         out["device"] = device(data, a.chains, a.late_only, a.sm_prob, a.sm_steps, a.eup)

@@ -11,7 +11,9 @@
 # (--sampler device-sm, no -smp passed, so run_BnpC.py's defaults -smp 0.33 -sms 3 -smr 0.75 0.25 apply as in the reference's rule), the
 # parameter moves, fixed error rates.  CellClust.BnpC.sampler: device is the same without the split-merge move (--sampler device -smp 0).
 # CellClust.BnpC.sampler: device-errors is device-sm with the error rates learned (--sampler device-errors): the rule passes the config's
-# -eup, and any value of it runs on the GPU, where device and device-sm need eup: 0.
+# -eup, and any value of it runs on the GPU, where device and device-sm need eup: 0.  CellClust.BnpC.sampler: device-open is device-errors
+# with chains of open length (--sampler device-open): with the optional key CellClust.BnpC.lugsail the rule passes it as -ls, and the chains
+# run until their lugsail PSRF is at most that cutoff (which overrides -s, as in run_BnpC.py); without the key it equals device-errors.
 
 GPU_SCRIPTS = str(workflow.basedir) + "/scripts_gpu"
 FUSE_BNPC = config['Run'].get('fuse_bnpc_input', False)
@@ -126,7 +128,9 @@ rule BnpC_clustering:
         FP = config['CellClust']['BnpC']['FP'],
         FN = config['CellClust']['BnpC']['FN'],
         pp= config['CellClust']['BnpC']['pp'],
-        sampler={'device': "--sampler device -smp 0", 'device-sm': "--sampler device-sm", 'device-errors': "--sampler device-errors"}.get(config['CellClust']['BnpC'].get('sampler', 'reference'), ""),
+        sampler={'device': "--sampler device -smp 0", 'device-sm': "--sampler device-sm", 'device-errors': "--sampler device-errors",
+                 'device-open': "--sampler device-open"}.get(config['CellClust']['BnpC'].get('sampler', 'reference'), ""),
+        lugsail=("-ls %s" % config['CellClust']['BnpC']['lugsail']) if 'lugsail' in config['CellClust']['BnpC'] else "",
     conda:
         "../envs/BnpC.yaml"
     threads: 16
@@ -150,6 +154,6 @@ rule BnpC_clustering:
         -FP {params.FP} \
         -FN {params.FN} \
         -pp {params.pp} \
-        -ap {params.dpa} {params.sampler} \
+        -ap {params.dpa} {params.sampler} {params.lugsail} \
         --barcodes {input.barcodes}
         """
