@@ -351,12 +351,14 @@ int lsg_export_calls(lsg_ctx* ctx, int32_t kind, void* dst_device, int64_t capac
  *   LSG_TABLE_CELL_LONG   <id>.SingleCellGenotype.tsv rows      CellClustering/SingleCellGenotype.py:181-224,305 (see lsg_cellgeno_count below)
  *   LSG_TABLE_CELL_DP / _ALT / _VAF / _BIN   the rows of <id>.DpMatrix.tsv, AltMatrix, VAFMatrix, BinaryMatrix (SingleCellGenotype.py:351-379)
  *   LSG_TABLE_BNPC_BIN / _VAF   the SNV rows of BnpC_input/<id>.BinaryMatrix.tsv and VAFMatrix.tsv (FormatInputBnpC.py:16-34; see lsg_cellgeno_filter)
+ *   LSG_TABLE_FASTQ       the FASTQ records of a BAM for ctat-LR-fusion (FusionCalling/BamToFastq.py:9-42; made by lsg_bam_fastq below,
+ *                         not by lsg_format_table)
  * Rows only (the header lines are the caller's), in the reference's order: contigs in Python string order, positions ascending.
  * At 24 M sites these are 17 GB of text: a kernel prints them from the count rows and call records where they lie (two passes:
  * lengths, then bytes), the host only moves bytes.  The merged and step-1 tables need lsg_call_step1 (its merged site list). */
 enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG_TABLE_STEP1, LSG_TABLE_STEP1_KEPT, LSG_TABLE_STEP2, LSG_TABLE_STEP3_ROWS,
                  LSG_TABLE_CELL_LONG, LSG_TABLE_CELL_DP, LSG_TABLE_CELL_ALT, LSG_TABLE_CELL_VAF, LSG_TABLE_CELL_BIN,
-                 LSG_TABLE_BNPC_BIN, LSG_TABLE_BNPC_VAF, LSG_TABLE_SLOTS };
+                 LSG_TABLE_BNPC_BIN, LSG_TABLE_BNPC_VAF, LSG_TABLE_FASTQ, LSG_TABLE_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -377,6 +379,50 @@ int lsg_append_table(lsg_ctx* ctx, int32_t table, const char* path);
 int lsg_step2_summary(lsg_ctx* ctx, int32_t n_cols, uint8_t* kinds, int64_t* n_survivor_bytes);
 /* Frees one table's text (table < 0: every table's, and the flat row copies they were printed from). */
 int lsg_free_table(lsg_ctx* ctx, int32_t table);
+
+/* ---- FASTQ for the fusion caller, printed on the device (csrc/fastq.hip) ---------------------------
+ * A BAM's records as the FASTQ text ctat-LR-fusion reads, into table LSG_TABLE_FASTQ (lsg_copy_table / lsg_append_table / lsg_free_table
+ * serve it like any table; all offsets are 64-bit).  Replaces bam_to_fastq (FusionCalling/BamToFastq.py:9-42: pysam iteration,
+ * read.to_dict(), four f.write per read) and, in routed mode, the chain of rules/FusionCalling.smk:3-37: the per-cell-type BAMs of
+ * SplitBamCellTypes, one BamToFastq per cell type and ConcatFastq.  The front half is lsg_load_bam's (H2D, BGZF inflate + CRC32, record
+ * chain, record list); -4 likewise means the record chain did not settle: print that file on the host (lsio_bam_fastq).  The reference
+ * table the records are validated against is read from the file's own header (the bytes before first_record_offset), so an unaligned BAM
+ * without references works; the call reads and changes nothing of a resident load (store, rows, call records).
+ *
+ * Every printed record is   @<CB>^<UMI>^<name>\n<seq>\n+\n<qual>\n   with
+ *   name  the NUL-terminated read name
+ *   seq   "=ACMGRSVTWYHKDBN"[code] per base, "*" when l_seq == 0;  qual  byte + 33 per base, "*" when l_seq == 0 or the first byte is 0xFF
+ *         (the SAM text pysam's to_dict() goes through)
+ *   CB    the value of the FIRST aux field named CB (bam_aux_get order) without ONE trailing "-1" (re.sub("-1$", ...): "X-2" stays,
+ *         "X-1-1" -> "X-1", "-1" -> "")
+ *   UMI   the first UB field's value; else, for a name with at least one '.', its second-to-last '.'-separated field without its last
+ *         three characters (may be empty); else "NA"
+ * A record that cannot be printed ends the call with an error naming its ordinal, and no text is kept: no CB field (LSG_FASTQ_NO_CB:
+ * the reference would print the PREVIOUS read's barcode, or raise on the first read - not reproduced), a first CB / UB field that is not
+ * of type Z (LSG_FASTQ_CB_TYPE / _UB_TYPE: get_tag(.., "Z")[0] would print one character or raise), and in routed mode with --max_nM /
+ * --max_NH set an nM / NH tag that is not a number (LSG_FASTQ_NM_TYPE / _NH_TYPE, as lsg_load_bam refuses it).  info->bad_ordinal /
+ * bad_kind name the smallest such ordinal (-1 / LSG_FASTQ_OK: none) also when the call fails for it.
+ *
+ * Plain mode (barcodes == NULL; celltype_of, n_celltypes, min_mapq unused): every record of the file in file order, unmapped ones
+ * included (the script opens with check_sq=False and iterates, it does not fetch()); n_printed[0] / n_bytes[0].
+ * Routed mode: barcodes = n_barcodes cleaned strings joined by '\n', celltype_of[i] in [0, n_celltypes) (duplicated strings: the last
+ * wins).  A record is printed iff SplitBamCellTypes.py:65-124 writes it to a cell type's BAM - placed on a reference, CB:Z found, its
+ * cleaned barcode listed, filter reason 0 under min_mapq and the handle's lsg_set_split_filters limits - decided by the same code as
+ * lsg_load_bam's (bamrec_core.h scan_aux / cb_lookup / reason_of).  The text is cell type 0's records in file order, then cell type 1's,
+ * ...: n_printed[t] records and n_bytes[t] bytes each.  A record that is routed nowhere cannot be a bad record, with
+ * one exception: the nM / NH type of a read whose barcode is listed is reported whatever its MAPQ, because the reference compares the tag
+ * (and raises TypeError) before its MAPQ test (SplitBamCellTypes.py:95-108), as lsg_load_bam refuses such a read.  With --n_trim set on the handle
+ * (lsg_set_split_filters n_trim > 0) the call refuses: the reference would write qualities of 0 into the split BAMs, and none of
+ * LongSom's rules sets it. */
+enum { LSG_FASTQ_OK = -1, LSG_FASTQ_NO_CB = 0, LSG_FASTQ_CB_TYPE = 1, LSG_FASTQ_UB_TYPE = 2, LSG_FASTQ_NM_TYPE = 3, LSG_FASTQ_NH_TYPE = 4 };
+typedef struct {
+    int64_t n_records;
+    int64_t n_printed[LSG_MAX_CELLTYPES], n_bytes[LSG_MAX_CELLTYPES];   /* plain mode: index 0 only */
+    int64_t bad_ordinal; int32_t bad_kind;                               /* smallest record ordinal that cannot be printed, and why */
+    float   ms_h2d, ms_inflate, ms_chain, ms_length, ms_print, ms_total; /* HIP-event times of the phases, wall time of the call */
+} lsg_fastq_info;
+int lsg_bam_fastq(lsg_ctx* ctx, const uint8_t* file_bytes, int64_t n_bytes, int64_t first_record_offset, const char* barcodes, int32_t n_barcodes,
+                  const int32_t* celltype_of, int32_t n_celltypes, int32_t min_mapq, lsg_fastq_info* info);
 
 /* Position sets (RNA-editing / PoN_SR / PoN_LR; build_dict, BaseCellCalling.step2.py:197-221):
  * sorted unique keys (tid<<32)|pos1 resident in HBM; kind in [0,3). */

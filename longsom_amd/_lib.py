@@ -119,6 +119,19 @@ class BamInfo(C.Structure):
     ]
 
 
+class FastqInfo(C.Structure):
+    """lsg_fastq_info (lsg_bam_fastq / lsio_bam_fastq): records of the file, printed records and bytes per cell type (plain mode: index 0),
+    the smallest ordinal that cannot be printed and why (-1 / FASTQ_OK: none), the phases' times"""
+    _fields_ = [
+        ("n_records", C.c_int64), ("n_printed", C.c_int64 * 4), ("n_bytes", C.c_int64 * 4),
+        ("bad_ordinal", C.c_int64), ("bad_kind", C.c_int32),
+        ("ms_h2d", C.c_float), ("ms_inflate", C.c_float), ("ms_chain", C.c_float), ("ms_length", C.c_float), ("ms_print", C.c_float), ("ms_total", C.c_float),
+    ]
+
+
+FASTQ_OK, FASTQ_NO_CB, FASTQ_CB_TYPE, FASTQ_UB_TYPE, FASTQ_NM_TYPE, FASTQ_NH_TYPE = -1, 0, 1, 2, 3, 4
+
+
 class CountStats(C.Structure):
     _fields_ = [
         ("n_reads_admitted", C.c_int64), ("n_segs_admitted", C.c_int64), ("n_events_admitted", C.c_int64),
@@ -216,6 +229,7 @@ SIGNATURES = {
     "lsg_unload_reads": (C.c_int, [C.c_void_p]),
     "lsg_load_bam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BamInfo), C.c_void_p, C.c_void_p, C.c_int64]),
     "lsg_load_bam_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(BamInfo), C.c_void_p, C.c_void_p, C.c_int64]),
+    "lsg_bam_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(FastqInfo)]),
     "lsg_set_load_filter": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32]),
     "lsg_set_events_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "lsg_max_live_reads_all": (C.c_int64, [C.c_void_p]),
@@ -252,10 +266,13 @@ def load():
 
 
 class LsgError(RuntimeError):
-    pass
+    """a failed library call; .rc is the call's return value (-4: a BAM whose record chain the device cannot settle)"""
+    rc = None
 
 
 def check(rc, what):
     if rc != 0:
         msg = load().lsg_last_error().decode("utf-8", "replace")
-        raise LsgError(f"{what} failed (rc={rc}): {msg}")
+        e = LsgError(f"{what} failed (rc={rc}): {msg}")
+        e.rc = rc
+        raise e

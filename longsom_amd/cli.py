@@ -32,6 +32,79 @@ def split_bam(argv=None):
     pipeline.write_report(os.path.join(a.outdir, a.id + ".report.txt"), rep, time.time() - t0)
 
 
+def _print_fastq(bam, fastq, table, min_mapq, filters, device, host):
+    """BAM -> FASTQ file: printed on the device (lsg_bam_fastq) and streamed into the file with lsg_append_table; `host`, or a BAM whose
+    record chain the device cannot settle (rc -4, said on stderr), takes the host twin.  Returns (info dict, "device" | "host")."""
+    from . import _lib
+    if not host:
+        try:
+            with Engine(device) as eng:
+                if table is not None:
+                    eng.set_split_filters(filters)
+                info = eng.bam_fastq(bam, None if table is None else table.barcodes, None if table is None else table.celltype_of,
+                                     0 if table is None else len(table.celltype_names), min_mapq)
+                open(fastq, "wb").close()
+                eng.append_table(eng.TABLE_FASTQ, fastq)
+                return info, "device"
+        except _lib.LsgError as e:
+            if e.rc != -4:
+                raise
+            print("%s: its records straddle its BGZF blocks; printing it on the host" % bam, file=sys.stderr)
+    return hostio.bam_fastq(bam, fastq, table, min_mapq, filters), "host"
+
+
+def bam_to_fastq(argv=None):
+    """BamToFastq.py --bam --fastq  (FusionCalling/BamToFastq.py:44-48); --device N / --host are this project's"""
+    ap = argparse.ArgumentParser(description="Convert a BAM into the FASTQ ctat-LR-fusion reads: @CB^UMI^name")
+    ap.add_argument("--bam", required=True); ap.add_argument("--fastq", required=True)
+    ap.add_argument("--device", type=int, default=0); ap.add_argument("--host", action="store_true", help="print on the host (no GPU)")
+    a = ap.parse_args(argv)
+    t0 = time.time()
+    info, where = _print_fastq(a.bam, a.fastq, None, 0, None, a.device, a.host)
+    print(json.dumps({"fastq": a.fastq, "records": info["n_printed"][0], "bytes": info["n_bytes"][0], "printed_on": where, "seconds": round(time.time() - t0, 3)}))
+
+
+def fusion_fastq(argv=None):
+    """The unsplit BAM + the barcode table -> {outdir}/{id}.fastq: the reads SplitBamCellTypes writes per cell type, printed cell type after
+    cell type - rules BamToFastq + ConcatFastq without the split BAMs (workflow/rules/FusionCalling.gpu.smk FusionFastq_gpu)."""
+    ap = argparse.ArgumentParser(description="FASTQ for ctat-LR-fusion from the unsplit BAM, routed by cell type on the GPU")
+    ap.add_argument("--bam", required=True); ap.add_argument("--meta", required=True); ap.add_argument("--id", default="Sample"); ap.add_argument("--outdir", default=".")
+    ap.add_argument("--min_MQ", type=int, default=255)
+    ap.add_argument("--max_nM", type=_limit, default=None); ap.add_argument("--max_NH", type=_limit, default=None)
+    ap.add_argument("--device", type=int, default=0); ap.add_argument("--host", action="store_true", help="print on the host (no GPU)")
+    ap.add_argument("--per_celltype", action="store_true", help="also write {id}.{celltype}.fastq, the files rule BamToFastq made")
+    a = ap.parse_args(argv)
+    t0 = time.time()
+    table = hostio.read_barcodes(a.meta)
+    os.makedirs(a.outdir, exist_ok=True)
+    out = os.path.join(a.outdir, a.id + ".fastq")
+    info, where = _print_fastq(a.bam, out, table, a.min_MQ, hostio.SplitFilters(a.max_nM, a.max_NH, 0), a.device, a.host)
+    if a.per_celltype:
+        with open(out, "rb") as f:
+            for t, ct in enumerate(table.celltype_names):
+                with open(os.path.join(a.outdir, "%s.%s.fastq" % (a.id, ct)), "wb") as g:
+                    left = info["n_bytes"][t]
+                    while left:
+                        piece = f.read(min(left, 64 << 20))
+                        if not piece:
+                            raise RuntimeError("%s is %d bytes shorter than the %d bytes printed for %s" % (out, left, info["n_bytes"][t], ct))
+                        g.write(piece); left -= len(piece)
+    print(json.dumps({"fastq": out, "records": dict(zip(table.celltype_names, info["n_printed"])), "bytes": dict(zip(table.celltype_names, info["n_bytes"])),
+                      "printed_on": where, "seconds": round(time.time() - t0, 3)}))
+
+
+def somatic_fusions(argv=None):
+    """FusionCalling.py --fusions --barcodes --min_ac_reads --min_ac_cells --max_MCF_noncancer --deltaMCF --outdir  (FusionCalling.py:88-97)"""
+    from . import fusions
+    ap = argparse.ArgumentParser(description="Report all fusions found in cancer cells and passing filters")
+    ap.add_argument("--fusions", required=True); ap.add_argument("--barcodes", required=True)
+    ap.add_argument("--min_ac_reads", type=int, required=True); ap.add_argument("--min_ac_cells", type=int, required=True)
+    ap.add_argument("--max_MCF_noncancer", type=float, required=True); ap.add_argument("--deltaMCF", type=float, required=True)
+    ap.add_argument("--outdir", required=True)
+    a = ap.parse_args(argv)
+    fusions.fusion_report(a.fusions, a.barcodes, a.min_ac_reads, a.min_ac_cells, a.max_MCF_noncancer, a.deltaMCF, a.outdir)
+
+
 def _read_bed(path):
     out = {}
     for line in open(path):

@@ -271,7 +271,7 @@ int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_dep
     const char* who = "lsg_cellgeno_count";
     CellGeno& g = c->cg;
     g.valid = g.text_valid = g.filt_valid = false;
-    for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
+    for (int t = LSG_TABLE_CELL_LONG; t <= LSG_TABLE_BNPC_VAF; ++t) c->tab_bytes[t] = -1;
     if (int rc = check_tail_params(who, alpha2, beta2, pvalue)) return rc;
     if (c->n_contigs <= 0) { set_error("%s: no contigs set", who); return -2; }
     if (c->n_cb <= 0) { set_error("%s: no barcodes set", who); return -2; }
@@ -294,7 +294,7 @@ int run_cellgeno_load_counts(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const ui
     const char* who = "lsg_cellgeno_load_counts";
     CellGeno& g = c->cg;
     g.valid = g.text_valid = g.filt_valid = false;
-    for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
+    for (int t = LSG_TABLE_CELL_LONG; t <= LSG_TABLE_BNPC_VAF; ++t) c->tab_bytes[t] = -1;
     if (int rc = check_tail_params(who, alpha2, beta2, pvalue)) return rc;
     if ((double)n_sites * (double)n_cb >= 2147483648.0) { set_error("%s: %lld sites x %d barcodes", who, (long long)n_sites, n_cb); return -2; }
     if (reserve_cells(c, n_sites, n_cb)) return -1;
@@ -323,7 +323,7 @@ int run_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* t) {
     const char* who = "lsg_cellgeno_set_text";
     CellGeno& g = c->cg;
     g.text_valid = g.filt_valid = false;
-    for (int q = LSG_TABLE_CELL_LONG; q < LSG_TABLE_SLOTS; ++q) c->tab_bytes[q] = -1;
+    for (int q = LSG_TABLE_CELL_LONG; q <= LSG_TABLE_BNPC_VAF; ++q) c->tab_bytes[q] = -1;
     if (!g.valid) { set_error("%s: nothing classified (lsg_cellgeno_count first)", who); return -2; }
     const int64_t S = g.n_sites; const int32_t B = g.n_cb;
     if (t->n_long < 0 || t->n_long > S || t->n_mat < 0 || t->n_mat > S || t->n_cols < 0 || (t->n_long > 0 && !t->long_order) || (t->n_mat > 0 && !t->mat_order) ||
@@ -361,7 +361,7 @@ int run_cellgeno_load_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uin
     const char* who = "lsg_cellgeno_load_cells";
     CellGeno& g = c->cg;
     g.valid = g.text_valid = g.filt_valid = false;
-    for (int t = LSG_TABLE_CELL_LONG; t < LSG_TABLE_SLOTS; ++t) c->tab_bytes[t] = -1;
+    for (int t = LSG_TABLE_CELL_LONG; t <= LSG_TABLE_BNPC_VAF; ++t) c->tab_bytes[t] = -1;
     if ((double)n_sites * (double)n_cb >= 2147483648.0) { set_error("%s: %lld sites x %d barcodes", who, (long long)n_sites, n_cb); return -2; }
     const int64_t cells = n_sites * (int64_t)n_cb;
     for (int64_t i = 0; i < cells; ++i) {

@@ -26,6 +26,8 @@
 
 #include "../synth_model.h"
 #include "../bamrec_core.h"
+#include "../cbtable_host.h"
+#include "../fastq_core.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -889,6 +891,81 @@ int lsio_split_bam_filtered(const char* path, const char* barcodes, int32_t n_ba
 int lsio_split_bam(const char* path, const char* barcodes, int32_t n_barcodes, const uint8_t* celltype_of_barcode, int32_t n_ct,
                    const char* out_paths, int32_t min_mapq, int64_t* counters) {
     return lsio_split_bam_filtered(path, barcodes, n_barcodes, celltype_of_barcode, n_ct, out_paths, min_mapq, counters, -1, -1, 0, nullptr, nullptr);
+}
+
+// FASTQ for the fusion caller: the host twin of lsg_bam_fastq (csrc/fastq.hip; the semantics are in include/longsom_hip.h), the same bytes
+// written to `fastq_path` (truncated).  Replaces bam_to_fastq (FusionCalling/BamToFastq.py:9-42) and, with a barcode list (routed mode),
+// SplitBamCellTypes' BAMs + one BamToFastq per cell type + ConcatFastq (rules/FusionCalling.smk:3-37).  What a BAM whose record chain the
+// device cannot settle (rc -4) is printed with, and what the GPU tests compare against.  The per-record decisions are fastq_core.h's,
+// shared with the device.  max_nm / max_nh / n_trim: SplitBam's filters of routed mode (-1 / -1 / 0: off; n_trim > 0 is refused).
+int lsio_bam_fastq(const char* bam_path, const char* fastq_path, const char* barcodes, int32_t n_barcodes, const int32_t* celltype_of, int32_t n_celltypes,
+                   int32_t min_mapq, int32_t max_nm, int32_t max_nh, int32_t n_trim, lsg_fastq_info* info) {
+    if (!bam_path || !fastq_path || !info) { set_err("lsio_bam_fastq: bad arguments"); return -2; }
+    const bool routed = barcodes != nullptr;
+    *info = lsg_fastq_info{};
+    info->bad_ordinal = -1; info->bad_kind = LSG_FASTQ_OK;
+    if (routed) {
+        if (n_barcodes <= 0 || !celltype_of || n_celltypes <= 0 || n_celltypes > LSG_MAX_CELLTYPES) { set_err("lsio_bam_fastq: routed mode needs a barcode list and 1..%d cell types", LSG_MAX_CELLTYPES); return -2; }
+        for (int32_t i = 0; i < n_barcodes; ++i)
+            if (celltype_of[i] < 0 || celltype_of[i] >= n_celltypes) { set_err("lsio_bam_fastq: barcode %d has cell type %d of %d", i, celltype_of[i], n_celltypes); return -2; }
+        if (n_trim > 0) { set_err("lsio_bam_fastq: --n_trim %d is set: the reference would write qualities of 0 into the split BAMs; print those with BamToFastq", n_trim); return -2; }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t n_ct = routed ? n_celltypes : 1;
+    lsr::CbTableHost cbt;
+    if (routed) cbt.build(barcodes, n_barcodes, celltype_of);
+    lsio_stream* st = nullptr;
+    if (lsio_stream_open(bam_path, nullptr, 0, nullptr, min_mapq, 0, &st) != 0) return -1;
+    std::vector<uint8_t> data; std::vector<size_t> recs;
+    const int rcs = next_records(*st, (size_t)-1, data, recs);           // validated: block sizes, header, every record's fields
+    if (rcs < 0 || !st->header_done) { if (rcs >= 0) set_err("lsio_bam_fastq: %s has no BAM header", bam_path); delete st; return -1; }
+    delete st;
+    const uint8_t* d = data.data();
+    info->n_records = (int64_t)recs.size();
+    // pass 1: every record's cell type and length, the first record that cannot be printed
+    std::vector<int8_t> ct(recs.size(), -1);
+    std::vector<lsf::FqRec> desc(recs.size());
+    for (size_t i = 0; i < recs.size(); ++i) {
+        const uint32_t bs = rd32(d + recs[i]); const uint8_t* rec = d + recs[i] + 4;
+        int bad = lsf::FQ_OK;
+        int32_t t = routed ? lsf::route(rec, bs, cbt.view(), min_mapq, max_nm < 0 ? -1 : max_nm, max_nh < 0 ? -1 : max_nh, &bad) : 0;
+        if (bad == lsf::FQ_OK && t >= 0) bad = lsf::describe(rec, bs, &desc[i]);
+        if (bad != lsf::FQ_OK) {
+            info->bad_ordinal = (int64_t)i; info->bad_kind = bad;
+            set_err("lsio_bam_fastq: read '%s' (record %zu): %s", read_name(rec).c_str(), i, lsf::bad_text(bad));
+            return -1;
+        }
+        ct[i] = (int8_t)t;
+        if (t >= 0) { ++info->n_printed[t]; info->n_bytes[t] += (int64_t)lsf::text_len(desc[i]); }
+    }
+    // pass 2: the bytes, cell type after cell type
+    FILE* f = fopen(fastq_path, "wb");
+    if (!f) { set_err("lsio_bam_fastq: cannot write %s", fastq_path); return -1; }
+    static const char NT16[] = "=ACMGRSVTWYHKDBN";
+    std::string line;
+    bool ok = true;
+    for (int32_t t = 0; t < n_ct && ok; ++t)
+        for (size_t i = 0; i < recs.size() && ok; ++i) {
+            if (ct[i] != t) continue;
+            const uint8_t* rec = d + recs[i] + 4;
+            const lsf::FqRec& r = desc[i];
+            const uint8_t* seq = rec + 32 + rec[8] + 4ull * rd16(rec + 12);
+            const uint8_t* qual = seq + (r.l_seq + 1) / 2;
+            line.clear();
+            const uint32_t H = lsf::header_len(r);
+            for (uint32_t k = 0; k < H; ++k) line.push_back((char)lsf::header_byte(rec, r, k));
+            if (!r.l_seq) line.push_back('*');
+            else for (uint32_t j = 0; j < r.l_seq; ++j) line.push_back(NT16[(seq[j >> 1] >> ((~j & 1u) << 2)) & 0xfu]);
+            line += "\n+\n";
+            if (r.no_qual) line.push_back('*');
+            else for (uint32_t j = 0; j < r.l_seq; ++j) line.push_back((char)(uint8_t)(qual[j] + 33u));
+            line.push_back('\n');
+            ok = fwrite(line.data(), 1, line.size(), f) == line.size();
+        }
+    if (fclose(f) != 0) ok = false;
+    if (!ok) { set_err("lsio_bam_fastq: write failed"); return -1; }
+    info->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
 }
 
 // Host evaluation of the model's read-record arrays (the same arrays lsg_synth_reads generates in HBM).

@@ -21,6 +21,7 @@
 #include "inflate_core.h"
 #include "crc_core.h"
 #include "cbtable_host.h"
+#include "ingest_front.h"
 #include <hipcub/hipcub.hpp>
 #include <chrono>
 #include <cstdio>
@@ -232,6 +233,154 @@ __global__ __launch_bounds__(256) void k_rec_emit(EmitArgs a) {
 
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; }
 
+// ingest_front.h: BGZF blocks -> uncompressed stream -> settled record chain -> every record's offset
+int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_bytes, int64_t first_record_offset, int range, IngestFront& f) {
+    hipStream_t st = c->stream;
+    // ---- the BGZF blocks (every length field checked against the bytes that are there)
+    std::vector<IngBlk> blocks;
+    uint64_t utotal = 0;
+    for (uint64_t off = 0; off < (uint64_t)n_bytes;) {
+        if (off + 18 > (uint64_t)n_bytes) { set_error("%s: truncated BGZF block header at offset %llu", who, (unsigned long long)off); return -1; }
+        const uint8_t* h = file + off;
+        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) { set_error("%s: not BGZF (offset %llu)", who, (unsigned long long)off); return -1; }
+        const uint32_t xlen = lsr::rd16(h + 10);
+        if (off + 12 + xlen > (uint64_t)n_bytes) { set_error("%s: truncated BGZF extra field at offset %llu", who, (unsigned long long)off); return -1; }
+        uint32_t bsize = 0; bool found = false;
+        for (uint32_t q = 0; q + 4 <= xlen;) {
+            const uint8_t* sf = h + 12 + q; const uint32_t slen = lsr::rd16(sf + 2);
+            if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && q + 6 <= xlen) { bsize = lsr::rd16(sf + 4) + 1u; found = true; }
+            q += 4 + slen;
+        }
+        if (!found || bsize < xlen + 20u || off + bsize > (uint64_t)n_bytes) { set_error("%s: corrupt BGZF block at offset %llu", who, (unsigned long long)off); return -1; }
+        const uint32_t usize = lsr::rd32(h + bsize - 4);
+        if (usize > 65536u) { set_error("%s: BGZF block at offset %llu claims %u uncompressed bytes", who, (unsigned long long)off, usize); return -1; }
+        blocks.push_back(IngBlk{off + 12 + xlen, utotal, bsize - xlen - 20, usize, lsr::rd32(h + bsize - 8), 0u});
+        utotal += usize; off += bsize;
+    }
+    const uint32_t n_blk = (uint32_t)blocks.size();
+    if ((uint64_t)first_record_offset > utotal) { set_error("%s: the first record lies behind the file's %llu uncompressed bytes", who, (unsigned long long)utotal); return -1; }
+    f.utotal = utotal; f.n_blk = n_blk;
+    // ---- device buffers
+    if (f.d_comp.reserve((size_t)n_bytes + 16) || f.d_u.reserve((size_t)utotal + 64) || f.d_blk.reserve((size_t)n_blk * sizeof(IngBlk) + 16) || f.d_in.reserve(((size_t)n_blk + 1) * 8) ||
+        f.d_land.reserve(((size_t)n_blk + 1) * 8) || f.d_nrec.reserve(((size_t)n_blk + 2) * 4) || f.d_base.reserve(((size_t)n_blk + 2) * 4) || f.d_status.reserve(64))
+        return -1;
+    for (auto& e : f.ev) if (hipEventCreate(&e) != hipSuccess) { set_error("%s: hipEventCreate failed", who); return -1; }
+#define ING_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
+    ING_HIP(hipEventRecord(f.ev[0], st));
+    {   // the file's bytes, through two pinned staging buffers (the caller's memory is usually a read-only file mapping: pageable, and
+        // not every runtime can pin it): the CPU fills one while the DMA engine drains the other
+        const size_t CH = 32u << 20;
+        uint8_t* pin[2] = {nullptr, nullptr}; hipEvent_t pe[2] = {nullptr, nullptr};
+        bool ok = true;
+        for (int i = 0; i < 2 && ok; ++i) ok = hipHostMalloc(reinterpret_cast<void**>(&pin[i]), CH, hipHostMallocDefault) == hipSuccess && hipEventCreate(&pe[i]) == hipSuccess;
+        size_t off = 0; int slot = 0; bool used[2] = {false, false};
+        while (ok && off < (size_t)n_bytes) {
+            const size_t n = (size_t)n_bytes - off < CH ? (size_t)n_bytes - off : CH;
+            if (used[slot]) ok = hipEventSynchronize(pe[slot]) == hipSuccess;
+            if (!ok) break;
+            memcpy(pin[slot], file + off, n);
+            ok = hipMemcpyAsync(f.d_comp.as<uint8_t>() + off, pin[slot], n, hipMemcpyHostToDevice, st) == hipSuccess && hipEventRecord(pe[slot], st) == hipSuccess;
+            used[slot] = true; off += n; slot ^= 1;
+        }
+        if (ok) ok = hipStreamSynchronize(st) == hipSuccess;
+        for (int i = 0; i < 2; ++i) { if (pe[i]) (void)hipEventDestroy(pe[i]); if (pin[i]) (void)hipHostFree(pin[i]); }
+        if (!ok) { set_error("%s: copying the file to the device failed: %s", who, hipGetErrorString(hipGetLastError())); return -1; }
+    }
+    ING_HIP(hipMemcpyAsync(f.d_blk.p, blocks.data(), (size_t)n_blk * sizeof(IngBlk), hipMemcpyHostToDevice, st));
+    ING_HIP(hipMemsetAsync(f.d_status.p, 0, 64, st));
+    ING_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f.d_status.as<uint32_t>() + 1), (int)0x7fffffff, 2, st));
+    ING_HIP(hipEventRecord(f.ev[1], st));
+    // ---- inflate
+    const IngBlk* dblk = f.d_blk.as<IngBlk>();
+    uint32_t* status = f.d_status.as<uint32_t>();
+    {                                                        // a lane per block; 26.9 KB of LDS tables per wave: five waves per CU
+        static const unsigned per_cu = getenv("LSG_INFLATE_WAVES") ? (unsigned)atoi(getenv("LSG_INFLATE_WAVES")) : 5u;
+        unsigned g = (n_blk + 63) / 64; const unsigned cap = (unsigned)c->n_cus * (per_cu ? per_cu : 5u);
+        if (g > cap) g = cap;
+        if (!g) g = 1;
+        if (f.d_tmp.reserve((size_t)g * lsi::T_LENS * 64)) return -3;
+        hipLaunchKernelGGL(k_inflate, dim3(g), dim3(64), 0, st, f.d_comp.as<uint8_t>(), dblk, n_blk, f.d_u.as<uint8_t>(), status, f.d_tmp.as<uint8_t>());
+    }
+    ING_HIP(hipEventRecord(f.ev[2], st));
+    uint32_t hstat[4] = {0, 0, 0, 0};
+    ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
+    ING_HIP(hipStreamSynchronize(st));
+    if (hstat[0] & 1u) { set_error("%s: inflate failed in BGZF block %u", who, hstat[1]); return -1; }
+    f.d_comp.release();
+    if (!getenv("LSG_NO_BGZF_CRC")) {                     // every block's CRC32 against its trailer (k_block_crc)
+        static CrcTables h_tabs; static bool h_tabs_made = false;
+        if (!h_tabs_made) { lsc::make_crc_tables(h_tabs); h_tabs_made = true; }
+        DevBuf d_tabs;
+        if (d_tabs.reserve(sizeof(CrcTables))) return -1;
+        hipError_t es = hipMemcpyAsync(d_tabs.p, &h_tabs, sizeof(CrcTables), hipMemcpyHostToDevice, st);
+        if (es == hipSuccess) es = hipMemsetAsync(status, 0, 4, st);
+        if (es == hipSuccess) es = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status + 1), (int)0x7fffffff, 1, st);
+        if (es == hipSuccess) {
+            unsigned g = (n_blk + 3) / 4; const unsigned cap = (unsigned)(c->n_cus * 8);
+            if (g > cap) g = cap;
+            hipLaunchKernelGGL(k_block_crc, dim3(g ? g : 1), dim3(256), 0, st, f.d_u.as<uint8_t>(), dblk, n_blk, d_tabs.as<CrcTables>(), status);
+            es = hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st);
+        }
+        const hipError_t es2 = hipStreamSynchronize(st);
+        d_tabs.release();
+        if (es != hipSuccess || es2 != hipSuccess) { set_error("%s: the CRC pass failed: %s", who, hipGetErrorString(es != hipSuccess ? es : es2)); return -1; }
+        if (hstat[0] & 32u) { set_error("%s: CRC32 mismatch in BGZF block %u", who, hstat[1]); return -1; }
+    }
+    // ---- the record chain
+    const uint8_t* u = f.d_u.as<uint8_t>();
+    uint64_t* in = f.d_in.as<uint64_t>(); uint64_t* land = f.d_land.as<uint64_t>();
+    {
+        std::vector<uint64_t> h_in(n_blk);
+        for (uint32_t b = 0; b < n_blk; ++b) h_in[b] = b == 0 ? (uint64_t)first_record_offset : blocks[b].uoff;      // htslib: a block starts on a record boundary
+        ING_HIP(hipMemcpyAsync(in, h_in.data(), (size_t)n_blk * 8, hipMemcpyHostToDevice, st));
+        ING_HIP(hipStreamSynchronize(st));
+    }
+    const int max_rounds = env_int("LSG_CHAIN_ROUNDS", 512);
+    int rounds = 0;
+    uint32_t* changed = status + 3;
+    for (;; ++rounds) {
+        if (rounds > max_rounds) {
+            set_error("%s: the records of this BAM straddle its BGZF blocks (not written by htslib's bam_write1?): %d rounds did not settle the record chain; decode it on the host", who, max_rounds);
+            return -4;
+        }
+        ING_HIP(hipMemsetAsync(status, 0, 4, st));
+        ING_HIP(hipMemsetAsync(changed, 0, 4, st));
+        hipLaunchKernelGGL(k_chain, dim3((n_blk + 255) / 256), dim3(256), 0, st, u, utotal, dblk, n_blk, in, land, f.d_nrec.as<uint32_t>(), status, range);
+        hipLaunchKernelGGL(k_chain_fix, dim3((n_blk + 255) / 256), dim3(256), 0, st, dblk, n_blk, (uint64_t)first_record_offset, in, land, changed);
+        ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
+        ING_HIP(hipStreamSynchronize(st));
+        if (hstat[3] == 0) break;                      // every block started where its predecessor's chain landed: the walk just made is the true one
+    }
+    f.rounds = rounds;
+    if (hstat[0] & 6u) { set_error("%s: %s", who, (hstat[0] & 2u) ? "truncated record at the end of the file" : "record with an impossible block_size"); return -1; }
+    {
+        uint64_t last_land = 0;
+        ING_HIP(hipMemcpyAsync(&last_land, land + (n_blk - 1), 8, hipMemcpyDeviceToHost, st));
+        ING_HIP(hipStreamSynchronize(st));
+        if (!range && last_land != utotal) { set_error("%s: truncated record at the end of the file", who); return -1; }
+    }
+    ING_HIP(hipEventRecord(f.ev[3], st));
+    uint32_t n_rec32 = 0;
+    {
+        ING_HIP(hipMemsetAsync(f.d_nrec.as<uint32_t>() + n_blk, 0, 4, st));
+        size_t tb = 0;
+        ING_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, f.d_nrec.as<uint32_t>(), f.d_base.as<uint32_t>(), (int)(n_blk + 1), st));
+        if (f.d_tmp.reserve(tb + 256)) return -1;
+        tb = f.d_tmp.cap;
+        ING_HIP(hipcub::DeviceScan::ExclusiveSum(f.d_tmp.p, tb, f.d_nrec.as<uint32_t>(), f.d_base.as<uint32_t>(), (int)(n_blk + 1), st));
+        ING_HIP(hipMemcpyAsync(&n_rec32, f.d_base.as<uint32_t>() + n_blk, 4, hipMemcpyDeviceToHost, st));
+        ING_HIP(hipStreamSynchronize(st));
+    }
+    const uint64_t n_rec = n_rec32;
+    if (n_rec >= 0x7fffff00ull) { set_error("%s: more than 2^31 records; load the file in windows on the host", who); return -2; }
+    f.n_rec = n_rec;
+    if (f.d_recoff.reserve((n_rec + 1) * 8)) return -1;
+    if (n_rec) hipLaunchKernelGGL(k_rec_list, dim3((n_blk + 255) / 256), dim3(256), 0, st, u, dblk, n_blk, in, f.d_base.as<uint32_t>(), f.d_recoff.as<uint64_t>());
+    (void)hipEventElapsedTime(&f.ms_h2d, f.ev[0], f.ev[1]); (void)hipEventElapsedTime(&f.ms_inflate, f.ev[1], f.ev[2]); (void)hipEventElapsedTime(&f.ms_chain, f.ev[2], f.ev[3]);
+    return 0;
+#undef ING_HIP
+}
+
 } // namespace lsg
 
 using namespace lsg;
@@ -248,171 +397,50 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     hipStream_t st = c->stream;
     const auto t_all = std::chrono::steady_clock::now();
     *info = lsg_bam_info{};
-    // ---- the BGZF blocks (every length field checked against the bytes that are there)
-    std::vector<IngBlk> blocks;
-    uint64_t utotal = 0;
-    for (uint64_t off = 0; off < (uint64_t)n_bytes;) {
-        if (off + 18 > (uint64_t)n_bytes) { set_error("lsg_load_bam: truncated BGZF block header at offset %llu", (unsigned long long)off); return -1; }
-        const uint8_t* h = file + off;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) { set_error("lsg_load_bam: not BGZF (offset %llu)", (unsigned long long)off); return -1; }
-        const uint32_t xlen = lsr::rd16(h + 10);
-        if (off + 12 + xlen > (uint64_t)n_bytes) { set_error("lsg_load_bam: truncated BGZF extra field at offset %llu", (unsigned long long)off); return -1; }
-        uint32_t bsize = 0; bool found = false;
-        for (uint32_t q = 0; q + 4 <= xlen;) {
-            const uint8_t* sf = h + 12 + q; const uint32_t slen = lsr::rd16(sf + 2);
-            if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && q + 6 <= xlen) { bsize = lsr::rd16(sf + 4) + 1u; found = true; }
-            q += 4 + slen;
-        }
-        if (!found || bsize < xlen + 20u || off + bsize > (uint64_t)n_bytes) { set_error("lsg_load_bam: corrupt BGZF block at offset %llu", (unsigned long long)off); return -1; }
-        const uint32_t usize = lsr::rd32(h + bsize - 4);
-        if (usize > 65536u) { set_error("lsg_load_bam: BGZF block at offset %llu claims %u uncompressed bytes", (unsigned long long)off, usize); return -1; }
-        blocks.push_back(IngBlk{off + 12 + xlen, utotal, bsize - xlen - 20, usize, lsr::rd32(h + bsize - 8), 0u});
-        utotal += usize; off += bsize;
-    }
-    const uint32_t n_blk = (uint32_t)blocks.size();
-    if ((uint64_t)first_record_offset > utotal) { set_error("lsg_load_bam: the first record lies behind the file's %llu uncompressed bytes", (unsigned long long)utotal); return -1; }
     lsr::CbTableHost cbt; cbt.build(barcodes, n_barcodes, ids);
     const int64_t n_tally = cbt.n_tally;
-    // ---- device buffers
-    DevBuf d_comp, d_u, d_blk, d_in, d_land, d_nrec, d_base, d_status, d_recoff, d_keep, d_cb, d_nseg, d_nev, d_ridx, d_soff, d_eoff, d_cnt, d_tpass, d_tlow, d_tmp;
+    // ---- device buffers: the front half's (ingest_front.h) and the decode's
+    IngestFront fr;
+    DevBuf &d_u = fr.d_u, &d_recoff = fr.d_recoff, &d_tmp = fr.d_tmp;
+    DevBuf d_keep, d_cb, d_nseg, d_nev, d_ridx, d_soff, d_eoff, d_cnt, d_tpass, d_tlow;
     DevBuf d_h, d_id, d_so, d_sl, d_str, d_rsn;
     for (int r = 0; r < lsr::N_REASONS; ++r) { c->split_n[r] = 0; c->split_first[r] = -1; }
-    auto done = [&](int rc) {
-        for (DevBuf* b : {&d_comp, &d_u, &d_blk, &d_in, &d_land, &d_nrec, &d_base, &d_status, &d_recoff, &d_keep, &d_cb, &d_nseg, &d_nev, &d_ridx, &d_soff, &d_eoff, &d_cnt, &d_tpass,
-                          &d_tlow, &d_tmp, &d_h, &d_id, &d_so, &d_sl, &d_str, &d_rsn}) b->release();
+    hipEvent_t ev_end = nullptr;
+    auto done_ev = [&](int rc) {
+        for (DevBuf* b : {&d_keep, &d_cb, &d_nseg, &d_nev, &d_ridx, &d_soff, &d_eoff, &d_cnt, &d_tpass, &d_tlow, &d_h, &d_id, &d_so, &d_sl, &d_str, &d_rsn}) b->release();
+        if (ev_end) (void)hipEventDestroy(ev_end);
+        fr.release();
         return rc;
     };
-    if (d_comp.reserve((size_t)n_bytes + 16) || d_u.reserve((size_t)utotal + 64) || d_blk.reserve((size_t)n_blk * sizeof(IngBlk) + 16) || d_in.reserve(((size_t)n_blk + 1) * 8) ||
-        d_land.reserve(((size_t)n_blk + 1) * 8) || d_nrec.reserve(((size_t)n_blk + 2) * 4) || d_base.reserve(((size_t)n_blk + 2) * 4) || d_status.reserve(64) || d_cnt.reserve(64) ||
-        d_rsn.reserve((2 * lsr::N_REASONS + 2) * 8) ||
-        d_tpass.reserve(((size_t)n_tally + 1) * 8) || d_tlow.reserve(((size_t)n_tally + 1) * 8) ||
+    if (d_cnt.reserve(64) || d_rsn.reserve((2 * lsr::N_REASONS + 2) * 8) || d_tpass.reserve(((size_t)n_tally + 1) * 8) || d_tlow.reserve(((size_t)n_tally + 1) * 8) ||
         d_h.reserve(cbt.hash.size() * 8) || d_id.reserve(cbt.id.size() * 4) || d_so.reserve(cbt.str_off.size() * 4) || d_sl.reserve(cbt.str_len.size() * 4) || d_str.reserve(cbt.strs.size() + 16))
-        return done(-1);
-    hipEvent_t ev[6];
-    for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) { set_error("lsg_load_bam: hipEventCreate failed"); return done(-1); }
-    auto done_ev = [&](int rc) { for (auto& e : ev) (void)hipEventDestroy(e); return done(rc); };
+        return done_ev(-1);
+    if (hipEventCreate(&ev_end) != hipSuccess) { set_error("lsg_load_bam: hipEventCreate failed"); return done_ev(-1); }
 #define ING_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return done_ev(-1); } } while (0)
-    ING_HIP(hipEventRecord(ev[0], st));
-    {   // the file's bytes, through two pinned staging buffers (the caller's memory is usually a read-only file mapping: pageable, and
-        // not every runtime can pin it): the CPU fills one while the DMA engine drains the other
-        const size_t CH = 32u << 20;
-        uint8_t* pin[2] = {nullptr, nullptr}; hipEvent_t pe[2] = {nullptr, nullptr};
-        bool ok = true;
-        for (int i = 0; i < 2 && ok; ++i) ok = hipHostMalloc(reinterpret_cast<void**>(&pin[i]), CH, hipHostMallocDefault) == hipSuccess && hipEventCreate(&pe[i]) == hipSuccess;
-        size_t off = 0; int slot = 0; bool used[2] = {false, false};
-        while (ok && off < (size_t)n_bytes) {
-            const size_t n = (size_t)n_bytes - off < CH ? (size_t)n_bytes - off : CH;
-            if (used[slot]) ok = hipEventSynchronize(pe[slot]) == hipSuccess;
-            if (!ok) break;
-            memcpy(pin[slot], file + off, n);
-            ok = hipMemcpyAsync(d_comp.as<uint8_t>() + off, pin[slot], n, hipMemcpyHostToDevice, st) == hipSuccess && hipEventRecord(pe[slot], st) == hipSuccess;
-            used[slot] = true; off += n; slot ^= 1;
-        }
-        if (ok) ok = hipStreamSynchronize(st) == hipSuccess;
-        for (int i = 0; i < 2; ++i) { if (pe[i]) (void)hipEventDestroy(pe[i]); if (pin[i]) (void)hipHostFree(pin[i]); }
-        if (!ok) { set_error("lsg_load_bam: copying the file to the device failed: %s", hipGetErrorString(hipGetLastError())); return done_ev(-1); }
-    }
-    ING_HIP(hipMemcpyAsync(d_blk.p, blocks.data(), (size_t)n_blk * sizeof(IngBlk), hipMemcpyHostToDevice, st));
     ING_HIP(hipMemcpyAsync(d_h.p, cbt.hash.data(), cbt.hash.size() * 8, hipMemcpyHostToDevice, st));
     ING_HIP(hipMemcpyAsync(d_id.p, cbt.id.data(), cbt.id.size() * 4, hipMemcpyHostToDevice, st));
     ING_HIP(hipMemcpyAsync(d_so.p, cbt.str_off.data(), cbt.str_off.size() * 4, hipMemcpyHostToDevice, st));
     ING_HIP(hipMemcpyAsync(d_sl.p, cbt.str_len.data(), cbt.str_len.size() * 4, hipMemcpyHostToDevice, st));
     ING_HIP(hipMemcpyAsync(d_str.p, cbt.strs.data(), cbt.strs.size(), hipMemcpyHostToDevice, st));
-    ING_HIP(hipMemsetAsync(d_status.p, 0, 64, st));
-    ING_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status.as<uint32_t>() + 1), (int)0x7fffffff, 2, st));
     ING_HIP(hipMemsetAsync(d_cnt.p, 0, 64, st));
     ING_HIP(hipMemsetAsync(d_rsn.p, 0, lsr::N_REASONS * 8, st));                                    // reason counts 0, first ordinals and the error ~0
     ING_HIP(hipMemsetAsync(d_rsn.as<unsigned long long>() + lsr::N_REASONS, 0xff, (lsr::N_REASONS + 1) * 8, st));
     ING_HIP(hipMemsetAsync(d_tpass.p, 0, ((size_t)n_tally + 1) * 8, st));
     ING_HIP(hipMemsetAsync(d_tlow.p, 0, ((size_t)n_tally + 1) * 8, st));
-    ING_HIP(hipEventRecord(ev[1], st));
-    // ---- inflate
-    const IngBlk* dblk = d_blk.as<IngBlk>();
-    uint32_t* status = d_status.as<uint32_t>();
-    {                                                        // a lane per block; 26.9 KB of LDS tables per wave: five waves per CU
-        static const unsigned per_cu = getenv("LSG_INFLATE_WAVES") ? (unsigned)atoi(getenv("LSG_INFLATE_WAVES")) : 5u;
-        unsigned g = (n_blk + 63) / 64; const unsigned cap = (unsigned)c->n_cus * (per_cu ? per_cu : 5u);
-        if (g > cap) g = cap;
-        if (!g) g = 1;
-        if (d_tmp.reserve((size_t)g * lsi::T_LENS * 64)) return done_ev(-3);
-        hipLaunchKernelGGL(k_inflate, dim3(g), dim3(64), 0, st, d_comp.as<uint8_t>(), dblk, n_blk, d_u.as<uint8_t>(), status, d_tmp.as<uint8_t>());
-    }
-    ING_HIP(hipEventRecord(ev[2], st));
-    uint32_t hstat[4] = {0, 0, 0, 0};
-    ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
-    ING_HIP(hipStreamSynchronize(st));
-    if (hstat[0] & 1u) { set_error("lsg_load_bam: inflate failed in BGZF block %u", hstat[1]); return done_ev(-1); }
-    d_comp.release();
-    if (!getenv("LSG_NO_BGZF_CRC")) {                     // every block's CRC32 against its trailer (k_block_crc)
-        static CrcTables h_tabs; static bool h_tabs_made = false;
-        if (!h_tabs_made) { lsc::make_crc_tables(h_tabs); h_tabs_made = true; }
-        DevBuf d_tabs;
-        if (d_tabs.reserve(sizeof(CrcTables))) return done_ev(-1);
-        ING_HIP(hipMemcpyAsync(d_tabs.p, &h_tabs, sizeof(CrcTables), hipMemcpyHostToDevice, st));
-        ING_HIP(hipMemsetAsync(status, 0, 4, st));
-        ING_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status + 1), (int)0x7fffffff, 1, st));
-        unsigned g = (n_blk + 3) / 4; const unsigned cap = (unsigned)(c->n_cus * 8);
-        if (g > cap) g = cap;
-        hipLaunchKernelGGL(k_block_crc, dim3(g ? g : 1), dim3(256), 0, st, d_u.as<uint8_t>(), dblk, n_blk, d_tabs.as<CrcTables>(), status);
-        ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
-        const hipError_t es = hipStreamSynchronize(st);
-        d_tabs.release();
-        if (es != hipSuccess) { set_error("lsg_load_bam: the CRC pass failed: %s", hipGetErrorString(es)); return done_ev(-1); }
-        if (hstat[0] & 32u) { set_error("lsg_load_bam: CRC32 mismatch in BGZF block %u", hstat[1]); return done_ev(-1); }
-    }
-    // ---- the record chain
+    // ---- H2D, inflate, CRC, the record chain, every record's offset
+    if (const int rc = ingest_front(c, "lsg_load_bam", file, n_bytes, first_record_offset, range, fr)) return done_ev(rc);
+    const uint64_t utotal = fr.utotal, n_rec = fr.n_rec;
+    const uint32_t n_blk = fr.n_blk;
+    const int rounds = fr.rounds;
     const uint8_t* u = d_u.as<uint8_t>();
-    uint64_t* in = d_in.as<uint64_t>(); uint64_t* land = d_land.as<uint64_t>();
-    {
-        std::vector<uint64_t> h_in(n_blk);
-        for (uint32_t b = 0; b < n_blk; ++b) h_in[b] = b == 0 ? (uint64_t)first_record_offset : blocks[b].uoff;      // htslib: a block starts on a record boundary
-        ING_HIP(hipMemcpyAsync(in, h_in.data(), (size_t)n_blk * 8, hipMemcpyHostToDevice, st));
-        ING_HIP(hipStreamSynchronize(st));
-    }
-    const int max_rounds = env_int("LSG_CHAIN_ROUNDS", 512);
-    int rounds = 0;
-    uint32_t* changed = status + 3;
-    for (;; ++rounds) {
-        if (rounds > max_rounds) {
-            set_error("lsg_load_bam: the records of this BAM straddle its BGZF blocks (not written by htslib's bam_write1?): %d rounds did not settle the record chain; decode it on the host", max_rounds);
-            return done_ev(-4);
-        }
-        ING_HIP(hipMemsetAsync(status, 0, 4, st));
-        ING_HIP(hipMemsetAsync(changed, 0, 4, st));
-        hipLaunchKernelGGL(k_chain, dim3((n_blk + 255) / 256), dim3(256), 0, st, u, utotal, dblk, n_blk, in, land, d_nrec.as<uint32_t>(), status, range);
-        hipLaunchKernelGGL(k_chain_fix, dim3((n_blk + 255) / 256), dim3(256), 0, st, dblk, n_blk, (uint64_t)first_record_offset, in, land, changed);
-        ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
-        if (hstat[3] == 0) break;                      // every block started where its predecessor's chain landed: the walk just made is the true one
-    }
-    if (hstat[0] & 6u) { set_error("lsg_load_bam: %s", (hstat[0] & 2u) ? "truncated record at the end of the file" : "record with an impossible block_size"); return done_ev(-1); }
-    {
-        uint64_t last_land = 0;
-        ING_HIP(hipMemcpyAsync(&last_land, land + (n_blk - 1), 8, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
-        if (!range && last_land != utotal) { set_error("lsg_load_bam: truncated record at the end of the file"); return done_ev(-1); }
-    }
-    ING_HIP(hipEventRecord(ev[3], st));
-    uint32_t n_rec32 = 0;
-    {
-        ING_HIP(hipMemsetAsync(d_nrec.as<uint32_t>() + n_blk, 0, 4, st));
-        size_t tb = 0;
-        ING_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_nrec.as<uint32_t>(), d_base.as<uint32_t>(), (int)(n_blk + 1), st));
-        if (d_tmp.reserve(tb + 256)) return done_ev(-1);
-        tb = d_tmp.cap;
-        ING_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_nrec.as<uint32_t>(), d_base.as<uint32_t>(), (int)(n_blk + 1), st));
-        ING_HIP(hipMemcpyAsync(&n_rec32, d_base.as<uint32_t>() + n_blk, 4, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
-    }
+    uint32_t* status = fr.d_status.as<uint32_t>();
+    uint32_t hstat[4] = {0, 0, 0, 0};
     // the events in the tile-phased layout (LSG_LAYOUT_PHASED): the count then fetches every entry as ONE 128-byte line; LSG_INGEST_COMPACT=1: segment after segment
     const int32_t phased = getenv("LSG_INGEST_COMPACT") ? 0 : 1;
-    const uint64_t n_rec = n_rec32;
-    if (n_rec >= 0x7fffff00ull) { set_error("lsg_load_bam: more than 2^31 records; load the file in windows on the host"); return done_ev(-2); }
-    if (d_recoff.reserve((n_rec + 1) * 8) || d_keep.reserve(n_rec + 16) || d_cb.reserve((n_rec + 1) * 4) || d_nseg.reserve((n_rec + 2) * 4) || d_nev.reserve((n_rec + 2) * 4) ||
+    if (d_keep.reserve(n_rec + 16) || d_cb.reserve((n_rec + 1) * 4) || d_nseg.reserve((n_rec + 2) * 4) || d_nev.reserve((n_rec + 2) * 4) ||
         d_ridx.reserve((n_rec + 2) * 4) || d_soff.reserve((n_rec + 2) * 4) || d_eoff.reserve((n_rec + 2) * 8)) return done_ev(-1);
     uint32_t R = 0, S = 0; unsigned long long E = 0;
     if (n_rec) {
-        hipLaunchKernelGGL(k_rec_list, dim3((n_blk + 255) / 256), dim3(256), 0, st, u, dblk, n_blk, in, d_base.as<uint32_t>(), d_recoff.as<uint64_t>());
         RecArgs ra{};
         ra.u = u; ra.total = utotal; ra.rec_off = d_recoff.as<uint64_t>(); ra.n_rec = n_rec; ra.n_ref = c->n_contigs; ra.ref_len = c->d_contig_len.as<int64_t>();
         ra.cbt = lsr::CbTable{d_h.as<uint64_t>(), d_id.as<int32_t>(), d_so.as<uint32_t>(), d_sl.as<uint32_t>(), d_str.as<uint8_t>(), cbt.mask};
@@ -500,7 +528,7 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
         if (g > cap) g = cap;
         hipLaunchKernelGGL(k_rec_emit, dim3(g), dim3(256), 0, st, ea);
     }
-    ING_HIP(hipEventRecord(ev[4], st));
+    ING_HIP(hipEventRecord(ev_end, st));
     unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     ING_HIP(hipMemcpyAsync(cnt, d_cnt.p, 56, hipMemcpyDeviceToHost, st));
     unsigned long long rsn[2 * lsr::N_REASONS];
@@ -515,8 +543,8 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     }
     ING_HIP(hipGetLastError());
     ING_HIP(hipStreamSynchronize(st));
-    float ms[4] = {0, 0, 0, 0};
-    (void)hipEventElapsedTime(&ms[0], ev[0], ev[1]); (void)hipEventElapsedTime(&ms[1], ev[1], ev[2]); (void)hipEventElapsedTime(&ms[2], ev[2], ev[3]); (void)hipEventElapsedTime(&ms[3], ev[3], ev[4]);
+    float ms[4] = {fr.ms_h2d, fr.ms_inflate, fr.ms_chain, 0};
+    (void)hipEventElapsedTime(&ms[3], fr.ev[3], ev_end);
     // the uncompressed stream and the per-record words are done with before the store is built
     for (DevBuf* b : {&d_u, &d_recoff, &d_keep, &d_cb, &d_nseg, &d_nev, &d_ridx, &d_soff, &d_eoff}) b->release();
     lsg_reads g{};

@@ -476,7 +476,7 @@ int lsg_set_table_names(lsg_ctx* c, int32_t n_contigs, const char* contig_names,
 int lsg_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     if (!c) { set_error("lsg_format_table: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
-    if (table >= LSG_TABLE_CELL_LONG && table < LSG_TABLE_SLOTS) return run_format_cell_table(c, table, n_bytes);
+    if (table >= LSG_TABLE_CELL_LONG && table <= LSG_TABLE_BNPC_VAF) return run_format_cell_table(c, table, n_bytes);
     return run_format_table(c, table, n_bytes);
 }
 int lsg_copy_table(lsg_ctx* c, int32_t table, char* dst_host, int64_t capacity) {

@@ -477,6 +477,7 @@ int run_set_table_names(lsg_ctx* c, int32_t n_contigs, const char* contig_names,
 int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     if (n_bytes) *n_bytes = 0;
     if (table < 0 || table >= LSG_TABLE_SLOTS) { set_error("lsg_format_table: no table %d", table); return -2; }
+    if (table == LSG_TABLE_FASTQ) { set_error("lsg_format_table: table %d is made by lsg_bam_fastq", table); return -2; }
     if (!c->counted) { set_error("lsg_format_table: no count rows (lsg_pileup_count or lsg_load_counts first)"); return -2; }
     if (c->tab_n_contigs != c->n_contigs || c->tab_n_ct < c->n_ct) { set_error("lsg_format_table: lsg_set_table_names first (names of %d contigs and %d cell types)", c->n_contigs, c->n_ct); return -2; }
     if (table == LSG_TABLE_STEP3_ROWS) { set_error("lsg_format_table: table %d is made by lsg_step2_summary", table); return -2; }

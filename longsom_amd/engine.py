@@ -453,6 +453,44 @@ class Engine:
     TABLE_COUNTS, TABLE_MERGED, TABLE_STEP1, TABLE_STEP1_KEPT, TABLE_STEP2, TABLE_STEP3_ROWS = 0, 4, 5, 6, 7, 8
     TABLE_CELL_LONG, TABLE_CELL_DP, TABLE_CELL_ALT, TABLE_CELL_VAF, TABLE_CELL_BIN = 9, 10, 11, 12, 13
     TABLE_BNPC_BIN, TABLE_BNPC_VAF = 14, 15
+    TABLE_FASTQ = 16
+
+    def bam_fastq(self, path: str, barcodes=None, celltype_of=None, n_celltypes: int = 0, min_mapq: int = 60, first_record_offset: Optional[int] = None) -> dict:
+        """lsg_bam_fastq: the BAM's records as the FASTQ text ctat-LR-fusion reads (BamToFastq.py:9-42), printed on the device into table
+        TABLE_FASTQ - fetch it with table_bytes(TABLE_FASTQ, sum(info["n_bytes"])) or stream it into a file with append_table.  barcodes
+        None: plain mode, every record in file order.  barcodes (cleaned strings) + celltype_of + n_celltypes: routed mode, the records
+        SplitBamCellTypes would write to a cell type's BAM (under min_mapq and set_split_filters' limits), cell type after cell type
+        (FusionCalling.smk:3-37).  Reads and changes nothing of a resident load.  Returns the info dict (n_records, n_printed, n_bytes,
+        bad_ordinal, bad_kind, the phases' times).  Raises _lib.LsgError for a record that cannot be printed (the error names it; .info
+        holds bad_ordinal / bad_kind) and, with "straddle" in its text (rc -4), for a BAM to print on the host (hostio.bam_fastq)."""
+        import mmap
+        from . import hostio
+        from ._lib import FastqInfo
+        if first_record_offset is None:
+            first_record_offset = hostio.bam_header(path)[2]
+        info = FastqInfo()
+        joined, n_cb, ct = None, 0, None
+        if barcodes is not None:
+            joined, n_cb = "\n".join(barcodes).encode(), len(barcodes)
+            ct = np.ascontiguousarray(celltype_of, np.int32)
+            if len(ct) != n_cb:
+                raise ValueError("celltype_of holds %d entries for %d barcodes" % (len(ct), n_cb))
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+                buf = np.frombuffer(mm, dtype=np.uint8)
+                try:
+                    rc = self._lib.lsg_bam_fastq(self._h, C.c_void_p(buf.ctypes.data), size, int(first_record_offset), joined, n_cb, _ptr(ct), int(n_celltypes),
+                                                 int(min_mapq), C.byref(info))
+                finally:
+                    del buf
+        d = hostio.fastq_info_dict(info)
+        try:
+            _lib.check(rc, "lsg_bam_fastq")
+        except _lib.LsgError as e:
+            e.info = d
+            raise
+        return d
 
     def set_table_names(self, contig_names, celltype_names) -> None:
         """Names the rows print (contigs in set_contigs order, cell types in index order)."""

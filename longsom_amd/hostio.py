@@ -127,6 +127,8 @@ def load():
                                                  C.POINTER(C.POINTER(Decoded))]
         lib.lsio_stream_set_split_filters.restype = C.c_int
         lib.lsio_stream_set_split_filters.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        lib.lsio_bam_fastq.restype = C.c_int
+        lib.lsio_bam_fastq.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         lib.lsio_build_bai.restype = C.c_int
         lib.lsio_build_bai.argtypes = [C.c_char_p, C.c_char_p]
         lib.lsio_set_legacy_del_merge.argtypes = [C.c_int]
@@ -372,6 +374,40 @@ def split_bam(path: str, table: "BarcodeTable", out_paths: Sequence[str], min_ma
                                    *(filters or SplitFilters()).args(), rn, rf) != 0:
         _err("lsio_split_bam")
     return split_report(cnt, [(list(rn), list(rf))])
+
+
+class FastqError(RuntimeError):
+    """a record that cannot be printed; .info holds bad_ordinal / bad_kind (the _lib.FASTQ_* kinds)"""
+    info: dict = {}
+
+
+def fastq_info_dict(info) -> dict:
+    """a lsg_fastq_info as a dict (the arrays as lists of 4)"""
+    d = {k: getattr(info, k) for k, _ in info._fields_}
+    d["n_printed"] = [int(x) for x in info.n_printed]; d["n_bytes"] = [int(x) for x in info.n_bytes]
+    return d
+
+
+def bam_fastq(path: str, fastq: str, table: Optional["BarcodeTable"] = None, min_mapq: int = 60, filters: Optional[SplitFilters] = None) -> dict:
+    """The host twin of Engine.bam_fastq (lsio_bam_fastq): the BAM's records as FASTQ for ctat-LR-fusion, written to `fastq`.  table None:
+    plain mode = BamToFastq.py over one BAM.  With a BarcodeTable: routed mode = the records SplitBamCellTypes writes per cell type (under
+    min_mapq and filters), printed cell type after cell type (FusionCalling.smk:3-37).  Returns the info dict; raises FastqError for a
+    record that cannot be printed."""
+    from ._lib import FastqInfo
+    lib = load()
+    info = FastqInfo()
+    joined, n_cb, ct, n_ct = None, 0, None, 0
+    if table is not None:
+        joined, n_cb, n_ct = "\n".join(table.barcodes).encode(), len(table.barcodes), len(table.celltype_names)
+        ct = np.ascontiguousarray(table.celltype_of, np.int32)
+    rc = lib.lsio_bam_fastq(os.fsencode(path), os.fsencode(fastq), joined, n_cb, None if ct is None else ct.ctypes.data_as(C.c_void_p), n_ct, int(min_mapq),
+                            *(filters or SplitFilters()).args(), C.byref(info))
+    d = fastq_info_dict(info)
+    if rc != 0:
+        e = FastqError("lsio_bam_fastq: %s" % lib.lsio_last_error().decode("utf-8", "replace"))
+        e.info = d
+        raise e
+    return d
 
 
 def synth_barcodes(model) -> List[str]:
