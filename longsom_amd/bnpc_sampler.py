@@ -1094,6 +1094,8 @@ def run_chains_host(data, seeds, steps, burn_in, FN, FP, pp=(1, 1), dpa=(-1, -1)
 class _HostRun:
     """the chains of run_chains_host under _drive: open(steps), advance(n, keep_from), stats(first), extend(add), results(burn_in)"""
 
+    _PER_STEP = ("ML", "MAP", "DP_alpha", "FN", "FP", "assignments", "_crp", "_beta", "sm_moves")      # a result's records that hold a row per step
+
     def __init__(self, shared, seeds, start, sm_prob, sm_ratios, sm_steps, fixed):
         self.sm, self.fixed, self.done = (sm_prob, sm_ratios, sm_steps), fixed, 0
         self.chains = []
@@ -1108,7 +1110,7 @@ class _HostRun:
     def extend(self, add):
         for ch in self.chains:
             r, more = ch["r"], _empty_result(ch["model"], add - 1, 0)
-            for k in ("ML", "MAP", "DP_alpha", "FN", "FP", "assignments", "_crp", "_beta", "sm_moves"):
+            for k in self._PER_STEP:
                 r[k] = np.concatenate([r[k], more[k]])
 
     def advance(self, n, keep_from):
@@ -1151,7 +1153,7 @@ class _HostRun:
         out = []
         for ch in self.chains:
             r = ch["r"]
-            for k in ("ML", "MAP", "DP_alpha", "FN", "FP", "assignments", "_crp", "_beta", "sm_moves"):
+            for k in self._PER_STEP:
                 r[k] = r[k][:self.done]
             r["burn_in"], r["variate_errors"] = burn_in, ch["errors"]
             out.append(_finish_result(ch["model"], r))

@@ -2,9 +2,8 @@
 // non-conjugate split-merge move, the Escobar-West concentration update, the parameter Metropolis-Hastings and the Metropolis-Hastings
 // updates of the error rates, every chain of a run in every kernel.  A chain has error rates of its own (Rates): with the updates off
 // they are the run's for every chain, with them on they move between steps.  A run with a fixed assignment makes only the parameter move
-// and the error update.  The stream, the
-// variates and the order of a step are defined in longsom_amd/bnpc_sampler.py's docstring; its numpy twin is what these kernels are held
-// to.  See include/longsom_hip.h, lsg_bnpcs_*.  Everything is fp64 except theta.
+// and the error update.  The stream, the variates and the order of a step are defined in longsom_amd/bnpc_sampler.py's docstring; its numpy
+// twin is what these kernels are held to.  See include/longsom_hip.h, lsg_bnpcs_*.  Everything is fp64 except theta.
 #include "lsg_ctx.h"
 #include <algorithm>
 #include <cmath>
@@ -30,8 +29,11 @@ struct Rates {
     double FP, FN, omFP, omFN, new1, new0, sm_anchor[6];
 };
 
+// the four numbers log_terms reads: enough for a likelihood under trial rates (err_ll)
+__host__ __device__ inline void rates_set(Rates& r, double FP, double FN) { r.FP = FP; r.FN = FN; r.omFP = 1 - FP; r.omFN = 1 - FN; }
+
 __host__ __device__ inline void rates_fill(Rates& r, double FP, double FN, double mix0, double mix1) {
-    r.FP = FP; r.FN = FN; r.omFP = 1 - FP; r.omFN = 1 - FN;
+    rates_set(r, FP, FN);
     r.new1 = log(mix1 * (1 - FN) + mix0 * FP); r.new0 = log(mix1 * FN + mix0 * (1 - FP));
     const double v[6] = {1 - FN, FN, FP, 1 - FP, mix0 * (1 - FN) + (1 - mix0) * FP, mix0 * FN + (1 - mix0) * (1 - FP)};
     for (int k = 0; k < 6; ++k) r.sm_anchor[k] = log(v[k]);
@@ -56,7 +58,7 @@ struct SDev {
     uint32_t *n1, *n0;
     uint64_t* keys;
     // the split-merge move: a step takes it with probability sm_prob, a split with sm_edge = r0 / (r0 + r1).  Per chain: sm_i 5 N (the cells of cluster i, of cluster j, S, the
-    // assignment of S, the walk's picks), sm_d 6 N + 6 M + SM_OUT (ll [N][2], u [N], the same in walk order, the rows' L1 / L0, the outcome),
+    // assignment of S, the walk's picks), sm_d sm_d_size(N, M) doubles (ll [N][2], u [N], the same in walk order, the rows' L1 / L0, the outcome),
     // sm_c 6 M (the rows' n1 / n0), sm_t 3 M (the rows), rec_sm steps1 (the codes of sm_moves)
     double sm_prob, sm_edge;
     int32_t sm_scans;
@@ -118,14 +120,9 @@ __device__ inline float truncnorm_variate(double u, float old, double sd) {
     return (float)((double)old + sd * normcdfinv(pa + u * (pb - pa)));
 }
 
-__device__ inline double truncnorm_logpdf(float x, float loc, double sd) {
-    const double pa = normcdf(f32diff((float)S_TMIN, loc) / sd), pb = normcdf(f32diff((float)S_TMAX, loc) / sd);
-    const double z = (double)(x - loc) / sd;
-    return -0.5 * z * z - 0.5 * log(2.0 * M_PI) - log(sd) - log(pb - pa);
-}
-
-// the same density truncated to [lo, hi]: _rg_get_split_prob passes (0 - theta) / sd and (1 - theta) / sd (CRP.py:779-780)
-__device__ inline double truncnorm_logpdf_in(float x, float loc, double sd, float lo, float hi) {
+// the density truncated to [lo, hi]: (float)S_TMIN, (float)S_TMAX as the proposals are, but _rg_get_split_prob passes (0 - theta) / sd and
+// (1 - theta) / sd (CRP.py:779-780).  The differences are formed in float32, as the twin forms them
+__device__ inline double truncnorm_logpdf(float x, float loc, double sd, float lo, float hi) {
     const double pa = normcdf(f32diff(lo, loc) / sd), pb = normcdf(f32diff(hi, loc) / sd);
     const double z = (double)(x - loc) / sd;
     return -0.5 * z * z - 0.5 * log(2.0 * M_PI) - log(sd) - log(pb - pa);
@@ -144,45 +141,83 @@ __device__ inline double beta_logpdf(const SDev& d, float theta) {
 }
 
 // ---- reductions over a workgroup of 256 (four waves): every lane gets the result; sh holds 4 -------------------------------------
-__device__ inline double block_max(double v, double* sh) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+// The order is fixed: the butterfly within a wave, then (wave 0 . wave 1) . (wave 2 . wave 3)
+template <class T, class Op> __device__ inline T block_reduce(T v, T* sh, Op op) {
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
-    v = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+    v = op(op(sh[0], sh[1]), op(sh[2], sh[3]));
     __syncthreads();
     return v;
 }
 
-__device__ inline double block_sum(double v, double* sh) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return v;
+__device__ inline double block_max(double v, double* sh) { return block_reduce(v, sh, [](double a, double b) { return fmax(a, b); }); }
+__device__ inline double block_sum(double v, double* sh) { return block_reduce(v, sh, [](double a, double b) { return a + b; }); }
+__device__ inline int block_min_int(int v, int* sh) { return block_reduce(v, sh, [](int a, int b) { return min(a, b); }); }
+
+// a lane's run of the ids 0 .. n-1 in a workgroup of 256: k0 .. k1-1, the lanes' runs adjacent and ascending.  Every running sum and every
+// compaction here relies on that: going through the lanes in their order goes through the ids in theirs.
+struct Run { int k0, k1; };
+__device__ inline Run lane_run(int n) {
+    const int ch = (n + 255) / 256, k0 = min((int)threadIdx.x * ch, n);
+    return {k0, min(k0 + ch, n)};
 }
 
-__device__ inline int block_min_int(int v, int* sh) {
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = min(min(sh[0], sh[1]), min(sh[2], sh[3]));
-    __syncthreads();
-    return v;
+// the smallest id below `bound` whose cluster is empty (get_empty_cluster), `bound` if there is none; every lane gets it
+__device__ inline int first_free(const int32_t* size, int bound, int* shi) {
+    const auto [k0, k1] = lane_run(bound);
+    int fr = bound;
+    for (int k = k0; k < k1; ++k) if (size[k] == 0) { fr = k; break; }
+    return block_min_int(fr, shi);
+}
+
+// a masked sum over the mutations: a cell against one row of tables (a cluster's own, or a row of the split-merge move)
+__device__ inline double masked_ll(const SDev& d, int cell, const double* l1, const double* l0) {
+    double acc = 0.0;
+    for (int w = 0; w < d.W; ++w) {
+        uint64_t o = d.one[(size_t)cell * d.W + w], z = d.zero[(size_t)cell * d.W + w];
+        while (o) { acc += l1[w * 64 + __ffsll((unsigned long long)o) - 1]; o &= o - 1; }
+        while (z) { acc += l0[w * 64 + __ffsll((unsigned long long)z) - 1]; z &= z - 1; }
+    }
+    return acc;
+}
+
+// a cell's ones and zeros counted into a row of n1 / n0: integer atomics, exact in any order
+__device__ inline void count_cell(const SDev& d, int cell, uint32_t* n1, uint32_t* n0) {
+    for (int w = 0; w < d.W; ++w) {
+        uint64_t o = d.one[(size_t)cell * d.W + w], z = d.zero[(size_t)cell * d.W + w];
+        while (o) { atomicAdd(&n1[w * 64 + __ffsll((unsigned long long)o) - 1], 1u); o &= o - 1; }
+        while (z) { atomicAdd(&n0[w * 64 + __ffsll((unsigned long long)z) - 1], 1u); z &= z - 1; }
+    }
+}
+
+// which of its three sds a proposal takes: word 0 of the block at `attempt`, modulo 3
+__device__ inline uint32_t sd_pick(uint64_t key, uint32_t index, uint32_t step, uint32_t purpose, uint32_t attempt) {
+    uint32_t w[4];
+    philox4x32(key, index, step, purpose, attempt, w);
+    return w[0] % 3u;
+}
+
+__device__ const double PROPOSAL_SD[3] = {0.1, 0.25, 0.5};     // param_proposal_sd (CRP.py:65): the parameter proposals' three, by sd_pick
+
+// _get_log_A (:347-383) of one entry, not clipped; unit: the forward density's bounds are 0 and 1 (_rg_get_split_prob)
+__device__ inline double log_A(const SDev& d, const Rates& er, float nw, float old, double n1, double n0, double sd, bool unit) {
+    double nl1, nl0, ol1, ol0;
+    log_terms(er, nw, nl1, nl0);
+    log_terms(er, old, ol1, ol0);
+    const double new_ll = n1 * nl1 + n0 * nl0, old_ll = n1 * ol1 + n0 * ol0;
+    const double new_prior = d.uniform ? 0.0 : beta_logpdf(d, nw), old_prior = d.uniform ? 0.0 : beta_logpdf(d, old);
+    const float lo = (float)S_TMIN, hi = (float)S_TMAX;
+    const double new_p = unit ? truncnorm_logpdf(nw, old, sd, 0.0f, 1.0f) : truncnorm_logpdf(nw, old, sd, lo, hi), old_p = truncnorm_logpdf(old, nw, sd, lo, hi);
+    return new_ll + new_prior - old_ll - old_prior + old_p - new_p;
 }
 
 // ---- counts: n1 / n0 [chain][cluster][mutation] from the masks and the labels (zeroed before).  A lane per cell. ------------------------
 __global__ __launch_bounds__(256) void k_bnpcs_counts(SDev d) {
     const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= d.N) return;
-    const int32_t l = d.lab[(size_t)c * d.N + i];
-    uint32_t* n1 = d.n1 + ((size_t)c * d.N + l) * d.M;
-    uint32_t* n0 = d.n0 + ((size_t)c * d.N + l) * d.M;
-    for (int w = 0; w < d.W; ++w) {
-        uint64_t o = d.one[(size_t)i * d.W + w], z = d.zero[(size_t)i * d.W + w];
-        while (o) { const int b = __ffsll((unsigned long long)o) - 1; atomicAdd(&n1[w * 64 + b], 1u); o &= o - 1; }
-        while (z) { const int b = __ffsll((unsigned long long)z) - 1; atomicAdd(&n0[w * 64 + b], 1u); z &= z - 1; }
-    }
+    const size_t row = ((size_t)c * d.N + d.lab[(size_t)c * d.N + i]) * d.M;
+    count_cell(d, i, d.n1 + row, d.n0 + row);
 }
 
 // ---- tables: L1 / L0 of every live cluster, and per cluster the likelihood sum_m n1 L1 + n0 L0 and the beta prior's log density of its
@@ -211,7 +246,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_live(SDev d) {
     __shared__ int cnt[256];
     const int c = blockIdx.x, t = threadIdx.x;
     const int32_t* size = d.size + (size_t)c * d.N;
-    const int ch = (d.N + 255) / 256, k0 = min(t * ch, d.N), k1 = min(k0 + ch, d.N);
+    const auto [k0, k1] = lane_run(d.N);
     int n = 0;
     for (int k = k0; k < k1; ++k) n += size[k] > 0;
     cnt[t] = n;
@@ -265,33 +300,25 @@ __global__ __launch_bounds__(256) void k_bnpcs_keys(SDev d, uint32_t step) {
     d.keys[(size_t)c * d.N + i] = ((uint64_t)w[1] << 32) | w[0];
 }
 
+// the rank of keys[i] among keys[0 .. n-1], by counting; every lane of the workgroup calls it (one with i >= n for the others' sake).  tile: 256 words of LDS
+__device__ inline int block_rank(const uint64_t* keys, int n, int i, uint64_t* tile) {
+    const uint64_t mine = i < n ? keys[i] : 0;
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += 256) {
+        __syncthreads();
+        tile[threadIdx.x] = j0 + (int)threadIdx.x < n ? keys[j0 + threadIdx.x] : ~0ull;
+        __syncthreads();
+        const int cnt = min(256, n - j0);
+        for (int j = 0; j < cnt; ++j) rank += (tile[j] < mine) || (tile[j] == mine && j0 + j < i);
+    }
+    return rank;
+}
+
 __global__ __launch_bounds__(256) void k_bnpcs_perm(SDev d) {
     __shared__ uint64_t tile[256];
     const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const uint64_t* keys = d.keys + (size_t)c * d.N;
-    const uint64_t mine = i < d.N ? keys[i] : 0;
-    int rank = 0;
-    for (int j0 = 0; j0 < d.N; j0 += 256) {
-        __syncthreads();
-        tile[threadIdx.x] = j0 + (int)threadIdx.x < d.N ? keys[j0 + threadIdx.x] : ~0ull;
-        __syncthreads();
-        const int n = min(256, d.N - j0);
-        for (int j = 0; j < n; ++j) rank += (tile[j] < mine) || (tile[j] == mine && j0 + j < i);
-    }
+    const int rank = block_rank(d.keys + (size_t)c * d.N, d.N, i, tile);
     if (i < d.N) d.order[(size_t)c * d.N + rank] = i;
-}
-
-// a cell against one cluster from the cluster's own tables: a masked sum over the mutations
-__device__ inline double ll_direct(const SDev& d, int c, int cell, int k) {
-    const double* l1 = d.L1 + ((size_t)c * d.N + k) * d.M;
-    const double* l0 = d.L0 + ((size_t)c * d.N + k) * d.M;
-    double acc = 0.0;
-    for (int w = 0; w < d.W; ++w) {
-        uint64_t o = d.one[(size_t)cell * d.W + w], z = d.zero[(size_t)cell * d.W + w];
-        while (o) { acc += l1[w * 64 + __ffsll((unsigned long long)o) - 1]; o &= o - 1; }
-        while (z) { acc += l0[w * 64 + __ffsll((unsigned long long)z) - 1]; z &= z - 1; }
-    }
-    return acc;
 }
 
 // ---- the concentration update (update_DP_alpha, :386-410) that follows a chain's sweep or its split-merge move: the whole workgroup calls it
@@ -299,9 +326,9 @@ __device__ inline double ll_direct(const SDev& d, int c, int cell, int k) {
 __device__ void alpha_update(const SDev& d, int c, uint32_t step, const int32_t* size, double alpha, double* shd) {
     const int t = threadIdx.x, N = d.N;
     const uint64_t key = d.seeds[c];
-    const int chn = (N + 255) / 256;
+    const auto [k0, k1] = lane_run(N);
     double kk = 0.0;
-    for (int k = min(t * chn, N); k < min(t * chn + chn, N); ++k) kk += size[k] > 0;
+    for (int k = k0; k < k1; ++k) kk += size[k] > 0;
     kk = block_sum(kk, shd);
     if (t == 0) {
         double u0, u1;
@@ -318,7 +345,7 @@ __device__ void alpha_update(const SDev& d, int c, uint32_t step, const int32_t*
 }
 
 // ---- the sweep: one workgroup per chain walks the permuted cells (update_assignments_Gibbs, CRP.py:254-288), then the concentration
-// update (update_DP_alpha, :386-410).  No workgroup waits for another.  A lane owns a run of cluster ids, so the running sum of the
+// update (update_DP_alpha, :386-410).  No workgroup waits for another.  A lane owns a run of cluster ids (lane_run), so the running sum of the
 // probabilities keeps the ids' order.  A cluster alive at the sweep's start reads its column of LL; one born in the sweep, or an id that
 // emptied and was issued again, has colof = -1 and is evaluated from its own tables (the stale-column rule).  With `decide` a chain whose
 // step is a split-merge move (Chain.do_step, MCMC.py:322) leaves here at once: k_bnpcs_sm moves it and makes its concentration update.
@@ -347,7 +374,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step, int d
         if (t == 0) { const int sz = size[old] - 1; size[old] = sz; if (sz == 0) colof[old] = -1; s_pick = hi; }
         __syncthreads();
         // slots 0 .. hi-1 are cluster ids, slot hi is the new cluster
-        const int ch = (hi + 1 + 255) / 256, k0 = min(t * ch, hi + 1), k1 = min(k0 + ch, hi + 1);
+        const auto [k0, k1] = lane_run(hi + 1);
         double mx = -INFINITY;
         for (int k = k0; k < k1; ++k) {
             double lp = -INFINITY;
@@ -356,7 +383,8 @@ __global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step, int d
                 const int sz = size[k];
                 if (sz > 0) {
                     const int col = colof[k];
-                    const double ll = col >= 0 ? d.LL[((size_t)c * N + cell) * d.ll_pitch + col] : ll_direct(d, c, cell, k);
+                    const size_t own = ((size_t)c * N + k) * d.M;
+                    const double ll = col >= 0 ? d.LL[((size_t)c * N + cell) * d.ll_pitch + col] : masked_ll(d, cell, d.L1 + own, d.L0 + own);
                     lp = ll + (log((double)sz) - lden);
                 }
             }
@@ -395,9 +423,7 @@ __global__ __launch_bounds__(256) void k_bnpcs_scan(SDev d, uint32_t step, int d
         const int pick = s_pick;
         if (pick >= hi) {
             // a new cluster: the smallest free id, its parameters drawn from the cell (_init_cl_params_new), its tables made here
-            int fr = hi;
-            for (int k = k0; k < k1 && k < hi; ++k) if (size[k] == 0) { fr = k; break; }
-            const int slot = block_min_int(fr, shi);
+            const int slot = first_free(size, hi, shi);
             const size_t row = (size_t)c * N + slot;
             for (int m = t; m < d.M; m += 256) {
                 const int w = m >> 6, b = m & 63;
@@ -426,22 +452,11 @@ __global__ __launch_bounds__(64) void k_bnpcs_mh(SDev d, uint32_t step) {
     const uint32_t pw = (uint32_t)P_MH | ((uint32_t)k << 8);
     double u, v;
     doubles(key, (uint32_t)m, step, pw, 0, u, v);
-    uint32_t w[4];
-    philox4x32(key, (uint32_t)m, step, pw, 1, w);
-    const uint32_t pick = w[0] % 3u;
-    const double sd = pick == 0 ? 0.1 : pick == 1 ? 0.25 : 0.5;
+    const double sd = PROPOSAL_SD[sd_pick(key, (uint32_t)m, step, pw, 1)];
     const float old = d.theta[at];
     const float nw = truncnorm_variate(u, old, sd);
-    const double n1 = (double)d.n1[at], n0 = (double)d.n0[at];
     const Rates er = d.rates[c];
-    double nl1, nl0, ol1, ol0;
-    log_terms(er, nw, nl1, nl0);
-    log_terms(er, old, ol1, ol0);
-    const double new_ll = n1 * nl1 + n0 * nl0, old_ll = n1 * ol1 + n0 * ol0;
-    const double new_prior = d.uniform ? 0.0 : beta_logpdf(d, nw), old_prior = d.uniform ? 0.0 : beta_logpdf(d, old);
-    const double new_p = truncnorm_logpdf(nw, old, sd), old_p = truncnorm_logpdf(old, nw, sd);
-    const double A = new_ll + new_prior - old_ll - old_prior + old_p - new_p;
-    if (log(v) < A) d.theta[at] = nw;
+    if (log(v) < log_A(d, er, nw, old, (double)d.n1[at], (double)d.n0[at], sd, false)) d.theta[at] = nw;
 }
 
 // ---- the split-merge move (update_assignments_split_merge and what it calls, CRP.py:417-820; the stream and the order of the draws are in
@@ -456,21 +471,50 @@ struct SmBuf {
     float* th;
 };
 
+// a chain's doubles of sm_d, and where the outcome (SmBuf::out) lies among them: behind ll, u, wll, wu (6 N) and the rows' L1, L0 (6 M)
+__host__ __device__ inline size_t sm_d_out(size_t N, size_t M) { return 6 * N + 6 * M; }
+__host__ __device__ inline size_t sm_d_size(size_t N, size_t M) { return sm_d_out(N, M) + SM_OUT; }
+
 __device__ inline SmBuf sm_buf(const SDev& d, int c) {
     const size_t N = d.N, M = d.M;
     SmBuf b;
     int32_t* pi = d.sm_i + (size_t)c * 5 * N;
     b.A = pi; b.B = pi + N; b.S = pi + 2 * N; b.asg = pi + 3 * N; b.pick = pi + 4 * N;
-    double* pd = d.sm_d + (size_t)c * (6 * N + 6 * M + SM_OUT);
-    b.ll = pd; b.u = pd + 2 * N; b.wll = pd + 3 * N; b.wu = pd + 5 * N; b.L1 = pd + 6 * N; b.L0 = b.L1 + 3 * M; b.out = b.L0 + 3 * M;
+    double* pd = d.sm_d + (size_t)c * sm_d_size(N, M);
+    b.ll = pd; b.u = pd + 2 * N; b.wll = pd + 3 * N; b.wu = pd + 5 * N; b.L1 = pd + 6 * N; b.L0 = b.L1 + 3 * M; b.out = pd + sm_d_out(N, M);
     b.n1 = d.sm_c + (size_t)c * 6 * M; b.n0 = b.n1 + 3 * M;
     b.th = d.sm_t + (size_t)c * 3 * M;
     return b;
 }
 
+// a move as its phases see it: the chain, then what sm_choose decides.  Every lane holds the same values
+struct Sm {
+    int c, K;
+    uint32_t step;
+    uint64_t key;
+    double alpha;
+    Rates er;
+    SmBuf b;
+    int32_t *lab, *size;
+    const int32_t* live;
+    bool split;
+    int cli, clj;                                     // the clusters; a split's clj is the smallest free id, which the new cluster takes if the move is accepted
+    int ai, aj, nS;                                   // the anchors; |S|: the clusters' cells without the anchors
+    float *th_i, *th_j;                               // the clusters' parameters in the chain's state
+    double size_data;                                 // ltrans_prob_size (:454-456) of a split, cluster_size_data (:505-507) of a merge
+};
+
+// the kernel's LDS: what the reductions, the compactions and the rank count need, and what lane 0 hands to the others
+struct SmLds {
+    double shd[4], val[2];
+    uint64_t tile[256];
+    int shi[4], cnt[256], pick[5];
+};
+
 // the cells labelled a or b, without the cells xi and xj, in ascending id into out; every lane gets their number.  cnt: 256 ints of LDS
 __device__ int sm_compact(const int32_t* lab, int N, int a, int b, int xi, int xj, int32_t* out, int* cnt) {
-    const int t = threadIdx.x, ch = (N + 255) / 256, k0 = min(t * ch, N), k1 = min(k0 + ch, N);
+    const int t = threadIdx.x;
+    const auto [k0, k1] = lane_run(N);
     int n = 0;
     for (int k = k0; k < k1; ++k) { const int l = lab[k]; n += (l == a || l == b) && k != xi && k != xj; }
     __syncthreads();
@@ -483,201 +527,14 @@ __device__ int sm_compact(const int32_t* lab, int N, int a, int b, int xi, int x
     return total;
 }
 
-// _rg_init_split's likelihood of a cell under an anchor's data as parameters (:557-560): popcounts times the six constants, in their order
-__device__ inline double sm_anchor_ll(const SDev& d, const Rates& er, int cell, int anchor) {
-    int n[6] = {0, 0, 0, 0, 0, 0};
-    for (int w = 0; w < d.W; ++w) {
-        const uint64_t co = d.one[(size_t)cell * d.W + w], cz = d.zero[(size_t)cell * d.W + w];
-        const uint64_t ao = d.one[(size_t)anchor * d.W + w], az = d.zero[(size_t)anchor * d.W + w], am = ~(ao | az);
-        n[0] += __popcll(co & ao); n[1] += __popcll(cz & ao); n[2] += __popcll(co & az); n[3] += __popcll(cz & az); n[4] += __popcll(co & am); n[5] += __popcll(cz & am);
-    }
-    double ll = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) ll = ll + (double)n[k] * er.sm_anchor[k];
-    return ll;
-}
-
-// n1 / n0 of rows 0 and 1 from the assignment of S and the two anchors, and row 2 as their sum
-__device__ void sm_count(const SDev& d, const SmBuf& b, int nS, int ai, int aj) {
-    const int M = d.M;
-    for (int e = threadIdx.x; e < 2 * M; e += 256) { b.n1[e] = 0; b.n0[e] = 0; }
-    __syncthreads();
-    for (int s = threadIdx.x; s < nS + 2; s += 256) {
-        const int cell = s < nS ? b.S[s] : s == nS ? ai : aj, r = s < nS ? b.asg[s] : s - nS;
-        for (int w = 0; w < d.W; ++w) {
-            uint64_t o = d.one[(size_t)cell * d.W + w], z = d.zero[(size_t)cell * d.W + w];
-            while (o) { atomicAdd(&b.n1[r * M + w * 64 + __ffsll((unsigned long long)o) - 1], 1u); o &= o - 1; }
-            while (z) { atomicAdd(&b.n0[r * M + w * 64 + __ffsll((unsigned long long)z) - 1], 1u); z &= z - 1; }
-        }
-    }
-    __syncthreads();
-    for (int m = threadIdx.x; m < M; m += 256) { b.n1[2 * M + m] = b.n1[m] + b.n1[M + m]; b.n0[2 * M + m] = b.n0[m] + b.n0[M + m]; }
-    __syncthreads();
-}
-
-__device__ void sm_tables(const SDev& d, const Rates& er, const SmBuf& b, int r0, int r1) {
-    for (int e = r0 * d.M + threadIdx.x; e < r1 * d.M; e += 256) { double l1, l0; log_terms(er, b.th[e], l1, l0); b.L1[e] = l1; b.L0[e] = l0; }
-    __syncthreads();
-}
-
-__device__ inline double sm_sd(uint64_t key, uint32_t m, uint32_t step, uint32_t purpose, uint32_t attempt) {
-    uint32_t w[4];
-    philox4x32(key, m, step, purpose, attempt, w);
-    const uint32_t pick = w[0] % 3u;
-    return pick == 0 ? 0.1 : pick == 1 ? 0.25 : 0.5;
-}
-
-// _get_log_A with clip (:347-383) of one entry; unit: the forward density's bounds are 0 and 1
-__device__ inline double sm_log_A(const SDev& d, const Rates& er, float nw, float old, double n1, double n0, double sd, bool unit) {
-    double nl1, nl0, ol1, ol0;
-    log_terms(er, nw, nl1, nl0);
-    log_terms(er, old, ol1, ol0);
-    const double new_ll = n1 * nl1 + n0 * nl0, old_ll = n1 * ol1 + n0 * ol0;
-    const double new_prior = d.uniform ? 0.0 : beta_logpdf(d, nw), old_prior = d.uniform ? 0.0 : beta_logpdf(d, old);
-    const double new_p = unit ? truncnorm_logpdf_in(nw, old, sd, 0.0f, 1.0f) : truncnorm_logpdf(nw, old, sd), old_p = truncnorm_logpdf(old, nw, sd);
-    return fmin(new_ll + new_prior - old_ll - old_prior + old_p - new_p, 0.0);
-}
-
-// MH_cluster_params(trans_prob=True) (:314-342) of rows r0 .. r1-1 at scan `scan`, a lane per (row, mutation); sums[r] gets the row's
-// transition probability in every lane, and the moved rows' tables are made again
-__device__ void sm_move_rows(const SDev& d, const Rates& er, const SmBuf& b, uint64_t key, uint32_t step, int scan, int r0, int r1, double* sums, double* shd) {
-    const int M = d.M;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    for (int e = r0 * M + threadIdx.x; e < r1 * M; e += 256) {
-        const int r = e / M, m = e - r * M;
-        const uint32_t pw = (uint32_t)P_SM_MH | ((uint32_t)(4 * scan + r) << 8);
-        double u, v;
-        doubles(key, (uint32_t)m, step, pw, 0, u, v);
-        const double sd = sm_sd(key, (uint32_t)m, step, pw, 1);
-        const float old = b.th[e];
-        const float nw = truncnorm_variate(u, old, sd);
-        const double A = sm_log_A(d, er, nw, old, (double)b.n1[e], (double)b.n0[e], sd, false);
-        double share;
-        if (log(v) < A) { b.th[e] = nw; share = A; }
-        else share = log(-expm1(A));
-        if (r == 0) a0 += share; else if (r == 1) a1 += share; else a2 += share;
-    }
-    sums[0] = block_sum(a0, shd); sums[1] = block_sum(a1, shd); sums[2] = block_sum(a2, shd);
-    sm_tables(d, er, b, r0, r1);
-}
-
-// a masked sum of a cell over one row's tables
-__device__ inline double sm_row_ll(const SDev& d, int cell, const double* l1, const double* l0) {
-    double acc = 0.0;
-    for (int w = 0; w < d.W; ++w) {
-        uint64_t o = d.one[(size_t)cell * d.W + w], z = d.zero[(size_t)cell * d.W + w];
-        while (o) { acc += l1[w * 64 + __ffsll((unsigned long long)o) - 1]; o &= o - 1; }
-        while (z) { acc += l0[w * 64 + __ffsll((unsigned long long)z) - 1]; z &= z - 1; }
-    }
-    return acc;
-}
-
-// _rg_scan_assign (:609-632) with its transition probability; with clj >= 0 the in-order walk of _rg_get_split_prob (:803-818), which
-// assigns the original cluster instead of drawing.  The likelihoods of all cells of S under the two rows (la / lb: their L1, L0) are
-// taken once; the walk's records are laid out in walk order, lane 0 walks them, the lanes scatter its picks.  Every lane gets the sum.
-__device__ double sm_scan(const SDev& d, const SmBuf& b, int c, uint64_t key, uint32_t step, int scan, int nS, double alpha, const double* l1a, const double* l0a,
-                          const double* l1b, const double* l0b, int clj, uint64_t* tile, double* s_out) {
-    const int t = threadIdx.x;
-    uint64_t* keys = d.keys + (size_t)c * d.N;
-    int32_t* pos = d.order + (size_t)c * d.N;
-    const int32_t* lab = d.lab + (size_t)c * d.N;
-    for (int s = t; s < nS; s += 256) {
-        const int cell = b.S[s];
-        b.ll[2 * s] = sm_row_ll(d, cell, l1a, l0a); b.ll[2 * s + 1] = sm_row_ll(d, cell, l1b, l0b);
-        if (clj < 0) {
-            uint32_t w[4];
-            philox4x32(key, (uint32_t)cell, step, (uint32_t)P_SM_PERM | ((uint32_t)scan << 8), 0, w);
-            keys[s] = ((uint64_t)w[1] << 32) | w[0];
-            double u, u_unused;
-            doubles(key, (uint32_t)cell, step, (uint32_t)P_SM_CHOICE | ((uint32_t)scan << 8), 0, u, u_unused);
-            b.u[s] = u;
-        }
-    }
-    __syncthreads();
-    for (int base = 0; base < nS; base += 256) {
-        const int s = base + t;
-        int rank = s;
-        if (clj < 0) {
-            // the rank of the cell's key among the keys of S: ties go by the position in S, which is the order of the ids
-            const uint64_t mine = s < nS ? keys[s] : 0;
-            rank = 0;
-            for (int j0 = 0; j0 < nS; j0 += 256) {
-                __syncthreads();
-                tile[t] = j0 + t < nS ? keys[j0 + t] : ~0ull;
-                __syncthreads();
-                const int n = min(256, nS - j0);
-                for (int j = 0; j < n; ++j) rank += (tile[j] < mine) || (tile[j] == mine && j0 + j < s);
-            }
-        }
-        if (s < nS) {
-            pos[rank] = s;
-            b.wll[2 * rank] = b.ll[2 * s]; b.wll[2 * rank + 1] = b.ll[2 * s + 1];
-            b.wu[rank] = clj < 0 ? b.u[s] : 0.0;
-            b.pick[rank] = clj < 0 ? b.asg[s] : (b.asg[s] | ((lab[b.S[s]] == clj ? 1 : 0) << 1));      // bit 0: where it is, bit 1: where it goes
-        }
-    }
-    __syncthreads();
-    if (t == 0) {
-        const int nn = nS + 2;
-        const double lden = log((double)(nn - 1) + alpha);
-        int on_j = 0;
-        for (int r = 0; r < nS; ++r) on_j += b.pick[r] & 1;
-        double prob = 0.0;
-        for (int r = 0; r < nS; ++r) {
-            const int was = b.pick[r];
-            const int others = on_j - (was & 1), n_j = others + 1, n_i = nn - n_j - 1;
-            const double lp0 = b.wll[2 * r] + (log((double)n_i) - lden), lp1 = b.wll[2 * r + 1] + (log((double)n_j) - lden);
-            // _normalize_log (:104-116): the tables are finite, so its FloatingPointError branch is never met
-            double o0, o1;
-            if (lp0 >= lp1) { const double z = log1p(exp(lp1 - lp0)); o0 = 0.0 - z; o1 = (lp1 - lp0) - z; }
-            else { const double z = log1p(exp(lp0 - lp1)); o0 = (lp0 - lp1) - z; o1 = 0.0 - z; }
-            int nw;
-            if (clj < 0) { const double p0 = exp(o0), p1 = exp(o1); nw = p0 / (p0 + p1) > b.wu[r] ? 0 : 1; }
-            else nw = was >> 1;
-            b.pick[r] = nw;
-            on_j = others + nw;
-            prob += nw ? o1 : o0;
-        }
-        *s_out = prob;
-    }
-    __syncthreads();
-    for (int r = t; r < nS; r += 256) b.asg[pos[r]] = b.pick[r];
-    __syncthreads();
-    return *s_out;
-}
-
-// sum over a row's mutations of n1 L1 + n0 L0: the likelihood of the row's cells under the row
-__device__ double sm_ll_of_row(const SDev& d, const SmBuf& b, int r, double* shd) {
-    double acc = 0.0;
-    for (int m = threadIdx.x; m < d.M; m += 256) { const int e = r * d.M + m; acc += (double)b.n1[e] * b.L1[e] + (double)b.n0[e] * b.L0[e]; }
-    return block_sum(acc, shd);
-}
-
-__global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int force) {
-    __shared__ double shd[4];
-    __shared__ int shi[4];
-    __shared__ int cnt[256];
-    __shared__ uint64_t tile[256];
-    __shared__ int s_int[5];
-    __shared__ double s_dbl[2];
-    const int c = blockIdx.x, t = threadIdx.x, N = d.N, M = d.M;
-    const uint64_t key = d.seeds[c];
-    double u0, u_kind;
-    doubles(key, 0, step, P_SM, 0, u0, u_kind);
-    if (!force && !(u0 < d.sm_prob)) return;                       // this chain's step is a sweep: k_bnpcs_scan has made it
-    int32_t* lab = d.lab + (size_t)c * N; int32_t* size = d.size + (size_t)c * N;
-    const int32_t* live = d.live + (size_t)c * N;
-    const int K = d.nlive[c];
-    const SmBuf b = sm_buf(d, c);
-    const double alpha = d.alpha[c];
-    const Rates er = d.rates[c];
-    // get_empty_cluster: the smallest free id (N if there is none: then every cluster has one cell and the move is a merge)
-    int fr = N;
-    { const int ch = (N + 255) / 256; for (int k = min(t * ch, N); k < min(t * ch + ch, N); ++k) if (size[k] == 0) { fr = k; break; } }
-    const int free_id = block_min_int(fr, shi);
+// do_split_move (:434-462) / do_merge_move (:480-510) up to run_rg_nc: the kind of move, the clusters, the anchors and S
+__device__ inline void sm_choose(const SDev& d, Sm& m, double u_kind, SmLds& L) {
+    const int t = threadIdx.x, N = d.N, K = m.K;
+    const int32_t* size = m.size; const int32_t* live = m.live;
+    const int free_id = first_free(size, N, L.shi);                // N if there is none: then every cluster has one cell and the move is a merge
     if (t == 0) {
         double c0, c1;
-        doubles(key, 0, step, P_SM, 1, c0, c1);
+        doubles(m.key, 0, m.step, P_SM, 1, c0, c1);
         const bool split = K == 1 ? true : K == N ? false : u_kind < d.sm_edge;
         int cli = -1, clj = -1;
         double size_data;
@@ -701,134 +558,292 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
             const double si = (double)size[cli], sj = (double)size[clj];
             size_data = (log(1.0 / si / tot) + log(1.0 / sj / tot)) - (log(si) + log(sj));           // :505-507
         }
-        s_int[0] = split; s_int[1] = cli; s_int[2] = clj; s_dbl[0] = size_data;
+        L.pick[0] = split; L.pick[1] = cli; L.pick[2] = clj; L.val[0] = size_data;
     }
     __syncthreads();
-    const bool split = s_int[0] != 0;
-    const int cli = s_int[1], clj = split ? free_id : s_int[2];
-    const double size_data = s_dbl[0];
-    const int nA = sm_compact(lab, N, cli, cli, -1, -1, b.A, cnt);
-    const int nB = split ? 0 : sm_compact(lab, N, clj, clj, -1, -1, b.B, cnt);
+    m.split = L.pick[0] != 0; m.cli = L.pick[1]; m.clj = m.split ? free_id : L.pick[2]; m.size_data = L.val[0];
+    m.th_i = d.theta + ((size_t)m.c * N + m.cli) * d.M; m.th_j = d.theta + ((size_t)m.c * N + m.clj) * d.M;
+    const int nA = sm_compact(m.lab, N, m.cli, m.cli, -1, -1, m.b.A, L.cnt);
+    const int nB = m.split ? 0 : sm_compact(m.lab, N, m.clj, m.clj, -1, -1, m.b.B, L.cnt);
     if (t == 0) {
         double a0, a1;
-        doubles(key, 0, step, P_SM, 2, a0, a1);
+        doubles(m.key, 0, m.step, P_SM, 2, a0, a1);
         const int ii = min((int)(a0 * (double)nA), nA - 1);
         int aj;
-        if (split) { int jj = min((int)(a1 * (double)(nA - 1)), nA - 2); jj += jj >= ii; aj = b.A[jj]; }
-        else aj = b.B[min((int)(a1 * (double)nB), nB - 1)];
-        s_int[3] = b.A[ii]; s_int[4] = aj;
+        if (m.split) { int jj = min((int)(a1 * (double)(nA - 1)), nA - 2); jj += jj >= ii; aj = m.b.A[jj]; }
+        else aj = m.b.B[min((int)(a1 * (double)nB), nB - 1)];
+        L.pick[3] = m.b.A[ii]; L.pick[4] = aj;
     }
     __syncthreads();
-    const int ai = s_int[3], aj = s_int[4];
-    const int nS = sm_compact(lab, N, cli, split ? cli : clj, ai, aj, b.S, cnt);
-    const int nn = nS + 2, scans = d.sm_scans;
-    // run_rg_nc (:527-544): the launch state
-    for (int s = t; s < nS; s += 256) { const int cell = b.S[s]; b.asg[s] = sm_anchor_ll(d, er, cell, aj) > sm_anchor_ll(d, er, cell, ai) ? 1 : 0; }
+    m.ai = L.pick[3]; m.aj = L.pick[4];
+    m.nS = sm_compact(m.lab, N, m.cli, m.split ? m.cli : m.clj, m.ai, m.aj, m.b.S, L.cnt);
+}
+
+// _rg_init_split's likelihood of a cell under an anchor's data as parameters (:557-560): popcounts times the six constants, in their order
+__device__ inline double sm_anchor_ll(const SDev& d, const Rates& er, int cell, int anchor) {
+    int n[6] = {0, 0, 0, 0, 0, 0};
+    for (int w = 0; w < d.W; ++w) {
+        const uint64_t co = d.one[(size_t)cell * d.W + w], cz = d.zero[(size_t)cell * d.W + w];
+        const uint64_t ao = d.one[(size_t)anchor * d.W + w], az = d.zero[(size_t)anchor * d.W + w], am = ~(ao | az);
+        n[0] += __popcll(co & ao); n[1] += __popcll(cz & ao); n[2] += __popcll(co & az); n[3] += __popcll(cz & az); n[4] += __popcll(co & am); n[5] += __popcll(cz & am);
+    }
+    double ll = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ll = ll + (double)n[k] * er.sm_anchor[k];
+    return ll;
+}
+
+// n1 / n0 of rows 0 and 1 from the assignment of S and the two anchors, and row 2 as their sum
+__device__ void sm_count(const SDev& d, const Sm& m) {
+    const int M = d.M, nS = m.nS, ai = m.ai, aj = m.aj;           // by value: a choice between two members of m is one between their addresses, and keeps m in memory
+    const SmBuf& b = m.b;
+    for (int e = threadIdx.x; e < 2 * M; e += 256) { b.n1[e] = 0; b.n0[e] = 0; }
     __syncthreads();
-    sm_count(d, b, nS, ai, aj);
+    for (int s = threadIdx.x; s < nS + 2; s += 256) {
+        const int cell = s < nS ? b.S[s] : s == nS ? ai : aj, r = s < nS ? b.asg[s] : s - nS;
+        count_cell(d, cell, b.n1 + r * M, b.n0 + r * M);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < M; k += 256) { b.n1[2 * M + k] = b.n1[k] + b.n1[M + k]; b.n0[2 * M + k] = b.n0[k] + b.n0[M + k]; }
+    __syncthreads();
+}
+
+__device__ void sm_tables(const SDev& d, const Sm& m, int r0, int r1) {
+    for (int e = r0 * d.M + threadIdx.x; e < r1 * d.M; e += 256) { double l1, l0; log_terms(m.er, m.b.th[e], l1, l0); m.b.L1[e] = l1; m.b.L0[e] = l0; }
+    __syncthreads();
+}
+
+// _rg_init_split (:547-568), the launch state of run_rg_nc (:527-544): S assigned by the anchors, the rows' counts, Beta draws and tables
+__device__ inline void sm_launch(const SDev& d, const Sm& m) {
+    const int t = threadIdx.x, M = d.M;
+    const SmBuf& b = m.b;
+    for (int s = t; s < m.nS; s += 256) { const int cell = b.S[s]; b.asg[s] = sm_anchor_ll(d, m.er, cell, m.aj) > sm_anchor_ll(d, m.er, cell, m.ai) ? 1 : 0; }
+    __syncthreads();
+    sm_count(d, m);
     for (int e = t; e < 3 * M; e += 256) {
-        const int r = e / M, m = e - r * M;
-        const double x = beta_variate(key, (uint32_t)m, step, (uint32_t)P_SM_BETA | ((uint32_t)r << 8), d.p + (double)b.n1[e], d.q + (double)b.n0[e], d.err + c);
+        const int r = e / M, k = e - r * M;
+        const double x = beta_variate(m.key, (uint32_t)k, m.step, (uint32_t)P_SM_BETA | ((uint32_t)r << 8), d.p + (double)b.n1[e], d.q + (double)b.n0[e], d.err + m.c);
         b.th[e] = (float)fmin(fmax(x, S_TMIN), S_TMAX);
     }
     __syncthreads();
-    sm_tables(d, er, b, 0, 3);
-    double sums[3];
-    for (int sc = 0; sc < scans; ++sc) {
-        if (nS > 0) {
-            sm_scan(d, b, c, key, step, sc, nS, alpha, b.L1, b.L0, b.L1 + M, b.L0 + M, -1, tile, &s_dbl[1]);
-            sm_count(d, b, nS, ai, aj);
-        }
-        sm_move_rows(d, er, b, key, step, sc, 0, 3, sums, shd);
+    sm_tables(d, m, 0, 3);
+}
+
+// MH_cluster_params(trans_prob=True) (:314-342) of rows r0 .. r1-1 at scan `scan`, a lane per (row, mutation); sums[r] gets the row's
+// transition probability in every lane, and the moved rows' tables are made again
+__device__ void sm_move_rows(const SDev& d, const Sm& m, int scan, int r0, int r1, double* sums, double* shd) {
+    const int M = d.M;
+    const SmBuf& b = m.b;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int e = r0 * M + threadIdx.x; e < r1 * M; e += 256) {
+        const int r = e / M, k = e - r * M;
+        const uint32_t pw = (uint32_t)P_SM_MH | ((uint32_t)(4 * scan + r) << 8);
+        double u, v;
+        doubles(m.key, (uint32_t)k, m.step, pw, 0, u, v);
+        const double sd = PROPOSAL_SD[sd_pick(m.key, (uint32_t)k, m.step, pw, 1)];
+        const float old = b.th[e];
+        const float nw = truncnorm_variate(u, old, sd);
+        const double A = fmin(log_A(d, m.er, nw, old, (double)b.n1[e], (double)b.n0[e], sd, false), 0.0);
+        double share;
+        if (log(v) < A) { b.th[e] = nw; share = A; }
+        else share = log(-expm1(A));
+        if (r == 0) a0 += share; else if (r == 1) a1 += share; else a2 += share;
     }
-    const float* th_i = d.theta + ((size_t)c * N + cli) * M;
-    const float* th_j = d.theta + ((size_t)c * N + (split ? cli : clj)) * M;
-    double t1, t2, t3, t4;
-    int on_j;
-    if (split) {
-        // _do_rg_split_MH (:641-653), _get_trans_prob_ratio_split (:668-682)
-        double prob_cl = 0.0;
-        if (nS > 0) {
-            prob_cl = sm_scan(d, b, c, key, step, scans, nS, alpha, b.L1, b.L0, b.L1 + M, b.L0 + M, -1, tile, &s_dbl[1]);
-            sm_count(d, b, nS, ai, aj);
-        }
-        sm_move_rows(d, er, b, key, step, scans, 0, 2, sums, shd);
-        const double gs_split = prob_cl + (sums[0] + sums[1]);
-        double rev = 0.0, pa = 0.0, pb = 0.0, cj = 0.0, inv = 0.0;
-        for (int m = t; m < M; m += 256) {
-            const int e = 2 * M + m;
-            rev += sm_log_A(d, er, th_i[m], b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | (2u << 8), 0), false);
-            if (!d.uniform) { pa += beta_logpdf(d, b.th[m]) + beta_logpdf(d, b.th[M + m]); pb += beta_logpdf(d, th_i[m]); }
-        }
-        for (int s = t; s < nS; s += 256) cj += b.asg[s];
-        for (int j = t; j < K; j += 256) if (live[j] != cli) inv += 1.0 / (double)size[live[j]];
-        rev = block_sum(rev, shd); pa = block_sum(pa, shd); pb = block_sum(pb, shd); cj = block_sum(cj, shd); inv = block_sum(inv, shd);
-        on_j = (int)cj;
-        const double n_j = (double)(on_j + 1), n_i = (double)nn - n_j;
-        t1 = rev - gs_split;
-        t2 = (log(alpha) - lgamma((double)nn)) + lgamma(n_j);        // :702-706
-        t2 += lgamma(n_i);
-        if (!d.uniform) t2 += pa - pb;
-        const double ll0 = sm_ll_of_row(d, b, 0, shd), ll1 = sm_ll_of_row(d, b, 1, shd), ll2 = sm_ll_of_row(d, b, 2, shd);
-        t3 = ll0 + ll1 - ll2;
-        const double norm = inv + 1.0 / n_i + 1.0 / n_j;             // :762-764
-        t4 = log(1.0 / n_i / norm) + log(1.0 / n_j / norm) - size_data;
-    } else {
-        // _do_rg_merge_MH (:656-665), _get_trans_prob_ratio_merge (:685-692), _rg_get_split_prob (:777-820)
-        sm_move_rows(d, er, b, key, step, scans, 2, 3, sums, shd);
-        const double gs_merge = sums[2];
-        double par = 0.0, pa = 0.0, pb = 0.0, cj = 0.0;
-        for (int e = t; e < 2 * M; e += 256) {
-            const int r = e / M, m = e - r * M;
-            const float orig = r == 0 ? th_i[m] : th_j[m];
-            par += sm_log_A(d, er, orig, b.th[e], (double)b.n1[e], (double)b.n0[e], sm_sd(key, (uint32_t)m, step, (uint32_t)P_SM_SD | ((uint32_t)r << 8), 0), true);
-            if (!d.uniform) pb += beta_logpdf(d, orig);
-        }
-        if (!d.uniform) for (int m = t; m < M; m += 256) pa += beta_logpdf(d, b.th[2 * M + m]);
-        par = block_sum(par, shd); pa = block_sum(pa, shd); pb = block_sum(pb, shd);
-        double prob_assign = 0.0;
-        if (nS > 0) {
-            const double* L1 = d.L1 + (size_t)c * N * M; const double* L0 = d.L0 + (size_t)c * N * M;
-            prob_assign = sm_scan(d, b, c, key, step, scans, nS, alpha, L1 + (size_t)cli * M, L0 + (size_t)cli * M, L1 + (size_t)clj * M, L0 + (size_t)clj * M, clj, tile, &s_dbl[1]);
-            sm_count(d, b, nS, ai, aj);                              // the assignment is the original one by now (:817)
-        }
-        for (int s = t; s < nS; s += 256) cj += b.asg[s];
-        cj = block_sum(cj, shd);
-        on_j = (int)cj;
-        const double n_j = (double)(on_j + 1), n_i = (double)nn - n_j;
-        t1 = (par + prob_assign) - gs_merge;
-        t2 = -(log(alpha) - lgamma((double)nn)) - lgamma(n_j);       // :743-747
-        t2 -= lgamma(n_i);
-        if (!d.uniform) t2 += pa - pb;
-        const double ll0 = sm_ll_of_row(d, b, 0, shd), ll1 = sm_ll_of_row(d, b, 1, shd), ll2 = sm_ll_of_row(d, b, 2, shd);
-        t3 = ll2 - ll0 - ll1;
-        // log(|S| - 1) raises for |S| of 0 or 1 under the reference's np.seterr, and the term falls back (:769-773)
-        t4 = (nS > 1 ? -log((double)N) - log((double)(nS - 1)) : -log((double)N)) - size_data;
-    }
-    const double A = ((t1 + t2) + t3) + t4;
-    double v, v_unused;
-    doubles(key, 0, step, P_SM, 3, v, v_unused);
-    const bool refused = split && nS > 0 && (on_j == 0 || on_j == nS);   // np.unique(rg_assignment).size == 1 (:647)
-    const bool accept = !refused && log(v) < A;
-    const int code = split ? (accept ? 2 : 1) : (accept ? 4 : 3);
-    if (accept) {
-        if (split) {
-            for (int m = t; m < M; m += 256) { d.theta[((size_t)c * N + cli) * M + m] = b.th[m]; d.theta[((size_t)c * N + clj) * M + m] = b.th[M + m]; }
-            for (int s = t; s < nS; s += 256) if (b.asg[s]) lab[b.S[s]] = clj;
-            if (t == 0) { lab[aj] = clj; size[clj] = on_j + 1; size[cli] -= on_j + 1; }
-        } else {
-            for (int m = t; m < M; m += 256) d.theta[((size_t)c * N + cli) * M + m] = b.th[2 * M + m];
-            for (int s = t; s < nS; s += 256) if (b.asg[s]) lab[b.S[s]] = cli;
-            if (t == 0) { lab[aj] = cli; size[cli] += size[clj]; size[clj] = 0; }
+    sums[0] = block_sum(a0, shd); sums[1] = block_sum(a1, shd); sums[2] = block_sum(a2, shd);
+    sm_tables(d, m, r0, r1);
+}
+
+// _rg_scan_assign (:609-632) of S over rows 0 and 1 with its transition probability, and the rows' counts under the assignment it leaves;
+// with `back` the in-order walk of _rg_get_split_prob (:803-818) over the two clusters' own tables, which assigns the original cluster
+// instead of drawing.  The likelihoods of all cells of S under the two rows are taken once; the walk's records are laid out in walk order,
+// lane 0 walks them, the lanes scatter its picks.  Every lane gets the sum; 0 without a walk for an empty S (:571-572)
+__device__ double sm_scan(const SDev& d, const Sm& m, int scan, bool back, SmLds& L) {
+    const int t = threadIdx.x, nS = m.nS, clj = back ? m.clj : -1;
+    if (nS == 0) return 0.0;
+    const SmBuf& b = m.b;
+    const size_t M = d.M, own = (size_t)m.c * d.N * M;
+    const double* l1a = back ? d.L1 + own + m.cli * M : b.L1; const double* l0a = back ? d.L0 + own + m.cli * M : b.L0;
+    const double* l1b = back ? d.L1 + own + m.clj * M : b.L1 + M; const double* l0b = back ? d.L0 + own + m.clj * M : b.L0 + M;
+    uint64_t* keys = d.keys + (size_t)m.c * d.N;
+    int32_t* pos = d.order + (size_t)m.c * d.N;
+    for (int s = t; s < nS; s += 256) {
+        const int cell = b.S[s];
+        b.ll[2 * s] = masked_ll(d, cell, l1a, l0a); b.ll[2 * s + 1] = masked_ll(d, cell, l1b, l0b);
+        if (clj < 0) {
+            uint32_t w[4];
+            philox4x32(m.key, (uint32_t)cell, m.step, (uint32_t)P_SM_PERM | ((uint32_t)scan << 8), 0, w);
+            keys[s] = ((uint64_t)w[1] << 32) | w[0];
+            double u, u_unused;
+            doubles(m.key, (uint32_t)cell, m.step, (uint32_t)P_SM_CHOICE | ((uint32_t)scan << 8), 0, u, u_unused);
+            b.u[s] = u;
         }
     }
+    __syncthreads();
+    for (int base = 0; base < nS; base += 256) {
+        const int s = base + t;
+        // the rank of the cell's key among the keys of S: ties go by the position in S, which is the order of the ids
+        const int rank = clj < 0 ? block_rank(keys, nS, s, L.tile) : s;
+        if (s < nS) {
+            pos[rank] = s;
+            b.wll[2 * rank] = b.ll[2 * s]; b.wll[2 * rank + 1] = b.ll[2 * s + 1];
+            b.wu[rank] = clj < 0 ? b.u[s] : 0.0;
+            b.pick[rank] = clj < 0 ? b.asg[s] : (b.asg[s] | ((m.lab[b.S[s]] == clj ? 1 : 0) << 1));      // bit 0: where it is, bit 1: where it goes
+        }
+    }
+    __syncthreads();
     if (t == 0) {
-        b.out[0] = (double)code; b.out[1] = (double)cli; b.out[2] = (double)clj; b.out[3] = (double)ai; b.out[4] = (double)aj; b.out[5] = A;
-        b.out[6] = t1; b.out[7] = t2; b.out[8] = t3; b.out[9] = t4; b.out[10] = log(v); b.out[11] = (double)nS;
+        const int nn = nS + 2;
+        const double lden = log((double)(nn - 1) + m.alpha);
+        int on_j = 0;
+        for (int r = 0; r < nS; ++r) on_j += b.pick[r] & 1;
+        double prob = 0.0;
+        for (int r = 0; r < nS; ++r) {
+            const int was = b.pick[r];
+            const int others = on_j - (was & 1), n_j = others + 1, n_i = nn - n_j - 1;
+            const double lp0 = b.wll[2 * r] + (log((double)n_i) - lden), lp1 = b.wll[2 * r + 1] + (log((double)n_j) - lden);
+            // _normalize_log (:104-116): the tables are finite, so its FloatingPointError branch is never met
+            double o0, o1;
+            if (lp0 >= lp1) { const double z = log1p(exp(lp1 - lp0)); o0 = 0.0 - z; o1 = (lp1 - lp0) - z; }
+            else { const double z = log1p(exp(lp0 - lp1)); o0 = (lp0 - lp1) - z; o1 = 0.0 - z; }
+            int nw;
+            if (clj < 0) { const double p0 = exp(o0), p1 = exp(o1); nw = p0 / (p0 + p1) > b.wu[r] ? 0 : 1; }
+            else nw = was >> 1;
+            b.pick[r] = nw;
+            on_j = others + nw;
+            prob += nw ? o1 : o0;
+        }
+        L.val[1] = prob;
+    }
+    __syncthreads();
+    for (int r = t; r < nS; r += 256) b.asg[pos[r]] = b.pick[r];
+    __syncthreads();
+    sm_count(d, m);
+    return L.val[1];
+}
+
+// the way from rows r0 .. r1-1 back to the clusters' own parameters (row 1: cluster j's) under fresh sds: the sum of their clipped log A
+// (_get_trans_prob_ratio_split, :672-676; _rg_get_split_prob with unit bounds, :783-797)
+__device__ inline double sm_way_back(const SDev& d, const Sm& m, int r0, int r1, bool unit, double* shd) {
+    const int M = d.M;
+    double acc = 0.0;
+    for (int e = r0 * M + threadIdx.x; e < r1 * M; e += 256) {
+        const int r = e / M, k = e - r * M;
+        const double sd = PROPOSAL_SD[sd_pick(m.key, (uint32_t)k, m.step, (uint32_t)P_SM_SD | ((uint32_t)r << 8), 0)];
+        acc += fmin(log_A(d, m.er, r == 1 ? m.th_j[k] : m.th_i[k], m.b.th[e], (double)m.b.n1[e], (double)m.b.n0[e], sd, unit), 0.0);
+    }
+    return block_sum(acc, shd);
+}
+
+// _do_rg_split_MH's proposal (:641-645), one more scan and move of rows 0 and 1, and _get_trans_prob_ratio_split (:668-682) of it
+__device__ inline double sm_split_proposal(const SDev& d, const Sm& m, SmLds& L) {
+    double sums[3];
+    const double prob_cl = sm_scan(d, m, d.sm_scans, false, L);
+    sm_move_rows(d, m, d.sm_scans, 0, 2, sums, L.shd);
+    const double gs_split = prob_cl + (sums[0] + sums[1]);
+    return sm_way_back(d, m, 2, 3, false, L.shd) - gs_split;
+}
+
+// _do_rg_merge_MH's proposal (:656-660), one more move of row 2, and _get_trans_prob_ratio_merge (:685-692) of it: _rg_get_split_prob
+// (:777-820) walks S in order to the two clusters' cells, so the assignment and the rows' counts are the original ones afterwards (:817)
+__device__ inline double sm_merge_proposal(const SDev& d, const Sm& m, SmLds& L) {
+    double sums[3];
+    sm_move_rows(d, m, d.sm_scans, 2, 3, sums, L.shd);
+    const double par = sm_way_back(d, m, 0, 2, true, L.shd);
+    const double prob_assign = sm_scan(d, m, d.sm_scans, true, L);
+    return (par + prob_assign) - sums[2];
+}
+
+// sum over a row's mutations of n1 L1 + n0 L0: the likelihood of the row's cells under the row
+__device__ inline double sm_ll_of_row(const SDev& d, const SmBuf& b, int r, double* shd) {
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < d.M; k += 256) { const int e = r * d.M + k; acc += (double)b.n1[e] * b.L1[e] + (double)b.n0[e] * b.L0[e]; }
+    return block_sum(acc, shd);
+}
+
+// the ratio's terms behind the transition's into t[1 .. 3], from the state the proposal leaves (_do_rg_split_MH :646-653, _do_rg_merge_MH
+// :661-665): _get_lprior_ratio_split / _merge (:695-713, :736-754) of the rows proposed (a split's 0 and 1, a merge's 2) against the clusters'
+// own parameters, _get_ll_ratio (:716-733), _get_ltrans_prob_size_ratio_split / _merge (:757-774).  Returns how many cells of S are on the j side
+__device__ inline int sm_ratio_terms(const SDev& d, const Sm& m, double* shd, double* t) {
+    const int tx = threadIdx.x, M = d.M, nn = m.nS + 2;
+    double cj = 0.0, pa = 0.0, pb = 0.0, inv = 0.0;
+    for (int s = tx; s < m.nS; s += 256) cj += m.b.asg[s];
+    const int on_j = (int)block_sum(cj, shd);
+    const double n_j = (double)(on_j + 1), n_i = (double)nn - n_j;
+    const double ll0 = sm_ll_of_row(d, m.b, 0, shd), ll1 = sm_ll_of_row(d, m.b, 1, shd), ll2 = sm_ll_of_row(d, m.b, 2, shd);
+    if (!d.uniform && m.split) for (int k = tx; k < M; k += 256) { pa += beta_logpdf(d, m.b.th[k]) + beta_logpdf(d, m.b.th[M + k]); pb += beta_logpdf(d, m.th_i[k]); }
+    if (!d.uniform && !m.split) {
+        for (int e = tx; e < 2 * M; e += 256) pb += beta_logpdf(d, e < M ? m.th_i[e] : m.th_j[e - M]);
+        for (int k = tx; k < M; k += 256) pa += beta_logpdf(d, m.b.th[2 * M + k]);
+    }
+    pa = block_sum(pa, shd); pb = block_sum(pb, shd);
+    if (m.split) {
+        for (int j = tx; j < m.K; j += 256) if (m.live[j] != m.cli) inv += 1.0 / (double)m.size[m.live[j]];
+        inv = block_sum(inv, shd);
+        t[1] = (log(m.alpha) - lgamma((double)nn)) + lgamma(n_j);    // :702-706
+        t[1] += lgamma(n_i);
+        t[2] = ll0 + ll1 - ll2;
+        const double norm = inv + 1.0 / n_i + 1.0 / n_j;             // :762-764
+        t[3] = log(1.0 / n_i / norm) + log(1.0 / n_j / norm) - m.size_data;
+    } else {
+        t[1] = -(log(m.alpha) - lgamma((double)nn)) - lgamma(n_j);   // :743-747
+        t[1] -= lgamma(n_i);
+        t[2] = ll2 - ll0 - ll1;
+        // log(|S| - 1) raises for |S| of 0 or 1 under the reference's np.seterr, and the term falls back (:769-773)
+        t[3] = (m.nS > 1 ? -log((double)d.N) - log((double)(m.nS - 1)) : -log((double)d.N)) - m.size_data;
+    }
+    if (!d.uniform) t[1] += pa - pb;
+    return on_j;
+}
+
+// an accepted move on the chain's state (:465-477, :513-520): the rows become the clusters' parameters, the j side's cells change cluster
+__device__ inline void sm_apply(const SDev& d, const Sm& m, int on_j) {
+    const int t = threadIdx.x, M = d.M, to = m.split ? m.clj : m.cli;
+    for (int k = t; k < M; k += 256) {
+        if (m.split) { m.th_i[k] = m.b.th[k]; m.th_j[k] = m.b.th[M + k]; }
+        else m.th_i[k] = m.b.th[2 * M + k];
+    }
+    for (int s = t; s < m.nS; s += 256) if (m.b.asg[s]) m.lab[m.b.S[s]] = to;
+    if (t == 0) {
+        m.lab[m.aj] = to;
+        if (m.split) { m.size[m.clj] = on_j + 1; m.size[m.cli] -= on_j + 1; }
+        else { m.size[m.cli] += m.size[m.clj]; m.size[m.clj] = 0; }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int force) {
+    __shared__ SmLds L;
+    const int c = blockIdx.x, t = threadIdx.x;
+    Sm m;
+    m.c = c; m.step = step; m.key = d.seeds[c];
+    double u0, u_kind;
+    doubles(m.key, 0, step, P_SM, 0, u0, u_kind);
+    if (!force && !(u0 < d.sm_prob)) return;                       // this chain's step is a sweep: k_bnpcs_scan has made it
+    m.K = d.nlive[c]; m.alpha = d.alpha[c]; m.er = d.rates[c]; m.b = sm_buf(d, c);
+    m.lab = d.lab + (size_t)c * d.N; m.size = d.size + (size_t)c * d.N; m.live = d.live + (size_t)c * d.N;
+    sm_choose(d, m, u_kind, L);
+    sm_launch(d, m);
+    double sums[3], term[4];
+    for (int sc = 0; sc < d.sm_scans; ++sc) {                      // run_rg_nc's restricted scans (:537-542)
+        sm_scan(d, m, sc, false, L);
+        sm_move_rows(d, m, sc, 0, 3, sums, L.shd);
+    }
+    term[0] = m.split ? sm_split_proposal(d, m, L) : sm_merge_proposal(d, m, L);
+    const int on_j = sm_ratio_terms(d, m, L.shd, term);
+    const double A = ((term[0] + term[1]) + term[2]) + term[3];
+    double v, v_unused;
+    doubles(m.key, 0, step, P_SM, 3, v, v_unused);
+    const bool refused = m.split && m.nS > 0 && (on_j == 0 || on_j == m.nS);   // np.unique(rg_assignment).size == 1 (:647)
+    const bool accept = !refused && log(v) < A;
+    const int code = m.split ? (accept ? 2 : 1) : (accept ? 4 : 3);
+    if (accept) sm_apply(d, m, on_j);
+    if (t == 0) {
+        double* o = m.b.out;
+        o[0] = (double)code; o[1] = (double)m.cli; o[2] = (double)m.clj; o[3] = (double)m.ai; o[4] = (double)m.aj; o[5] = A;
+        o[6] = term[0]; o[7] = term[1]; o[8] = term[2]; o[9] = term[3]; o[10] = log(v); o[11] = (double)m.nS;
         if ((int)step < d.steps1) d.rec_sm[(size_t)c * d.steps1 + step] = code;
     }
     __syncthreads();
-    alpha_update(d, c, step, size, alpha, shd);
+    alpha_update(d, c, step, m.size, m.alpha, L.shd);
 }
 
 // ---- the error-rate update (update_error_rates / MH_error_rates, CRP_learning_errors.py:52-111; Chain.do_step, MCMC.py:339-342; the draws
@@ -836,6 +851,8 @@ __global__ __launch_bounds__(256) void k_bnpcs_sm(SDev d, uint32_t step, int for
 // the FN move, which sees the FP move's result.  get_ll_full_error (:58-63) under the trial rates is sum_k sum_m n1 L1' + n0 L0' over the live
 // clusters: the lanes stride over clusters x mutations, block_sum adds in a fixed order.  The scalar terms are the same in every lane.
 // An accepted move rewrites the chain's Rates; the host makes the tables again behind this kernel.
+// The rates' own density, apart from truncnorm_logpdf: a rate and its bounds 0 and 1 are doubles and the differences are formed in double,
+// where a parameter's are formed in float32
 __device__ inline double unit_truncnorm_logpdf(double x, double loc, double sd) {
     const double pa = normcdf((0.0 - loc) / sd), pb = normcdf((1.0 - loc) / sd);
     const double z = (x - loc) / sd;
@@ -844,14 +861,15 @@ __device__ inline double unit_truncnorm_logpdf(double x, double loc, double sd) 
 
 __device__ double err_ll(const SDev& d, int c, int K, double FP, double FN, double* shd) {
     const int32_t* live = d.live + (size_t)c * d.N;
-    const double omFP = 1 - FP, omFN = 1 - FN;
+    Rates trial;
+    rates_set(trial, FP, FN);
     double acc = 0.0;
     for (int64_t e = threadIdx.x; e < (int64_t)K * d.M; e += 256) {
         const int j = (int)(e / d.M), m = (int)(e - (int64_t)j * d.M);
         const size_t at = ((size_t)c * d.N + live[j]) * d.M + m;
-        const float theta = d.theta[at];
-        const double th = (double)theta, om = (double)(1.0f - theta);
-        acc += (double)d.n1[at] * log(th * omFN + om * FP) + (double)d.n0[at] * log(th * FN + om * omFP);
+        double l1, l0;
+        log_terms(trial, d.theta[at], l1, l0);
+        acc += (double)d.n1[at] * l1 + (double)d.n0[at] * l0;
     }
     return block_sum(acc, shd);
 }
@@ -867,18 +885,18 @@ __global__ __launch_bounds__(256) void k_bnpcs_err(SDev d, uint32_t step) {
     const int32_t* live = d.live + (size_t)c * N;
     double rate[2] = {d.rates[c].FP, d.rates[c].FN};
     // the likelihood under the current rates: the sum of the tables' rows, as the record takes it
+    const auto [j0, j1] = lane_run(K);
     double old_ll = 0.0;
-    { const int ch = (K + 255) / 256; for (int j = min(t * ch, K); j < min(t * ch + ch, K); ++j) old_ll += d.rowml[(size_t)c * N + live[j]]; }
+    for (int j = j0; j < j1; ++j) old_ll += d.rowml[(size_t)c * N + live[j]];
     old_ll = block_sum(old_ll, shd);
     bool moved = false;
     for (int e = 0; e < 2; ++e) {
         const uint32_t purpose = e == 0 ? P_ERR_FP : P_ERR_FN;
         double u, v;
         doubles(key, 0, step, purpose, 0, u, v);
-        uint32_t w[4];
-        philox4x32(key, 0, step, purpose, 1, w);
-        const uint32_t pick = w[0] % 3u;
-        const double psd = d.err_sd[e], sd = pick == 0 ? psd * 0.5 : pick == 1 ? psd : psd * 1.5;
+        constexpr double of_prior[3] = {0.5, 1.0, 1.5};                // FP_sd, FN_sd (CRP_learning_errors.py:26, 32): three, times the prior's sd
+        const uint32_t pick = sd_pick(key, 0, step, purpose, 1);
+        const double psd = d.err_sd[e], sd = psd * of_prior[pick];
         const double old = rate[e];
         const double pa = normcdf((0.0 - old) / sd), pb = normcdf((1.0 - old) / sd);
         const double nw = old + sd * normcdfinv(pa + u * (pb - pa));
@@ -912,9 +930,9 @@ __global__ __launch_bounds__(256) void k_bnpcs_record(SDev d, int32_t step, int3
     const int c = blockIdx.x, t = threadIdx.x, N = d.N, K = d.nlive[c];
     const int32_t* live = d.live + (size_t)c * N;
     const double alpha = d.alpha[c], lden = log((double)(N - 1) + alpha);
-    const int ch = (K + 255) / 256;
+    const auto [j0, j1] = lane_run(K);
     double ml = 0.0, crp = 0.0, bp = 0.0;
-    for (int j = min(t * ch, K); j < min(t * ch + ch, K); ++j) {
+    for (int j = j0; j < j1; ++j) {
         const size_t row = (size_t)c * N + live[j];
         ml += d.rowml[row]; bp += d.rowb[row];
         crp += log((double)d.size[row]) - lden;
@@ -1017,9 +1035,9 @@ static int sync_check(lsg_ctx* c, const char* who) {
 static SDev dev_of(const Bnpcs& b) {
     SDev d{};
     d.N = b.n_cells; d.M = b.n_muts; d.W = b.n_words; d.C = b.n_chains; d.steps1 = b.steps1; d.ll_pitch = b.ll_pitch; d.arena_rows = b.arena_rows;
-    d.p = b.cfg[2]; d.q = b.cfg[3]; d.g0 = b.cfg[4]; d.g1 = b.cfg[5]; d.dpa_prob = b.cfg[6];
+    d.p = b.p; d.q = b.q; d.g0 = b.g0; d.g1 = b.g1; d.dpa_prob = b.dpa_prob;
     d.uniform = d.p == 1.0 && d.q == 1.0;
-    d.betaln = b.cfg[9]; d.mix0 = b.mix[0]; d.mix1 = b.mix[1];
+    d.betaln = b.betaln; d.mix0 = b.mix[0]; d.mix1 = b.mix[1];
     d.err_prob = b.err_prob; d.err_mean[0] = b.err_prior[0]; d.err_sd[0] = b.err_prior[1]; d.err_mean[1] = b.err_prior[2]; d.err_sd[1] = b.err_prior[3];
     d.rates = b.rates.as<Rates>(); d.rec_err = b.rec_err.as<double>(); d.err_out = b.err_out.as<double>(); d.err_cnt = b.err_cnt.as<int32_t>();
     d.one = b.one.as<uint64_t>(); d.zero = b.zero.as<uint64_t>(); d.seeds = b.seeds.as<uint64_t>(); d.pop = b.pop.as<int32_t>();
@@ -1041,24 +1059,24 @@ static int need(lsg_ctx* c, const char* who) {
     return 0;
 }
 
-// the live list and its count on the host
-static int fetch_live(lsg_ctx* c, const char* who) {
+// the tables under the chains' parameters and rates as they are now
+static void launch_tables(lsg_ctx* c) {
+    Bnpcs& b = c->bnpcs;
+    hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, dev_of(b));
+}
+
+// what follows a change of the assignment: the live list and its count on the host, then the clusters' counts and tables
+static int refresh_clusters(lsg_ctx* c, const char* who) {
     Bnpcs& b = c->bnpcs;
     hipLaunchKernelGGL(k_bnpcs_live, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b));
     LSG_HIP(hipMemcpyAsync(b.h_k.data(), b.nlive.p, (size_t)b.n_chains * 4, hipMemcpyDeviceToHost, c->stream));
     if (sync_check(c, who)) return -1;
     b.k_max = *std::max_element(b.h_k.begin(), b.h_k.end());
-    return 0;
-}
-
-static int launch_counts_tables(lsg_ctx* c) {
-    Bnpcs& b = c->bnpcs;
     const size_t cells = (size_t)b.n_chains * b.n_cells * b.n_muts;
     LSG_HIP(hipMemsetAsync(b.n1.p, 0, cells * 4, c->stream));
     LSG_HIP(hipMemsetAsync(b.n0.p, 0, cells * 4, c->stream));
-    const SDev d = dev_of(b);
-    hipLaunchKernelGGL(k_bnpcs_counts, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, d);
-    hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, d);
+    hipLaunchKernelGGL(k_bnpcs_counts, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, dev_of(b));
+    launch_tables(c);
     return 0;
 }
 
@@ -1066,44 +1084,64 @@ static int launch_counts_tables(lsg_ctx* c) {
 static int prepare(lsg_ctx* c, const char* who) {
     Bnpcs& b = c->bnpcs;
     if (b.prepared) return 0;
-    if (fetch_live(c, who)) return -1;
-    if (int rc = launch_counts_tables(c)) return rc;
+    if (int rc = refresh_clusters(c, who)) return rc;
     b.prepared = true;
     return 0;
 }
 
-// decide: each chain draws whether this step is a sweep or a split-merge move; else every chain sweeps
-static int launch_sweep(lsg_ctx* c, uint32_t step, int decide) {
+// the likelihood matrix against the clusters alive now, a column each
+static int launch_ll(lsg_ctx* c) {
     Bnpcs& b = c->bnpcs;
     b.ll_pitch = std::max(b.k_max, 1);
     if (b.LL.reserve((size_t)b.n_chains * b.n_cells * b.ll_pitch * 8)) return -1;
-    const SDev d = dev_of(b);
-    hipLaunchKernelGGL(k_bnpcs_ll, dim3((b.ll_pitch + LT - 1) / LT, (b.n_cells + LT - 1) / LT, b.n_chains), dim3(256), 0, c->stream, d);
-    hipLaunchKernelGGL(k_bnpcs_keys, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, d, step);
-    hipLaunchKernelGGL(k_bnpcs_perm, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, d);
-    hipLaunchKernelGGL(k_bnpcs_scan, dim3(b.n_chains), dim3(256), 0, c->stream, d, step, decide);
+    hipLaunchKernelGGL(k_bnpcs_ll, dim3((b.ll_pitch + LT - 1) / LT, (b.n_cells + LT - 1) / LT, b.n_chains), dim3(256), 0, c->stream, dev_of(b));
     return 0;
 }
 
-// the split-merge move of the chains whose step is one (force: of every chain)
-static int launch_sm(lsg_ctx* c, uint32_t step, int force) {
+// ---- the three phases of a step (Chain.do_step, MCMC.py:316-342), in its order.  Each leaves the tables right for the next. -------------
+// The assignment: with `sweep` and `move` each chain draws which of the two its step is, as a run has it; with one of them every chain
+// makes that one; with neither (a fixed assignment) none.  Then what follows a change of the assignment
+static int step_assign(lsg_ctx* c, const char* who, uint32_t step, bool sweep, bool move) {
     Bnpcs& b = c->bnpcs;
-    hipLaunchKernelGGL(k_bnpcs_sm, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), step, force);
-    return 0;
+    if (sweep) {
+        if (int rc = launch_ll(c)) return rc;
+        const SDev d = dev_of(b);
+        hipLaunchKernelGGL(k_bnpcs_keys, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, d, step);
+        hipLaunchKernelGGL(k_bnpcs_perm, dim3((b.n_cells + 255) / 256, b.n_chains), dim3(256), 0, c->stream, d);
+        hipLaunchKernelGGL(k_bnpcs_scan, dim3(b.n_chains), dim3(256), 0, c->stream, d, step, move ? 1 : 0);
+    }
+    if (move) hipLaunchKernelGGL(k_bnpcs_sm, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), step, sweep ? 0 : 1);
+    return refresh_clusters(c, who);
 }
 
-static int launch_mh(lsg_ctx* c, uint32_t step) {
+// the parameter move
+static void step_params(lsg_ctx* c, uint32_t step) {
     Bnpcs& b = c->bnpcs;
     hipLaunchKernelGGL(k_bnpcs_mh, dim3((b.n_muts + 63) / 64, std::max(b.k_max, 1), b.n_chains), dim3(64), 0, c->stream, dev_of(b), step);
-    return 0;
+    launch_tables(c);
 }
 
-// the error-rate update of the chains whose draw says so, behind the parameter move's tables; then the tables under the rates it left
-static int launch_err(lsg_ctx* c, uint32_t step) {
+// the error-rate update of the chains whose draw says so
+static void step_errors(lsg_ctx* c, uint32_t step) {
     Bnpcs& b = c->bnpcs;
-    const SDev d = dev_of(b);
-    hipLaunchKernelGGL(k_bnpcs_err, dim3(b.n_chains), dim3(256), 0, c->stream, d, step);
-    hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, d);
+    hipLaunchKernelGGL(k_bnpcs_err, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), step);
+    launch_tables(c);
+}
+
+// the state's size, which the chains' parameters, tables and counts, the label records and the arena make up; refused past 64 GB
+static int check_state_size(const char* who, const char* verb, size_t C, size_t N, size_t M, size_t S1, int64_t arena_rows) {
+    const double bytes = (double)C * N * M * (4 + 8 + 8 + 4 + 4) + (double)C * S1 * N * 4 + (double)C * arena_rows * M * 4;
+    if (bytes <= 64e9) return 0;
+    set_error("%s: %zu chains x %zu cells x %zu mutations x %zu steps %s %.0f GB of state", who, C, N, M, S1 - 1, verb, bytes / 1e9);
+    return -2;
+}
+
+// every chain's rates become r
+static int upload_rates(lsg_ctx* c, const Rates& r) {
+    Bnpcs& b = c->bnpcs;
+    const std::vector<Rates> all((size_t)b.n_chains, r);
+    LSG_HIP(hipMemcpyAsync(b.rates.p, all.data(), all.size() * sizeof(Rates), hipMemcpyHostToDevice, c->stream));
+    LSG_HIP(hipStreamSynchronize(c->stream));                      // (`all` is read by the copy until here)
     return 0;
 }
 
@@ -1122,16 +1160,18 @@ int lsg_bnpcs_create(lsg_ctx* c, int32_t n_cells, int32_t n_muts, int32_t n_chai
     if (n_muts < 1 || n_chains < 1 || n_steps < 1 || arena_rows < 1 || !one || !zero || !cfg || !seeds) { set_error("%s: bad arguments", who); return -2; }
     if (!(cfg[0] > 0 && cfg[0] < 1 && cfg[1] > 0 && cfg[1] < 1 && cfg[2] > 0 && cfg[3] > 0 && cfg[4] > 0)) { set_error("%s: error rates in (0, 1) and positive prior parameters are needed", who); return -2; }
     const size_t N = n_cells, M = n_muts, C = n_chains, W = (M + 63) / 64, S1 = (size_t)n_steps + 1;
-    const double bytes = (double)C * N * M * (4 + 8 + 8 + 4 + 4) + (double)C * S1 * N * 4 + (double)C * arena_rows * M * 4;
-    if (bytes > 64e9) { set_error("%s: %d chains x %d cells x %d mutations x %d steps need %.0f GB of state", who, n_chains, n_cells, n_muts, n_steps, bytes / 1e9); return -2; }
-    if (b.one.reserve(N * W * 8) || b.zero.reserve(N * W * 8) || b.pop.reserve(N * 8) || b.seeds.reserve(C * 8) || b.lab.reserve(C * N * 4) || b.size.reserve(C * N * 4) ||
-        b.colof.reserve(C * N * 4) || b.live.reserve(C * N * 4) || b.nlive.reserve(C * 4) || b.hi.reserve(C * 4) || b.theta.reserve(C * N * M * 4) || b.L1.reserve(C * N * M * 8) ||
-        b.L0.reserve(C * N * M * 8) || b.alpha.reserve(C * 8) || b.prow.reserve(C * (N + 1) * 8) || b.n1.reserve(C * N * M * 4) || b.n0.reserve(C * N * M * 4) ||
-        b.rowml.reserve(C * N * 8) || b.rowb.reserve(C * N * 8) || b.order.reserve(C * N * 4) || b.keys.reserve(C * N * 8) || b.rec_lab.reserve(C * S1 * N * 4) ||
-        b.rec_sc.reserve(C * S1 * REC * 8) || b.arena.reserve(C * (size_t)arena_rows * M * 4) || b.err.reserve(C * 4 + 8 * C + 8) ||
-        b.sm_i.reserve(C * 5 * N * 4) || b.sm_d.reserve(C * (6 * N + 6 * M + SM_OUT) * 8) || b.sm_c.reserve(C * 6 * M * 4) || b.sm_t.reserve(C * 3 * M * 4) ||
-        b.rec_sm.reserve(C * S1 * 4) || b.rates.reserve(C * sizeof(Rates)) || b.rec_err.reserve(C * S1 * 2 * 8) || b.err_cnt.reserve(C * 4 * 4) ||
-        b.err_out.reserve(C * ERR_OUT * 8)) return -1;
+    if (int rc = check_state_size(who, "need", C, N, M, S1, arena_rows)) return rc;
+    // the state's buffers and their bytes; the second list is of those that start as zeros
+    const struct { DevBuf* buf; size_t bytes; } plain[] = {
+        {&b.one, N * W * 8}, {&b.zero, N * W * 8}, {&b.pop, N * 8}, {&b.seeds, C * 8}, {&b.colof, C * N * 4}, {&b.live, C * N * 4}, {&b.nlive, C * 4}, {&b.hi, C * 4},
+        {&b.L1, C * N * M * 8}, {&b.L0, C * N * M * 8}, {&b.prow, C * (N + 1) * 8}, {&b.n1, C * N * M * 4}, {&b.n0, C * N * M * 4}, {&b.rowml, C * N * 8}, {&b.rowb, C * N * 8},
+        {&b.order, C * N * 4}, {&b.keys, C * N * 8}, {&b.arena, C * (size_t)arena_rows * M * 4}, {&b.used, C * 8}, {&b.sm_i, C * 5 * N * 4}, {&b.sm_c, C * 6 * M * 4},
+        {&b.sm_t, C * 3 * M * 4}, {&b.rates, C * sizeof(Rates)}},
+      zeroed[] = {
+        {&b.lab, C * N * 4}, {&b.size, C * N * 4}, {&b.theta, C * N * M * 4}, {&b.alpha, C * 8}, {&b.err, C * 4}, {&b.rec_lab, C * S1 * N * 4}, {&b.rec_sc, C * S1 * REC * 8},
+        {&b.rec_sm, C * S1 * 4}, {&b.sm_d, C * sm_d_size(N, M) * 8}, {&b.rec_err, C * S1 * 2 * 8}, {&b.err_cnt, C * 4 * 4}, {&b.err_out, C * ERR_OUT * 8}};
+    for (const auto& x : plain) if (x.buf->reserve(x.bytes)) return -1;
+    for (const auto& x : zeroed) if (x.buf->reserve(x.bytes)) return -1;
     std::vector<int32_t> pop(2 * N);
     const uint64_t tail = M % 64 ? ((1ull << (M % 64)) - 1) : ~0ull;
     for (size_t i = 0; i < N; ++i) {
@@ -1148,34 +1188,20 @@ int lsg_bnpcs_create(lsg_ctx* c, int32_t n_cells, int32_t n_muts, int32_t n_chai
     LSG_HIP(hipMemcpyAsync(b.zero.p, zero, N * W * 8, hipMemcpyHostToDevice, st));
     LSG_HIP(hipMemcpyAsync(b.pop.p, pop.data(), N * 8, hipMemcpyHostToDevice, st));
     LSG_HIP(hipMemcpyAsync(b.seeds.p, seeds, C * 8, hipMemcpyHostToDevice, st));
-    LSG_HIP(hipMemsetAsync(b.lab.p, 0, C * N * 4, st));
-    LSG_HIP(hipMemsetAsync(b.size.p, 0, C * N * 4, st));
-    LSG_HIP(hipMemsetAsync(b.theta.p, 0, C * N * M * 4, st));
-    LSG_HIP(hipMemsetAsync(b.alpha.p, 0, C * 8, st));
-    LSG_HIP(hipMemsetAsync(b.err.p, 0, C * 4 + 8 * C, st));
-    LSG_HIP(hipMemsetAsync(b.rec_lab.p, 0, C * S1 * N * 4, st));
-    LSG_HIP(hipMemsetAsync(b.rec_sc.p, 0, C * S1 * REC * 8, st));
-    LSG_HIP(hipMemsetAsync(b.rec_sm.p, 0, C * S1 * 4, st));
-    LSG_HIP(hipMemsetAsync(b.sm_d.p, 0, C * (6 * N + 6 * M + SM_OUT) * 8, st));
-    LSG_HIP(hipMemsetAsync(b.rec_err.p, 0, C * S1 * 2 * 8, st));
-    LSG_HIP(hipMemsetAsync(b.err_cnt.p, 0, C * 4 * 4, st));
-    LSG_HIP(hipMemsetAsync(b.err_out.p, 0, C * ERR_OUT * 8, st));
-    {
-        // every chain starts with cfg's rates: the new cluster's log terms as cfg gives them, _beta_mix_const (CRP.py:42-44) and the six
-        // values a likelihood term takes under an anchor's data as parameters (:557-560)
-        const double p = cfg[2], q = cfg[3];
-        const double m0 = std::tgamma(p) * std::tgamma(q + 1) / std::tgamma(p + q + 1), m1 = std::tgamma(p + 1) * std::tgamma(q) / std::tgamma(p + q + 1);
-        b.mix[0] = m0 / (m0 + m1); b.mix[1] = m1 / (m0 + m1);
-        Rates r;
-        rates_fill(r, cfg[1], cfg[0], b.mix[0], b.mix[1]);
-        r.new1 = cfg[7]; r.new0 = cfg[8];
-        const std::vector<Rates> all(C, r);
-        LSG_HIP(hipMemcpyAsync(b.rates.p, all.data(), C * sizeof(Rates), hipMemcpyHostToDevice, st));
-        LSG_HIP(hipStreamSynchronize(st));                         // (`all` is read by the copy until here)
-    }
+    for (const auto& x : zeroed) LSG_HIP(hipMemsetAsync(x.buf->p, 0, x.bytes, st));
     b.n_cells = n_cells; b.n_muts = n_muts; b.n_words = (int32_t)W; b.n_chains = n_chains; b.steps1 = (int32_t)S1; b.arena_rows = arena_rows;
     b.k_max = 0; b.ll_pitch = 1; b.pending = -1; b.next_step = 0; b.test_ml_end = 0;
-    std::copy(cfg, cfg + 10, b.cfg);
+    // cfg by name: FN, FP, p, q, DP_a_gamma, the concentration update's probability, the new cluster's two log terms, betaln(p, q)
+    const double FN = cfg[0], FP = cfg[1], p = cfg[2], q = cfg[3];
+    b.p = p; b.q = q; b.g0 = cfg[4]; b.g1 = cfg[5]; b.dpa_prob = cfg[6]; b.betaln = cfg[9];
+    // every chain starts with cfg's rates: the new cluster's log terms as cfg gives them, _beta_mix_const (CRP.py:42-44) and the six
+    // values a likelihood term takes under an anchor's data as parameters (:557-560)
+    const double m0 = std::tgamma(p) * std::tgamma(q + 1) / std::tgamma(p + q + 1), m1 = std::tgamma(p + 1) * std::tgamma(q) / std::tgamma(p + q + 1);
+    b.mix[0] = m0 / (m0 + m1); b.mix[1] = m1 / (m0 + m1);
+    Rates r;
+    rates_fill(r, FP, FN, b.mix[0], b.mix[1]);
+    r.new1 = cfg[7]; r.new0 = cfg[8];
+    if (int rc = upload_rates(c, r)) return rc;
     b.sm_prob = 0.0; b.sm_ratio[0] = 0.75; b.sm_ratio[1] = 0.25; b.sm_scans = 3;
     b.err_prob = 0.0; b.learn = b.fixed_assign = false; std::fill(b.err_prior, b.err_prior + 4, 0.0);
     b.h_k.assign(C, 0); b.h_used.assign(C, 0);
@@ -1234,18 +1260,11 @@ int lsg_bnpcs_run(lsg_ctx* c, int32_t first_step, int32_t n_steps, int32_t burn_
         return -2;
     }
     if (int rc = prepare(c, who)) return rc;
-    int64_t* d_used = reinterpret_cast<int64_t*>(b.err.as<int32_t>() + b.n_chains + (b.n_chains & 1));
     for (int32_t s = first_step; s < first_step + n_steps; ++s) {
         if (s > 0 && b.pending != s) {
-            if (!b.fixed_assign) {
-                if (int rc = launch_sweep(c, (uint32_t)s, b.sm_prob > 0)) return rc;
-                if (b.sm_prob > 0) if (int rc = launch_sm(c, (uint32_t)s, 0)) return rc;
-            }
-            if (fetch_live(c, who)) return -1;
-            if (int rc = launch_counts_tables(c)) return rc;
-            if (int rc = launch_mh(c, (uint32_t)s)) return rc;
-            hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, dev_of(b));
-            if (b.learn) if (int rc = launch_err(c, (uint32_t)s)) return rc;
+            if (int rc = step_assign(c, who, (uint32_t)s, !b.fixed_assign, !b.fixed_assign && b.sm_prob > 0)) return rc;
+            step_params(c, (uint32_t)s);
+            if (b.learn) step_errors(c, (uint32_t)s);
         }
         b.pending = s;
         const bool keep = s >= burn_in;
@@ -1255,8 +1274,8 @@ int lsg_bnpcs_run(lsg_ctx* c, int32_t first_step, int32_t n_steps, int32_t burn_
                     if (b.h_used[k] == 0) { set_error("%s: step %d has %d clusters, the arena holds %lld rows", who, s, b.h_k[k], (long long)b.arena_rows); return -2; }
                     return sync_check(c, who);                    // full: the caller fetches and goes on at this step
                 }
-        LSG_HIP(hipMemcpyAsync(d_used, b.h_used.data(), (size_t)b.n_chains * 8, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_bnpcs_record, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), s, keep ? 1 : 0, d_used);
+        LSG_HIP(hipMemcpyAsync(b.used.p, b.h_used.data(), (size_t)b.n_chains * 8, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_bnpcs_record, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), s, keep ? 1 : 0, b.used.as<int64_t>());
         if (sync_check(c, who)) return -1;                        // (h_used is read by the copy until here)
         if (keep) for (int32_t k = 0; k < b.n_chains; ++k) b.h_used[k] += b.h_k[k];
         b.pending = -1; b.next_step = s + 1; ++*done;
@@ -1320,9 +1339,7 @@ int lsg_bnpcs_set_error_learning(lsg_ctx* c, double prob, double fp_mean, double
     Bnpcs& b = c->bnpcs;
     Rates r;
     rates_fill(r, fp_mean, fn_mean, b.mix[0], b.mix[1]);
-    const std::vector<Rates> all((size_t)b.n_chains, r);
-    LSG_HIP(hipMemcpyAsync(b.rates.p, all.data(), all.size() * sizeof(Rates), hipMemcpyHostToDevice, c->stream));
-    LSG_HIP(hipStreamSynchronize(c->stream));
+    if (int rc = upload_rates(c, r)) return rc;
     b.err_prob = prob; std::copy(v, v + 4, b.err_prior); b.learn = true; b.prepared = false;
     return 0;
 }
@@ -1364,12 +1381,8 @@ int lsg_bnpcs_extend(lsg_ctx* c, int32_t add_steps) {
     Bnpcs& b = c->bnpcs;
     if (add_steps < 1) { set_error("%s: %d steps to add (at least 1)", who, add_steps); return -2; }
     const size_t N = b.n_cells, M = b.n_muts, C = b.n_chains, old1 = b.steps1, S1 = old1 + (size_t)add_steps;
-    const double bytes = (double)C * N * M * (4 + 8 + 8 + 4 + 4) + (double)C * S1 * N * 4 + (double)C * b.arena_rows * M * 4;
     if (S1 > (size_t)INT32_MAX) { set_error("%s: %zu steps are more than a run can number", who, S1 - 1); return -2; }
-    if (bytes > 64e9) {
-        set_error("%s: %d chains x %d cells x %d mutations x %zu steps would need %.0f GB of state", who, b.n_chains, b.n_cells, b.n_muts, S1 - 1, bytes / 1e9);
-        return -2;
-    }
+    if (int rc = check_state_size(who, "would need", C, N, M, S1, b.arena_rows)) return rc;
     // the four records, each [chain][steps1][words]: new buffers first, so that a refused allocation leaves the run as it was
     DevBuf* rec[4] = {&b.rec_lab, &b.rec_sc, &b.rec_sm, &b.rec_err};
     const size_t words[4] = {N, (size_t)REC * 2, 1, 4};
@@ -1414,12 +1427,10 @@ int lsg_bnpcs_psrf(lsg_ctx* c, const int32_t* first, int32_t last, double* stats
         const int32_t bsz = (int32_t)std::pow((double)(last - first[k]), 0.5);      // int(n ** 0.5), as utils.py:439 forms it
         par[3 * k] = first[k]; par[3 * k + 1] = bsz; par[3 * k + 2] = bsz / 3;
     }
-    const size_t out_at = (3 * C * 4 + 7) / 8 * 8;
-    if (b.psrf.reserve(out_at + C * 5 * 8)) return -1;
-    double* d_out = reinterpret_cast<double*>(b.psrf.as<char>() + out_at);
+    if (b.psrf.reserve(3 * C * 4) || b.psrf_out.reserve(C * 5 * 8)) return -1;
     LSG_HIP(hipMemcpyAsync(b.psrf.p, par.data(), 3 * C * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_bnpcs_psrf, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), b.psrf.as<int32_t>(), last, d_out);
-    LSG_HIP(hipMemcpyAsync(stats, d_out, C * 5 * 8, hipMemcpyDeviceToHost, c->stream));
+    hipLaunchKernelGGL(k_bnpcs_psrf, dim3(b.n_chains), dim3(256), 0, c->stream, dev_of(b), b.psrf.as<int32_t>(), last, b.psrf_out.as<double>());
+    LSG_HIP(hipMemcpyAsync(stats, b.psrf_out.p, C * 5 * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_check(c, who);                                        // (`par` is read by the copy until here)
 }
 
@@ -1481,9 +1492,7 @@ int lsg_bnpcs_test_ll(lsg_ctx* c, int32_t chain, double* ll, int32_t* clusters, 
     Bnpcs& b = c->bnpcs;
     if (chain < 0 || chain >= b.n_chains || !ll || !clusters || !n_clusters) { set_error("%s: bad arguments", who); return -2; }
     if (int rc = prepare(c, who)) return rc;
-    b.ll_pitch = std::max(b.k_max, 1);
-    if (b.LL.reserve((size_t)b.n_chains * b.n_cells * b.ll_pitch * 8)) return -1;
-    hipLaunchKernelGGL(k_bnpcs_ll, dim3((b.ll_pitch + LT - 1) / LT, (b.n_cells + LT - 1) / LT, b.n_chains), dim3(256), 0, c->stream, dev_of(b));
+    if (int rc = launch_ll(c)) return rc;
     const int32_t K = b.h_k[chain];
     const size_t N = b.n_cells;
     LSG_HIP(hipMemcpy2DAsync(ll, (size_t)K * 8, b.LL.as<double>() + chain * N * b.ll_pitch, (size_t)b.ll_pitch * 8, (size_t)K * 8, N, hipMemcpyDeviceToHost, c->stream));
@@ -1499,40 +1508,25 @@ int lsg_bnpcs_test_move(lsg_ctx* c, int32_t what, int32_t step) {
     if (what < 0 || what > 3 || step < 0) { set_error("%s: bad arguments", who); return -2; }
     if (what == 3 && !b.learn) { set_error("%s: no error-rate update (lsg_bnpcs_set_error_learning first)", who); return -2; }
     if (int rc = prepare(c, who)) return rc;
-    if (what == 3) {
-        if (int rc = launch_err(c, (uint32_t)step)) return rc;
-        return sync_check(c, who);
-    }
-    if (what == 0 || what == 2) {
-        if (what == 0) { if (int rc = launch_sweep(c, (uint32_t)step, 0)) return rc; }
-        else if (int rc = launch_sm(c, (uint32_t)step, 1)) return rc;
-        if (fetch_live(c, who)) return -1;
-        if (int rc = launch_counts_tables(c)) return rc;
-    } else {
-        if (int rc = launch_mh(c, (uint32_t)step)) return rc;
-        hipLaunchKernelGGL(k_bnpcs_tables, dim3(b.n_cells, b.n_chains), dim3(64), 0, c->stream, dev_of(b));
-    }
+    if (what == 0 || what == 2) { if (int rc = step_assign(c, who, (uint32_t)step, what == 0, what == 2)) return rc; }
+    else if (what == 1) step_params(c, (uint32_t)step);
+    else step_errors(c, (uint32_t)step);
     return sync_check(c, who);
 }
 
-int lsg_bnpcs_test_move_outcome(lsg_ctx* c, int32_t chain, double* outcome) {
-    const char* who = "lsg_bnpcs_test_move_outcome";
+// what a chain's last split-merge move left (SM_OUT doubles), or its last error update (ERR_OUT)
+static int fetch_outcome(lsg_ctx* c, const char* who, int32_t chain, bool move, double* outcome) {
     if (int rc = need(c, who)) return rc;
     Bnpcs& b = c->bnpcs;
     if (chain < 0 || chain >= b.n_chains || !outcome) { set_error("%s: bad arguments", who); return -2; }
-    const size_t per = 6 * (size_t)b.n_cells + 6 * (size_t)b.n_muts + SM_OUT;
-    LSG_HIP(hipMemcpyAsync(outcome, b.sm_d.as<double>() + (chain + 1) * per - SM_OUT, SM_OUT * 8, hipMemcpyDeviceToHost, c->stream));
+    const size_t N = b.n_cells, M = b.n_muts;
+    const double* src = move ? b.sm_d.as<double>() + chain * sm_d_size(N, M) + sm_d_out(N, M) : b.err_out.as<double>() + (size_t)chain * ERR_OUT;
+    LSG_HIP(hipMemcpyAsync(outcome, src, (move ? SM_OUT : ERR_OUT) * 8, hipMemcpyDeviceToHost, c->stream));
     return sync_check(c, who);
 }
 
-int lsg_bnpcs_test_error_outcome(lsg_ctx* c, int32_t chain, double* outcome) {
-    const char* who = "lsg_bnpcs_test_error_outcome";
-    if (int rc = need(c, who)) return rc;
-    Bnpcs& b = c->bnpcs;
-    if (chain < 0 || chain >= b.n_chains || !outcome) { set_error("%s: bad arguments", who); return -2; }
-    LSG_HIP(hipMemcpyAsync(outcome, b.err_out.as<double>() + (size_t)chain * ERR_OUT, ERR_OUT * 8, hipMemcpyDeviceToHost, c->stream));
-    return sync_check(c, who);
-}
+int lsg_bnpcs_test_move_outcome(lsg_ctx* c, int32_t chain, double* outcome) { return fetch_outcome(c, "lsg_bnpcs_test_move_outcome", chain, true, outcome); }
+int lsg_bnpcs_test_error_outcome(lsg_ctx* c, int32_t chain, double* outcome) { return fetch_outcome(c, "lsg_bnpcs_test_error_outcome", chain, false, outcome); }
 
 int lsg_bnpcs_test_set_ml(lsg_ctx* c, int32_t chain, int32_t first, int32_t n, const double* values) {
     const char* who = "lsg_bnpcs_test_set_ml";

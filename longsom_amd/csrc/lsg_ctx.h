@@ -88,7 +88,8 @@ struct Bnpcs {
     DevBuf one, zero, pop, seeds, lab, size, colof, live, nlive, hi, theta, L1, L0, LL, alpha, prow, n1, n0, rowml, rowb, order, keys, rec_lab, rec_sc, arena, err;
     DevBuf sm_i, sm_d, sm_c, sm_t, rec_sm;                          // the split-merge move's scratch and its record (SDev in bnpc_sampler.hip)
     DevBuf rates, rec_err, err_cnt, err_out;                        // per chain: the error rates and what follows from them, their record, the moves' counts, the last update
-    DevBuf psrf;                                                    // lsg_bnpcs_psrf: per chain first, b, b // 3 (int32) and behind them the five statistics (double)
+    DevBuf psrf, psrf_out;                                          // lsg_bnpcs_psrf: per chain first, b, b // 3 (int32); the five statistics (double)
+    DevBuf used;                                                    // per chain: the arena rows in use (int64), as k_bnpcs_record reads them
     double err_prob = 0.0, err_prior[4] = {}, mix[2] = {};          // the error-rate update: its probability, (FP mean, FP sd, FN mean, FN sd), _beta_mix_const
     bool learn = false, fixed_assign = false;
     double sm_prob = 0.0, sm_ratio[2] = {0.75, 0.25};
@@ -96,13 +97,13 @@ struct Bnpcs {
     int32_t n_cells = 0, n_muts = 0, n_words = 0, n_chains = 0, steps1 = 0, k_max = 0, ll_pitch = 0, pending = -1, next_step = 0;
     int32_t test_ml_end = 0;              // lsg_bnpcs_test_set_ml: the records below it count as made for lsg_bnpcs_psrf
     int64_t arena_rows = 0;
-    double cfg[10] = {};
+    double p = 1.0, q = 1.0, g0 = 0.0, g1 = 0.0, dpa_prob = 0.0, betaln = 0.0;   // of lsg_bnpcs_create's cfg: the parameter prior, DP_a_gamma, the concentration update's probability, betaln(p, q)
     bool valid = false, prepared = false;
     std::vector<int32_t> h_k;             // clusters alive per chain, as of the last sweep
     std::vector<int64_t> h_used;          // arena rows in use per chain
     void release() {
         for (DevBuf* b : {&one, &zero, &pop, &seeds, &lab, &size, &colof, &live, &nlive, &hi, &theta, &L1, &L0, &LL, &alpha, &prow, &n1, &n0, &rowml, &rowb, &order, &keys, &rec_lab, &rec_sc,
-                          &arena, &err, &sm_i, &sm_d, &sm_c, &sm_t, &rec_sm, &rates, &rec_err, &err_cnt, &err_out, &psrf}) b->release();
+                          &arena, &err, &sm_i, &sm_d, &sm_c, &sm_t, &rec_sm, &rates, &rec_err, &err_cnt, &err_out, &psrf, &psrf_out, &used}) b->release();
         valid = prepared = false;
     }
 };
