@@ -631,6 +631,36 @@ int lsg_bnpcs_fetch_error_rates(lsg_ctx* ctx, double* rates, int32_t* counts);
 int lsg_bnpcs_set_fixed_assignment(lsg_ctx* ctx, int32_t on);
 int lsg_bnpcs_destroy(lsg_ctx* ctx);
 
+/* ---- the beta-binomial fit of the panel-of-normals branch (scripts/PoN/BetaBinEstimation.py) ---------------------------------------
+ * The alpha / beta of the step-1 calls, fitted from the resident count rows instead of by VGAM.  Per row: Alt_CC / Alt_BC = the sum of
+ * CC / BC over the alleles a table prints (A C T G I D; N and O are not printed and never reach the reference's sums) that are not REF, Ref_CC = NC - Alt_CC, Ref_BC = DP - Alt_BC; a row is kept iff
+ * Alt_CC / (double)NC < 0.10 and Alt_BC / (double)DP < 0.15 (:101-104).  The data of both fits are six value histograms, in this order:
+ * Alt_CC, Ref_CC, NC (the cell counts' fit: alpha1, beta1), Alt_BC, Ref_BC, DP (the base counts' fit: alpha2, beta2).  The arithmetic,
+ * the start, the step and the stop of the solve are stated in longsom_amd/bbfit.py, whose numpy twin these calls are held to.
+ * lsg_bbfit_reset zeroes the six histograms of `capacity` bins each (uint64 [6][capacity]).
+ * lsg_bbfit_accumulate makes one pass over the resident count rows of cell type ct - those lsg_pileup_count left or those
+ *   lsg_load_counts installed - and adds the kept rows' values.  REF is the loaded reference at the row's site, or, with ref_or_null
+ *   given, ref_or_null[r] for row r of the cell type in genomic order (a table's own REF column: no reference need be loaded).
+ *   sample_n > 0 thins a table of more than sample_n rows before the filter: row r of table `table` stays iff the uniform of
+ *   Philox4x32-10 under key `seed` and counters (table, r low, r high, 0) is below sample_n / rows.  n_rows_seen: the rows the thinning
+ *   left; n_rows_kept: those of them the filter kept (either may be NULL).  Errors, after which the histograms must be reset: a value
+ *   >= capacity (the message names it - no site is left out silently), a row with DP or NC zero (the reference divides by them).
+ * lsg_bbfit_fetch copies the histograms out, lsg_bbfit_add adds foreign ones (same capacity) in: the ranks' exchange.
+ * lsg_bbfit_solve: est = alpha1, beta1, alpha2, beta2; one workgroup per fit, every sum in a fixed order: the same histograms give the
+ *   same bits on every run.  max_iter 0 means 100.  A fit without rows gives NaN and LSG_BBFIT_NO_DATA. */
+enum { LSG_BBFIT_CONVERGED = 0, LSG_BBFIT_ITERATION_CAP = 1, LSG_BBFIT_NO_DATA = 2, LSG_BBFIT_NO_FINITE_MAXIMUM = 3 };
+typedef struct {
+    int32_t iterations[2];      /* per fit (0 the cell counts', 1 the base counts'): Newton iterations made */
+    int32_t status[2];          /* LSG_BBFIT_*; NO_FINITE_MAXIMUM: the iterate left [1e-8, 1e8] (all alternative counts zero, or under-dispersed data) */
+    double last_step[2];        /* the larger component of the last step in (log alpha, log beta) */
+    double grad_norm[2];        /* norm of the gradient in the log-parameters where that step was made */
+} lsg_bbfit_info;
+int lsg_bbfit_reset(lsg_ctx* ctx, int64_t capacity);
+int lsg_bbfit_accumulate(lsg_ctx* ctx, int32_t ct, const uint8_t* ref_or_null, int32_t table, int64_t sample_n, uint64_t seed, int64_t* n_rows_seen, int64_t* n_rows_kept);
+int lsg_bbfit_fetch(lsg_ctx* ctx, uint64_t* hist);
+int lsg_bbfit_add(lsg_ctx* ctx, const uint64_t* hist);
+int lsg_bbfit_solve(lsg_ctx* ctx, double* est, lsg_bbfit_info* info, int32_t max_iter);
+
 /* ---- measurement helpers --------------------------------------------------------------------*/
 /* Statistics of the last lsg_pileup_count: admitted reads / segments / events (events that passed
  * read admission, before the base-quality gate), tile entries, non-empty units, deep units. */

@@ -129,6 +129,11 @@ class FastqInfo(C.Structure):
     ]
 
 
+class BbfitInfo(C.Structure):
+    """lsg_bbfit_info (lsg_bbfit_solve): per fit (0 the cell counts', 1 the base counts') the iterations, the status, the last step, the gradient norm"""
+    _fields_ = [("iterations", C.c_int32 * 2), ("status", C.c_int32 * 2), ("last_step", C.c_double * 2), ("grad_norm", C.c_double * 2)]
+
+
 FASTQ_OK, FASTQ_NO_CB, FASTQ_CB_TYPE, FASTQ_UB_TYPE, FASTQ_NM_TYPE, FASTQ_NH_TYPE = -1, 0, 1, 2, 3, 4
 
 
@@ -218,6 +223,11 @@ SIGNATURES = {
     "lsg_bnpcs_test_move_outcome": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "lsg_bnpcs_test_error_outcome": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "lsg_bnpcs_test_set_ml": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "lsg_bbfit_reset": (C.c_int, [C.c_void_p, C.c_int64]),
+    "lsg_bbfit_accumulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lsg_bbfit_fetch": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lsg_bbfit_add": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lsg_bbfit_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BbfitInfo), C.c_int32]),
     "lsg_betabinom_sf4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "lsg_betabinom_sf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "lsg_max_live_reads": (C.c_int64, [C.c_void_p]),

@@ -757,12 +757,38 @@ def pon(argv=None):
     _pon.build_from_files(a.in_tsv, a.out_file, a.min_samples, a.rm_prefix)
 
 
+def betabin_estimation(argv=None):
+    """BetaBinEstimation.py --in_tsv LIST --outfile OUT [--n_sites 500000] [--seed 1992]  (scripts/PoN/BetaBinEstimation.py:154-160), fitted on
+    the GPU from the listed BaseCellCounter tables (longsom_amd.bbfit).  --n_sites 0: every eligible site."""
+    from . import bbfit
+    ap = argparse.ArgumentParser(description="Script to estimate the Beta-binomial distribution parameters (alpha and beta) to be used afterwards in the BaseCellCalling.step1.py")
+    ap.add_argument("--in_tsv", required=True); ap.add_argument("--outfile", required=True)
+    ap.add_argument("--n_sites", type=int, default=500000); ap.add_argument("--seed", type=int, default=1992)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    paths = [l.rstrip("\n") for l in open(a.in_tsv)]
+    paths = [p for p in paths if os.path.isfile(p)]          # :183-187
+    print("\n- Number of tsv files to be used:\n  > ", len(paths))
+    with Engine(a.device) as eng:
+        est, infos, seen, kept = bbfit.fit_tables(eng, paths, a.n_sites, a.seed)
+    print("\n- Sites: %d read, %d kept by the filter" % (seen, kept))
+    for f, name in enumerate(("cell counts", "base counts")):
+        print("\n- Beta-binomial estimation finished for %s (%d iterations):\n  > Alpha %d: %r\n  > Beta %d: %r"
+              % (name, infos[f]["iterations"], f + 1, est[2 * f], f + 1, est[2 * f + 1]))
+    bbfit.write_estimates(a.outfile, est)
+    print("\n- Beta-binomial estimation report saved in:\n  > ", a.outfile)
+
+
 def pon_chain(argv=None):
     """rules/PoN.smk SplitBam_PoN .. PoN fused: --normals is a TSV of id, bam, barcodes.tsv (workflow/rules/PoN.gpu.smk)."""
     ap = argparse.ArgumentParser(description="Panel of normals of LongSom on one GPU: count + step-1 call of every normal, then the PoN table")
     ap.add_argument("--normals", required=True); ap.add_argument("--ref", required=True); ap.add_argument("--outdir", required=True)
-    ap.add_argument("--alpha1", type=float, required=True); ap.add_argument("--beta1", type=float, required=True)
-    ap.add_argument("--alpha2", type=float, required=True); ap.add_argument("--beta2", type=float, required=True)
+    ap.add_argument("--alpha1", type=float); ap.add_argument("--beta1", type=float)
+    ap.add_argument("--alpha2", type=float); ap.add_argument("--beta2", type=float)
+    ap.add_argument("--fit", action="store_true", help="fit the four beta-binomial parameters from the normals' count rows (BetaBinEstimation.py without R) and write "
+                    "<outdir>/PoN/PoN/BetaBinEstimates.txt; --alpha1 .. --beta2 are not read")
+    ap.add_argument("--fit_n_sites", type=int, default=0, help="BetaBinEstimation.py's --n_sites; 0 (default): every eligible site")
+    ap.add_argument("--fit_seed", type=int, default=1992)
     ap.add_argument("--min_ac_cells", type=int, default=1); ap.add_argument("--min_ac_reads", type=int, default=1)
     ap.add_argument("--min_cells", type=int, default=1); ap.add_argument("--min_cell_types", type=int, default=1)
     ap.add_argument("--min_mq", type=int, default=60); ap.add_argument("--min_samples", type=int, default=1)
@@ -771,15 +797,22 @@ def pon_chain(argv=None):
     _add_htslib_flag(ap)
     a = ap.parse_args(argv)
     _apply_htslib_flag(a)
+    bb = {k: getattr(a, k) for k in ("alpha1", "beta1", "alpha2", "beta2")}
+    if a.fit:
+        bb = {}
+    elif any(v is None for v in bb.values()):
+        ap.error("the following arguments are required: --alpha1, --beta1, --alpha2, --beta2 (or --fit)")
     normals = [tuple(l.rstrip("\n").split("\t")[:3]) for l in open(a.normals) if l.strip() and not l.startswith("#")]
-    p = pipeline.pon_params(alpha1=a.alpha1, beta1=a.beta1, alpha2=a.alpha2, beta2=a.beta2, min_ac_cells=a.min_ac_cells, min_ac_reads=a.min_ac_reads,
+    p = pipeline.pon_params(**bb, min_ac_cells=a.min_ac_cells, min_ac_reads=a.min_ac_reads,
                             min_cells=a.min_cells, min_cell_types=a.min_cell_types, min_mapping_quality=a.min_mq)
     # under torch.distributed.run: the normals are spread over the ranks (one GPU each)
     from . import regions
     comm = regions.Comm.from_env()
     try:
-        out = pipeline.run_pon(normals, a.ref, a.outdir, p, a.min_samples, a.rm_prefix, not a.no_tables, device=a.device, comm=comm)
+        out = pipeline.run_pon(normals, a.ref, a.outdir, p, a.min_samples, a.rm_prefix, not a.no_tables, device=a.device, comm=comm,
+                               fit=a.fit, fit_n_sites=a.fit_n_sites, fit_seed=a.fit_seed)
         if comm.rank == 0:
-            print(json.dumps({"pon": out.pon, "sites": out.n_sites, "seconds": out.timings, "ranks": comm.world}))
+            fitted = {"estimates": out.estimates, "estimates_file": out.estimates_path} if a.fit else {}
+            print(json.dumps({"pon": out.pon, "sites": out.n_sites, "seconds": out.timings, "ranks": comm.world, **fitted}))
     finally:
         comm.close()

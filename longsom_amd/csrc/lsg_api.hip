@@ -114,6 +114,7 @@ void lsg_destroy(lsg_ctx* c) {
     c->cg.release();
     c->bnpc.release();
     c->bnpcs.release();
+    c->bb.release();
     c->tab_names.release();
     for (auto& b : c->ws) b.release();
     for (auto& b : c->tm) b.release();

@@ -108,6 +108,15 @@ struct Bnpcs {
     }
 };
 
+// bbfit.hip: the six value histograms of the beta-binomial fit (lsg_bbfit_reset; uint64 [6][cap]), their tail counts as doubles
+// (lsg_bbfit_solve), the counters of a pass, a table's REF column and the staging of lsg_bbfit_add / the solve's results
+struct Bbfit {
+    DevBuf hist, tails, out, ref, tmp;
+    int64_t cap = 0;
+    bool valid = false;
+    void release() { for (DevBuf* b : {&hist, &tails, &out, &ref, &tmp}) b->release(); valid = false; cap = 0; }
+};
+
 // workspace buffers (lsg_ctx::ws)
 enum { WS_NE_NSLOT = 0, WS_NE_ACC, WS_NE_GEOM, WS_MULTI_LIST, WS_MACC, WS_EXPORT_K, WS_EXPORT_R,
        WS_EXPORT_C, WS_CALL_FLAGS, WS_CALL_SEL, WS_CALL_CANDS, WS_CALL_TASKS, WS_SEG_INFO };
@@ -154,6 +163,7 @@ __global__ void k_read_end(const uint32_t* seg_read, const int32_t* seg_start, c
 __global__ void k_read_end_init(const int32_t* read_pos, int64_t n_reads, int32_t* read_end);
 int depth_cap_drops(lsg_ctx* c, const lsg_count_params* p);   // layout.hip: htslib's max_depth rule -> d_read_drop (or none)
 struct GatherCountSrc { const uint16_t* events; int64_t n_events; const uint64_t* key; const uint32_t* rdv; int32_t cb_bits; int32_t src_shift; int32_t wsh; };
+int unit_row_offsets(lsg_ctx* c, int ct, const uint32_t** off);      // pileup.hip: per unit, the first of its rows in the cell type's genomic row order
 int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc& src, bool direct);      // pileup.hip: the load's gather and the first count in one pass (k_tm_gather_count), or the count alone from the caller's events (k_tm_count_direct)
 }
 
@@ -266,6 +276,7 @@ struct lsg_ctx {
 
     lsg::Bnpc bnpc;                       // bnpc.hip: the resident posterior samples and their pair distances
     lsg::Bnpcs bnpcs;                     // bnpc_sampler.hip: the sampler's chains
+    lsg::Bbfit bb;                        // bbfit.hip: the beta-binomial fit's histograms
 
     lsg::PosSet posset[3];
     lsg::DevBuf syn[12];                  // synthetic-model tables + scan scratch (synth.hip)

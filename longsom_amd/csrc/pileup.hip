@@ -2088,6 +2088,20 @@ __global__ void k_export_rows(CountArgs a, int ct, const uint32_t* rowoff, int64
         counts[dst * LSG_ROW_WORDS + 34 + sy] = counts[dst * LSG_ROW_WORDS + 10 + sy] - counts[dst * LSG_ROW_WORDS + 26 + sy];
 }
 
+// Where the rows of every unit of cell type ct start in the genomic order of that cell type's rows (n_ne + 1 entries, on the stream):
+// the order lsg_fetch_counts exports and bbfit.hip numbers a table's rows by.
+int unit_row_offsets(lsg_ctx* c, int ct, const uint32_t** off_out) {
+    hipStream_t st = c->stream;
+    const uint32_t n_ne = c->n_ne;
+    if (c->d_ne_rowoff.reserve((size_t)(n_ne + 2) * 8)) return -1;
+    uint32_t* cnt = c->d_ne_rowoff.as<uint32_t>();
+    uint32_t* off = cnt + (n_ne + 2);
+    hipLaunchKernelGGL(k_unit_rowcount, dim3((n_ne + 256) / 256), dim3(256), 0, st, c->d_ne_units.as<uint32_t>(), c->d_ne_mask.as<uint64_t>(), n_ne, c->n_ct, ct, cnt);
+    SCAN_U32(cnt, off, n_ne + 1);
+    *off_out = off;
+    return 0;
+}
+
 // The count rows of one cell type as flat device arrays (keys (tid << 32) | pos0, reference bases, LSG_ROW_WORDS counters per row), in
 // genomic order: what lsg_fetch_counts copies to the host and tables.hip prints.
 int run_export_rows(lsg_ctx* c, int ct, DevBuf& dk, DevBuf& dr, DevBuf& dc) {
@@ -2097,11 +2111,8 @@ int run_export_rows(lsg_ctx* c, int ct, DevBuf& dk, DevBuf& dr, DevBuf& dc) {
     CountArgs a{};
     fill_args(c, &c->last_params, a);
     uint32_t n_ne = c->n_ne;
-    if (c->d_ne_rowoff.reserve((size_t)(n_ne + 2) * 8)) return -1;
-    uint32_t* cnt = c->d_ne_rowoff.as<uint32_t>();
-    uint32_t* off = cnt + (n_ne + 2);
-    hipLaunchKernelGGL(k_unit_rowcount, dim3((n_ne + 256) / 256), dim3(256), 0, st, a.ne_units, a.ne_mask, n_ne, c->n_ct, ct, cnt);
-    SCAN_U32(cnt, off, n_ne + 1);
+    const uint32_t* off = nullptr;
+    if (int rc = unit_row_offsets(c, ct, &off)) return rc;
     if (dk.reserve((size_t)n * 8) || dr.reserve((size_t)n) || dc.reserve((size_t)n * LSG_ROW_WORDS * 4)) return -1;
     uint64_t threads = (uint64_t)n_ne * 64;
     hipLaunchKernelGGL(k_export_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, a, ct, off,

@@ -93,6 +93,7 @@ class Engine:
         self.n_contigs = 0
         self.contig_len = None
         self.pileup_window = 50000
+        self._bbfit_cap = 0
         self._load_settings = {"load_filter": (0, 0, 0), "count_at_load": None, "store_policy": 0, "keep_unlisted": False,      # the library's defaults
                                "split_filters": (-1, -1, 0)}
         if stream is not None:
@@ -890,6 +891,42 @@ class Engine:
         if len(k):
             _lib.check(self._lib.lsg_betabinom_sf(self._h, len(k), _ptr(k), _ptr(n), float(alpha), float(beta), _ptr(out), _ptr(raw)), "lsg_betabinom_sf")
         return out, raw
+
+    # ---- the beta-binomial fit (csrc/bbfit.hip; longsom_amd/bbfit.py states the arithmetic) -----
+    def bbfit_reset(self, capacity: int) -> None:
+        """zero the fit's six histograms (Alt_CC, Ref_CC, NC, Alt_BC, Ref_BC, DP) of `capacity` bins each"""
+        _lib.check(self._lib.lsg_bbfit_reset(self._h, int(capacity)), "lsg_bbfit_reset")
+        self._bbfit_cap = int(capacity)
+
+    def bbfit_accumulate(self, ct: int, ref=None, table: int = 0, sample_n: int = 0, seed: int = 1992):
+        """one pass over cell type ct's resident count rows; ref: the rows' REF bytes in genomic order (a table's own column) instead
+        of the loaded reference.  Returns (rows the thinning left, rows kept of them)."""
+        r = None if ref is None else np.ascontiguousarray(ref, dtype=np.uint8)
+        if r is not None and len(r) != self._n_rows[ct]:
+            raise ValueError("bbfit_accumulate: %d REF bytes for %d rows" % (len(r), self._n_rows[ct]))
+        seen, kept = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.lsg_bbfit_accumulate(self._h, int(ct), _ptr(r), int(table), int(sample_n),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(seen), C.byref(kept)), "lsg_bbfit_accumulate")
+        return int(seen.value), int(kept.value)
+
+    def bbfit_fetch(self) -> np.ndarray:
+        hist = np.zeros((6, self._bbfit_cap), np.uint64)
+        _lib.check(self._lib.lsg_bbfit_fetch(self._h, _ptr(hist)), "lsg_bbfit_fetch")
+        return hist
+
+    def bbfit_add(self, hist) -> None:
+        hist = np.ascontiguousarray(hist, dtype=np.uint64)
+        if hist.shape != (6, self._bbfit_cap):
+            raise ValueError("bbfit_add: histograms of shape %s for a capacity of %d" % (hist.shape, self._bbfit_cap))
+        _lib.check(self._lib.lsg_bbfit_add(self._h, _ptr(hist)), "lsg_bbfit_add")
+
+    def bbfit_solve(self, max_iter: int = 0):
+        """([alpha1, beta1, alpha2, beta2], [info of the cell counts' fit, info of the base counts' fit]); info as bbfit.solve gives it"""
+        est = np.zeros(4, np.float64)
+        info = _lib.BbfitInfo()
+        _lib.check(self._lib.lsg_bbfit_solve(self._h, _ptr(est), C.byref(info), int(max_iter)), "lsg_bbfit_solve")
+        return [float(x) for x in est], [dict(iterations=int(info.iterations[f]), status=int(info.status[f]), last_step=float(info.last_step[f]),
+                                              grad_norm=float(info.grad_norm[f])) for f in range(2)]
 
     def probe_posset_device(self, kind: int, keys_ptr: int, n: int, hits_ptr: int) -> None:
         """membership of n device-resident int64 keys in set `kind`, hits (uint8) written to device memory (both caller-owned)"""

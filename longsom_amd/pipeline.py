@@ -6,6 +6,7 @@ the merge is fused into the call kernel; only text formatting and steps 2/3 (can
 on the host.  Every output file has the name and the bytes the reference's scripts give it (except
 the wall-clock ##fileDate line).
 """
+import dataclasses
 import itertools
 import json
 import os
@@ -18,7 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import pandas as pd
 
-from . import calling, hostio, pon, regions, tsvio
+from . import bbfit, calling, hostio, pon, regions, tsvio
 from ._lib import CallParams, CountParams
 from . import _lib
 from .engine import Engine
@@ -1015,6 +1016,8 @@ class PonOutputs:
     step1: Dict[str, str]
     n_sites: int = 0
     timings: Dict[str, Dict[str, float]] = field(default_factory=dict)
+    estimates: Optional[List[float]] = None          # fit=True: alpha1, beta1, alpha2, beta2 as fitted from the normals' count rows
+    estimates_path: str = ""                         # ... and the BetaBinEstimates.txt they were written to
 
 
 def pon_params(**kw) -> SnvParams:
@@ -1024,15 +1027,51 @@ def pon_params(**kw) -> SnvParams:
     return SnvParams(**base)
 
 
+def _pon_fit(eng, normals, ref_fasta, params, comm, n_sites, seed, path) -> List[float]:
+    """BetaBinEstimation over the normals' resident count rows: every normal of the rank is loaded and counted (the load makes the
+    count and keeps no store), each of its cell types is one table of the fit (csrc/bbfit.hip); the ranks exchange their histograms,
+    every rank adds them in rank order and solves - the same integers, so the same bits everywhere - and rank 0 writes the file."""
+    cp = params.count()
+    first, sample_n = [0] * len(normals), 0
+    if n_sites > 0:                                    # the tables' numbers and their count, as every rank must know them: one per (normal, cell type)
+        n_ct = [len(hostio.read_barcodes(bct).celltype_names) for _, _, bct in normals]
+        first = [sum(n_ct[:i]) for i in range(len(normals))]
+        sample_n = bbfit.sample_size(n_sites, sum(n_ct))
+    eng.bbfit_reset(bbfit.capacity_for(params.max_depth))          # (no count exceeds the pileup's max_depth)
+    for i in range(comm.rank, len(normals), comm.world):
+        sample_id, bam, barcodes_tsv = normals[i]
+        res = load_sample(bam, barcodes_tsv, ref_fasta, eng, params.min_mapping_quality, count_params=cp, keep_store=False)
+        eng.set_barcodes(res.table.celltype_of, len(res.table.celltype_names))
+        eng.pileup_count(cp)
+        for ct in range(len(res.table.celltype_names)):
+            eng.bbfit_accumulate(ct, table=first[i] + ct, sample_n=sample_n, seed=seed)
+    if comm.world > 1:
+        mine = eng.bbfit_fetch()
+        top = int(np.flatnonzero(mine.any(axis=0))[-1]) + 1 if mine.any() else 0          # (the occupied part alone goes over the wire)
+        eng.bbfit_reset(mine.shape[1])
+        for blob in comm.allgather_bytes(np.ascontiguousarray(mine[:, :top]).tobytes()):
+            part = np.frombuffer(blob, np.uint64).reshape(6, -1)
+            full = np.zeros_like(mine)
+            full[:, :part.shape[1]] = part
+            eng.bbfit_add(full)
+    est, _ = bbfit.device_solve(eng)
+    if comm.rank == 0:
+        bbfit.write_estimates(path, est)
+    return est
+
+
 def run_pon(normals, ref_fasta: str, out_dir: str, params: Optional[SnvParams] = None, min_samples: int = 1, rm_prefix: str = "No",
             write_tables: bool = True, out_name: str = "PoN_LR.tsv", device: int = 0, engine: Optional[Engine] = None,
-            comm: Optional["regions.Comm"] = None) -> PonOutputs:
+            comm: Optional["regions.Comm"] = None, fit: bool = False, fit_n_sites: int = 0, fit_seed: int = 1992) -> PonOutputs:
     """rules/PoN.smk from SplitBam_PoN to PoN in one process: for every normal (id, bam, barcodes.tsv) the count + step-1 call
     chain, then scripts/PoN/PoN.py over the sites with a filter status.  The beta-binomial parameters come in through `params`
-    (BetaBinEstimation.py's VGAM fit stays outside).  write_tables=False skips the per-normal tables (the PoN needs only the call
+    (BetaBinEstimates.txt's four numbers), or are fitted here (fit=True, below).  write_tables=False skips the per-normal tables (the PoN needs only the call
     records); the PoN file is the same either way.  Output layout: <out_dir>/PoN/{SplitBam,BaseCellCounter,MergeCounts,
     BaseCellCalling,PoN}/ as in the rule file.  comm (world > 1): the normals are independent samples — rank r takes every world-th one
-    on its own GPU, the sites of their call records are gathered (one all-gather of a few MB) and rank 0 writes the panel."""
+    on its own GPU, the sites of their call records are gathered (one all-gather of a few MB) and rank 0 writes the panel.
+    fit=True: the four beta-binomial parameters of `params` are not read; a first pass counts every normal and fits them from the
+    resident rows (_pon_fit: BetaBinEstimation.py without R), <out_dir>/PoN/PoN/BetaBinEstimates.txt is written, and the loop runs with
+    the fitted values.  fit_n_sites / fit_seed: BetaBinEstimation.py's --n_sites (0, the default here: every eligible site) and --seed."""
     import json
     params = params or pon_params()
     comm = comm or regions.Comm()
@@ -1041,7 +1080,12 @@ def run_pon(normals, ref_fasta: str, out_dir: str, params: Optional[SnvParams] =
     root = os.path.join(out_dir, "PoN")
     entries, step1, timings = [], {}, {}
     normals = list(normals)
+    estimates, estimates_path = None, ""
     try:
+        if fit:
+            estimates_path = os.path.join(root, "PoN", "BetaBinEstimates.txt")
+            estimates = _pon_fit(eng, normals, ref_fasta, params, comm, fit_n_sites, fit_seed, estimates_path)
+            params = dataclasses.replace(params, alpha1=estimates[0], beta1=estimates[1], alpha2=estimates[2], beta2=estimates[3])
         for sample_id, bam, barcodes_tsv in normals[comm.rank::comm.world]:
             res = load_sample(bam, barcodes_tsv, ref_fasta, eng, params.min_mapping_quality)
             out, _, calls, t = chain_step1(res, res.table.celltype_of, res.table.celltype_names, res.dec.report, root, sample_id, params, write_tables)
@@ -1067,4 +1111,4 @@ def run_pon(normals, ref_fasta: str, out_dir: str, params: Optional[SnvParams] =
         with open(path, "w") as f:
             f.write(text)
     comm.barrier()
-    return PonOutputs(path, step1, sum(1 for l in text.split("\n") if l and not l.startswith("#")), timings)
+    return PonOutputs(path, step1, sum(1 for l in text.split("\n") if l and not l.startswith("#")), timings, estimates, estimates_path)
