@@ -559,12 +559,25 @@ int lsg_cellgeno_load_cells(lsg_ctx* ctx, int64_t n_sites, int32_t n_cb, const u
  * "same" (:183-189): the sum over all samples and all of c's cells of the row of the cell's label, divided by n_samples x cells.
  *   params [n_clusters][n_muts] doubles; branch[c] = 0 both criteria, 1 the first only, 2 neither, 3 a one-cell cluster; branch and
  *   n_used may be NULL.
+ * lsg_bnpc_linkage: scipy's linkage(D / n_samples, "ward") over the resident counts, every bit of its four columns: the nearest-neighbour
+ *            chain walked by one workgroup over a square fp64 working copy (n_cells^2 x 8 bytes of device memory: refused with the byte
+ *            count where that is not free), the merges sorted stably by height and named by scipy's union-find on the host.  The tree
+ *            stays resident for lsg_bnpc_cut_tree; Z [n_cells - 1][4] may be NULL.
+ * lsg_bnpc_cut_tree: scipy's cut_tree(Z, n_clusters) of that tree (made first where lsg_bnpc_linkage was not called since the last
+ *            lsg_bnpc_codist), one row of labels per requested cluster number: nodes applied in ascending height, equal heights in
+ *            cut_tree's own order, a cluster's label its rank by its lowest cell.  Refused: n_cuts < 1, an n_clusters outside
+ *            1 .. n_cells - 1 (scipy answers n_cells itself with zeros).
+ * lsg_bnpc_cluster_counts: per sample the labels that more than two cells carry, summed over the samples (utils.py:106-111 before its mean:
+ *            *sum_over_samples / n_samples in fp64 is np.mean of the counts).  Needs lsg_bnpc_load_samples alone.
  * lsg_bnpc_unload frees all of it. */
 int lsg_bnpc_load_samples(lsg_ctx* ctx, int64_t n_samples, int32_t n_cells, const int32_t* assign, int32_t k_max, int32_t n_muts, const float* params);
 int lsg_bnpc_codist(lsg_ctx* ctx);
 int lsg_bnpc_fetch_dist(lsg_ctx* ctx, uint32_t* dist, int64_t capacity);
 int lsg_bnpc_mpear(lsg_ctx* ctx, int32_t n_cuts, const int32_t* labels, uint64_t* same_pairs, uint64_t* same_sim, uint64_t* dist_sum);
 int lsg_bnpc_mean_params(lsg_ctx* ctx, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used);
+int lsg_bnpc_linkage(lsg_ctx* ctx, double* Z);
+int lsg_bnpc_cut_tree(lsg_ctx* ctx, int32_t n_cuts, const int32_t* n_clusters, int32_t* labels);
+int lsg_bnpc_cluster_counts(lsg_ctx* ctx, int64_t* sum_over_samples);
 int lsg_bnpc_unload(lsg_ctx* ctx);
 
 /* ---- BnpC's sampler (CellClustering/libs/CRP.py:17-820, libs/CRP_learning_errors.py, libs/MCMC.py:200-388) ------------------------------

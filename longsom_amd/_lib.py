@@ -200,6 +200,9 @@ SIGNATURES = {
     "lsg_bnpc_fetch_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "lsg_bnpc_mpear": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lsg_bnpc_mean_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_bnpc_linkage": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lsg_bnpc_cut_tree": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lsg_bnpc_cluster_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lsg_bnpc_unload": (C.c_int, [C.c_void_p]),
     "lsg_bnpcs_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "lsg_bnpcs_set_state": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double]),

@@ -444,6 +444,7 @@ def _bnpc_parser():
     g.add_argument("--chains_npz", default="", help="estimate from chains saved by --save_chains: no sampler is run")
     g.add_argument("--host_estimate", action="store_true", help="the numpy twin of the estimate, for a machine without a GPU")
     g.add_argument("--device", type=int, default=0)
+    g.add_argument("--scipy_linkage", action="store_true", help="the estimate's ward tree and its cuts by scipy on the host instead of the GPU (the same bits)")
     g.add_argument("--sampler", choices=["reference", "device", "device-sm", "device-errors", "device-open"], default="reference",
                    help="device: Gibbs sweeps, the concentration update and the parameter moves on the GPU, all chains at once (needs -smp 0); "
                         "device-sm: the same with the split-merge move, -smp / -sms / -smr honoured (-smp 0 equals device); "
@@ -604,7 +605,8 @@ def run_bnpc(argv=None):
             inferred["mean"][est] = bnpc.posterior_estimate_host(cat["assignments"], cat["params"], data, cat["DP_alpha"], cat["FN"], cat["FP"])
         else:
             with Engine(a.device) as eng:
-                inferred["mean"][est] = bnpc.posterior_estimate(eng, cat["assignments"], cat["params"], data, cat["DP_alpha"], cat["FN"], cat["FP"])
+                inferred["mean"][est] = bnpc.posterior_estimate(eng, cat["assignments"], cat["params"], data, cat["DP_alpha"], cat["FN"], cat["FP"],
+                                                                linkage="scipy" if a.scipy_linkage else "device")
     out_dir = bnpc.out_dir_of(a.output, a.input, f"{a.time[0]:%Y%m%d_%H:%M:%S}")
     if a.verbosity > 0 and io is not None and not a.chains_npz:
         io.show_MCMC_summary(a, results)

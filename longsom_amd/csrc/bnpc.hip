@@ -251,7 +251,7 @@ static int sync_check(lsg_ctx* c, const char* who) {
 int run_bnpc_load(lsg_ctx* c, int64_t n_samples, int32_t n_cells, const int32_t* assign, int32_t k_max, int32_t n_muts, const float* params) {
     const char* who = "lsg_bnpc_load_samples";
     Bnpc& b = c->bnpc;
-    b.valid = b.dist_valid = false;
+    b.valid = b.dist_valid = b.tree_valid = false;
     if (n_cells < 2 || n_cells > 65535) { set_error("%s: %d cells (2 .. 65535)", who, n_cells); return -2; }
     if (n_samples < 1 || n_samples > 0xFFFFFFFFll) { set_error("%s: %lld samples (at least 1)", who, (long long)n_samples); return -2; }
     if (!assign) { set_error("%s: assign is NULL", who); return -2; }
@@ -290,6 +290,7 @@ int run_bnpc_codist(lsg_ctx* c) {
     const char* who = "lsg_bnpc_codist";
     Bnpc& b = c->bnpc;
     if (!b.valid) { set_error("%s: no samples resident (lsg_bnpc_load_samples first)", who); return -2; }
+    b.tree_valid = false;
     const int64_t pairs = (int64_t)b.n_cells * (b.n_cells - 1) / 2;
     if (b.dist.reserve((size_t)pairs * 4)) return -1;
     const unsigned t = (unsigned)(b.pitch / BT);

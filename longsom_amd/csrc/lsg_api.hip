@@ -39,6 +39,9 @@ int run_bnpc_fetch_dist(lsg_ctx* c, uint32_t* out, int64_t capacity);
 int run_bnpc_mpear(lsg_ctx* c, int32_t n_cuts, const int32_t* labels, uint64_t* same_pairs, uint64_t* same_sim, uint64_t* dist_sum);
 int run_bnpc_mean_params(lsg_ctx* c, const int32_t* final_assign, int32_t n_clusters, double* params, uint8_t* branch, int32_t* n_used);
 int run_bnpc_unload(lsg_ctx* c);
+int run_bnpc_linkage(lsg_ctx* c, double* Z);
+int run_bnpc_cut_tree(lsg_ctx* c, int32_t n_cuts, const int32_t* n_clusters, int32_t* labels);
+int run_bnpc_cluster_counts(lsg_ctx* c, int64_t* sum_over_samples);
 int run_sf4(lsg_ctx* c, int64_t items, const uint32_t* k, const uint32_t* n, double al, double be, int32_t* out, double* raw);
 
 // copy a host or device array into a grow-only device buffer of the handle (the caller's array is free again when the call returns)
@@ -603,6 +606,24 @@ int lsg_bnpc_mean_params(lsg_ctx* c, const int32_t* final_assign, int32_t n_clus
     if (!c) { set_error("lsg_bnpc_mean_params: NULL handle"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
     return run_bnpc_mean_params(c, final_assign, n_clusters, params, branch, n_used);
+}
+
+int lsg_bnpc_linkage(lsg_ctx* c, double* Z) {
+    if (!c) { set_error("lsg_bnpc_linkage: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_linkage(c, Z);
+}
+
+int lsg_bnpc_cut_tree(lsg_ctx* c, int32_t n_cuts, const int32_t* n_clusters, int32_t* labels) {
+    if (!c) { set_error("lsg_bnpc_cut_tree: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_cut_tree(c, n_cuts, n_clusters, labels);
+}
+
+int lsg_bnpc_cluster_counts(lsg_ctx* c, int64_t* sum_over_samples) {
+    if (!c) { set_error("lsg_bnpc_cluster_counts: NULL handle"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_bnpc_cluster_counts(c, sum_over_samples);
 }
 
 int lsg_bnpc_unload(lsg_ctx* c) {

@@ -74,12 +74,19 @@ struct CellGeno {
 };
 
 // bnpc.hip: the posterior samples lsg_bnpc_load_samples made resident (labels as 16 bits, rows of `pitch` = n_cells rounded up to 64), the
-// pair distances of lsg_bnpc_codist and the scratch of the two calls that read them
+// pair distances of lsg_bnpc_codist, the scratch of the two calls that read them, and the ward tree over them
 struct Bnpc {
     DevBuf lab, raw, params, dist, cuts, sums, rank, flags, owner, cl16, idx, mean, part, ord2, small;
+    DevBuf work, wsmall, rec;             // bnpc_linkage.hip: the square working copy of the distances, the chain's small arrays, its merge records
+    std::vector<double> Z;                // lsg_bnpc_linkage's tree [n_cells - 1][4], kept on the host for lsg_bnpc_cut_tree
+    std::vector<int32_t> cut_order;       // the rows of Z in the order cut_tree applies them
     int64_t n_samples = 0; int32_t n_cells = 0, pitch = 0, k_max = 0, n_muts = 0;
-    bool valid = false, dist_valid = false, has_params = false;
-    void release() { for (DevBuf* b : {&lab, &raw, &params, &dist, &cuts, &sums, &rank, &flags, &owner, &cl16, &idx, &mean, &part, &ord2, &small}) b->release(); valid = dist_valid = has_params = false; }
+    bool valid = false, dist_valid = false, has_params = false, tree_valid = false;
+    void release() {
+        for (DevBuf* b : {&lab, &raw, &params, &dist, &cuts, &sums, &rank, &flags, &owner, &cl16, &idx, &mean, &part, &ord2, &small, &work, &wsmall, &rec}) b->release();
+        Z = {}; cut_order = {};
+        valid = dist_valid = has_params = tree_valid = false;
+    }
 };
 
 // bnpc_sampler.hip: the sampler's resident state (lsg_bnpcs_create): per cell the masks and popcounts; per chain the labels, the slot

@@ -723,6 +723,28 @@ class Engine:
         _lib.check(self._lib.lsg_bnpc_mean_params(self._h, fa.ctypes.data_as(C.c_void_p), n_cl, out.ctypes.data_as(C.c_void_p), _ptr(branch), _ptr(n_used)), "lsg_bnpc_mean_params")
         return out, branch, n_used
 
+    def bnpc_linkage(self, fetch: bool = True):
+        """scipy's linkage(D / S, "ward") of the resident D, Z [N - 1, 4] float64 (lsg_bnpc_linkage); the tree stays resident for bnpc_cut_tree"""
+        shape = getattr(self, "_bnpc_shape", None)
+        Z = np.zeros((shape[1] - 1, 4), np.float64) if fetch and shape is not None else None
+        _lib.check(self._lib.lsg_bnpc_linkage(self._h, _ptr(Z) if Z is not None else None), "lsg_bnpc_linkage")
+        return Z
+
+    def bnpc_cut_tree(self, ns):
+        """scipy's cut_tree(Z, n_clusters=ns) of the resident tree as rows: labels [len(ns), N] int32 (lsg_bnpc_cut_tree)"""
+        ns = np.ascontiguousarray(np.atleast_1d(ns), dtype=np.int32)
+        shape = getattr(self, "_bnpc_shape", None)
+        labels = np.zeros((len(ns), shape[1] if shape is not None else 0), np.int32)
+        _lib.check(self._lib.lsg_bnpc_cut_tree(self._h, len(ns), _ptr(ns), _ptr(labels)), "lsg_bnpc_cut_tree")
+        return labels
+
+    def bnpc_avg_cluster_number(self):
+        """bnpc.avg_cluster_number of the resident samples: per sample the labels of more than 2 cells counted on the device
+        (lsg_bnpc_cluster_counts), their integer sum divided once"""
+        total = C.c_int64(0)
+        _lib.check(self._lib.lsg_bnpc_cluster_counts(self._h, C.byref(total)), "lsg_bnpc_cluster_counts")
+        return np.float64(total.value) / np.float64(self._bnpc_shape[0])
+
     def bnpc_unload(self) -> None:
         _lib.check(self._lib.lsg_bnpc_unload(self._h), "lsg_bnpc_unload")
         self._bnpc_shape = None

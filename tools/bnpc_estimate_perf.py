@@ -3,10 +3,12 @@
                                     tools/bnpc_estimate_perf.py --cpu_reference DIR                        (on a CPU, no device)
 
 On the GPU: generated chains (planted clusters, every sample relabelled through a random injection, 5 % of the cells moved; default 5000
-cells, 10720 samples - 16 chains x 1000 steps after a burn-in of 0.33 - about 20 clusters, 200 mutations) are made resident, and the three
+cells, 10720 samples - 16 chains x 1000 steps after a burn-in of 0.33 - about 20 clusters, 200 mutations) are made resident, and the
 device calls of the estimate are timed by a host clock around calls that end in a device synchronise, warmed up and repeated:
-lsg_bnpc_codist, lsg_bnpc_mpear over the candidate cuts of the ward tree, lsg_bnpc_mean_params of the best cut.  The host's share
-(scipy's linkage and cut_tree) is timed once beside them.  Prints one JSON line.
+lsg_bnpc_codist, lsg_bnpc_cluster_counts, lsg_bnpc_linkage, lsg_bnpc_cut_tree over the candidate cuts, lsg_bnpc_mpear over them,
+lsg_bnpc_mean_params of the best cut.  What the tree, the cuts and the cluster count cost on the host (scipy's linkage and cut_tree, numpy's
+avg_cluster_number, and the fetch of D they need) is timed the same way beside them, in the same run, and the two sides' results are
+compared.  Prints one JSON line.
 
 --cpu_reference DIR: DIR is a LongSom checkout; its own utils.get_dist is timed at 1000 cells x 20 samples and the time per (pair, sample)
 is scaled to the GPU shape.  The scaled figure is an extrapolation, and is named one."""
@@ -72,13 +74,19 @@ def main():
         _, out["codist"] = timed(lambda: eng.bnpc_codist(fetch=False))
         out["codist"]["pair_samples_per_s"] = float("%.4g" % (out["pair_samples"] / (out["codist"]["ms_median"] * 1e-3)))
         print("codist timed:", out["codist"], flush=True)
-        D = eng.bnpc_codist()
-        t0 = time.perf_counter()
-        Z = linkage(D / S, method="ward")
-        n_range = bnpc.cut_range(bnpc.avg_cluster_number(a), N)
-        cuts = np.ascontiguousarray(cut_tree(Z, n_clusters=list(n_range)).T)
-        out["host_linkage_and_cuts_s"] = round(time.perf_counter() - t0, 3)
+        D, out["fetch_dist"] = timed(eng.bnpc_codist, warmup=1, repeats=3)          # (codist with its fetch: the copy is the difference to "codist")
+        avg, out["cluster_counts"] = timed(eng.bnpc_avg_cluster_number)
+        host_avg, out["host_avg_cluster_number"] = timed(lambda: bnpc.avg_cluster_number(a), warmup=1)
+        n_range = bnpc.cut_range(avg, N)
         out["cuts"] = len(n_range)
+        Zd, out["linkage"] = timed(eng.bnpc_linkage)
+        dcuts, out["cut_tree"] = timed(lambda: eng.bnpc_cut_tree(n_range))
+        print("device tree timed:", out["linkage"], out["cut_tree"], flush=True)
+        Z, out["host_linkage"] = timed(lambda: linkage(D / S, method="ward"), warmup=1)
+        cuts, out["host_cut_tree"] = timed(lambda: np.ascontiguousarray(cut_tree(Z, n_clusters=list(n_range)).T), warmup=1)
+        out["device_tree_and_cuts_ms"] = round(out["linkage"]["ms_median"] + out["cut_tree"]["ms_median"], 3)
+        out["host_tree_and_cuts_ms"] = round(out["host_linkage"]["ms_median"] + out["host_cut_tree"]["ms_median"], 3)
+        out["equal"] = {"avg_cluster_number": bool(avg == host_avg), "Z": bool(np.array_equal(Zd.view(np.uint64), Z.view(np.uint64))), "cuts": bool(np.array_equal(dcuts, cuts))}
         (pairs, sim, dsum), out["mpear"] = timed(lambda: eng.bnpc_mpear(cuts))
         scores = bnpc.mpear_scores(pairs, sim, dsum, S, N)
         best = int(np.argmax(scores))
