@@ -11,7 +11,10 @@
 // generic rv_discrete.sf evaluates as 1 - sum_{m<k} exp(logpmf(m)) (step1.py:196,201,329-330) is
 // summed here in fp64 from the shorter side with the pmf ratio recurrence, re-anchored with lgamma
 // every 1024 terms; p-values are stored as Python round(p, 4) * 1e4 (exact half-even on the binary
-// value).  Arithmetic type f64; the text the host prints is identical whenever |p - tie| > ~1e-13.
+// value).  Arithmetic type f64.  The text the host prints is scipy's whenever p lies further from a rounding tie (x.xxxx5) than
+// both sums' error, which grows with the depth: lgamma(n) has an ulp of 2.3e-10 near n = 150 000, and scipy's tail against a
+// 60-digit sum measures 2e-13 at n = 2048, 2e-11 at 30 000, 1.6e-10 at 100 000 and 3.8e-10 at 150 000 (the device's: DESIGN.md,
+// the call section).  tests/test_call_deep_gpu.py holds its pairs 1e-6 from a tie and asserts the exact integers.
 //
 // Device storage is compact (48 B per site + 56 B per (candidate site, cell type)); lsg_fetch_calls /
 // lsg_export_calls expand it into the C-ABI's lsg_call records.
@@ -849,6 +852,7 @@ int run_select_calls(lsg_ctx* c, int kind, lsg_call* dst_device, int64_t capacit
                            c->d_pass_list.as<uint32_t>(), (uint32_t)k, c->d_ref_ptrs.as<const uint8_t*>(), c->d_contig_len.as<int64_t>(), dst_device);
         LSG_HIP(hipGetLastError());
         LSG_HIP(hipStreamSynchronize(st));
+        if (getenv("LSG_TIMING")) fprintf(stderr, "[lsg] export: kind 2 from the PASS list, %lld rows\n", (long long)k);    // (both ways give the same rows: only this line tells them apart)
         return 0;
     }
     DevBuf& flags = c->ws[WS_CALL_FLAGS];
@@ -873,6 +877,7 @@ int run_select_calls(lsg_ctx* c, int kind, lsg_call* dst_device, int64_t capacit
                        c->d_ref_ptrs.as<const uint8_t*>(), c->d_contig_len.as<int64_t>(), dst_device);
     LSG_HIP(hipGetLastError());
     LSG_HIP(hipStreamSynchronize(st));
+    if (kind == 2 && getenv("LSG_TIMING")) fprintf(stderr, "[lsg] export: kind 2 from the scan, %u rows\n", k);
     return 0;
 }
 
