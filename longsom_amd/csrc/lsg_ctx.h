@@ -22,6 +22,8 @@ constexpr int ROW_QUADS = (ROW_PLANES + 3) / 4;
 constexpr uint64_t ROW_BLOCK_WORDS = (uint64_t)ROW_QUADS * 256;
 constexpr uint64_t ROW_STORED_WORDS = (uint64_t)ROW_QUADS * 4;          // words of HBM per row (36)
 constexpr uint32_t ROW_NARROW = 1u << 31;     // in a unit's row base: its rows are 16-bit planes in the first half of their blocks (emit_unit)
+constexpr uint32_t ROW_NARROW_MAX = 256;      // entries of a one-job tile (or window) up to which its rows are written narrow: a quality is a byte, so no plane can reach 2^16
+static_assert(ROW_NARROW_MAX * 255u < (1u << 16), "a narrow row's quality sum (two planes share a word) fits 16 bits");
 __host__ __device__ inline uint64_t row_word(uint64_t row, int plane) {
     return (row >> 6) * ROW_BLOCK_WORDS + (uint64_t)(plane >> 2) * 256 + (row & 63) * 4 + (uint64_t)(plane & 3);
 }

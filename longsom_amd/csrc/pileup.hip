@@ -454,6 +454,9 @@ constexpr uint32_t TMM_FIRST = 1u << 28;      // first entry that is there of a 
 // (+2048) count [0..15] | duplicates [16..31].  Every decision is a scalar branch on a bit of m; the lanes that count the event are
 // selected with EXEC (all lanes are active around the block).  A run of one entry: 7 vector operations; first entry of a longer
 // run 8 (+3 when it closes the run before it); others 10.
+static_assert(TM_JOB_LIMIT * 255 < (1 << 20), "plane 0: a packed job's quality sum of 8-bit qualities fits bits 0..19, no carry into the forward count");
+static_assert(TM_JOB_LIMIT < (1 << 12), "plane 0: a packed job's forward count fits bits 20..31");
+static_assert(TM_JOB_LIMIT < (1 << 16), "plane 1: a packed job's count and its duplicates fit 16 bits each");
 constexpr bool TM_ASM = LSG_TM_ASM;
 // AL (k_tm_count_direct over tile-phased events): the lane's event register was loaded from the entry's whole 128-byte LINE, so the lanes
 // outside the entry's positions [first, end) hold somebody else's events: the meta word carries first in its bits 0..5 and 64 - end in its
@@ -710,7 +713,7 @@ __device__ __forceinline__ void tm_finish(const CountArgs& a, const uint32_t* pc
     for (int k = 0; k < 8; ++k) dp += tot.BC(k);
     tot.ncdup = dp - nc;
     if (nj == 1) {
-        if (tcnt <= 256u) emit_unit<CNT, true>(a, tot, unit, ct, tid, tstart, lane, book, false, refb, arena_slot);
+        if (tcnt <= ROW_NARROW_MAX) emit_unit<CNT, true>(a, tot, unit, ct, tid, tstart, lane, book, false, refb, arena_slot);
         else emit_unit<CNT, false>(a, tot, unit, ct, tid, tstart, lane, book, false, refb, arena_slot + 1);
     } else {
         uint32_t* dst = a.macc + (uint64_t)slab * (NCTR * 64);
@@ -1385,6 +1388,9 @@ __global__ __launch_bounds__(TMW_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
 // m: the entry's meta word - TMM_CLOSE, TMM_FIRST, TMM_SKIP, TMM_SINGLE, TMM_CT12, TMM_FWD where tm_add has them, and in the bits between them
 // the lanes of the entry's positions: even ones [m & 63, 64 - (m >> 6 & 63)), odd ones [m >> 13 & 63, 64 - (m >> 21 & 63)) (tw_ranges).  The atomics' data are register PAIRS, which inline
 // asm can only name by number: v[92:93] = {low word, 1} (v93 holds 1 throughout: `one`), v[94:95] = {low word, 1 | seen << 16}.
+static_assert(TM_JOB_LIMIT * 255 < (1 << 20) && TM_JOB_LIMIT < (1 << 12), "low word: quality sum and forward count of a packed job, as in tm_add's plane 0");
+static_assert(TM_JOB_LIMIT < (1 << 13), "high word: a packed job's count fits bits 0..12");
+static_assert(TM_JOB_LIMIT - 1 < (1 << 12), "high word: the duplicates of symbol class 7, shifted up by 13 + 7, fit the 12 bits left (a run's first entry is no duplicate)");
 __device__ __forceinline__ void tw_add(TmState& s0, TmState& s1, uint32_t m, uint32_t ev, uint32_t thr, uint32_t pk0, uint32_t pk1, uint32_t one) {
     const uint32_t r = m;      // (ONE word: the decisions' bits and the lanes' ranges, TWM_* below)
     if (!TM_ASM) {                                   // the same in plain C++

@@ -1384,6 +1384,13 @@ static void plan_finish(lsg_ctx* c) {          // (after the stream plan_jobs ra
     plan_finish_tiles(c);
     c->tm_nchunks = c->plan_misc[1]; c->tm_n_wide = c->plan_misc[0];
     c->plan_n_ct = c->n_ct;
+    if (getenv("LSG_TIMING")) {                // what no statistic says: how close the jobs came to the packed planes' limit (a host copy of the job table, made for this line only)
+        std::vector<TmJob> jobs(c->tm_njobs);
+        uint32_t longest = 0;
+        if (c->tm_njobs && hipMemcpy(jobs.data(), c->tm[TM_JOBS].p, (size_t)c->tm_njobs * sizeof(TmJob), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return; }
+        for (const TmJob& jb : jobs) if (!(jb.nj & TMJ_WIDE) && jb.e1 - jb.e0 > longest) longest = jb.e1 - jb.e0;
+        fprintf(stderr, "[lsg] plan: %u jobs, %u multi-job tiles, %u wide, longest packed job %u entries\n", c->tm_njobs, c->plan1_tot[3], c->tm_n_wide, longest);
+    }
 }
 
 int ensure_plan(lsg_ctx* c) {

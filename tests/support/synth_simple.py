@@ -19,9 +19,11 @@ def random_reference(rng, length, n_frac=0.01):
 
 
 def random_records(seed, n_reads, contig_lens, n_cb, hot_regions=(), hot_frac=0.0, cb_skew=0.0,
-                   max_exons=4, exon_len=(30, 400), intron_len=(20, 3000)):
+                   max_exons=4, exon_len=(30, 400), intron_len=(20, 3000), qual_range=None):
     """hot_regions: list of (tid, start, end); a fraction hot_frac of the reads start inside one.
-    cb_skew: probability that a read takes barcode 0 (forces huge single-barcode runs)."""
+    cb_skew: probability that a read takes barcode 0 (forces huge single-barcode runs).
+    qual_range: (lo, hi) - base qualities uniform in lo..hi (up to the full byte, 255) instead of the default mix of 2..60; they are
+    the last thing drawn, so everything before them is the same records either way."""
     rng = np.random.default_rng(seed)
     contig_lens = np.asarray(contig_lens, dtype=np.int64)
     read_tid = np.zeros(n_reads, np.int32); read_pos = np.zeros(n_reads, np.int32)
@@ -74,6 +76,9 @@ def random_records(seed, n_reads, contig_lens, n_cb, hot_regions=(), hot_frac=0.
     # symbols: mostly A/C/T/G, some indel anchors / deletions / N / NA
     sym = rng.choice(np.array([0, 1, 2, 3, 4, 5, 6, 7, 15], dtype=np.uint16), size=n_ev,
                      p=[0.235, 0.235, 0.235, 0.235, 0.01, 0.01, 0.005, 0.025, 0.01])
-    qual = np.where(rng.random(n_ev) < 0.9, rng.integers(20, 61, n_ev), rng.integers(2, 20, n_ev)).astype(np.uint16)
+    if qual_range is None:
+        qual = np.where(rng.random(n_ev) < 0.9, rng.integers(20, 61, n_ev), rng.integers(2, 20, n_ev)).astype(np.uint16)
+    else:
+        qual = rng.integers(int(qual_range[0]), int(qual_range[1]) + 1, n_ev).astype(np.uint16)
     events = np.where(sym < 8, 0x0800 | (sym << 8) | qual, 0).astype(np.uint16)      # LSG_EVENT(sym, qual)
     return ReadRecords(read_tid, read_pos, read_flag, read_mapq, read_cb, seg_read, seg_start, seg_len, seg_ev_off, events)
