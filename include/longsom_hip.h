@@ -344,9 +344,10 @@ int lsg_export_calls(lsg_ctx* ctx, int32_t kind, void* dst_device, int64_t capac
  *   LSG_TABLE_MERGED      BaseCellCounts.AllCellTypes.tsv rows  MergeBaseCellCounts.py:59-84,116-204 (outer join, "NA" for an absent cell type)
  *   LSG_TABLE_STEP1       calling.step1.tsv rows                BaseCellCalling.step1.py:430-476 (one row per merged site)
  *   LSG_TABLE_STEP1_KEPT  the rows of that table step 2's awk filter keeps (ALT != "." and FILTER != ".", BaseCellCalling.step2.py:23)
- *   LSG_TABLE_STEP2       calling.step2.tsv rows when step 2 has no gnomAD source and --min_distance 0 (LongSom's setting): the kept rows,
+ *   LSG_TABLE_STEP2       calling.step2.tsv rows at --min_distance 0 (LongSom's setting): the kept rows,
  *                         FILTER tagged "RNA_editing_db" / "PoN_SR" / "PoN_LR" by the resident position sets (lsg_load_posset; GetExtraFilters,
- *                         BaseCellCalling.step2.py:142-158; a tag replaces a bare "PASS"), "NA" cells empty (step2.py's pandas round trip)
+ *                         BaseCellCalling.step2.py:142-158; a tag replaces a bare "PASS") and then "gnomAD" by the resident allele set
+ *                         (lsg_load_alleleset; none loaded: step 2 without a gnomAD source), "NA" cells empty (step2.py's pandas round trip)
  *   LSG_TABLE_STEP3_ROWS  the rows of LSG_TABLE_STEP2 step 3 can keep (made by lsg_step2_summary, not by lsg_format_table)
  *   LSG_TABLE_CELL_LONG   <id>.SingleCellGenotype.tsv rows      CellClustering/SingleCellGenotype.py:181-224,305 (see lsg_cellgeno_count below)
  *   LSG_TABLE_CELL_DP / _ALT / _VAF / _BIN   the rows of <id>.DpMatrix.tsv, AltMatrix, VAFMatrix, BinaryMatrix (SingleCellGenotype.py:351-379)
@@ -429,6 +430,25 @@ int lsg_bam_fastq(lsg_ctx* ctx, const uint8_t* file_bytes, int64_t n_bytes, int6
 int lsg_load_posset(lsg_ctx* ctx, int32_t kind, const int64_t* keys, int64_t n, int32_t on_device);
 /* Membership of n query keys in set `kind` (GetExtraFilters, step2.py:142-158). hits[i] = 0/1. */
 int lsg_probe_posset(lsg_ctx* ctx, int32_t kind, const int64_t* keys, int64_t n, uint8_t* hits, int32_t on_device);
+
+/* Allele set (step 2's gnomAD filter, BaseCellCalling.step2.py:98-114,223-235): the single-base alleles whose population AF is at or
+ * above --gnomAD_max, as sorted unique keys
+ *     (tid << 48) | (pos1 << 16) | (REF byte << 8) | ALT byte
+ * resident in HBM.  pos1 is the 1-based position the tables print, REF and ALT the bytes they print: two keys are equal exactly when the
+ * strings the reference looks up are.  Limits: tid < LSG_ALLELE_MAX_TID and pos1 < 2^32 (a run beyond them keeps step 2 on the host).
+ * While a set is loaded, LSG_TABLE_STEP2 probes every row whose ALT field is exactly one base (one cell type with candidates, carrying
+ * one alternative; "A|C" and "A,A" match nothing in the reference's lookup either) and appends "gnomAD" to the FILTER of a hit, after
+ * the position sets' tags (it replaces a bare "PASS").  n = 0 is a valid set (a source is present, nothing hits); n < 0 unloads the
+ * set, after which the table is what it is without a gnomAD source. */
+#define LSG_ALLELE_MAX_TID 32768
+int lsg_load_alleleset(lsg_ctx* ctx, const int64_t* keys, int64_t n, int32_t on_device);
+/* Membership of n query keys in the loaded allele set (an error when none is loaded). hits[i] = 0/1. */
+int lsg_probe_alleleset(lsg_ctx* ctx, const int64_t* keys, int64_t n, uint8_t* hits, int32_t on_device);
+/* The allele keys of the rows step 2 keeps (those of LSG_TABLE_STEP1_KEPT) whose ALT is one base, in the table's row order, into
+ * keys_out (host memory, `capacity` keys; NULL to only count): what a gnomAD source has to be asked about for this run.  *n = their
+ * number.  Needs lsg_call_step1 and lsg_set_table_names (the row order is the contigs' string order); fails when a contig index or a
+ * position is beyond the key's limits. */
+int lsg_step2_allele_queries(lsg_ctx* ctx, int64_t* keys_out, int64_t capacity, int64_t* n);
 
 /* ---- per-cell genotyping at target sites ---------------------------------
  * HCCVSingleCellGenotype.py:82-220 (twin: SNVCalling/SingleCellGenotype.py:84-228): for every target

@@ -74,14 +74,188 @@ class GnomadSqlite:
     def __bool__(self):
         return True
 
+    def get_many(self, chrom: str, alleles) -> list:
+        """.get()'s answers (None where it would give its default) for alleles [(pos, ref, alt)] of one contig, a SELECT per 500
+        positions instead of one per allele.  An allele the database holds more than one row of is asked again through .get(): which of
+        the rows fetchone() sees first is the database's business."""
+        c = chrom[3:] if chrom.startswith("chr") else chrom
+        found: Dict[tuple, list] = {}
+        pos = sorted({int(a[0]) for a in alleles})
+        for i in range(0, len(pos), 500):
+            part = pos[i:i + 500]
+            for p, r, a, af in self._db.execute("SELECT pos, ref, alt, AF FROM gnomad_db WHERE chrom = ? AND pos IN (%s)" % ",".join("?" * len(part)), [c] + part):
+                found.setdefault((p, r, a), []).append(af)
+        out = []
+        for p, r, a in alleles:
+            rows = found.get((int(p), r, a))
+            if rows is not None and len(rows) > 1:
+                out.append(self.get("%s:%d:%s:%s" % (chrom, p, r, a), None))
+            else:
+                out.append(None if rows is None or rows[0] is None else float(rows[0]))
+        return out
+
+    def single_base_alleles(self, af_floor: float):
+        """(chrom as stored, pos, ref, alt, AF) of every row with one-base REF and ALT and a number AF >= af_floor, in the table's order"""
+        for chrom, pos, ref, alt, af in self._db.execute("SELECT chrom, pos, ref, alt, AF FROM gnomad_db WHERE length(ref) = 1 AND length(alt) = 1 AND AF >= ?", (float(af_floor),)):
+            if af_hits(None if af is None else float(af), af_floor):
+                yield str(chrom), int(pos), ref, alt, float(af)
+
 
 class GnomadUnusable(RuntimeError):
     """a gnomAD source was named but cannot be read (the reference stops in gnomAD_DB() then, BaseCellCalling.step2.py:100)"""
 
 
+def af_hits(af, gnomad_max: float) -> bool:
+    """step 2's gnomAD rule (step2.py:223-235): AF is a number (a missing, None or NaN AF counts as 0) at or above --gnomAD_max"""
+    return isinstance(af, (int, float)) and af == af and af >= gnomad_max
+
+
+# ---- the gnomAD filter's alleles as 64-bit keys (csrc/tables.hip probes them while it prints the step-2 table) -----------------
+ALLELE_MAX_TID = 1 << 15
+ALLELE_MAX_POS = 1 << 32
+
+
+def allele_keys_fit(contig_lens: Sequence[int]) -> bool:
+    """a run's contigs within the key's limits (15 bits of contig index, positions below 2^32)"""
+    return len(contig_lens) <= ALLELE_MAX_TID and all(int(n) < ALLELE_MAX_POS for n in contig_lens)
+
+
+def keyed_by_alleles(source) -> bool:
+    """No key of a JSON table names an ALT string such as "A|C" or "A,A": the reference looks a row's whole ALT up (step2.py:98-114), no
+    database holds such an allele, but a hand-made table that does tags rows the allele set cannot express."""
+    return not isinstance(source, dict) or not any("|" in k or "," in k for k in source)
+
+
+def pack_allele_keys(tid, pos, ref, alt) -> np.ndarray:
+    """(contig index, 1-based position, REF byte, ALT byte) -> int64 keys tid << 48 | pos << 16 | ref << 8 | alt (lsg_load_alleleset):
+    equal keys = equal (chrom, pos, ref, alt) strings of a one-base allele.  ref / alt: byte values, or a bytes / str of one base each."""
+    def bytes_of(x):
+        if isinstance(x, str):
+            x = x.encode()
+        return np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x)
+    tid, pos, ref, alt = (np.asarray(v).astype(np.int64).reshape(-1) for v in (tid, pos, bytes_of(ref), bytes_of(alt)))
+    if not len(tid) == len(pos) == len(ref) == len(alt):
+        raise ValueError("pack_allele_keys: %d contigs, %d positions, %d REF and %d ALT bytes" % (len(tid), len(pos), len(ref), len(alt)))
+    for name, v, lim in (("contig index", tid, ALLELE_MAX_TID), ("position", pos, ALLELE_MAX_POS), ("REF byte", ref, 256), ("ALT byte", alt, 256)):
+        if len(v) and (v.min() < 0 or v.max() >= lim):
+            raise ValueError("pack_allele_keys: %s outside [0, %d)" % (name, lim))
+    return (tid << 48) | (pos << 16) | (ref << 8) | alt
+
+
+def unpack_allele_keys(keys):
+    """int64 keys -> (contig index, 1-based position, REF byte, ALT byte), the last two as uint8"""
+    k = np.asarray(keys, np.int64).reshape(-1)
+    return k >> 48, (k >> 16) & 0xFFFFFFFF, ((k >> 8) & 0xFF).astype(np.uint8), (k & 0xFF).astype(np.uint8)
+
+
+class GnomadSet:
+    """A prepared set (write_gnomad_set; `cli gnomad_set`): every one-base allele of a gnomAD source whose AF is at or above a floor F, so
+    that a run needs neither queries nor the database.  Holds the source's chrom strings as they were: hit_keys maps them to a run's
+    contigs by the source's own rule (a gnomad_db sqlite stores chroms without "chr": GnomadSqlite.get; a JSON table is keyed by the
+    run's names).  Answers only thresholds >= F: below it the set lacks alleles the filter would tag."""
+
+    def __init__(self, path: str):
+        with np.load(path, allow_pickle=False) as z:
+            self.chrom, self.pos, self.ref, self.alt, self.af = z["chrom"].astype(str), z["pos"].astype(np.int64), z["ref"].astype(np.uint8), z["alt"].astype(np.uint8), z["af"].astype(np.float64)
+            self.af_floor, self.strip_chr = float(z["af_floor"]), bool(z["strip_chr"])
+        if not len(self.chrom) == len(self.pos) == len(self.ref) == len(self.alt) == len(self.af):
+            raise ValueError("%s: columns of different lengths" % path)
+        self.path, self._af_of = path, None
+
+    def __bool__(self):
+        return True
+
+    def require(self, gnomad_max: float) -> None:
+        if not gnomad_max >= self.af_floor:
+            raise GnomadUnusable("gnomAD set %r holds the alleles with AF >= %r: it cannot answer --gnomAD_max %r; prepare one with --af_floor <= %r"
+                                 % (self.path, self.af_floor, gnomad_max, gnomad_max))
+
+    def _name(self, chrom: str) -> str:
+        return chrom[3:] if self.strip_chr and chrom.startswith("chr") else chrom
+
+    def get(self, key: str, default: float = 0.0) -> float:
+        """the source's .get() for every threshold the set answers (an allele it does not hold is below the floor, or absent)"""
+        if self._af_of is None:
+            self._af_of = {}
+            for c, p, r, a, f in zip(self.chrom.tolist(), self.pos.tolist(), self.ref.tobytes().decode("latin-1"), self.alt.tobytes().decode("latin-1"), self.af.tolist()):
+                self._af_of.setdefault((c, p, r, a), f)
+        chrom, pos, ref, alt = key.split(":", 3)
+        return self._af_of.get((self._name(chrom), int(pos), ref, alt), default)
+
+    def hit_keys(self, contig_names: Sequence[str], gnomad_max: float) -> np.ndarray:
+        """sorted unique allele keys of the set's alleles with AF >= gnomad_max on the run's contigs"""
+        self.require(gnomad_max)
+        sel = np.nonzero((self.af >= gnomad_max) & (self.pos >= 0) & (self.pos < ALLELE_MAX_POS))[0]
+        order = sel[np.argsort(self.chrom[sel], kind="stable")]
+        names, first = np.unique(self.chrom[order], return_index=True)
+        last = np.append(first[1:], len(order))
+        group = {n: order[a:b] for n, a, b in zip(names.tolist(), first.tolist(), last.tolist())}
+        out = []
+        for tid, name in enumerate(contig_names):
+            rows = group.get(self._name(name))
+            if rows is not None:
+                out.append(pack_allele_keys(np.full(len(rows), tid), self.pos[rows], self.ref[rows], self.alt[rows]))
+        return np.unique(np.concatenate(out)) if out else np.zeros(0, np.int64)
+
+
+def write_gnomad_set(source, out_path: str, af_floor: float) -> int:
+    """Scans a gnomAD source (open_gnomad's: a JSON table or a GnomadSqlite) once and writes its one-base alleles with AF >= af_floor as a
+    prepared set; returns their number.  The first row of an allele counts, as for .get()."""
+    if isinstance(source, GnomadSet):
+        raise ValueError("a prepared set is no source to prepare one from")
+    strip = isinstance(source, GnomadSqlite)
+    if strip:
+        rows = source.single_base_alleles(af_floor)
+    else:
+        def json_rows():
+            for key, af in source.items():
+                el = key.split(":")
+                if len(el) == 4 and af_hits(af, af_floor):
+                    if el[1].isdigit() and str(int(el[1])) == el[1]:      # (the table prints a position one way only)
+                        yield el[0], int(el[1]), el[2], el[3], float(af)
+        rows = json_rows()
+    seen, cols = set(), ([], [], [], [], [])
+    for chrom, pos, ref, alt, af in rows:
+        if not (isinstance(ref, str) and isinstance(alt, str) and len(ref.encode()) == 1 and len(alt.encode()) == 1) or (chrom, pos, ref, alt) in seen:
+            continue
+        seen.add((chrom, pos, ref, alt))
+        for c, v in zip(cols, (chrom, pos, ord(ref), ord(alt), af)):
+            c.append(v)
+    with open(out_path, "wb") as f:
+        np.savez(f, chrom=np.asarray(cols[0], dtype=str), pos=np.asarray(cols[1], np.int64), ref=np.asarray(cols[2], np.uint8), alt=np.asarray(cols[3], np.uint8),
+                 af=np.asarray(cols[4], np.float64), af_floor=np.float64(af_floor), strip_chr=np.bool_(strip))
+    return len(cols[0])
+
+
+def gnomad_hit_keys(source, contig_names: Sequence[str], queries, gnomad_max: float) -> np.ndarray:
+    """The allele keys among `queries` (pack_allele_keys over the run's contigs; Engine.step2_allele_queries) that step 2 tags "gnomAD":
+    those whose AF in `source` (whatever open_gnomad returned) is a number >= gnomad_max, sorted and unique - the set to load for the
+    step-2 table (Engine.load_alleleset).  A JSON table is asked "chrom:pos:ref:alt" per allele, a gnomad_db sqlite per contig
+    (GnomadSqlite.get_many: .get()'s answers), a prepared set not at all."""
+    q = np.unique(np.asarray(queries, np.int64))
+    if not source or not len(q):
+        return np.zeros(0, np.int64)
+    if isinstance(source, GnomadSet):
+        return np.intersect1d(q, source.hit_keys(contig_names, gnomad_max), assume_unique=True)
+    tid, pos, ref, alt = unpack_allele_keys(q)
+    ref_s, alt_s = ref.tobytes().decode("latin-1"), alt.tobytes().decode("latin-1")
+    hit = np.zeros(len(q), bool)
+    if isinstance(source, GnomadSqlite):
+        lo = 0
+        while lo < len(q):                                # (q is sorted: a contig's alleles are adjacent)
+            hi = int(np.searchsorted(tid, tid[lo], side="right"))
+            afs = source.get_many(contig_names[int(tid[lo])], list(zip(pos[lo:hi].tolist(), ref_s[lo:hi], alt_s[lo:hi])))
+            hit[lo:hi] = [af_hits(af, gnomad_max) for af in afs]
+            lo = hi
+    else:
+        for i, (t, p) in enumerate(zip(tid.tolist(), pos.tolist())):
+            hit[i] = af_hits(source.get("%s:%d:%s:%s" % (contig_names[t], p, ref_s[i], alt_s[i]), 0.0), gnomad_max)
+    return q[hit]
+
+
 def open_gnomad(source: Optional[str], allow_missing: Optional[bool] = None):
-    """--gnomAD_db / --gnomAD_json of the shims: a JSON {"chrom:pos:ref:alt": AF}, a gnomad_db directory or sqlite file, or
-    nothing.  A source that is named but cannot be used STOPS the run, as the reference's gnomAD_DB() does — running step 2 without
+    """--gnomAD_db / --gnomAD_json / --gnomAD_set of the shims: a JSON {"chrom:pos:ref:alt": AF}, a gnomad_db directory or sqlite file, a
+    prepared set (.npz: GnomadSet), or nothing.  A source that is named but cannot be used STOPS the run, as the reference's gnomAD_DB() does — running step 2 without
     its germline filter is a different call set, not a degraded one.  allow_missing=True (--allow_missing_gnomad,
     Run.allow_missing_gnomad, LONGSOM_ALLOW_MISSING_GNOMAD=1): warn on stderr and run with the filter off."""
     import json
@@ -92,6 +266,8 @@ def open_gnomad(source: Optional[str], allow_missing: Optional[bool] = None):
     try:
         if str(source).endswith(".json"):
             return json.load(open(source))
+        if str(source).endswith(".npz"):
+            return GnomadSet(source)
         return GnomadSqlite(source)
     except Exception as e:                                      # noqa: BLE001 - every failure ends the same way
         if allow_missing is None:
@@ -178,7 +354,7 @@ def step2_bytes(step1_text: bytes, engine, contig_names: Sequence[str], editing_
                 gnomad_af: Optional[Dict[str, float]] = None, gnomad_max: float = 0.01) -> bytes:
     """step2 on the bytes of the table (what the fused pipeline and the CLI hold): the scanned path when there is no gnomAD source
     (LONGSOM_STEP2_ROW_PATH=1 forces the row-by-row one), else step2() below."""
-    have_af = isinstance(gnomad_af, GnomadSqlite) or bool(gnomad_af)
+    have_af = bool(gnomad_af)                           # (a GnomadSqlite and a GnomadSet are true whatever they hold)
     if not have_af and os.environ.get("LONGSOM_STEP2_ROW_PATH", "0") != "1":
         out = _step2_scanned(step1_text, engine, contig_names, editing_keys, pon_sr_keys, pon_lr_keys, distance)
         if out is not None:
@@ -199,6 +375,8 @@ def step2(step1_text: str, engine, contig_names: Sequence[str], editing_keys, po
     database itself is not part of this repository — absent entries count as AF 0."""
     if gnomad_af is None:
         gnomad_af = {}
+    if isinstance(gnomad_af, GnomadSet):
+        gnomad_af.require(gnomad_max)
     comments, header, rows, kept = [], None, [], []
     for line in step1_text.split("\n"):
         if line.startswith("#"):
@@ -230,7 +408,7 @@ def step2(step1_text: str, engine, contig_names: Sequence[str], editing_keys, po
                 if rows[j][0] == chrom and pos[j] != p and abs(pos[j] - p) <= distance:
                     c += 1
             close[i] = c
-    have_af = isinstance(gnomad_af, GnomadSqlite) or bool(gnomad_af)
+    have_af = bool(gnomad_af)                           # (a GnomadSqlite and a GnomadSet are true whatever they hold)
     h_ed, h_sr, h_lr = hits
     # a row that gets no tag leaves as it came; the tagged ones (a handful among the hundreds of thousands of candidate rows of a real
     # sample; every row when a gnomAD source is given) get their FILTER rebuilt
@@ -249,8 +427,7 @@ def step2(step1_text: str, engine, contig_names: Sequence[str], editing_keys, po
         if h_sr[i]: tags.append("PoN_SR")
         if h_lr[i]: tags.append("PoN_LR")
         if have_af:
-            af = gnomad_af.get("%s:%s:%s:%s" % (el[0], el[1], el[3], el[4]), 0.0)
-            if af == af and af >= gnomad_max:
+            if af_hits(gnomad_af.get("%s:%s:%s:%s" % (el[0], el[1], el[3], el[4]), 0.0), gnomad_max):
                 tags.append("gnomAD")
         if not tags:
             continue

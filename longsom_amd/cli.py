@@ -656,6 +656,26 @@ def _apply_gnomad_flag(a):
         os.environ["LONGSOM_ALLOW_MISSING_GNOMAD"] = "1"
 
 
+def _gnomad_source(a):
+    """the gnomAD source of a fused run: a prepared set (--gnomAD_set, `gnomad_set` below: no database is opened) before --gnomAD_json before
+    --gnomAD_db"""
+    return a.gnomAD_set or a.gnomAD_json or a.gnomAD_db or None
+
+
+def gnomad_set(argv=None):
+    """--gnomAD_db SRC --out FILE.npz --af_floor F: scans a gnomAD source (a gnomad_db directory / sqlite file or a JSON table) once and
+    writes its one-base alleles with AF >= F as a prepared set (calling.GnomadSet) for --gnomAD_set; a run may then ask for any
+    --max_gnomad_vaf >= F."""
+    ap = argparse.ArgumentParser(description="Prepare the allele set of step 2's gnomAD filter from a gnomAD source")
+    ap.add_argument("--gnomAD_db", required=True); ap.add_argument("--out", required=True); ap.add_argument("--af_floor", type=float, default=0.01)
+    a = ap.parse_args(argv)
+    if not a.out.endswith(".npz"):
+        ap.error("--out must end in .npz (what --gnomAD_set recognises a prepared set by)")
+    t0 = time.time()
+    n = calling.write_gnomad_set(calling.open_gnomad(a.gnomAD_db, False), a.out, a.af_floor)
+    print(json.dumps({"out": a.out, "alleles": n, "af_floor": a.af_floor, "seconds": time.time() - t0}))
+
+
 def _add_htslib_flag(ap):
     ap.add_argument("--htslib_legacy_del_merge", action="store_true",
                     help="count the first column of a deletion that is followed by another deletion (CIGAR 1D2D) as 'D', as pysam over htslib <= 1.10 "
@@ -687,7 +707,7 @@ def snv(argv=None):
     ap = argparse.ArgumentParser(description="SplitBam -> BaseCellCounter -> MergeCounts -> BaseCellCalling step1-3 on one GPU")
     ap.add_argument("--bam", required=True); ap.add_argument("--meta", required=True); ap.add_argument("--ref", required=True)
     ap.add_argument("--id", required=True); ap.add_argument("--outdir", required=True)
-    _optional_paths(ap, "--editing", "--pon_SR", "--pon_LR", "--gnomAD_json", "--gnomAD_db")
+    _optional_paths(ap, "--editing", "--pon_SR", "--pon_LR", "--gnomAD_json", "--gnomAD_db", "--gnomAD_set")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--window_gb", type=float, default=0.0, help="stream the BAM in batches of about this many GiB of uncompressed BAM and count "
                     "window by window (for a BAM whose reads do not fit in HBM); 0 = the whole BAM at once")
@@ -706,7 +726,7 @@ def snv(argv=None):
     comm = regions.Comm.from_env()
     try:
         out = pipeline.run_snv(a.bam, a.meta, a.ref, a.outdir, a.id, params, a.editing or None, a.pon_SR or None, a.pon_LR or None,
-                               a.gnomAD_json or a.gnomAD_db or None, a.device, comm=comm, window_bytes=int(a.window_gb * (1 << 30)) or None,
+                               _gnomad_source(a), a.device, comm=comm, window_bytes=int(a.window_gb * (1 << 30)) or None,
                                filters=pipeline.SplitFilters(a.max_nM, a.max_NH, a.n_trim))
         if comm.rank == 0:
             print(json.dumps({"outputs": {k: v for k, v in vars(out).items() if k not in ("timings", "resident", "_pending")}, "seconds": out.timings, "ranks": comm.world}))
@@ -720,7 +740,7 @@ def reannotation(argv=None):
     ap = argparse.ArgumentParser(description="CellTypeReannotation + SNVCalling of LongSom on one GPU, reads resident across both passes")
     ap.add_argument("--bam", required=True); ap.add_argument("--meta", required=True); ap.add_argument("--ref", required=True)
     ap.add_argument("--id", required=True); ap.add_argument("--outdir", required=True)
-    _optional_paths(ap, "--fusions", "--editing", "--pon_SR", "--pon_LR", "--gnomAD_json", "--gnomAD_db")
+    _optional_paths(ap, "--fusions", "--editing", "--pon_SR", "--pon_LR", "--gnomAD_json", "--gnomAD_db", "--gnomAD_set")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--pass1_step3", action="store_true", help="also write pass 1's calling.step3.tsv (the reference's pass 1 stops at step 2)")
     # config['Reanno'] (pass 1: --reanno_* for the HCCV / re-annotation block, --p1_* for its BaseCellCounter / BaseCellCalling
@@ -738,7 +758,7 @@ def reannotation(argv=None):
     comm = regions.Comm.from_env()
     try:
         out = pipeline.run_reannotation(a.bam, a.meta, a.ref, a.outdir, a.id, rp, sp, fusions_tsv=a.fusions or None, editing=a.editing or None,
-                                        pon_sr=a.pon_SR or None, pon_lr=a.pon_LR or None, gnomad_af_json=a.gnomAD_json or a.gnomAD_db or None, device=a.device,
+                                        pon_sr=a.pon_SR or None, pon_lr=a.pon_LR or None, gnomad_af_json=_gnomad_source(a), device=a.device,
                                         pass1_step3=a.pass1_step3, comm=comm)
         if comm.rank == 0:
             print(json.dumps({"hccv": out.hccv, "genotype": out.genotype, "barcodes": out.barcodes, "cells_kept": out.n_cells_kept, "cancer_cells": out.n_cancer,
@@ -818,3 +838,16 @@ def pon_chain(argv=None):
             print(json.dumps({"pon": out.pon, "sites": out.n_sites, "seconds": out.timings, "ranks": comm.world, **fitted}))
     finally:
         comm.close()
+
+
+def main(argv=None):
+    """python -m longsom_amd.cli <entry point> [flags]: the entry points above by name"""
+    argv = sys.argv[1:] if argv is None else list(argv)
+    names = sorted(n for n, f in globals().items() if callable(f) and not n.startswith("_") and getattr(f, "__module__", None) == __name__ and n != "main")
+    if not argv or argv[0] not in names:
+        sys.exit("usage: python -m longsom_amd.cli {%s} [flags]" % ",".join(names))
+    globals()[argv[0]](argv[1:])
+
+
+if __name__ == "__main__":
+    main()

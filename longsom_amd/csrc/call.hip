@@ -902,8 +902,7 @@ int run_fetch_calls(lsg_ctx* c, lsg_call* out, int64_t capacity, int candidates_
     return 0;
 }
 
-int run_probe(lsg_ctx* c, int kind, const int64_t* keys, int64_t n, uint8_t* hits, int on_device) {
-    PosSet& s = c->posset[kind];
+int run_probe(lsg_ctx* c, const PosSet& s, const char* who, const int64_t* keys, int64_t n, uint8_t* hits, int on_device) {
     hipStream_t st = c->stream;
     if (n == 0) return 0;
     DevBuf dk, dh;
@@ -919,7 +918,7 @@ int run_probe(lsg_ctx* c, int kind, const int64_t* keys, int64_t n, uint8_t* hit
         if (!on_device && hipMemcpyAsync(hits, dh.p, (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -1;
         if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
     }
-    if (rc) set_error("lsg_probe_posset: %s", hipGetErrorString(hipGetLastError()));
+    if (rc) set_error("%s: %s", who, hipGetErrorString(hipGetLastError()));
     dk.release(); dh.release();
     return rc;
 }

@@ -15,7 +15,8 @@ int run_fetch_counts(lsg_ctx* c, int ct, int64_t* keys, uint8_t* ref, uint32_t* 
 int run_call(lsg_ctx* c, const lsg_call_params* p);
 int run_fetch_calls(lsg_ctx* c, lsg_call* out, int64_t capacity, int candidates_only, int64_t* n_out);
 int run_select_calls(lsg_ctx* c, int kind, lsg_call* dst_device, int64_t capacity, int64_t* n_out);
-int run_probe(lsg_ctx* c, int kind, const int64_t* keys, int64_t n, uint8_t* hits, int on_device);
+int run_probe(lsg_ctx* c, const PosSet& s, const char* who, const int64_t* keys, int64_t n, uint8_t* hits, int on_device);
+int run_step2_allele_queries(lsg_ctx* c, int64_t* keys_out, int64_t capacity, int64_t* n_out);
 int run_set_table_names(lsg_ctx* c, int32_t n_contigs, const char* contig_names, int32_t n_ct, const char* ct_names);
 int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes);
 int run_copy_table(lsg_ctx* c, int32_t table, char* dst, int64_t capacity);
@@ -111,6 +112,7 @@ void lsg_destroy(lsg_ctx* c) {
     for (auto& b : c->d_rows) b.release();
     for (auto& b : c->ref) b.release();
     for (auto& s : c->posset) s.keys.release();
+    c->alleleset.keys.release();
     for (auto& b : c->syn) b.release();
     for (auto& b : c->gen) b.release();
     (void)run_free_table(c, -1);
@@ -519,7 +521,35 @@ int lsg_load_posset(lsg_ctx* c, int32_t kind, const int64_t* keys, int64_t n, in
 int lsg_probe_posset(lsg_ctx* c, int32_t kind, const int64_t* keys, int64_t n, uint8_t* hits, int32_t on_device) {
     if (!c || kind < 0 || kind >= 3 || n < 0 || (n > 0 && (!keys || !hits))) { set_error("lsg_probe_posset: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
-    return run_probe(c, kind, keys, n, hits, on_device);
+    return run_probe(c, c->posset[kind], "lsg_probe_posset", keys, n, hits, on_device);
+}
+
+int lsg_load_alleleset(lsg_ctx* c, const int64_t* keys, int64_t n, int32_t on_device) {
+    if (!c || (n > 0 && !keys)) { set_error("lsg_load_alleleset: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    PosSet& s = c->alleleset;
+    s.n = 0; c->alleleset_loaded = false;
+    if (n < 0) return 0;
+    if (n > 0) {
+        if (s.keys.reserve((size_t)n * 8)) return -1;
+        LSG_HIP(hipMemcpyAsync(s.keys.p, keys, (size_t)n * 8, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        LSG_HIP(hipStreamSynchronize(c->stream));
+    }
+    s.n = n; c->alleleset_loaded = true;
+    return 0;
+}
+
+int lsg_probe_alleleset(lsg_ctx* c, const int64_t* keys, int64_t n, uint8_t* hits, int32_t on_device) {
+    if (!c || n < 0 || (n > 0 && (!keys || !hits))) { set_error("lsg_probe_alleleset: bad arguments"); return -2; }
+    if (!c->alleleset_loaded) { set_error("lsg_probe_alleleset: no allele set loaded (lsg_load_alleleset)"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_probe(c, c->alleleset, "lsg_probe_alleleset", keys, n, hits, on_device);
+}
+
+int lsg_step2_allele_queries(lsg_ctx* c, int64_t* keys_out, int64_t capacity, int64_t* n) {
+    if (!c || !n || capacity < 0 || (capacity > 0 && !keys_out)) { set_error("lsg_step2_allele_queries: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_step2_allele_queries(c, keys_out, capacity, n);
 }
 
 int lsg_genotype_cells(lsg_ctx* c, const lsg_genotype_params* params, int64_t n_sites, const int64_t* site_keys,

@@ -288,6 +288,7 @@ struct lsg_ctx {
     lsg::Bbfit bb;                        // bbfit.hip: the beta-binomial fit's histograms
 
     lsg::PosSet posset[3];
+    lsg::PosSet alleleset; bool alleleset_loaded = false;      // lsg_load_alleleset: step 2's gnomAD alleles (loaded with n = 0: a source that hits nothing)
     lsg::DevBuf syn[12];                  // synthetic-model tables + scan scratch (synth.hip)
     lsg::DevBuf gen[10];                  // the arrays lsg_synth_generate last produced
     lsg::DevBuf ws[16];                   // count-stage workspace (pileup.hip, enum WS_*)

@@ -45,6 +45,7 @@ struct FmtArgs {
     const char* ct_txt; const uint32_t* ct_off;
     uint32_t* len; const uint64_t* off; const int64_t* shift; char* text;
     const int64_t* posset[3]; int64_t n_posset[3];    // K_STEP2: the resident position sets (RNA editing, PoN_SR, PoN_LR)
+    const int64_t* alleles; int64_t n_alleles;        // K_STEP2: the resident allele set of the gnomAD filter (n_alleles < 0: none loaded)
 };
 enum { K_COUNTS = 0, K_MERGED, K_STEP1, K_KEPT, K_STEP2 };
 
@@ -113,11 +114,24 @@ template <class S> __device__ void merged_row(S& s, const FmtArgs& a, int64_t i)
     s.ch('\n');
 }
 
-__device__ __forceinline__ bool in_posset(const FmtArgs& a, int kind, int64_t key) {
-    const int64_t* k = a.posset[kind];
-    int64_t lo = 0, hi = a.n_posset[kind];
+__device__ __forceinline__ bool in_set(const int64_t* k, int64_t n, int64_t key) {
+    int64_t lo = 0, hi = n;
     while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (k[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo < a.n_posset[kind] && k[lo] == key;
+    return lo < n && k[lo] == key;
+}
+__device__ __forceinline__ bool in_posset(const FmtArgs& a, int kind, int64_t key) { return in_set(a.posset[kind], a.n_posset[kind], key); }
+
+// The allele key (lsg_load_alleleset) of a candidate site whose ALT field prints as exactly one base - one cell type with candidates,
+// carrying one alternative -, else -1.  That string is what step 2 looks up in gnomAD (BaseCellCalling.step2.py:98-114): "A|C" and "A,A"
+// are no allele of the database.
+__device__ __forceinline__ int64_t allele_key_of(const SiteRec& c, const CandCt* cands, int n_ct) {
+    int only = -1, n_with = 0;
+    for (int ct = 0; ct < n_ct; ++ct) if ((c.has_cand >> ct) & 1) { only = ct; ++n_with; }
+    if (n_with != 1) return -1;
+    const CandCt& d = cands[(uint64_t)c.cand * n_ct + only];
+    if (d.n_alt != 1) return -1;
+    const int64_t tid = c.key >> 32, pos1 = (c.key & 0xFFFFFFFFll) + 1;
+    return (tid << 48) | (pos1 << 16) | ((int64_t)c.ref << 8) | (int64_t)(uint8_t)"ACTG"[d.alt[0] & 3];
 }
 
 // one row of the step-1 table (tsvwrite.cpp lsio_write_step1_rows, from the compact records instead of their lsg_call expansion).
@@ -191,6 +205,13 @@ template <bool STEP2, class S> __device__ void step1_row(S& s, const FmtArgs& a,
                 if (bare_pass) bare_pass = false; else s.ch(',');
                 if (q == 0) LIT(s, "RNA_editing_db"); else if (q == 1) LIT(s, "PoN_SR"); else LIT(s, "PoN_LR");
             }
+            if (a.n_alleles > 0) {                     // gnomAD (step2.py:223-235): after the position sets' tags
+                const int64_t ak = allele_key_of(c, a.cands, a.n_ct);
+                if (ak >= 0 && in_set(a.alleles, a.n_alleles, ak)) {
+                    if (bare_pass) bare_pass = false; else s.ch(',');
+                    LIT(s, "gnomAD");
+                }
+            }
         }
         if (bare_pass) LIT(s, "PASS");
         s.ch('\t');
@@ -250,6 +271,18 @@ __global__ __launch_bounds__(256) void k_row_put(FmtArgs a) {
     if (i >= a.n) return;
     PutSink s{a.text + (int64_t)a.off[i] + a.shift[(int)(key_at(a, i) >> 32)]};
     any_row(s, a, i);
+}
+// the allele queries of the rows step 2 keeps (lsg_step2_allele_queries): a "row" of length 1 per candidate site with a one-base ALT,
+// placed like the tables' rows
+__global__ __launch_bounds__(256) void k_query_len(FmtArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > a.n) return;
+    a.len[i] = (i < a.n && (a.sites[i].site_filter & (uint32_t)LSG_SF_CANDIDATE) && allele_key_of(a.sites[i], a.cands, a.n_ct) >= 0) ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void k_query_put(FmtArgs a, int64_t* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n || a.len[i] == 0) return;
+    out[(int64_t)a.off[i] + a.shift[(int)(a.sites[i].key >> 32)]] = allele_key_of(a.sites[i], a.cands, a.n_ct);
 }
 // lo[t] = first row of contig t (t = n_contigs: the row count); then, contig after contig in output order, shift[t] = where the contig's
 // text starts in the output minus where it starts in genomic order
@@ -474,6 +507,14 @@ int run_set_table_names(lsg_ctx* c, int32_t n_contigs, const char* contig_names,
     return 0;
 }
 
+// the limits of the allele key: 15 bits of contig index, 32 of 1-based position
+static int allele_limits(lsg_ctx* c, const char* who) {
+    if (c->n_contigs > LSG_ALLELE_MAX_TID) { set_error("%s: %d contigs, an allele key holds %d", who, c->n_contigs, LSG_ALLELE_MAX_TID); return -2; }
+    for (int t = 0; t < c->n_contigs; ++t)
+        if (c->contig_len[(size_t)t] >= (int64_t)1 << 32) { set_error("%s: contig %d is %lld long, an allele key holds positions below 2^32", who, t, (long long)c->contig_len[(size_t)t]); return -2; }
+    return 0;
+}
+
 int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     if (n_bytes) *n_bytes = 0;
     if (table < 0 || table >= LSG_TABLE_SLOTS) { set_error("lsg_format_table: no table %d", table); return -2; }
@@ -496,6 +537,9 @@ int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     FmtArgs a{};
     a.kind = counts ? K_COUNTS : table == LSG_TABLE_MERGED ? K_MERGED : table == LSG_TABLE_STEP1 ? K_STEP1 : table == LSG_TABLE_STEP1_KEPT ? K_KEPT : K_STEP2;
     for (int q = 0; q < 3; ++q) { a.posset[q] = c->posset[q].keys.as<int64_t>(); a.n_posset[q] = c->posset[q].n; }
+    a.alleles = c->alleleset.keys.as<int64_t>(); a.n_alleles = c->alleleset_loaded ? c->alleleset.n : -1;
+    if (a.kind == K_STEP2 && a.n_alleles > 0)
+        if (int rc = allele_limits(c, "lsg_format_table")) return rc;
     a.ct = counts ? table : 0; a.n_ct = c->n_ct; a.n_contigs = c->n_contigs;
     a.n = counts ? c->n_rows[table] : c->n_sites;
     for (int ct = 0; ct < c->n_ct; ++ct) {
@@ -548,6 +592,59 @@ int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     c->tab_scratch_table = table; c->tab_scratch_rows = a.n;      // (the rows' places stay in the scratch: lsg_step2_summary reads the text by them)
     if (n_bytes) *n_bytes = bytes;
     return 0;
+}
+
+// Count, then compact: the keys' places come from the same scan and contig shifts as a table's rows, with every query one unit long
+int run_step2_allele_queries(lsg_ctx* c, int64_t* keys_out, int64_t capacity, int64_t* n_out) {
+    *n_out = 0;
+    if (!c->called) { set_error("lsg_step2_allele_queries: call lsg_call_step1 first"); return -2; }
+    if (c->tab_n_contigs != c->n_contigs) { set_error("lsg_step2_allele_queries: lsg_set_table_names first (the rows' order is the contig names')"); return -2; }
+    if (int rc = allele_limits(c, "lsg_step2_allele_queries")) return rc;
+    const int64_t n = c->n_sites;
+    if (n == 0) return 0;
+    if (n >= (int64_t)1 << 31) { set_error("lsg_step2_allele_queries: %lld sites", (long long)n); return -2; }
+    hipStream_t st = c->stream;
+    FmtArgs a{};
+    a.kind = K_KEPT; a.n_ct = c->n_ct; a.n_contigs = c->n_contigs; a.n = n;
+    a.sites = c->d_calls.as<SiteRec>(); a.cands = c->ws[WS_CALL_CANDS].as<CandCt>();
+    // scratch: len[n + 1] | off[n + 1] | lo[n_contigs + 1] | shift[n_contigs + 1]
+    const size_t at_off = align_up((size_t)(n + 1) * 4, 256), at_lo = at_off + align_up((size_t)(n + 1) * 8, 256),
+                 at_shift = at_lo + align_up((size_t)(c->n_contigs + 1) * 8, 256), total = at_shift + (size_t)(c->n_contigs + 1) * 8;
+    if (c->tab_scratch2.reserve(total)) return -1;
+    char* sc = c->tab_scratch2.as<char>();
+    a.len = reinterpret_cast<uint32_t*>(sc);
+    uint64_t* off = reinterpret_cast<uint64_t*>(sc + at_off);
+    int64_t* lo = reinterpret_cast<int64_t*>(sc + at_lo);
+    int64_t* shift = reinterpret_cast<int64_t*>(sc + at_shift);
+    a.off = off; a.shift = shift;
+    const unsigned blocks = (unsigned)((n + 1 + 255) / 256);
+    hipLaunchKernelGGL(k_query_len, dim3(blocks), dim3(256), 0, st, a);
+    {
+        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> in(a.len, Widen());
+        size_t tb = 0;
+        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, off, (int)(n + 1), st));
+        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
+        tb = c->d_cub_tmp.cap;
+        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, in, off, (int)(n + 1), st));
+    }
+    const int32_t* order = reinterpret_cast<const int32_t*>(c->tab_names.as<char>() + c->tab_order_at);
+    hipLaunchKernelGGL(k_contig_lo, dim3((unsigned)(c->n_contigs / 64 + 1)), dim3(64), 0, st, a, lo);
+    hipLaunchKernelGGL(k_contig_shift, dim3(1), dim3(1), 0, st, lo, off, order, c->n_contigs, shift);
+    LSG_HIP(hipMemcpyAsync(c->h_pin, off + n, 8, hipMemcpyDeviceToHost, st));
+    LSG_HIP(hipStreamSynchronize(st));
+    const int64_t k = (int64_t)c->h_pin[0];
+    *n_out = k;
+    if (!keys_out || k == 0) return 0;
+    if (k > capacity) { set_error("lsg_step2_allele_queries: capacity %lld < %lld keys", (long long)capacity, (long long)k); return -2; }
+    DevBuf dk;
+    if (dk.reserve((size_t)k * 8)) return -1;
+    hipLaunchKernelGGL(k_query_put, dim3(blocks), dim3(256), 0, st, a, dk.as<int64_t>());
+    int rc = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(keys_out, dk.p, (size_t)k * 8, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(st) != hipSuccess) rc = -1;
+    if (rc) set_error("lsg_step2_allele_queries: %s", hipGetErrorString(hipGetLastError()));
+    dk.release();
+    return rc;
 }
 
 // Column kinds of the step-2 text + its surviving rows as table LSG_TABLE_STEP3_ROWS

@@ -543,6 +543,35 @@ class Engine:
         keys = np.ascontiguousarray(keys, dtype=np.int64)
         _lib.check(self._lib.lsg_load_posset(self._h, kind, _ptr(keys), len(keys), 0), "lsg_load_posset")
 
+    def load_alleleset(self, keys, on_device: bool = False, n: Optional[int] = None) -> None:
+        """Step 2's gnomAD alleles (calling.pack_allele_keys, sorted and unique) resident for format_table(TABLE_STEP2); an empty array is
+        a source that hits nothing, keys=None unloads the set (the table is then step 2's without a gnomAD source)."""
+        if keys is None:
+            _lib.check(self._lib.lsg_load_alleleset(self._h, None, -1, 0), "lsg_load_alleleset")
+            return
+        if on_device:
+            _lib.check(self._lib.lsg_load_alleleset(self._h, C.c_void_p(int(keys)), int(n), 1), "lsg_load_alleleset")
+            return
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        _lib.check(self._lib.lsg_load_alleleset(self._h, _ptr(keys), len(keys), 0), "lsg_load_alleleset")
+
+    def probe_alleleset(self, keys) -> np.ndarray:
+        """membership (uint8) of allele keys in the loaded set"""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        hits = np.zeros(len(keys), np.uint8)
+        _lib.check(self._lib.lsg_probe_alleleset(self._h, _ptr(keys), len(keys), _ptr(hits), 0), "lsg_probe_alleleset")
+        return hits
+
+    def step2_allele_queries(self) -> np.ndarray:
+        """After call_step1 and set_table_names: the allele keys of the rows step 2 keeps whose ALT is one base, in TABLE_STEP1_KEPT's row
+        order (counted, then compacted, on the device)."""
+        n = C.c_int64(0)
+        _lib.check(self._lib.lsg_step2_allele_queries(self._h, None, 0, C.byref(n)), "lsg_step2_allele_queries")
+        keys = np.zeros(int(n.value), np.int64)
+        if len(keys):
+            _lib.check(self._lib.lsg_step2_allele_queries(self._h, _ptr(keys), len(keys), C.byref(n)), "lsg_step2_allele_queries")
+        return keys
+
     def genotype_cells(self, site_keys, alt_sym, params=None):
         """Per-cell (Dp, Alt) at target sites (HCCVSingleCellGenotype.py:82-220).  site_keys = (tid << 32) | pos0, strictly
         ascending; alt_sym = expected alt symbol class per site.  Returns two uint32 arrays [n_sites, n_cb]."""

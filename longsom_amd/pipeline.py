@@ -383,18 +383,24 @@ def run_chain(res: Resident, celltype_of: np.ndarray, celltype_names: List[str],
     resident reads (celltype_of[barcode id] = index into celltype_names, 255 = barcode not listed).  step3=False stops after
     step 2, as pass 1 of the reference does (rules/CellTypeReannotation.smk has no step-3 rule: HCCV reads calling.step2.tsv)."""
     eng, contig_names = res.engine, res.contig_names
-    # Step 2 without a gnomAD source and with --min_distance 0 (LongSom's own setting) tags rows by position sets and blanks NA cells: the
-    # device prints that table itself and tells step 3 what it needs of it (_device_steps23); any other step 2 runs on the host over the
-    # text of the rows it keeps.  LONGSOM_HOST_TABLES=1 / LONGSOM_HOST_STEP2=1 keep the host paths.
-    device23 = (os.environ.get("LONGSOM_HOST_TABLES", "0") != "1" and os.environ.get("LONGSOM_HOST_STEP2", "0") != "1" and not gnomad_af_json
+    # Step 2 with --min_distance 0 (LongSom's own setting) tags rows by position sets and by gnomAD alleles and blanks NA cells: the device
+    # prints that table itself and tells step 3 what it needs of it (_device_steps23); any other step 2 - a distance filter, a
+    # --gnomAD_max <= 0 (the reference then tags every row, whatever the database holds), contigs beyond the allele key's limits - runs on
+    # the host over the text of the rows it keeps.  LONGSOM_HOST_TABLES=1 / LONGSOM_HOST_STEP2=1 keep the host paths.  The gnomAD source
+    # is opened first: one that cannot be used stops the run before anything is counted (calling.open_gnomad).
+    gnomad = calling.open_gnomad(gnomad_af_json)
+    if isinstance(gnomad, calling.GnomadSet):
+        gnomad.require(params.max_gnomad_vaf)
+    device23 = (os.environ.get("LONGSOM_HOST_TABLES", "0") != "1" and os.environ.get("LONGSOM_HOST_STEP2", "0") != "1"
                 and int(params.min_distance) == 0 and len(set(contig_names)) == len(contig_names)
-                and not any(ch in n for n in list(contig_names) + list(celltype_names) for ch in "\t\n"))
+                and not any(ch in n for n in list(contig_names) + list(celltype_names) for ch in "\t\n")
+                and (not gnomad or (params.max_gnomad_vaf > 0 and calling.allele_keys_fit(eng.contig_len) and calling.keyed_by_alleles(gnomad))))
     out, s1, _, t = chain_step1(res, celltype_of, celltype_names, report, out_dir, sample_id, params, background_tables=True, kept_rows=not device23,
                                 last="step3" if step3 else "step2")
     try:
         if device23:
-            return _device_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3)
-        return _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad_af_json, step3)
+            return _device_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3, gnomad)
+        return _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad, step3)
     except BaseException:
         try:                                   # (the writers stream from the engine: nobody may close it under them)
             out.wait_for_tables()
@@ -403,10 +409,12 @@ def run_chain(res: Resident, celltype_of: np.ndarray, celltype_names: List[str],
         raise
 
 
-def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3):
+def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3, gnomad=None):
     """Steps 2 and 3 of run_chain with the step-2 table printed on the device (Engine.TABLE_STEP2: csrc/tables.hip): its text goes from
     the device straight into its file; the host sees the kinds of cell of its columns and the rows step 3 can keep
-    (Engine.step2_summary), which is all calling.step3 reads of a table this large."""
+    (Engine.step2_summary), which is all calling.step3 reads of a table this large.  gnomad (calling.open_gnomad's): the alleles it tags
+    are resident while the table is printed - a prepared set's as they are, a database's or a JSON table's after it was asked about the
+    one-base alleles this run holds (Engine.step2_allele_queries) and nothing else."""
     t0 = time.time()
     for kind, k in zip((calling.KIND_EDITING, calling.KIND_PON_SR, calling.KIND_PON_LR), _posset_keys(contig_names, params, editing, pon_sr, pon_lr)):
         eng.load_posset(kind, k)
@@ -414,7 +422,18 @@ def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, po
     cols = hdr.decode().split("\n")[-2].split("\t")
     with open(out.step2, "wb") as f:
         f.write(hdr)
-    n2 = eng.format_table(eng.TABLE_STEP2)
+    if gnomad:
+        t1 = time.time()
+        if isinstance(gnomad, calling.GnomadSet):
+            hits = gnomad.hit_keys(contig_names, params.max_gnomad_vaf)
+        else:
+            hits = calling.gnomad_hit_keys(gnomad, contig_names, eng.step2_allele_queries(), params.max_gnomad_vaf)
+        eng.load_alleleset(hits)
+        t["step2_gnomad"] = time.time() - t1          # (part of step2: the source's answers and the set's load)
+    try:
+        n2 = eng.format_table(eng.TABLE_STEP2)
+    finally:
+        eng.load_alleleset(None)                      # (a later run on this engine without a source must not be tagged)
     kinds, n_surv = eng.step2_summary(len(cols))
     survivors = eng.table_bytes(eng.TABLE_STEP3_ROWS, n_surv, prefix=hdr)
     eng.free_table(eng.TABLE_STEP3_ROWS)
@@ -433,9 +452,9 @@ def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, po
     return out
 
 
-def _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad_af_json, step3):
+def _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad, step3):
     t0 = time.time()
-    s2 = _step2_for(eng, contig_names, params, editing, pon_sr, pon_lr, gnomad_af_json)(s1, params.min_distance)
+    s2 = _step2_for(eng, contig_names, params, editing, pon_sr, pon_lr, None, gnomad)(s1, params.min_distance)
     tsvio.write_bytes(out.step2, s2)
     t["step2"] = time.time() - t0
     if step3:
@@ -450,11 +469,12 @@ def _posset_keys(contig_names, params: SnvParams, editing, pon_sr, pon_lr) -> li
     return [calling.read_posset_keys(p, contig_names, params.reference_gz_compat) for p in (editing, pon_sr, pon_lr)]
 
 
-def _step2_for(eng, contig_names, params: SnvParams, editing, pon_sr, pon_lr, gnomad_af_json):
+def _step2_for(eng, contig_names, params: SnvParams, editing, pon_sr, pon_lr, gnomad_af_json, gnomad=None):
     """step 2 of one run: (text of a step-1 table, distance) -> text of the step-2 table.  The position sets are read and the gnomAD source
-    (a JSON table or a gnomad_db directory / sqlite file) is opened here, once: one that cannot be used stops the run (calling.open_gnomad)."""
+    (a JSON table, a gnomad_db directory / sqlite file or a prepared set; or, as `gnomad`, one the caller opened) is opened here, once:
+    one that cannot be used stops the run (calling.open_gnomad)."""
     ed, sr, lr = _posset_keys(contig_names, params, editing, pon_sr, pon_lr)
-    af = calling.open_gnomad(gnomad_af_json)
+    af = gnomad if gnomad is not None else calling.open_gnomad(gnomad_af_json)
     return lambda text, distance: calling.step2_bytes(text, eng, contig_names, ed, sr, lr, distance, af, params.max_gnomad_vaf)
 
 

@@ -25,6 +25,8 @@ rule Reannotation_gpu:
     params:
         script=GPU_SCRIPTS+"/CellTypeReannotation/longsom_gpu_reannotation.py",
         gnomAD_db=str(workflow.basedir)+config['Reference']['gnomAD_db'],
+        # Reference.gnomAD_set (optional): the prepared allele set of `python -m longsom_amd.cli gnomad_set`; step 2 then opens no database.  Absent: a bare --gnomAD_set, which is no file
+        gnomAD_set=(str(workflow.basedir)+config['Reference']['gnomAD_set']) if config['Reference'].get('gnomAD_set') else "",
         gz_compat="--p1_reference_gz_compat --p2_reference_gz_compat" if config['Run'].get('reference_gz_compat', False) else "",
         # Run.htslib_legacy_del_merge: True counts CIGAR 1D2D's first deleted column as 'D' (pysam over htslib <= 1.10); default: htslib >= 1.11
         htslib="--htslib_legacy_del_merge" if config['Run'].get('htslib_legacy_del_merge', False) else "",
@@ -47,7 +49,7 @@ rule Reannotation_gpu:
     shell:
         r"""
         {params.launcher} {params.script} --bam {input.bam} --meta {input.barcodes} --ref {input.ref} --id {wildcards.id} --outdir . \
-        --fusions {input.fusions} --editing {input.RNA_editing} --pon_SR {input.pon_SR} --pon_LR {input.pon_LR} --gnomAD_db {params.gnomAD_db} {params.gz_compat} {params.htslib} {params.no_gnomad} \
+        --fusions {input.fusions} --editing {input.RNA_editing} --pon_SR {input.pon_SR} --pon_LR {input.pon_LR} --gnomAD_db {params.gnomAD_db} --gnomAD_set {params.gnomAD_set} {params.gz_compat} {params.htslib} {params.no_gnomad} \
         --p1_min_mapping_quality {params.m1} --p1_min_cell_types {params.r1[Min_cell_types]} --p1_min_distance {params.r1[min_distance]} \
         --p1_max_gnomad_vaf {params.r1[max_gnomAD_VAF]} \
         --p1_alpha1 {params.r1[alpha1]} --p1_beta1 {params.r1[beta1]} --p1_alpha2 {params.r1[alpha2]} --p1_beta2 {params.r1[beta2]} \

@@ -34,6 +34,8 @@ rule SNVCalling_gpu:
         c=config['SNVCalling']['BaseCellCalling'],
         mapq=config['SNVCalling']['BaseCellCounter']['min_mapping_quality'],
         gnomAD_db=str(workflow.basedir)+config['Reference']['gnomAD_db'],
+        # Reference.gnomAD_set (optional): the prepared allele set of `python -m longsom_amd.cli gnomad_set`; step 2 then opens no database.  Absent: a bare --gnomAD_set, which is no file
+        gnomAD_set=(str(workflow.basedir)+config['Reference']['gnomAD_set']) if config['Reference'].get('gnomAD_set') else "",
         # Run.reference_gz_compat: True reproduces the reference's reading of the .gz position sets (opened as text, the
         # decode error is swallowed, the sets are EMPTY: SURVEY quirk Q1); default False = the sets are read
         gz_compat="--reference_gz_compat" if config['Run'].get('reference_gz_compat', False) else "",
@@ -55,7 +57,7 @@ rule SNVCalling_gpu:
         r"""
         {params.launcher} {params.script} \
         --bam {input.bam} --meta {input.barcodes} --ref {input.ref} --id {wildcards.id} --outdir SNVCalling \
-        --editing {input.RNA_editing} --pon_SR {input.pon_SR} --pon_LR {input.pon_LR} --gnomAD_db {params.gnomAD_db} {params.gz_compat} {params.htslib} {params.no_gnomad} \
+        --editing {input.RNA_editing} --pon_SR {input.pon_SR} --pon_LR {input.pon_LR} --gnomAD_db {params.gnomAD_db} --gnomAD_set {params.gnomAD_set} {params.gz_compat} {params.htslib} {params.no_gnomad} \
         --min_mapping_quality {params.mapq} --max_nM={params.max_nm} --max_NH={params.max_nh} --n_trim={params.n_trim} \
         --min_cell_types {params.c[Min_cell_types]} --min_distance {params.c[min_distance]} \
         --max_gnomad_vaf {params.c[max_gnomAD_VAF]} --delta_vaf {params.c[deltaVAF]} --delta_mcf {params.c[deltaMCF]} \
