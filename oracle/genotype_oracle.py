@@ -4,7 +4,7 @@ on the read-record arrays, plus the text of its output rows.  Only tests/ may im
 
 PARITY UNPINNED for the pileup part: the reference's arithmetic here IS pysam's pileup (absent from this image and from
 the reference tree), so it is restated from the htslib/pysam semantics of SURVEY.md §8a exactly as oracle/count_oracle.c
-does, and pinned by hand-derived known answers (tests/test_genotype_cpu.py).  The per-cell status / p-value / text part
+does, and pinned by hand-derived known answers (tests/test_reanno_cpu.py, tests/test_genotype_cases_cpu.py).  The per-cell status / p-value / text part
 uses scipy.stats.betabinom like the reference (:204).
 """
 import numpy as np
