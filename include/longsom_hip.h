@@ -354,12 +354,18 @@ int lsg_export_calls(lsg_ctx* ctx, int32_t kind, void* dst_device, int64_t capac
  *   LSG_TABLE_BNPC_BIN / _VAF   the SNV rows of BnpC_input/<id>.BinaryMatrix.tsv and VAFMatrix.tsv (FormatInputBnpC.py:16-34; see lsg_cellgeno_filter)
  *   LSG_TABLE_FASTQ       the FASTQ records of a BAM for ctat-LR-fusion (FusionCalling/BamToFastq.py:9-42; made by lsg_bam_fastq below,
  *                         not by lsg_format_table)
+ *   LSG_TABLE_GENE_COUNTS the whole of <id>.counts.formated.txt, its header line included: the cell-by-gene read counts inferCNV reads
+ *                         (rules featureCount + format_featureCount, rules/CNACalling.smk:29-75; see lsg_gene_counts below)
  * Rows only (the header lines are the caller's), in the reference's order: contigs in Python string order, positions ascending.
  * At 24 M sites these are 17 GB of text: a kernel prints them from the count rows and call records where they lie (two passes:
  * lengths, then bytes), the host only moves bytes.  The merged and step-1 tables need lsg_call_step1 (its merged site list). */
 enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG_TABLE_STEP1, LSG_TABLE_STEP1_KEPT, LSG_TABLE_STEP2, LSG_TABLE_STEP3_ROWS,
                  LSG_TABLE_CELL_LONG, LSG_TABLE_CELL_DP, LSG_TABLE_CELL_ALT, LSG_TABLE_CELL_VAF, LSG_TABLE_CELL_BIN,
                  LSG_TABLE_BNPC_BIN, LSG_TABLE_BNPC_VAF, LSG_TABLE_FASTQ, LSG_TABLE_SLOTS };
+/* Tables added since continue the numbering where enum lsg_table ends, so that none of its values moves - LSG_TABLE_SLOTS, the number
+ * of tables its callers were built against, among them.  LSG_TABLE_ALL_SLOTS bounds every table index lsg_format_table,
+ * lsg_copy_table, lsg_append_table and lsg_free_table serve. */
+enum lsg_table_more { LSG_TABLE_GENE_COUNTS = LSG_TABLE_SLOTS, LSG_TABLE_ALL_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -693,6 +699,53 @@ int lsg_bbfit_accumulate(lsg_ctx* ctx, int32_t ct, const uint8_t* ref_or_null, i
 int lsg_bbfit_fetch(lsg_ctx* ctx, uint64_t* hist);
 int lsg_bbfit_add(lsg_ctx* ctx, const uint64_t* hist);
 int lsg_bbfit_solve(lsg_ctx* ctx, double* est, lsg_bbfit_info* info, int32_t max_iter);
+
+/* ---- cell-by-gene read counts: the expression matrix of the CNA branch ------------------------------------------------------------
+ * Replaces rules split_per_bc, featureCount and format_featureCount of workflow/rules/CNACalling.smk:11-75 - one BAM per barcode,
+ * `featureCounts -L -a <gtf>` over all of them, a pandas step that names and sums the rows - by one pass over the reads a load left
+ * resident.  What is counted (longsom_amd/genecounts.py states it in numpy): the annotation's exons by gene_id,
+ * unstranded (featureCounts -t exon -g gene_id -s 0); a read's blocks are its segments; a read with a listed barcode is CONSIDERED
+ * when flag & flag_exclude == 0 and mapq >= min_mapq, else tallied Filtered; a considered read is Assigned to the one gene whose
+ * exons its blocks overlap by a base or more, NoFeatures without any, Ambiguity with two or more (no -O).  NH is not resident: the
+ * multi-mapping rule of featureCounts without -M is not modelled (lsg_set_split_filters' max_NH is what a BAM load offers). */
+
+/* The flattened annotation (stands in for featureCounts' reading of `-a <gtf>`, CNACalling.smk:42-44): n_intervals sorted, disjoint
+ * elementary intervals [key, key + len) with key = tid << 32 | start0 (0-based) and start0 + len <= 2^32, label = the index of the
+ * one gene covering it or LSG_GENE_AMBIG; row_of_gene[g] in [0, n_rows) = the matrix row gene g adds to (several genes may share a
+ * row: format_featureCount's groupby('Geneid').sum(), CNACalling.smk:71) or -1 for a gene that is assigned but printed nowhere (a
+ * gene id without a name, :69-70).  Every index a kernel follows is checked here.  Drops a matrix counted under another annotation. */
+#define LSG_GENE_AMBIG 0xFFFFFFFEu
+int lsg_load_annotation(lsg_ctx* ctx, int64_t n_intervals, const uint64_t* keys, const uint32_t* lens, const uint32_t* labels, int32_t n_genes,
+                        const int32_t* row_of_gene, int32_t n_rows);
+/* The read filters of a count: featureCounts' -Q (min_mapq, default 0) and the SAM flag bits that remove a record (0x4 = featureCounts
+ * without --primary: secondary and supplementary records count, each on its own; | 0x900 = --primary).  CNACalling.smk:41-44 sets none. */
+typedef struct { int32_t min_mapq; uint32_t flag_exclude; } lsg_gene_count_params;
+/* Of one lsg_gene_counts call: the reads and segments it looked at, its reads per outcome (unlisted: no listed barcode, tallied
+ * nowhere), and the HIP-event times of its phases: the segment kernel (interval lookup + fold), the read kernel (matrix and tallies). */
+typedef struct {
+    int64_t n_reads, n_segs;
+    int64_t n_assigned, n_no_features, n_ambiguity, n_filtered, n_unlisted;
+    float   ms_segments, ms_reads, ms_total;
+    int32_t pad_;
+} lsg_gene_count_info;
+/* Counts the resident load (stands in for rule featureCount's run, CNACalling.smk:29-44) and ADDS it to the resident matrix (uint32
+ * [n_rows][n_cb], barcodes in dense-id order) and tallies (uint64 [n_cb][4]: Assigned, NoFeatures, Ambiguity, Filtered): a second load
+ * of more reads of the same sample accumulates, as lsg_bbfit_accumulate does.  Refused with an error code when no annotation is
+ * loaded, no reads are resident, or the barcode count differs from the one the matrix was started with; a cell that would pass
+ * 2^32 - 1 fails the call.  Reads and changes nothing of the store, the count rows or the calls; lsg_unload_reads leaves the matrix. */
+int lsg_gene_counts(lsg_ctx* ctx, const lsg_gene_count_params* params, lsg_gene_count_info* info);
+/* The matrix (n_rows x n_cb uint32) and the tallies (n_cb x 4 uint64) to the host; either may be NULL.  What rule featureCount
+ * writes as <id>.counts.txt and <id>.counts.txt.summary (CNACalling.smk:34), after format_featureCount's row sums. */
+int lsg_gene_counts_fetch(lsg_ctx* ctx, uint32_t* matrix, uint64_t* tallies);
+/* The strings LSG_TABLE_GENE_COUNTS prints (stands in for DataFrame.to_csv in format_featureCount, CNACalling.smk:72): the row names
+ * (blob + n_rows + 1 offsets; the caller sorts and vets them), the columns as dense barcode ids in output order with their strings
+ * (blob + n_cols + 1 offsets, in column order) and the separator byte (',' as the rule writes, '\t' as infercnv.R:14 reads).
+ * lsg_format_table(LSG_TABLE_GENE_COUNTS) then prints "Geneid<sep><bc>...\n" and one "<name><sep><count>...\n" per row. */
+int lsg_gene_counts_set_text(lsg_ctx* ctx, const char* row_names, const uint32_t* row_off, int32_t n_cols, const int32_t* col_src,
+                             const char* col_names, const uint32_t* col_off, int32_t separator);
+/* Frees the annotation, the matrix, the tallies, the strings and the table's text (the per-barcode BAMs and count files rules
+ * split_per_bc and featureCount leave behind, CNACalling.smk:17,34, have no counterpart to clean up). */
+int lsg_gene_counts_reset(lsg_ctx* ctx);
 
 /* ---- measurement helpers --------------------------------------------------------------------*/
 /* Statistics of the last lsg_pileup_count: admitted reads / segments / events (events that passed

@@ -134,6 +134,20 @@ class BbfitInfo(C.Structure):
     _fields_ = [("iterations", C.c_int32 * 2), ("status", C.c_int32 * 2), ("last_step", C.c_double * 2), ("grad_norm", C.c_double * 2)]
 
 
+class GeneCountParams(C.Structure):
+    """lsg_gene_count_params: featureCounts' -Q and the SAM flag bits that remove a record (0x4; | 0x900 = --primary)"""
+    _fields_ = [("min_mapq", C.c_int32), ("flag_exclude", C.c_uint32)]
+
+
+class GeneCountInfo(C.Structure):
+    """lsg_gene_count_info (lsg_gene_counts): the reads and segments of the call, its reads per outcome, the phases' HIP-event times"""
+    _fields_ = [
+        ("n_reads", C.c_int64), ("n_segs", C.c_int64),
+        ("n_assigned", C.c_int64), ("n_no_features", C.c_int64), ("n_ambiguity", C.c_int64), ("n_filtered", C.c_int64), ("n_unlisted", C.c_int64),
+        ("ms_segments", C.c_float), ("ms_reads", C.c_float), ("ms_total", C.c_float), ("pad_", C.c_int32),
+    ]
+
+
 FASTQ_OK, FASTQ_NO_CB, FASTQ_CB_TYPE, FASTQ_UB_TYPE, FASTQ_NM_TYPE, FASTQ_NH_TYPE = -1, 0, 1, 2, 3, 4
 
 
@@ -234,6 +248,11 @@ SIGNATURES = {
     "lsg_bbfit_fetch": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lsg_bbfit_add": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lsg_bbfit_solve": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(BbfitInfo), C.c_int32]),
+    "lsg_load_annotation": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "lsg_gene_counts": (C.c_int, [C.c_void_p, C.POINTER(GeneCountParams), C.POINTER(GeneCountInfo)]),
+    "lsg_gene_counts_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lsg_gene_counts_set_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int32]),
+    "lsg_gene_counts_reset": (C.c_int, [C.c_void_p]),
     "lsg_betabinom_sf4": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]),
     "lsg_betabinom_sf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "lsg_max_live_reads": (C.c_int64, [C.c_void_p]),

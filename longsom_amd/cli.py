@@ -93,6 +93,65 @@ def fusion_fastq(argv=None):
                       "printed_on": where, "seconds": round(time.time() - t0, 3)}))
 
 
+def _resident_for_gene_counts(eng, bam, table, lens, first, filters):
+    """the BAM's reads resident with no load filter (a count under --min_MQ 0 admits every record): the device ingest, the host decoder for
+    a BAM whose records straddle its BGZF blocks"""
+    from . import _lib
+    eng.set_contigs(lens)
+    eng.set_barcodes(table.celltype_of, len(table.celltype_names))
+    with eng.loading(filters=filters):
+        try:
+            eng.load_bam(bam, table.barcodes, min_mapq=0, first_record_offset=first)
+        except _lib.LsgError as e:
+            if e.rc != -4:
+                raise
+            print("%s: its records straddle its BGZF blocks; decoding it on the host" % bam, file=sys.stderr)
+            eng.load_reads(hostio.decode_bam(bam, table.barcodes, min_mapq=0, filters=filters).records)
+
+
+def gene_counts(argv=None):
+    """The unsplit BAM + the barcode table + a GTF -> {outdir}/{id}.counts.formated.txt, the cell-by-gene read counts inferCNV reads, and
+    {id}.counts.summary.tsv: rules split_per_bc + featureCount + format_featureCount (workflow/rules/CNACalling.smk:11-75) without the
+    per-barcode BAMs (workflow/rules/CNACalling.gpu.smk GeneCounts_gpu; longsom_amd/genecounts.py states what is counted)."""
+    ap = argparse.ArgumentParser(description="Cell-by-gene read counts (featureCounts' exon / gene_id / unstranded defaults) of a BAM on the GPU")
+    ap.add_argument("--bam", required=True); ap.add_argument("--meta", required=True); ap.add_argument("--gtf", required=True)
+    ap.add_argument("--names_gtf", default="", help="the GTF whose `gene` lines name the gene ids (default: --gtf)")
+    ap.add_argument("--id", default="Sample"); ap.add_argument("--outdir", default=".")
+    ap.add_argument("--min_MQ", type=int, default=0, help="featureCounts -Q")
+    ap.add_argument("--primary_only", action="store_true", help="featureCounts --primary: secondary and supplementary records are not counted")
+    ap.add_argument("--gene_names", default="third", help="third (format_featureCount's rule: the third attribute of a gene line), gene_name, or none (rows are gene ids)")
+    ap.add_argument("--tsv", action="store_true", help="tabs instead of commas (infercnv.R reads tabs)")
+    ap.add_argument("--max_NH", type=_limit, default=None, help="SplitBamCellTypes' NH limit for BAMs that carry the tag (reads without it are dropped too)")
+    ap.add_argument("--device", type=int, default=0); ap.add_argument("--host", action="store_true", help="count on the host (no GPU)")
+    a = ap.parse_args(argv)
+    from . import genecounts
+    if a.gene_names not in genecounts.NAME_RULES:
+        ap.error("--gene_names %s: one of %s" % (a.gene_names, ", ".join(genecounts.NAME_RULES)))
+    t0 = time.time()
+    table = hostio.read_barcodes(a.meta)
+    filters = hostio.SplitFilters(None, a.max_NH, 0) if a.max_NH is not None else None
+    flag_exclude = genecounts.FLAG_EXCLUDE | (genecounts.FLAG_PRIMARY_ONLY if a.primary_only else 0)
+    names, lens, first = hostio.bam_header(a.bam)
+    ann = genecounts.load_annotation(a.gtf, names)
+    rows, row_of_gene = genecounts.name_rows(ann, a.gtf, a.names_gtf or None, a.gene_names)
+    order = genecounts.column_order(table.barcodes)
+    sep = "\t" if a.tsv else ","
+    os.makedirs(a.outdir, exist_ok=True)
+    out = os.path.join(a.outdir, a.id + ".counts.formated.txt")
+    if a.host:
+        rec = hostio.decode_bam(a.bam, table.barcodes, min_mapq=0, filters=filters).records
+        matrix, tallies = genecounts.count(rec, ann, row_of_gene, len(rows), len(table.barcodes), a.min_MQ, flag_exclude)
+        text, info = genecounts.matrix_text(matrix, rows, table.barcodes, order, sep), {}
+    else:
+        with Engine(a.device) as eng:
+            _resident_for_gene_counts(eng, a.bam, table, lens, first, filters)
+            info, tallies, text = genecounts.device_matrix(eng, ann, rows, row_of_gene, table.barcodes, order, sep, a.min_MQ, flag_exclude, out_path=out)
+    _, summary = genecounts.write_outputs(a.outdir, a.id, text, tallies, table.barcodes, order)
+    print(json.dumps({"counts": out, "summary": summary, "genes": ann.n_genes, "rows": len(rows), "intervals": ann.n_intervals, "exons_on_absent_contigs": ann.n_dropped_exons,
+                      "reads": {k: int(tallies[:, i].sum()) for i, k in enumerate(genecounts.OUTCOMES)}, "counted_on": "host" if a.host else "device",
+                      "ms": {k[3:]: round(float(v), 3) for k, v in info.items() if k.startswith("ms_")}, "seconds": round(time.time() - t0, 3)}))
+
+
 def somatic_fusions(argv=None):
     """FusionCalling.py --fusions --barcodes --min_ac_reads --min_ac_cells --max_MCF_noncancer --deltaMCF --outdir  (FusionCalling.py:88-97)"""
     from . import fusions
@@ -714,12 +773,23 @@ def snv(argv=None):
     # SplitBamCellTypes' read filters, with its names and defaults (SplitBamCellTypes.py:199-202); not SnvParams fields, so that the flag
     # surfaces of `reannotation` and `pon` stay as they are
     ap.add_argument("--max_nM", type=_limit, default=None); ap.add_argument("--max_NH", type=_limit, default=None); ap.add_argument("--n_trim", type=int, default=0)
+    # the CNA branch's cell-by-gene read counts from the same load (cli.gene_counts has the flags' meaning); off without --gene_counts_gtf
+    ap.add_argument("--gene_counts_gtf", default="", help="also write {gene_counts_out}/{id}.counts.formated.txt from the load this chain holds")
+    ap.add_argument("--gene_counts_out", default="", help="its directory (default: {outdir}/InferCNV/featurecount/output)")
+    ap.add_argument("--gene_counts_names", default="third"); ap.add_argument("--gene_counts_tsv", action="store_true")
     d = pipeline.SnvParams()
     _add_dataclass_flags(ap, d)
     _add_htslib_flag(ap); _add_gnomad_flag(ap)
     a = ap.parse_args(argv)
     _apply_htslib_flag(a); _apply_gnomad_flag(a)
     params = pipeline.SnvParams(**{k: getattr(a, k) for k in vars(d)})
+    gene_counts = None
+    if a.gene_counts_gtf:
+        from . import genecounts
+        if a.gene_counts_names not in genecounts.NAME_RULES:
+            ap.error("--gene_counts_names %s: one of %s" % (a.gene_counts_names, ", ".join(genecounts.NAME_RULES)))
+        gene_counts = genecounts.Request(a.gene_counts_gtf, a.gene_counts_out or os.path.join(a.outdir, "InferCNV", "featurecount", "output"),
+                                         gene_names=a.gene_counts_names, tsv=a.gene_counts_tsv)
     # under torch.distributed.run (WORLD_SIZE > 1): one rank per GPU, regions sharded over the ranks; the process group comes up
     # before anything touches the GPU
     from . import regions
@@ -727,7 +797,7 @@ def snv(argv=None):
     try:
         out = pipeline.run_snv(a.bam, a.meta, a.ref, a.outdir, a.id, params, a.editing or None, a.pon_SR or None, a.pon_LR or None,
                                _gnomad_source(a), a.device, comm=comm, window_bytes=int(a.window_gb * (1 << 30)) or None,
-                               filters=pipeline.SplitFilters(a.max_nM, a.max_NH, a.n_trim))
+                               filters=pipeline.SplitFilters(a.max_nM, a.max_NH, a.n_trim), gene_counts=gene_counts)
         if comm.rank == 0:
             print(json.dumps({"outputs": {k: v for k, v in vars(out).items() if k not in ("timings", "resident", "_pending")}, "seconds": out.timings, "ranks": comm.world}))
     finally:

@@ -34,6 +34,7 @@ int run_cellgeno_filter(lsg_ctx* c, int32_t min_cells_per_mut, int32_t min_pos_c
 int run_cellgeno_filter_fetch(lsg_ctx* c, uint8_t* row_keep, uint8_t* col_keep, int32_t* row_mut, int32_t* col_cov_kept, int32_t* col_cov_all, uint8_t* col_int);
 int run_cellgeno_load_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb, const uint8_t* bin, const int32_t* vaf4);
 int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes);
+int run_format_gene_table(lsg_ctx* c, int64_t* n_bytes);
 int run_bnpc_load(lsg_ctx* c, int64_t n_samples, int32_t n_cells, const int32_t* assign, int32_t k_max, int32_t n_muts, const float* params);
 int run_bnpc_codist(lsg_ctx* c);
 int run_bnpc_fetch_dist(lsg_ctx* c, uint32_t* out, int64_t capacity);
@@ -120,6 +121,7 @@ void lsg_destroy(lsg_ctx* c) {
     c->bnpc.release();
     c->bnpcs.release();
     c->bb.release();
+    c->gc.release();
     c->tab_names.release();
     for (auto& b : c->ws) b.release();
     for (auto& b : c->tm) b.release();
@@ -483,6 +485,7 @@ int lsg_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     if (!c) { set_error("lsg_format_table: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
     if (table >= LSG_TABLE_CELL_LONG && table <= LSG_TABLE_BNPC_VAF) return run_format_cell_table(c, table, n_bytes);
+    if (table == LSG_TABLE_GENE_COUNTS) return run_format_gene_table(c, n_bytes);
     return run_format_table(c, table, n_bytes);
 }
 int lsg_copy_table(lsg_ctx* c, int32_t table, char* dst_host, int64_t capacity) {

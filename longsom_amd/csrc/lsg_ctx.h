@@ -126,6 +126,16 @@ struct Bbfit {
     void release() { for (DevBuf* b : {&hist, &tails, &out, &ref, &tmp}) b->release(); valid = false; cap = 0; }
 };
 
+// genecounts.hip: the flattened annotation (lsg_load_annotation), the matrix and tallies lsg_gene_counts adds to, the two state words
+// per read of one call, and what lsg_gene_counts_set_text uploaded (one buffer; the *_at fields are byte offsets into it)
+struct GeneCounts {
+    DevBuf iv, row_of_gene, matrix, tallies, state, small, text, scratch;
+    int64_t n_iv = 0; int32_t n_genes = 0, n_rows = 0, n_cb = 0, n_cols = 0; char sep = ',';
+    bool ann_valid = false, mat_valid = false, text_valid = false;
+    size_t row_off_at = 0, col_src_at = 0, col_off_at = 0, row_txt_at = 0, col_txt_at = 0;
+    void release() { for (DevBuf* b : {&iv, &row_of_gene, &matrix, &tallies, &state, &small, &text, &scratch}) b->release(); ann_valid = mat_valid = text_valid = false; n_iv = 0; n_genes = n_rows = n_cb = n_cols = 0; }
+};
+
 // workspace buffers (lsg_ctx::ws)
 enum { WS_NE_NSLOT = 0, WS_NE_ACC, WS_NE_GEOM, WS_MULTI_LIST, WS_MACC, WS_EXPORT_K, WS_EXPORT_R,
        WS_EXPORT_C, WS_CALL_FLAGS, WS_CALL_SEL, WS_CALL_CANDS, WS_CALL_TASKS, WS_SEG_INFO };
@@ -276,8 +286,8 @@ struct lsg_ctx {
     int32_t tab_scratch_table = -1; int64_t tab_scratch_rows = 0;      // whose rows' lengths and places tab_scratch holds
     uint64_t tab_rows_serial[LSG_MAX_CELLTYPES] = {0, 0, 0, 0};      // count_serial the flat copy was made of (0 = none)
     uint64_t count_serial = 0;            // bumped by every count / lsg_load_counts
-    lsg::DevBuf tab_text[LSG_TABLE_SLOTS];
-    int64_t tab_bytes[LSG_TABLE_SLOTS];   // -1: not formatted
+    lsg::DevBuf tab_text[LSG_TABLE_ALL_SLOTS];
+    int64_t tab_bytes[LSG_TABLE_ALL_SLOTS];   // -1: not formatted
     lsg_ctx() { for (auto& b : tab_bytes) b = -1; }
     int32_t tab_n_contigs = 0, tab_n_ct = 0; uint32_t tab_ct_off_at = 0, tab_order_at = 0, tab_ct_txt_at = 0, tab_contig_txt_at = 0;
 
@@ -286,6 +296,7 @@ struct lsg_ctx {
     lsg::Bnpc bnpc;                       // bnpc.hip: the resident posterior samples and their pair distances
     lsg::Bnpcs bnpcs;                     // bnpc_sampler.hip: the sampler's chains
     lsg::Bbfit bb;                        // bbfit.hip: the beta-binomial fit's histograms
+    lsg::GeneCounts gc;                   // genecounts.hip: the annotation's intervals and the cell-by-gene matrix
 
     lsg::PosSet posset[3];
     lsg::PosSet alleleset; bool alleleset_loaded = false;      // lsg_load_alleleset: step 2's gnomAD alleles (loaded with n = 0: a source that hits nothing)

@@ -704,7 +704,7 @@ int run_step2_summary(lsg_ctx* c, int32_t n_cols, uint8_t* kinds, int64_t* n_sur
 }
 
 static int table_ready(lsg_ctx* c, int32_t table, const char* who) {
-    if (table < 0 || table >= LSG_TABLE_SLOTS || c->tab_bytes[table] < 0) { set_error("%s: table %d is not formatted (lsg_format_table)", who, table); return -2; }
+    if (table < 0 || table >= LSG_TABLE_ALL_SLOTS || c->tab_bytes[table] < 0) { set_error("%s: table %d is not formatted (lsg_format_table)", who, table); return -2; }
     return 0;
 }
 
@@ -761,8 +761,8 @@ int run_append_table(lsg_ctx* c, int32_t table, const char* path) {
 }
 
 int run_free_table(lsg_ctx* c, int32_t table) {
-    if (table >= LSG_TABLE_SLOTS) { set_error("lsg_free_table: no table %d", table); return -2; }
-    for (int t = 0; t < LSG_TABLE_SLOTS; ++t)
+    if (table >= LSG_TABLE_ALL_SLOTS) { set_error("lsg_free_table: no table %d", table); return -2; }
+    for (int t = 0; t < LSG_TABLE_ALL_SLOTS; ++t)
         if (table < 0 || t == table) { c->tab_text[t].release(); c->tab_bytes[t] = -1; }
     if (table < 0) {
         for (int ct = 0; ct < LSG_MAX_CELLTYPES; ++ct) { c->tab_keys[ct].release(); c->tab_refs[ct].release(); c->tab_rows[ct].release(); c->tab_rows_serial[ct] = 0; }

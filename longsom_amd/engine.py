@@ -703,6 +703,62 @@ class Engine:
         _lib.check(self._lib.lsg_cellgeno_set_text(self._h, C.byref(t)), "lsg_cellgeno_set_text")
         self._mat_shape = (len(mo), len(cs))
 
+    # ---- cell-by-gene read counts (rules/CNACalling.smk:11-75; csrc/genecounts.hip; longsom_amd/genecounts.py states the contract) ----
+    TABLE_GENE_COUNTS = 17
+
+    def load_annotation(self, ann, row_of_gene, n_rows: int) -> None:
+        """The flattened exons (a genecounts.Annotation) and the matrix row every gene adds to (-1: assigned, printed nowhere) resident
+        for gene_counts (lsg_load_annotation).  Drops a matrix counted under another annotation."""
+        keys = np.ascontiguousarray(ann.keys, dtype=np.uint64); lens = np.ascontiguousarray(ann.lens, dtype=np.uint32)
+        labels = np.ascontiguousarray(ann.labels, dtype=np.uint32); rows = np.ascontiguousarray(row_of_gene, dtype=np.int32)
+        if not (len(keys) == len(lens) == len(labels)) or len(rows) != ann.n_genes:
+            raise ValueError("load_annotation: %d keys, %d lengths, %d labels; %d rows for %d genes" % (len(keys), len(lens), len(labels), len(rows), ann.n_genes))
+        self._gene_shape = None
+        _lib.check(self._lib.lsg_load_annotation(self._h, len(keys), _ptr(keys), _ptr(lens), _ptr(labels), len(rows), _ptr(rows), int(n_rows)), "lsg_load_annotation")
+        self._gene_rows = int(n_rows)
+
+    def gene_counts(self, min_mapq: int = 0, flag_exclude: int = 0x4) -> dict:
+        """Counts the resident load's reads per (gene row, barcode) and ADDS them to the resident matrix and tallies (lsg_gene_counts):
+        another load of the same sample accumulates.  Returns the call's info (its reads per outcome, the phases' times)."""
+        from ._lib import GeneCountInfo, GeneCountParams
+        p = GeneCountParams(int(min_mapq), int(flag_exclude)); info = GeneCountInfo()
+        _lib.check(self._lib.lsg_gene_counts(self._h, C.byref(p), C.byref(info)), "lsg_gene_counts")
+        self._gene_shape = (getattr(self, "_gene_rows", 0), self.n_cb)
+        return {k: getattr(info, k) for k, _ in GeneCountInfo._fields_ if k != "pad_"}
+
+    def gene_counts_fetch(self, matrix: bool = True):
+        """(matrix uint32 [n_rows, n_cb] in barcode-id order or None, tallies uint64 [n_cb, 4]: Assigned, NoFeatures, Ambiguity, Filtered)"""
+        shape = getattr(self, "_gene_shape", None)
+        if shape is None:
+            raise _lib.LsgError("gene_counts_fetch: nothing counted (gene_counts first)")
+        m = np.zeros(shape, np.uint32) if matrix else None
+        t = np.zeros((shape[1], 4), np.uint64)
+        _lib.check(self._lib.lsg_gene_counts_fetch(self._h, _ptr(m), _ptr(t)), "lsg_gene_counts_fetch")
+        return m, t
+
+    def gene_counts_set_text(self, row_names, col_order, barcodes, sep: str = ",") -> None:
+        """The strings format_table(TABLE_GENE_COUNTS) prints: the row names, the columns as barcode ids in output order (their strings
+        are barcodes[id]) and the separator (lsg_gene_counts_set_text)."""
+        def blob(strings):
+            enc = [s.encode() for s in strings]
+            off = np.zeros(len(enc) + 1, np.uint32)
+            if enc:
+                off[1:] = np.cumsum([len(e) for e in enc])
+            return b"".join(enc), off
+        order = np.ascontiguousarray(col_order, dtype=np.int32)
+        rows, row_off = blob(row_names)
+        cols, col_off = blob([barcodes[i] for i in order])
+        if len(sep.encode()) != 1:
+            raise ValueError("gene_counts_set_text: the separator is one byte")
+        if len(row_names) != getattr(self, "_gene_rows", 0):                      # (the library reads one name per row of the annotation)
+            raise ValueError("gene_counts_set_text: %d names for %d rows" % (len(row_names), getattr(self, "_gene_rows", 0)))
+        _lib.check(self._lib.lsg_gene_counts_set_text(self._h, rows, row_off.ctypes.data, len(order), _ptr(order), cols, col_off.ctypes.data, ord(sep)), "lsg_gene_counts_set_text")
+
+    def gene_counts_reset(self) -> None:
+        """frees the annotation, the matrix, the tallies and the table's text (lsg_gene_counts_reset)"""
+        _lib.check(self._lib.lsg_gene_counts_reset(self._h), "lsg_gene_counts_reset")
+        self._gene_shape = None; self._gene_rows = 0
+
     # ---- BnpC's posterior estimate (CellClustering/libs/utils.py:90-245; csrc/bnpc.hip; longsom_amd/bnpc.py drives it) ----
     def bnpc_load_samples(self, assignments, params=None) -> None:
         """Posterior samples resident: assignments [S, N] (labels in [0, N)) and, for bnpc_mean_params, params [S, k_max, M] float32

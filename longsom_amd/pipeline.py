@@ -19,7 +19,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import pandas as pd
 
-from . import bbfit, calling, hostio, pon, regions, tsvio
+from . import bbfit, calling, genecounts, hostio, pon, regions, tsvio
 from ._lib import CallParams, CountParams
 from . import _lib
 from .engine import Engine
@@ -491,13 +491,19 @@ def _write_step3(out: SnvOutputs, s2: bytes, params: SnvParams, t, **kw) -> None
 def run_snv(bam: str, barcodes_tsv: str, ref_fasta: str, out_dir: str, sample_id: str, params: Optional[SnvParams] = None,
             editing: Optional[str] = None, pon_sr: Optional[str] = None, pon_lr: Optional[str] = None,
             gnomad_af_json: Optional[str] = None, device: int = 0, engine: Optional[Engine] = None,
-            comm: Optional["regions.Comm"] = None, window_bytes: Optional[int] = None, filters: Optional[SplitFilters] = None) -> SnvOutputs:
+            comm: Optional["regions.Comm"] = None, window_bytes: Optional[int] = None, filters: Optional[SplitFilters] = None,
+            gene_counts: Optional["genecounts.Request"] = None) -> SnvOutputs:
     """One sample through the whole chain.  comm (world > 1): one rank per GPU, genomic regions sharded over the ranks, call
     `regions.Comm.from_env()` before anything touches the GPU.  window_bytes: stream the BAM in batches of about that many
     uncompressed bytes and count window by window (a BAM whose reads do not fit in HBM; decode overlaps the GPU work).  filters: SplitBam's
-    --max_nM / --max_NH / --n_trim (SplitFilters; None = off), applied by every form of the ingest."""
+    --max_nM / --max_NH / --n_trim (SplitFilters; None = off), applied by every form of the ingest.  gene_counts (a genecounts.Request):
+    the cell-by-gene read counts of the CNA branch are made from the same load before the chain runs (rules/CNACalling.gpu.smk); the load
+    then keeps every record (no load filter), and sharded or windowed runs refuse it: a read that reaches into two regions would count twice."""
     params = params or SnvParams()
     comm = comm or regions.Comm()
+    if gene_counts is not None and (comm.world > 1 or window_bytes):
+        raise ValueError("gene_counts needs the whole BAM resident at once: a read that reaches into two regions of a sharded (%d ranks) or windowed "
+                         "(--window_gb) run would be counted twice; run cli.gene_counts on its own" % comm.world)
     own = engine is None
     eng = engine or Engine(comm.local_device_index if comm.world > 1 else device)
     try:
@@ -508,7 +514,11 @@ def run_snv(bam: str, barcodes_tsv: str, ref_fasta: str, out_dir: str, sample_id
             return _run_snv_regions(bam, barcodes_tsv, ref_fasta, out_dir, sample_id, params, editing, pon_sr, pon_lr, gnomad_af_json, eng, comm, window_bytes, keep_store=not own,
                                     filters=filters)
         # (the chain counts its sample once: an engine of our own keeps no store for counts nobody will ask for)
-        res = load_sample(bam, barcodes_tsv, ref_fasta, eng, params.min_mapping_quality, count_params=params.count(), keep_store=not own, filters=filters)
+        # (... unless the gene counts read the load as well: a load without a store drops the reads its one count refuses)
+        res = load_sample(bam, barcodes_tsv, ref_fasta, eng, params.min_mapping_quality, count_params=params.count(), keep_store=not own or gene_counts is not None,
+                          filters=filters)
+        if gene_counts is not None:
+            genecounts.run_resident(eng, res.contig_names, res.table.barcodes, gene_counts, sample_id)
         return run_chain(res, res.table.celltype_of, res.table.celltype_names, res.dec.report, out_dir, sample_id, params, editing, pon_sr, pon_lr,
                          gnomad_af_json)
     finally:
