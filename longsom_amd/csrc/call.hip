@@ -24,7 +24,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
-#include <hipcub/hipcub.hpp>
+#include "cub_tmp.h"
 
 namespace lsg {
 
@@ -774,20 +774,12 @@ static int run_call_sized(lsg_ctx* c, const lsg_call_params* p, uint32_t tasks_p
     a.head_ref = reinterpret_cast<uint64_t*>(a.head_recs + (size_t)n_ne * 16);
     LSG_HIP(hipMemsetAsync(a.counters, 0, CT_WORDS * 8, st));
     hipLaunchKernelGGL(k_site_count, dim3((n_ne + 256) / 256), dim3(256), 0, st, a);
-    size_t tb = 0;
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, a.site_cnt, a.site_off, (int)(n_ne + 1), st));
-    if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-    tb = c->d_cub_tmp.cap;
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, a.site_cnt, a.site_off, (int)(n_ne + 1), st));
+    if (exclusive_sum(c->d_cub_tmp, a.site_cnt, a.site_off, n_ne + 1, st)) return -1;
     {   // the tile heads with at least one site, in order
         HasSites pred{a.site_cnt};
         hipcub::CountingInputIterator<uint32_t> it(0);
         uint32_t* d_nh = reinterpret_cast<uint32_t*>(a.counters + CT_HEADS);
-        size_t tb2 = 0;
-        LSG_HIP(hipcub::DeviceSelect::If(nullptr, tb2, it, heads, d_nh, (int)n_ne, pred, st));
-        if (c->d_cub_tmp.reserve(tb2 + 256)) return -1;
-        tb2 = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceSelect::If(c->d_cub_tmp.p, tb2, it, heads, d_nh, (int)n_ne, pred, st));
+        if (with_cub_tmp(c->d_cub_tmp, "hipcub::DeviceSelect::If", [&](void* p, size_t& tb) { return hipcub::DeviceSelect::If(p, tb, it, heads, d_nh, (int)n_ne, pred, st); })) return -1;
     }
     hipLaunchKernelGGL(k_head_recs, dim3((n_ne + 255) / 256), dim3(256), 0, st, a);
     LSG_HIP(hipMemcpyAsync(c->h_pin, a.site_off + n_ne, 4, hipMemcpyDeviceToHost, st));     // pinned landing zone
@@ -862,11 +854,7 @@ int run_select_calls(lsg_ctx* c, int kind, lsg_call* dst_device, int64_t capacit
     const SiteRec* sites = c->d_calls.as<SiteRec>();
     const CandCt* cands = c->ws[WS_CALL_CANDS].as<CandCt>();
     hipLaunchKernelGGL(k_flag_keep, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, st, sites, cands, c->n_ct, n, kind, keep);
-    size_t tb = 0;
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, off, (int)(n + 1), st));
-    if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-    tb = c->d_cub_tmp.cap;
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, keep, off, (int)(n + 1), st));
+    if (exclusive_sum(c->d_cub_tmp, keep, off, n + 1, st)) return -1;
     LSG_HIP(hipMemcpyAsync(c->h_pin, off + n, 4, hipMemcpyDeviceToHost, st));
     LSG_HIP(hipStreamSynchronize(st));
     const uint32_t k = *reinterpret_cast<const uint32_t*>(c->h_pin);

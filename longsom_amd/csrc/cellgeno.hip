@@ -18,10 +18,10 @@
 #include "lsg_ctx.h"
 #include "bb_tail.h"
 #include "text_sink.h"
+#include "text_table.h"
 #include <cmath>
 #include <cstring>
 #include <vector>
-#include <hipcub/hipcub.hpp>
 
 namespace lsg {
 int run_genotype(lsg_ctx* c, const lsg_genotype_params* p, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
@@ -231,9 +231,6 @@ template <bool PUT> __global__ __launch_bounds__(256) void k_cell_matrix(CellArg
     if (threadIdx.x == 0) { if (PUT) out[base] = '\n'; else a.len[r] = base + 1; }
 }
 
-struct Widen { __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)v; } };
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 int reserve_cells(lsg_ctx* c, int64_t n_sites, int32_t n_cb) {
     CellGeno& g = c->cg;
     const size_t cells = (size_t)(n_sites > 0 ? n_sites : 1) * (size_t)n_cb;
@@ -337,21 +334,12 @@ int run_cellgeno_set_text(lsg_ctx* c, const lsg_cellgeno_text* t) {
     if ((double)t->n_long * (double)B >= 2147483648.0) { set_error("%s: %lld x %d rows", who, (long long)t->n_long, B); return -2; }
     const size_t n_head = t->head_off[S], n_index = t->index_off[S], n_label = t->label_off[S], n_cbt = t->cb_off[B], n_ctt = t->ct_off[B];
     if ((n_head && !t->head) || (n_index && !t->index) || (n_label && !t->label) || (n_cbt && !t->cb) || (n_ctt && !t->ct)) { set_error("%s: bad arguments", who); return -2; }
-    size_t at = 0;
-    auto place = [&](size_t bytes) { const size_t here = at; at = align_up(at + bytes, 8); return here; };
-    g.head_off_at = place((size_t)(S + 1) * 4); g.index_off_at = place((size_t)(S + 1) * 4); g.label_off_at = place((size_t)(S + 1) * 4);
-    g.cb_off_at = place((size_t)(B + 1) * 4); g.ct_off_at = place((size_t)(B + 1) * 4);
-    g.long_order_at = place((size_t)t->n_long * 4); g.mat_order_at = place((size_t)t->n_mat * 4); g.col_src_at = place((size_t)t->n_cols * 4);
-    g.head_at = place(n_head); g.index_at = place(n_index); g.label_at = place(n_label); g.cb_at = place(n_cbt); g.ct_at = place(n_ctt);
-    std::vector<char> host(at + 8, 0);
-    auto copy = [&](size_t where, const void* src, size_t bytes) { if (bytes) memcpy(host.data() + where, src, bytes); };
-    copy(g.head_off_at, t->head_off, (size_t)(S + 1) * 4); copy(g.index_off_at, t->index_off, (size_t)(S + 1) * 4); copy(g.label_off_at, t->label_off, (size_t)(S + 1) * 4);
-    copy(g.cb_off_at, t->cb_off, (size_t)(B + 1) * 4); copy(g.ct_off_at, t->ct_off, (size_t)(B + 1) * 4);
-    copy(g.long_order_at, t->long_order, (size_t)t->n_long * 4); copy(g.mat_order_at, t->mat_order, (size_t)t->n_mat * 4); copy(g.col_src_at, t->col_src, (size_t)t->n_cols * 4);
-    copy(g.head_at, t->head, n_head); copy(g.index_at, t->index, n_index); copy(g.label_at, t->label, n_label); copy(g.cb_at, t->cb, n_cbt); copy(g.ct_at, t->ct, n_ctt);
-    if (g.text.reserve(host.size())) return -1;
-    LSG_HIP(hipMemcpyAsync(g.text.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-    LSG_HIP(hipStreamSynchronize(c->stream));
+    HostBlob b;
+    g.head_off_at = b.add(t->head_off, (size_t)(S + 1) * 4); g.index_off_at = b.add(t->index_off, (size_t)(S + 1) * 4); g.label_off_at = b.add(t->label_off, (size_t)(S + 1) * 4);
+    g.cb_off_at = b.add(t->cb_off, (size_t)(B + 1) * 4); g.ct_off_at = b.add(t->ct_off, (size_t)(B + 1) * 4);
+    g.long_order_at = b.add(t->long_order, (size_t)t->n_long * 4); g.mat_order_at = b.add(t->mat_order, (size_t)t->n_mat * 4); g.col_src_at = b.add(t->col_src, (size_t)t->n_cols * 4);
+    g.head_at = b.add(t->head, n_head); g.index_at = b.add(t->index, n_index); g.label_at = b.add(t->label, n_label); g.cb_at = b.add(t->cb, n_cbt); g.ct_at = b.add(t->ct, n_ctt);
+    if (b.upload(g.text, c->stream)) return -1;
     g.n_long = t->n_long; g.n_mat = t->n_mat; g.n_cols = t->n_cols; g.float_cells = t->float_cells ? 1 : 0;
     g.text_valid = true;
     return 0;
@@ -422,21 +410,9 @@ int run_cellgeno_filter(lsg_ctx* c, int32_t min_mut, int32_t min_cov, const uint
     if (N > 0) hipLaunchKernelGGL(k_bnpc_col_flags, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, cov_kept, cov_all, col_ok, N, (int32_t)R, min_cov, col_keep, col_int);
     LSG_HIP(hipGetLastError());
     // the kept rows (as sites) and the kept columns, compacted in input order
-    if (R > 0) {
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, mat_order, row_keep, rows, nsel, (int)R, st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceSelect::Flagged(c->d_cub_tmp.p, tb, mat_order, row_keep, rows, nsel, (int)R, st));
-    }
-    if (N > 0) {
-        hipcub::CountingInputIterator<int32_t> iota(0);
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, iota, col_keep, cols, nsel + 1, (int)N, st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceSelect::Flagged(c->d_cub_tmp.p, tb, iota, col_keep, cols, nsel + 1, (int)N, st));
-    }
+    hipcub::CountingInputIterator<int32_t> iota(0);
+    if (R > 0 && with_cub_tmp(c->d_cub_tmp, "hipcub::DeviceSelect::Flagged", [&](void* p, size_t& tb) { return hipcub::DeviceSelect::Flagged(p, tb, mat_order, row_keep, rows, nsel, (int)R, st); })) return -1;
+    if (N > 0 && with_cub_tmp(c->d_cub_tmp, "hipcub::DeviceSelect::Flagged", [&](void* p, size_t& tb) { return hipcub::DeviceSelect::Flagged(p, tb, iota, col_keep, cols, nsel + 1, (int)N, st); })) return -1;
     LSG_HIP(hipMemcpyAsync(c->h_pin, nsel, 8, hipMemcpyDeviceToHost, st));
     LSG_HIP(hipStreamSynchronize(st));
     int32_t got[2];
@@ -492,35 +468,19 @@ int run_format_cell_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     }
     c->tab_bytes[table] = -1;
     if (a.n == 0) { c->tab_bytes[table] = 0; return 0; }
-    // scratch: len[n + 1] | off[n + 1]
-    const size_t at_off = align_up((size_t)(a.n + 1) * 4, 256), total = at_off + (size_t)(a.n + 1) * 8;
-    if (g.scratch.reserve(total)) return -1;
-    a.len = g.scratch.as<uint32_t>();
-    uint64_t* off = reinterpret_cast<uint64_t*>(g.scratch.as<char>() + at_off);
-    a.off = off;
+    RowPlaces r;
+    if (row_places(g.scratch, a.n, -1, r)) return -1;
+    a.len = r.len; a.off = r.off;
     const unsigned row_blocks = (unsigned)((a.n + 1 + 255) / 256);
     if (is_long) hipLaunchKernelGGL(k_cell_row_len, dim3(row_blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_cell_matrix<false>, dim3((unsigned)(a.n + 1)), dim3(256), 0, st, a);
-    {
-        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> in(a.len, Widen());
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, off, (int)(a.n + 1), st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, in, off, (int)(a.n + 1), st));
-    }
-    LSG_HIP(hipMemcpyAsync(c->h_pin, off + a.n, 8, hipMemcpyDeviceToHost, st));
-    LSG_HIP(hipStreamSynchronize(st));
-    const int64_t bytes = (int64_t)c->h_pin[0];
-    if (bytes > 0) {
-        if (c->tab_text[table].reserve((size_t)bytes)) return -1;
-        a.text = c->tab_text[table].as<char>();
-        if (is_long) hipLaunchKernelGGL(k_cell_row_put, dim3(row_blocks), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_cell_matrix<true>, dim3((unsigned)a.n), dim3(256), 0, st, a);
-        LSG_HIP(hipGetLastError());
-        LSG_HIP(hipStreamSynchronize(st));
-    }
-    c->tab_bytes[table] = bytes;
+    int64_t bytes = 0;
+    if (finish_places(c, r, &bytes)) return -1;
+    if (print_table(c, table, bytes, [&](char* text) {
+            a.text = text;
+            if (is_long) hipLaunchKernelGGL(k_cell_row_put, dim3(row_blocks), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(k_cell_matrix<true>, dim3((unsigned)a.n), dim3(256), 0, st, a);
+        })) return -1;
     if (n_bytes) *n_bytes = bytes;
     return 0;
 }

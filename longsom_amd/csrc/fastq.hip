@@ -16,7 +16,7 @@
 #include "ingest_front.h"
 #include "fastq_core.h"
 #include "cbtable_host.h"
-#include <hipcub/hipcub.hpp>
+#include "cub_tmp.h"
 #include <chrono>
 #include <cstring>
 #include <string>
@@ -188,16 +188,15 @@ extern "C" int lsg_bam_fastq(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
         fr.release();
         return rc;
     };
-#define FQ_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return done(-1); } } while (0)
-    for (auto& e : ev) FQ_HIP(hipEventCreate(&e));
+    for (auto& e : ev) LSG_HIP_OR(hipEventCreate(&e), done(-1));
     if (routed) {
         if (d_h.reserve(cbt.hash.size() * 8) || d_id.reserve(cbt.id.size() * 4) || d_so.reserve(cbt.str_off.size() * 4) || d_sl.reserve(cbt.str_len.size() * 4) || d_str.reserve(cbt.strs.size() + 16))
             return done(-1);
-        FQ_HIP(hipMemcpyAsync(d_h.p, cbt.hash.data(), cbt.hash.size() * 8, hipMemcpyHostToDevice, st));
-        FQ_HIP(hipMemcpyAsync(d_id.p, cbt.id.data(), cbt.id.size() * 4, hipMemcpyHostToDevice, st));
-        FQ_HIP(hipMemcpyAsync(d_so.p, cbt.str_off.data(), cbt.str_off.size() * 4, hipMemcpyHostToDevice, st));
-        FQ_HIP(hipMemcpyAsync(d_sl.p, cbt.str_len.data(), cbt.str_len.size() * 4, hipMemcpyHostToDevice, st));
-        FQ_HIP(hipMemcpyAsync(d_str.p, cbt.strs.data(), cbt.strs.size(), hipMemcpyHostToDevice, st));
+        LSG_HIP_OR(hipMemcpyAsync(d_h.p, cbt.hash.data(), cbt.hash.size() * 8, hipMemcpyHostToDevice, st), done(-1));
+        LSG_HIP_OR(hipMemcpyAsync(d_id.p, cbt.id.data(), cbt.id.size() * 4, hipMemcpyHostToDevice, st), done(-1));
+        LSG_HIP_OR(hipMemcpyAsync(d_so.p, cbt.str_off.data(), cbt.str_off.size() * 4, hipMemcpyHostToDevice, st), done(-1));
+        LSG_HIP_OR(hipMemcpyAsync(d_sl.p, cbt.str_len.data(), cbt.str_len.size() * 4, hipMemcpyHostToDevice, st), done(-1));
+        LSG_HIP_OR(hipMemcpyAsync(d_str.p, cbt.strs.data(), cbt.strs.size(), hipMemcpyHostToDevice, st), done(-1));
     }
     // ---- H2D, inflate, CRC, the record chain, every record's offset
     if (const int rc = ingest_front(c, "lsg_bam_fastq", file, n_bytes, first_record_offset, 0, fr)) return done(rc);
@@ -209,23 +208,23 @@ extern "C" int lsg_bam_fastq(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
     std::vector<int64_t> ref_len;
     {
         std::vector<uint8_t> head((size_t)first_record_offset);
-        FQ_HIP(hipMemcpyAsync(head.data(), u, head.size(), hipMemcpyDeviceToHost, st));
-        FQ_HIP(hipStreamSynchronize(st));
+        LSG_HIP_OR(hipMemcpyAsync(head.data(), u, head.size(), hipMemcpyDeviceToHost, st), done(-1));
+        LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
         if (!parse_refs(head, ref_len)) { set_error("lsg_bam_fastq: no BAM header that ends at first_record_offset %lld", (long long)first_record_offset); return done(-1); }
     }
     if (d_reflen.reserve((ref_len.size() + 1) * 8) || d_recs.reserve((n_rec + 1) * sizeof(lsf::FqRec)) || d_len.reserve((n_rec + 2) * 4) || d_ct.reserve(n_rec + 16) ||
         d_offt.reserve((n_rec + 2) * 8) || d_off.reserve((n_rec + 2) * 8) || d_small.reserve(64)) return done(-1);
-    if (!ref_len.empty()) FQ_HIP(hipMemcpyAsync(d_reflen.p, ref_len.data(), ref_len.size() * 8, hipMemcpyHostToDevice, st));
+    if (!ref_len.empty()) LSG_HIP_OR(hipMemcpyAsync(d_reflen.p, ref_len.data(), ref_len.size() * 8, hipMemcpyHostToDevice, st), done(-1));
     unsigned long long* d_err = d_small.as<unsigned long long>();
     unsigned long long* d_np = d_err + 1;
-    FQ_HIP(hipMemsetAsync(d_err, 0xff, 8, st));
-    FQ_HIP(hipMemsetAsync(d_np, 0, LSG_MAX_CELLTYPES * 8, st));
-    FQ_HIP(hipMemsetAsync(status, 0, 4, st));
-    FQ_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status + 2), (int)0x7fffffff, 1, st));
-    FQ_HIP(hipMemsetAsync(d_len.as<uint32_t>() + n_rec, 0, 4, st));
-    FQ_HIP(hipMemsetAsync(d_ct.as<int8_t>() + n_rec, 0xff, 1, st));
+    LSG_HIP_OR(hipMemsetAsync(d_err, 0xff, 8, st), done(-1));
+    LSG_HIP_OR(hipMemsetAsync(d_np, 0, LSG_MAX_CELLTYPES * 8, st), done(-1));
+    LSG_HIP_OR(hipMemsetAsync(status, 0, 4, st), done(-1));
+    LSG_HIP_OR(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(status + 2), (int)0x7fffffff, 1, st), done(-1));
+    LSG_HIP_OR(hipMemsetAsync(d_len.as<uint32_t>() + n_rec, 0, 4, st), done(-1));
+    LSG_HIP_OR(hipMemsetAsync(d_ct.as<int8_t>() + n_rec, 0xff, 1, st), done(-1));
     // ---- pass 1: lengths, cell types, the first record that cannot be printed
-    FQ_HIP(hipEventRecord(ev[0], st));
+    LSG_HIP_OR(hipEventRecord(ev[0], st), done(-1));
     unsigned long long h_small[1 + LSG_MAX_CELLTYPES] = {~0ull, 0, 0, 0, 0};
     uint32_t hstat[4] = {0, 0, 0, 0};
     if (n_rec) {
@@ -236,9 +235,9 @@ extern "C" int lsg_bam_fastq(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
         a.min_mapq = min_mapq; a.max_nm = c->split_max_nm; a.max_nh = c->split_max_nh;
         a.recs = d_recs.as<lsf::FqRec>(); a.len = d_len.as<uint32_t>(); a.ct = d_ct.as<int8_t>(); a.err = d_err; a.n_printed = d_np; a.status = status;
         hipLaunchKernelGGL(k_fq_len, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, a);
-        FQ_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
-        FQ_HIP(hipMemcpyAsync(h_small, d_small.p, sizeof(h_small), hipMemcpyDeviceToHost, st));
-        FQ_HIP(hipStreamSynchronize(st));
+        LSG_HIP_OR(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st), done(-1));
+        LSG_HIP_OR(hipMemcpyAsync(h_small, d_small.p, sizeof(h_small), hipMemcpyDeviceToHost, st), done(-1));
+        LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
         if (hstat[0]) {
             static const char* why[] = {"", "a record shorter than its fixed fields", "a record whose fields exceed its block_size", "a record on a reference the header does not list",
                                         "a CIGAR operation above 8", "a CIGAR that does not cover the stored sequence", "an alignment that leaves its reference"};
@@ -248,11 +247,11 @@ extern "C" int lsg_bam_fastq(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
         if (h_small[0] != ~0ull) {
             const uint64_t ord = h_small[0] >> 3; const int kind = (int)(h_small[0] & 7u);
             uint64_t roff = 0; uint8_t head[32 + 256];
-            FQ_HIP(hipMemcpyAsync(&roff, fr.d_recoff.as<uint64_t>() + ord, 8, hipMemcpyDeviceToHost, st));
-            FQ_HIP(hipStreamSynchronize(st));
+            LSG_HIP_OR(hipMemcpyAsync(&roff, fr.d_recoff.as<uint64_t>() + ord, 8, hipMemcpyDeviceToHost, st), done(-1));
+            LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
             const size_t n_head = (size_t)(utotal - (roff + 4)) < sizeof(head) ? (size_t)(utotal - (roff + 4)) : sizeof(head);
-            FQ_HIP(hipMemcpyAsync(head, u + roff + 4, n_head, hipMemcpyDeviceToHost, st));
-            FQ_HIP(hipStreamSynchronize(st));
+            LSG_HIP_OR(hipMemcpyAsync(head, u + roff + 4, n_head, hipMemcpyDeviceToHost, st), done(-1));
+            LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
             const uint32_t l_name = head[8];                 // validated: the name lies inside the record
             const std::string name((const char*)head + 32, l_name ? strnlen((const char*)head + 32, l_name - 1u) : 0u);
             info->bad_ordinal = (int64_t)ord; info->bad_kind = kind;
@@ -265,20 +264,16 @@ extern "C" int lsg_bam_fastq(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
     hipcub::CountingInputIterator<uint32_t> iota(0);
     for (int32_t t = 0; t < n_ct && n_rec; ++t) {
         hipcub::TransformInputIterator<unsigned long long, LenOf, hipcub::CountingInputIterator<uint32_t>> it(iota, LenOf{d_len.as<uint32_t>(), d_ct.as<int8_t>(), t});
-        size_t tb = 0;
-        FQ_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, d_offt.as<unsigned long long>(), (int)(n_rec + 1), st));
-        if (fr.d_tmp.reserve(tb + 256)) return done(-1);
-        tb = fr.d_tmp.cap;
-        FQ_HIP(hipcub::DeviceScan::ExclusiveSum(fr.d_tmp.p, tb, it, d_offt.as<unsigned long long>(), (int)(n_rec + 1), st));
+        if (exclusive_sum(fr.d_tmp, it, d_offt.as<unsigned long long>(), n_rec + 1, st)) return done(-1);
         hipLaunchKernelGGL(k_fq_place, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, d_ct.as<int8_t>(), t, d_offt.as<unsigned long long>(), (unsigned long long)total, n_rec,
                            d_off.as<unsigned long long>());
         unsigned long long bytes_t = 0;
-        FQ_HIP(hipMemcpyAsync(&bytes_t, d_offt.as<unsigned long long>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-        FQ_HIP(hipStreamSynchronize(st));
+        LSG_HIP_OR(hipMemcpyAsync(&bytes_t, d_offt.as<unsigned long long>() + n_rec, 8, hipMemcpyDeviceToHost, st), done(-1));
+        LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
         info->n_printed[t] = (int64_t)h_small[1 + t]; info->n_bytes[t] = (int64_t)bytes_t;
         total += (int64_t)bytes_t;
     }
-    FQ_HIP(hipEventRecord(ev[1], st));
+    LSG_HIP_OR(hipEventRecord(ev[1], st), done(-1));
     // ---- pass 2: the bytes
     if (total) {
         if (c->tab_text[LSG_TABLE_FASTQ].reserve((size_t)total + 16)) return done(-1);
@@ -287,12 +282,11 @@ extern "C" int lsg_bam_fastq(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
         if (g > cap) g = cap;
         hipLaunchKernelGGL(k_fq_print, dim3(g), dim3(256), 0, st, p);
     }
-    FQ_HIP(hipEventRecord(ev[2], st));
-    FQ_HIP(hipGetLastError());
-    FQ_HIP(hipStreamSynchronize(st));
+    LSG_HIP_OR(hipEventRecord(ev[2], st), done(-1));
+    LSG_HIP_OR(hipGetLastError(), done(-1));
+    LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
     (void)hipEventElapsedTime(&info->ms_length, ev[0], ev[1]); (void)hipEventElapsedTime(&info->ms_print, ev[1], ev[2]);
     c->tab_bytes[LSG_TABLE_FASTQ] = total;
     info->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_all).count();
     return done(0);
-#undef FQ_HIP
 }

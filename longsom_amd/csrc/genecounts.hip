@@ -17,7 +17,7 @@
 #include "lsg_ctx.h"
 #include "genecounts_core.h"
 #include "text_sink.h"
-#include <hipcub/hipcub.hpp>
+#include "text_table.h"
 #include <chrono>
 #include <cstring>
 #include <vector>
@@ -118,9 +118,6 @@ template <bool PUT> __global__ __launch_bounds__(256) void k_gc_print(GcPrint a)
     if (lane == 0) { if (PUT) out[base] = '\n'; else a.len[line] = base + 1u; }
 }
 
-struct Widen { __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)v; } };
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 void drop_matrix(lsg_ctx* c) {
     GeneCounts& g = c->gc;
     g.matrix.release(); g.tallies.release(); g.state.release(); g.text.release(); g.scratch.release();
@@ -143,30 +140,13 @@ int run_format_gene_table(lsg_ctx* c, int64_t* n_bytes) {
     a.row_off = reinterpret_cast<const uint32_t*>(tx + g.row_off_at); a.row_txt = tx + g.row_txt_at;
     a.col_src = reinterpret_cast<const int32_t*>(tx + g.col_src_at); a.col_off = reinterpret_cast<const uint32_t*>(tx + g.col_off_at); a.col_txt = tx + g.col_txt_at;
     const int64_t lines = (int64_t)g.n_rows + 1;
-    // scratch: len[lines + 1] | off[lines + 1]
-    const size_t at_off = align_up((size_t)(lines + 1) * 4, 256), total = at_off + (size_t)(lines + 1) * 8;
-    if (g.scratch.reserve(total)) return -1;
-    a.len = g.scratch.as<uint32_t>();
-    uint64_t* off = reinterpret_cast<uint64_t*>(g.scratch.as<char>() + at_off);
-    a.off = off;
+    RowPlaces r;
+    if (row_places(g.scratch, lines, -1, r)) return -1;
+    a.len = r.len; a.off = r.off;
     hipLaunchKernelGGL(k_gc_print<false>, dim3((unsigned)((lines + 1 + 3) / 4)), dim3(256), 0, st, a);
-    {
-        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> in(a.len, Widen());
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, off, (int)(lines + 1), st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, in, off, (int)(lines + 1), st));
-    }
-    LSG_HIP(hipMemcpyAsync(c->h_pin, off + lines, 8, hipMemcpyDeviceToHost, st));
-    LSG_HIP(hipStreamSynchronize(st));
-    const int64_t bytes = (int64_t)c->h_pin[0];
-    if (c->tab_text[LSG_TABLE_GENE_COUNTS].reserve((size_t)bytes)) return -1;
-    a.text = c->tab_text[LSG_TABLE_GENE_COUNTS].as<char>();
-    hipLaunchKernelGGL(k_gc_print<true>, dim3((unsigned)((lines + 3) / 4)), dim3(256), 0, st, a);
-    LSG_HIP(hipGetLastError());
-    LSG_HIP(hipStreamSynchronize(st));
-    c->tab_bytes[LSG_TABLE_GENE_COUNTS] = bytes;
+    int64_t bytes = 0;
+    if (finish_places(c, r, &bytes)) return -1;
+    if (print_table(c, LSG_TABLE_GENE_COUNTS, bytes, [&](char* text) { a.text = text; hipLaunchKernelGGL(k_gc_print<true>, dim3((unsigned)((lines + 3) / 4)), dim3(256), 0, st, a); })) return -1;
     if (n_bytes) *n_bytes = bytes;
     return 0;
 }
@@ -238,18 +218,17 @@ extern "C" int lsg_gene_counts(lsg_ctx* c, const lsg_gene_count_params* p, lsg_g
     a.matrix = g.matrix.as<uint32_t>(); a.tallies = g.tallies.as<unsigned long long>(); a.small = g.small.as<unsigned long long>();
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto done = [&](int rc) { for (auto& e : ev) if (e) (void)hipEventDestroy(e); return rc; };
-#define GC_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return done(-1); } } while (0)
-    for (auto& e : ev) GC_HIP(hipEventCreate(&e));
-    if (R) { GC_HIP(hipMemsetAsync(a.lo, 0xff, (size_t)R * 4, st)); GC_HIP(hipMemsetAsync(a.hi, 0, (size_t)R * 4, st)); }
-    GC_HIP(hipMemsetAsync(a.small, 0, 64, st));
-    GC_HIP(hipEventRecord(ev[0], st));
+    for (auto& e : ev) LSG_HIP_OR(hipEventCreate(&e), done(-1));
+    if (R) { LSG_HIP_OR(hipMemsetAsync(a.lo, 0xff, (size_t)R * 4, st), done(-1)); LSG_HIP_OR(hipMemsetAsync(a.hi, 0, (size_t)R * 4, st), done(-1)); }
+    LSG_HIP_OR(hipMemsetAsync(a.small, 0, 64, st), done(-1));
+    LSG_HIP_OR(hipEventRecord(ev[0], st), done(-1));
     if (S && R && g.n_iv) hipLaunchKernelGGL(k_gc_segments, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, a);
-    GC_HIP(hipEventRecord(ev[1], st));
+    LSG_HIP_OR(hipEventRecord(ev[1], st), done(-1));
     if (R) hipLaunchKernelGGL(k_gc_reads, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, a);
-    GC_HIP(hipEventRecord(ev[2], st));
-    GC_HIP(hipGetLastError());
-    GC_HIP(hipMemcpyAsync(c->h_pin, a.small, 48, hipMemcpyDeviceToHost, st));
-    GC_HIP(hipStreamSynchronize(st));
+    LSG_HIP_OR(hipEventRecord(ev[2], st), done(-1));
+    LSG_HIP_OR(hipGetLastError(), done(-1));
+    LSG_HIP_OR(hipMemcpyAsync(c->h_pin, a.small, 48, hipMemcpyDeviceToHost, st), done(-1));
+    LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
     unsigned long long h[6];
     memcpy(h, c->h_pin, sizeof(h));
     info->n_reads = R; info->n_segs = S;
@@ -258,7 +237,6 @@ extern "C" int lsg_gene_counts(lsg_ctx* c, const lsg_gene_count_params* p, lsg_g
     info->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_all).count();
     if (h[5]) { set_error("%s: a cell of the matrix passed 2^32 - 1 reads", who); return done(-1); }
     return done(0);
-#undef GC_HIP
 }
 
 extern "C" int lsg_gene_counts_fetch(lsg_ctx* c, uint32_t* matrix, uint64_t* tallies) {
@@ -288,17 +266,10 @@ extern "C" int lsg_gene_counts_set_text(lsg_ctx* c, const char* row_names, const
     for (int32_t i = 0; i < n_cols; ++i) if (col_src[i] < 0 || col_src[i] >= g.n_cb) { set_error("%s: col_src[%d] is not a barcode", who, i); return -2; }
     const size_t n_row_txt = row_off[N], n_col_txt = col_off[n_cols];
     if ((n_row_txt && !row_names) || (n_col_txt && !col_names)) { set_error("%s: bad arguments", who); return -2; }
-    size_t at = 0;
-    auto place = [&](size_t bytes) { const size_t here = at; at = align_up(at + bytes, 8); return here; };
-    g.row_off_at = place((size_t)(N + 1) * 4); g.col_src_at = place((size_t)n_cols * 4); g.col_off_at = place((size_t)(n_cols + 1) * 4);
-    g.row_txt_at = place(n_row_txt); g.col_txt_at = place(n_col_txt);
-    std::vector<char> host(at + 8, 0);
-    auto copy = [&](size_t where, const void* src, size_t bytes) { if (bytes) memcpy(host.data() + where, src, bytes); };
-    copy(g.row_off_at, row_off, (size_t)(N + 1) * 4); copy(g.col_src_at, col_src, (size_t)n_cols * 4); copy(g.col_off_at, col_off, (size_t)(n_cols + 1) * 4);
-    copy(g.row_txt_at, row_names, n_row_txt); copy(g.col_txt_at, col_names, n_col_txt);
-    if (g.text.reserve(host.size())) return -1;
-    LSG_HIP(hipMemcpyAsync(g.text.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-    LSG_HIP(hipStreamSynchronize(c->stream));
+    HostBlob b;
+    g.row_off_at = b.add(row_off, (size_t)(N + 1) * 4); g.col_src_at = b.add(col_src, (size_t)n_cols * 4); g.col_off_at = b.add(col_off, (size_t)(n_cols + 1) * 4);
+    g.row_txt_at = b.add(row_names, n_row_txt); g.col_txt_at = b.add(col_names, n_col_txt);
+    if (b.upload(g.text, c->stream)) return -1;
     g.n_cols = n_cols; g.sep = (char)separator; g.text_valid = true;
     return 0;
 }

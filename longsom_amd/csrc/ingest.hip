@@ -22,7 +22,7 @@
 #include "crc_core.h"
 #include "cbtable_host.h"
 #include "ingest_front.h"
-#include <hipcub/hipcub.hpp>
+#include "cub_tmp.h"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -203,7 +203,7 @@ __global__ void k_rec_info(RecArgs a) {
 }
 
 struct KeepFlag { const uint8_t* k; __host__ __device__ uint32_t operator()(const uint32_t& i) const { return k[i] & 1u; } };
-struct Widen { const uint32_t* v; __host__ __device__ unsigned long long operator()(const uint32_t& i) const { return (unsigned long long)v[i]; } };
+struct WidenAt { const uint32_t* v; __host__ __device__ unsigned long long operator()(const uint32_t& i) const { return (unsigned long long)v[i]; } };
 
 struct EmitArgs {
     const uint8_t* u; const uint64_t* rec_off; uint64_t n_rec; int32_t legacy, phased, n_trim;
@@ -265,8 +265,7 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
         f.d_land.reserve(((size_t)n_blk + 1) * 8) || f.d_nrec.reserve(((size_t)n_blk + 2) * 4) || f.d_base.reserve(((size_t)n_blk + 2) * 4) || f.d_status.reserve(64))
         return -1;
     for (auto& e : f.ev) if (hipEventCreate(&e) != hipSuccess) { set_error("%s: hipEventCreate failed", who); return -1; }
-#define ING_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
-    ING_HIP(hipEventRecord(f.ev[0], st));
+    LSG_HIP(hipEventRecord(f.ev[0], st));
     {   // the file's bytes, through two pinned staging buffers (the caller's memory is usually a read-only file mapping: pageable, and
         // not every runtime can pin it): the CPU fills one while the DMA engine drains the other
         const size_t CH = 32u << 20;
@@ -286,10 +285,10 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
         for (int i = 0; i < 2; ++i) { if (pe[i]) (void)hipEventDestroy(pe[i]); if (pin[i]) (void)hipHostFree(pin[i]); }
         if (!ok) { set_error("%s: copying the file to the device failed: %s", who, hipGetErrorString(hipGetLastError())); return -1; }
     }
-    ING_HIP(hipMemcpyAsync(f.d_blk.p, blocks.data(), (size_t)n_blk * sizeof(IngBlk), hipMemcpyHostToDevice, st));
-    ING_HIP(hipMemsetAsync(f.d_status.p, 0, 64, st));
-    ING_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f.d_status.as<uint32_t>() + 1), (int)0x7fffffff, 2, st));
-    ING_HIP(hipEventRecord(f.ev[1], st));
+    LSG_HIP(hipMemcpyAsync(f.d_blk.p, blocks.data(), (size_t)n_blk * sizeof(IngBlk), hipMemcpyHostToDevice, st));
+    LSG_HIP(hipMemsetAsync(f.d_status.p, 0, 64, st));
+    LSG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(f.d_status.as<uint32_t>() + 1), (int)0x7fffffff, 2, st));
+    LSG_HIP(hipEventRecord(f.ev[1], st));
     // ---- inflate
     const IngBlk* dblk = f.d_blk.as<IngBlk>();
     uint32_t* status = f.d_status.as<uint32_t>();
@@ -301,10 +300,10 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
         if (f.d_tmp.reserve((size_t)g * lsi::T_LENS * 64)) return -3;
         hipLaunchKernelGGL(k_inflate, dim3(g), dim3(64), 0, st, f.d_comp.as<uint8_t>(), dblk, n_blk, f.d_u.as<uint8_t>(), status, f.d_tmp.as<uint8_t>());
     }
-    ING_HIP(hipEventRecord(f.ev[2], st));
+    LSG_HIP(hipEventRecord(f.ev[2], st));
     uint32_t hstat[4] = {0, 0, 0, 0};
-    ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
-    ING_HIP(hipStreamSynchronize(st));
+    LSG_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
+    LSG_HIP(hipStreamSynchronize(st));
     if (hstat[0] & 1u) { set_error("%s: inflate failed in BGZF block %u", who, hstat[1]); return -1; }
     f.d_comp.release();
     if (!getenv("LSG_NO_BGZF_CRC")) {                     // every block's CRC32 against its trailer (k_block_crc)
@@ -332,8 +331,8 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
     {
         std::vector<uint64_t> h_in(n_blk);
         for (uint32_t b = 0; b < n_blk; ++b) h_in[b] = b == 0 ? (uint64_t)first_record_offset : blocks[b].uoff;      // htslib: a block starts on a record boundary
-        ING_HIP(hipMemcpyAsync(in, h_in.data(), (size_t)n_blk * 8, hipMemcpyHostToDevice, st));
-        ING_HIP(hipStreamSynchronize(st));
+        LSG_HIP(hipMemcpyAsync(in, h_in.data(), (size_t)n_blk * 8, hipMemcpyHostToDevice, st));
+        LSG_HIP(hipStreamSynchronize(st));
     }
     const int max_rounds = env_int("LSG_CHAIN_ROUNDS", 512);
     int rounds = 0;
@@ -343,33 +342,29 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
             set_error("%s: the records of this BAM straddle its BGZF blocks (not written by htslib's bam_write1?): %d rounds did not settle the record chain; decode it on the host", who, max_rounds);
             return -4;
         }
-        ING_HIP(hipMemsetAsync(status, 0, 4, st));
-        ING_HIP(hipMemsetAsync(changed, 0, 4, st));
+        LSG_HIP(hipMemsetAsync(status, 0, 4, st));
+        LSG_HIP(hipMemsetAsync(changed, 0, 4, st));
         hipLaunchKernelGGL(k_chain, dim3((n_blk + 255) / 256), dim3(256), 0, st, u, utotal, dblk, n_blk, in, land, f.d_nrec.as<uint32_t>(), status, range);
         hipLaunchKernelGGL(k_chain_fix, dim3((n_blk + 255) / 256), dim3(256), 0, st, dblk, n_blk, (uint64_t)first_record_offset, in, land, changed);
-        ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
+        LSG_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
+        LSG_HIP(hipStreamSynchronize(st));
         if (hstat[3] == 0) break;                      // every block started where its predecessor's chain landed: the walk just made is the true one
     }
     f.rounds = rounds;
     if (hstat[0] & 6u) { set_error("%s: %s", who, (hstat[0] & 2u) ? "truncated record at the end of the file" : "record with an impossible block_size"); return -1; }
     {
         uint64_t last_land = 0;
-        ING_HIP(hipMemcpyAsync(&last_land, land + (n_blk - 1), 8, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
+        LSG_HIP(hipMemcpyAsync(&last_land, land + (n_blk - 1), 8, hipMemcpyDeviceToHost, st));
+        LSG_HIP(hipStreamSynchronize(st));
         if (!range && last_land != utotal) { set_error("%s: truncated record at the end of the file", who); return -1; }
     }
-    ING_HIP(hipEventRecord(f.ev[3], st));
+    LSG_HIP(hipEventRecord(f.ev[3], st));
     uint32_t n_rec32 = 0;
     {
-        ING_HIP(hipMemsetAsync(f.d_nrec.as<uint32_t>() + n_blk, 0, 4, st));
-        size_t tb = 0;
-        ING_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, f.d_nrec.as<uint32_t>(), f.d_base.as<uint32_t>(), (int)(n_blk + 1), st));
-        if (f.d_tmp.reserve(tb + 256)) return -1;
-        tb = f.d_tmp.cap;
-        ING_HIP(hipcub::DeviceScan::ExclusiveSum(f.d_tmp.p, tb, f.d_nrec.as<uint32_t>(), f.d_base.as<uint32_t>(), (int)(n_blk + 1), st));
-        ING_HIP(hipMemcpyAsync(&n_rec32, f.d_base.as<uint32_t>() + n_blk, 4, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
+        LSG_HIP(hipMemsetAsync(f.d_nrec.as<uint32_t>() + n_blk, 0, 4, st));
+        if (exclusive_sum(f.d_tmp, f.d_nrec.as<uint32_t>(), f.d_base.as<uint32_t>(), n_blk + 1, st)) return -1;
+        LSG_HIP(hipMemcpyAsync(&n_rec32, f.d_base.as<uint32_t>() + n_blk, 4, hipMemcpyDeviceToHost, st));
+        LSG_HIP(hipStreamSynchronize(st));
     }
     const uint64_t n_rec = n_rec32;
     if (n_rec >= 0x7fffff00ull) { set_error("%s: more than 2^31 records; load the file in windows on the host", who); return -2; }
@@ -378,7 +373,6 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
     if (n_rec) hipLaunchKernelGGL(k_rec_list, dim3((n_blk + 255) / 256), dim3(256), 0, st, u, dblk, n_blk, in, f.d_base.as<uint32_t>(), f.d_recoff.as<uint64_t>());
     (void)hipEventElapsedTime(&f.ms_h2d, f.ev[0], f.ev[1]); (void)hipEventElapsedTime(&f.ms_inflate, f.ev[1], f.ev[2]); (void)hipEventElapsedTime(&f.ms_chain, f.ev[2], f.ev[3]);
     return 0;
-#undef ING_HIP
 }
 
 } // namespace lsg
@@ -416,17 +410,16 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
         d_h.reserve(cbt.hash.size() * 8) || d_id.reserve(cbt.id.size() * 4) || d_so.reserve(cbt.str_off.size() * 4) || d_sl.reserve(cbt.str_len.size() * 4) || d_str.reserve(cbt.strs.size() + 16))
         return done_ev(-1);
     if (hipEventCreate(&ev_end) != hipSuccess) { set_error("lsg_load_bam: hipEventCreate failed"); return done_ev(-1); }
-#define ING_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return done_ev(-1); } } while (0)
-    ING_HIP(hipMemcpyAsync(d_h.p, cbt.hash.data(), cbt.hash.size() * 8, hipMemcpyHostToDevice, st));
-    ING_HIP(hipMemcpyAsync(d_id.p, cbt.id.data(), cbt.id.size() * 4, hipMemcpyHostToDevice, st));
-    ING_HIP(hipMemcpyAsync(d_so.p, cbt.str_off.data(), cbt.str_off.size() * 4, hipMemcpyHostToDevice, st));
-    ING_HIP(hipMemcpyAsync(d_sl.p, cbt.str_len.data(), cbt.str_len.size() * 4, hipMemcpyHostToDevice, st));
-    ING_HIP(hipMemcpyAsync(d_str.p, cbt.strs.data(), cbt.strs.size(), hipMemcpyHostToDevice, st));
-    ING_HIP(hipMemsetAsync(d_cnt.p, 0, 64, st));
-    ING_HIP(hipMemsetAsync(d_rsn.p, 0, lsr::N_REASONS * 8, st));                                    // reason counts 0, first ordinals and the error ~0
-    ING_HIP(hipMemsetAsync(d_rsn.as<unsigned long long>() + lsr::N_REASONS, 0xff, (lsr::N_REASONS + 1) * 8, st));
-    ING_HIP(hipMemsetAsync(d_tpass.p, 0, ((size_t)n_tally + 1) * 8, st));
-    ING_HIP(hipMemsetAsync(d_tlow.p, 0, ((size_t)n_tally + 1) * 8, st));
+    LSG_HIP_OR(hipMemcpyAsync(d_h.p, cbt.hash.data(), cbt.hash.size() * 8, hipMemcpyHostToDevice, st), done_ev(-1));
+    LSG_HIP_OR(hipMemcpyAsync(d_id.p, cbt.id.data(), cbt.id.size() * 4, hipMemcpyHostToDevice, st), done_ev(-1));
+    LSG_HIP_OR(hipMemcpyAsync(d_so.p, cbt.str_off.data(), cbt.str_off.size() * 4, hipMemcpyHostToDevice, st), done_ev(-1));
+    LSG_HIP_OR(hipMemcpyAsync(d_sl.p, cbt.str_len.data(), cbt.str_len.size() * 4, hipMemcpyHostToDevice, st), done_ev(-1));
+    LSG_HIP_OR(hipMemcpyAsync(d_str.p, cbt.strs.data(), cbt.strs.size(), hipMemcpyHostToDevice, st), done_ev(-1));
+    LSG_HIP_OR(hipMemsetAsync(d_cnt.p, 0, 64, st), done_ev(-1));
+    LSG_HIP_OR(hipMemsetAsync(d_rsn.p, 0, lsr::N_REASONS * 8, st), done_ev(-1));                                    // reason counts 0, first ordinals and the error ~0
+    LSG_HIP_OR(hipMemsetAsync(d_rsn.as<unsigned long long>() + lsr::N_REASONS, 0xff, (lsr::N_REASONS + 1) * 8, st), done_ev(-1));
+    LSG_HIP_OR(hipMemsetAsync(d_tpass.p, 0, ((size_t)n_tally + 1) * 8, st), done_ev(-1));
+    LSG_HIP_OR(hipMemsetAsync(d_tlow.p, 0, ((size_t)n_tally + 1) * 8, st), done_ev(-1));
     // ---- H2D, inflate, CRC, the record chain, every record's offset
     if (const int rc = ingest_front(c, "lsg_load_bam", file, n_bytes, first_record_offset, range, fr)) return done_ev(rc);
     const uint64_t utotal = fr.utotal, n_rec = fr.n_rec;
@@ -451,20 +444,20 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
         ra.range = range; ra.count_lo = count_lo; ra.count_hi = count_hi; ra.last_key = d_cnt.as<unsigned long long>() + 6;
         ra.max_nm = c->split_max_nm; ra.max_nh = c->split_max_nh; ra.n_trim = c->split_n_trim;
         ra.rsn_n = d_rsn.as<unsigned long long>(); ra.rsn_first = ra.rsn_n + lsr::N_REASONS; ra.err = ra.rsn_n + 2 * lsr::N_REASONS;
-        ING_HIP(hipMemsetAsync(status, 0, 4, st));
+        LSG_HIP_OR(hipMemsetAsync(status, 0, 4, st), done_ev(-1));
         hipLaunchKernelGGL(k_rec_info, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, ra);
-        ING_HIP(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st));
+        LSG_HIP_OR(hipMemcpyAsync(hstat, status, 16, hipMemcpyDeviceToHost, st), done_ev(-1));
         unsigned long long herr = ~0ull;
-        ING_HIP(hipMemcpyAsync(&herr, ra.err, 8, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
+        LSG_HIP_OR(hipMemcpyAsync(&herr, ra.err, 8, hipMemcpyDeviceToHost, st), done_ev(-1));
+        LSG_HIP_OR(hipStreamSynchronize(st), done_ev(-1));
         if (!hstat[0] && herr != ~0ull) {                  // a read the reference's split_bam raises on (SplitBamCellTypes.py:98-109,161-168): named, not crashed on
             const uint64_t ord = herr >> 3; const unsigned kind = (unsigned)(herr & 7u);
             uint64_t roff = 0; uint8_t head[32 + 256];
-            ING_HIP(hipMemcpyAsync(&roff, d_recoff.as<uint64_t>() + ord, 8, hipMemcpyDeviceToHost, st));
-            ING_HIP(hipStreamSynchronize(st));
+            LSG_HIP_OR(hipMemcpyAsync(&roff, d_recoff.as<uint64_t>() + ord, 8, hipMemcpyDeviceToHost, st), done_ev(-1));
+            LSG_HIP_OR(hipStreamSynchronize(st), done_ev(-1));
             const size_t n_head = (size_t)(utotal - (roff + 4)) < sizeof(head) ? (size_t)(utotal - (roff + 4)) : sizeof(head);
-            ING_HIP(hipMemcpyAsync(head, u + roff + 4, n_head, hipMemcpyDeviceToHost, st));
-            ING_HIP(hipStreamSynchronize(st));
+            LSG_HIP_OR(hipMemcpyAsync(head, u + roff + 4, n_head, hipMemcpyDeviceToHost, st), done_ev(-1));
+            LSG_HIP_OR(hipStreamSynchronize(st), done_ev(-1));
             const uint32_t l_name = head[8];                 // validated: the name lies inside the record
             char name[256]; const size_t ln = l_name ? l_name - 1u : 0u;      // (<= 254: l_name is a byte)
             memcpy(name, head + 32, ln); name[ln] = 0;
@@ -484,32 +477,20 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
         hipcub::CountingInputIterator<uint32_t> iota(0);
         {
             hipcub::TransformInputIterator<uint32_t, KeepFlag, hipcub::CountingInputIterator<uint32_t>> it(iota, KeepFlag{d_keep.as<uint8_t>()});
-            size_t tb = 0;
-            ING_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, d_ridx.as<uint32_t>(), (int)(n_rec + 1), st));
-            if (d_tmp.reserve(tb + 256)) return done_ev(-1);
-            tb = d_tmp.cap;
-            ING_HIP(hipMemsetAsync(d_keep.as<uint8_t>() + n_rec, 0, 1, st));
-            ING_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, it, d_ridx.as<uint32_t>(), (int)(n_rec + 1), st));
+            LSG_HIP_OR(hipMemsetAsync(d_keep.as<uint8_t>() + n_rec, 0, 1, st), done_ev(-1));
+            if (exclusive_sum(d_tmp, it, d_ridx.as<uint32_t>(), n_rec + 1, st)) return done_ev(-1);
         }
         {
-            ING_HIP(hipMemsetAsync(d_nseg.as<uint32_t>() + n_rec, 0, 4, st));
-            ING_HIP(hipMemsetAsync(d_nev.as<uint32_t>() + n_rec, 0, 4, st));
-            size_t tb = 0;
-            ING_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_nseg.as<uint32_t>(), d_soff.as<uint32_t>(), (int)(n_rec + 1), st));
-            if (d_tmp.reserve(tb + 256)) return done_ev(-1);
-            tb = d_tmp.cap;
-            ING_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_nseg.as<uint32_t>(), d_soff.as<uint32_t>(), (int)(n_rec + 1), st));
-            hipcub::TransformInputIterator<unsigned long long, Widen, hipcub::CountingInputIterator<uint32_t>> it(iota, Widen{d_nev.as<uint32_t>()});
-            tb = 0;
-            ING_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, it, d_eoff.as<unsigned long long>(), (int)(n_rec + 1), st));
-            if (d_tmp.reserve(tb + 256)) return done_ev(-1);
-            tb = d_tmp.cap;
-            ING_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, it, d_eoff.as<unsigned long long>(), (int)(n_rec + 1), st));
+            LSG_HIP_OR(hipMemsetAsync(d_nseg.as<uint32_t>() + n_rec, 0, 4, st), done_ev(-1));
+            LSG_HIP_OR(hipMemsetAsync(d_nev.as<uint32_t>() + n_rec, 0, 4, st), done_ev(-1));
+            if (exclusive_sum(d_tmp, d_nseg.as<uint32_t>(), d_soff.as<uint32_t>(), n_rec + 1, st)) return done_ev(-1);
+            hipcub::TransformInputIterator<unsigned long long, WidenAt, hipcub::CountingInputIterator<uint32_t>> it(iota, WidenAt{d_nev.as<uint32_t>()});
+            if (exclusive_sum(d_tmp, it, d_eoff.as<unsigned long long>(), n_rec + 1, st)) return done_ev(-1);
         }
-        ING_HIP(hipMemcpyAsync(&R, d_ridx.as<uint32_t>() + n_rec, 4, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipMemcpyAsync(&S, d_soff.as<uint32_t>() + n_rec, 4, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipMemcpyAsync(&E, d_eoff.as<unsigned long long>() + n_rec, 8, hipMemcpyDeviceToHost, st));
-        ING_HIP(hipStreamSynchronize(st));
+        LSG_HIP_OR(hipMemcpyAsync(&R, d_ridx.as<uint32_t>() + n_rec, 4, hipMemcpyDeviceToHost, st), done_ev(-1));
+        LSG_HIP_OR(hipMemcpyAsync(&S, d_soff.as<uint32_t>() + n_rec, 4, hipMemcpyDeviceToHost, st), done_ev(-1));
+        LSG_HIP_OR(hipMemcpyAsync(&E, d_eoff.as<unsigned long long>() + n_rec, 8, hipMemcpyDeviceToHost, st), done_ev(-1));
+        LSG_HIP_OR(hipStreamSynchronize(st), done_ev(-1));
     }
     // ---- the read-record arrays, on the device
     DevBuf &o_tid = c->gen[0], &o_pos = c->gen[1], &o_flag = c->gen[2], &o_mapq = c->gen[3], &o_cb = c->gen[4], &o_sread = c->gen[5], &o_sstart = c->gen[6],
@@ -517,7 +498,7 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     if (o_tid.reserve(((size_t)R + 1) * 4) || o_pos.reserve(((size_t)R + 1) * 4) || o_flag.reserve(((size_t)R + 1) * 2) || o_mapq.reserve((size_t)R + 1) || o_cb.reserve(((size_t)R + 1) * 4) ||
         o_sread.reserve(((size_t)S + 1) * 4) || o_sstart.reserve(((size_t)S + 1) * 4) || o_slen.reserve(((size_t)S + 1) * 4) || o_sevoff.reserve(((size_t)S + 1) * 8) ||
         o_events.reserve(((size_t)E + 1) * 2)) return done_ev(-1);
-    if (phased && E) ING_HIP(hipMemsetAsync(o_events.p, 0, (size_t)E * 2, st));      // (the gaps between the segments hold 0)
+    if (phased && E) LSG_HIP_OR(hipMemsetAsync(o_events.p, 0, (size_t)E * 2, st), done_ev(-1));      // (the gaps between the segments hold 0)
     if (R) {
         EmitArgs ea{};
         ea.u = u; ea.rec_off = d_recoff.as<uint64_t>(); ea.n_rec = n_rec; ea.legacy = legacy_del_merge ? 1 : 0; ea.phased = phased; ea.n_trim = c->split_n_trim;
@@ -528,21 +509,21 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
         if (g > cap) g = cap;
         hipLaunchKernelGGL(k_rec_emit, dim3(g), dim3(256), 0, st, ea);
     }
-    ING_HIP(hipEventRecord(ev_end, st));
+    LSG_HIP_OR(hipEventRecord(ev_end, st), done_ev(-1));
     unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    ING_HIP(hipMemcpyAsync(cnt, d_cnt.p, 56, hipMemcpyDeviceToHost, st));
+    LSG_HIP_OR(hipMemcpyAsync(cnt, d_cnt.p, 56, hipMemcpyDeviceToHost, st), done_ev(-1));
     unsigned long long rsn[2 * lsr::N_REASONS];
-    ING_HIP(hipMemcpyAsync(rsn, d_rsn.p, sizeof(rsn), hipMemcpyDeviceToHost, st));
+    LSG_HIP_OR(hipMemcpyAsync(rsn, d_rsn.p, sizeof(rsn), hipMemcpyDeviceToHost, st), done_ev(-1));
     if (cb_pass_out && cb_low_out) {
         const int64_t n_copy = n_tally < n_tally_out ? n_tally : n_tally_out;
         for (int64_t i = 0; i < n_tally_out; ++i) { cb_pass_out[i] = 0; cb_low_out[i] = 0; }
         if (n_copy > 0) {
-            ING_HIP(hipMemcpyAsync(cb_pass_out, d_tpass.p, (size_t)n_copy * 8, hipMemcpyDeviceToHost, st));
-            ING_HIP(hipMemcpyAsync(cb_low_out, d_tlow.p, (size_t)n_copy * 8, hipMemcpyDeviceToHost, st));
+            LSG_HIP_OR(hipMemcpyAsync(cb_pass_out, d_tpass.p, (size_t)n_copy * 8, hipMemcpyDeviceToHost, st), done_ev(-1));
+            LSG_HIP_OR(hipMemcpyAsync(cb_low_out, d_tlow.p, (size_t)n_copy * 8, hipMemcpyDeviceToHost, st), done_ev(-1));
         }
     }
-    ING_HIP(hipGetLastError());
-    ING_HIP(hipStreamSynchronize(st));
+    LSG_HIP_OR(hipGetLastError(), done_ev(-1));
+    LSG_HIP_OR(hipStreamSynchronize(st), done_ev(-1));
     float ms[4] = {fr.ms_h2d, fr.ms_inflate, fr.ms_chain, 0};
     (void)hipEventElapsedTime(&ms[3], fr.ev[3], ev_end);
     // the uncompressed stream and the per-record words are done with before the store is built
@@ -565,7 +546,6 @@ static int load_bam_impl(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64
     info->last_key = n_rec ? (int64_t)cnt[6] : -1;
     for (int r = 0; r < lsr::N_REASONS; ++r) { c->split_n[r] = (int64_t)rsn[r]; c->split_first[r] = rsn[lsr::N_REASONS + r] == ~0ull ? -1 : (int64_t)rsn[lsr::N_REASONS + r]; }
     return done_ev(0);
-#undef ING_HIP
 }
 
 int lsg_load_bam(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, int64_t first_record_offset, const char* barcodes, int32_t n_barcodes, const int32_t* ids,

@@ -3,7 +3,7 @@
 #include "lsg_ctx.h"
 #include <algorithm>
 #include <vector>
-#include <hipcub/hipcub.hpp>
+#include "cub_tmp.h"
 
 namespace lsg {
 
@@ -59,6 +59,17 @@ __global__ __launch_bounds__(SPAN_THREADS) void k_span_marks(const uint32_t* seg
 // tile, maximum over tiles and cell types.  Evaluated on request (lsg_max_live_reads), cached until reads or barcodes change.
 static int live_read_bound_impl(lsg_ctx* c, bool by_ct, int64_t* out);
 
+// the running sums of diff[0 .. n) and the largest of them (mx[0]): a scan and a reduction through one temp buffer, sized for the larger
+static int max_running_sum(DevBuf& tmp, const DevBuf& diff, const DevBuf& run, const DevBuf& mx, size_t n, hipStream_t st) {
+    return with_cub_tmp(tmp, "hipcub::DeviceScan::InclusiveSum, DeviceReduce::Max", [&](void* p, size_t& bytes) {
+        size_t tb = bytes, tb2 = bytes;
+        hipError_t e = hipcub::DeviceScan::InclusiveSum(p, tb, diff.as<int32_t>(), run.as<int32_t>(), (int)n, st);
+        if (e == hipSuccess) e = hipcub::DeviceReduce::Max(p, tb2, run.as<int32_t>(), mx.as<int32_t>(), (int)n, st);
+        bytes = tb > tb2 ? tb : tb2;
+        return e;
+    });
+}
+
 int live_read_bound(lsg_ctx* c) {
     if (c->max_live_reads >= 0) return 0;
     return live_read_bound_impl(c, c->n_ct > 0 && c->n_cb > 0, &c->max_live_reads);
@@ -79,19 +90,13 @@ static int live_read_bound_impl(lsg_ctx* c, bool by_ct, int64_t* out) {
     DevBuf diff, run, tmp, mx;
     auto fail = [&](int rc) { diff.release(); run.release(); tmp.release(); mx.release(); return rc; };
     if (diff.reserve(T * 4) || run.reserve(T * 4) || mx.reserve(64)) return fail(-1);
-    size_t tb = 0, tb2 = 0;
-    if (hipcub::DeviceScan::InclusiveSum(nullptr, tb, diff.as<int32_t>(), run.as<int32_t>(), (int)T, st) != hipSuccess ||
-        hipcub::DeviceReduce::Max(nullptr, tb2, run.as<int32_t>(), mx.as<int32_t>(), (int)T, st) != hipSuccess ||
-        tmp.reserve((tb > tb2 ? tb : tb2) + 256)) return fail(-1);
     int64_t best = 0;
     for (int ct = 0; ct < (by_ct ? c->n_ct : 1); ++ct) {
         if (hipMemsetAsync(diff.p, 0, T * 4, st) != hipSuccess) { set_error("live bound: memset failed"); return fail(-1); }
         hipLaunchKernelGGL(k_span_marks, dim3((unsigned)((S + SPAN_THREADS - 1) / SPAN_THREADS)), dim3(SPAN_THREADS), 0, st, c->rd.seg_read, c->rd.seg_start, c->rd.seg_len, S,
                            c->rd.read_tid, c->rd.read_cb, by_ct ? c->d_celltype_of.as<uint8_t>() : (const uint8_t*)nullptr, c->n_cb, ct,
                            c->d_tile_base.as<uint32_t>(), c->n_contigs, diff.as<int32_t>());
-        tb = tb2 = tmp.cap;
-        if (hipcub::DeviceScan::InclusiveSum(tmp.p, tb, diff.as<int32_t>(), run.as<int32_t>(), (int)T, st) != hipSuccess ||
-            hipcub::DeviceReduce::Max(tmp.p, tb2, run.as<int32_t>(), mx.as<int32_t>(), (int)T, st) != hipSuccess) { set_error("live bound: scan failed"); return fail(-1); }
+        if (max_running_sum(tmp, diff, run, mx, T, st)) return fail(-1);
         int32_t m = 0;
         if (hipMemcpyAsync(&m, mx.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("live bound: %s", hipGetErrorString(hipGetLastError())); return fail(-1); }
         if (m > best) best = m;
@@ -139,19 +144,13 @@ int live_read_bound_exact(lsg_ctx* c) {
     DevBuf diff, run, tmp, mx, dbase;
     auto fail = [&](int rc) { diff.release(); run.release(); tmp.release(); mx.release(); dbase.release(); return rc; };
     if (diff.reserve((size_t)P * 4 + 64) || run.reserve((size_t)P * 4 + 64) || mx.reserve(64) || dbase.reserve(base.size() * 8)) return fail(-1);
-    size_t tb = 0, tb2 = 0;
-    if (hipcub::DeviceScan::InclusiveSum(nullptr, tb, diff.as<int32_t>(), run.as<int32_t>(), (int)P, st) != hipSuccess ||
-        hipcub::DeviceReduce::Max(nullptr, tb2, run.as<int32_t>(), mx.as<int32_t>(), (int)P, st) != hipSuccess ||
-        tmp.reserve((tb > tb2 ? tb : tb2) + 256)) return fail(-1);
     if (hipMemcpyAsync(dbase.p, base.data(), base.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) return fail(-1);
     int64_t best = 0;
     for (int ct = 0; ct < c->n_ct; ++ct) {
         if (hipMemsetAsync(diff.p, 0, (size_t)P * 4, st) != hipSuccess) { set_error("exact live bound: memset failed"); return fail(-1); }
         hipLaunchKernelGGL(k_exact_marks, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, c->rd.seg_read, c->rd.seg_start, c->rd.seg_len, S, c->rd.read_tid, c->rd.read_cb,
                            c->d_celltype_of.as<uint8_t>(), c->n_cb, ct, dbase.as<int64_t>(), c->d_contig_len.as<int64_t>(), c->n_contigs, diff.as<int32_t>());
-        tb = tb2 = tmp.cap;
-        if (hipcub::DeviceScan::InclusiveSum(tmp.p, tb, diff.as<int32_t>(), run.as<int32_t>(), (int)P, st) != hipSuccess ||
-            hipcub::DeviceReduce::Max(tmp.p, tb2, run.as<int32_t>(), mx.as<int32_t>(), (int)P, st) != hipSuccess) { set_error("exact live bound: scan failed"); return fail(-1); }
+        if (max_running_sum(tmp, diff, run, mx, (size_t)P, st)) return fail(-1);
         int32_t m = 0;
         if (hipMemcpyAsync(&m, mx.p, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { set_error("exact live bound: %s", hipGetErrorString(hipGetLastError())); return fail(-1); }
         if (m > best) best = m;

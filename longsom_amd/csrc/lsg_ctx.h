@@ -31,14 +31,18 @@ __host__ __device__ inline uint64_t row_word(uint64_t row, int plane) {
 void set_error(const char* fmt, ...);
 const char* get_error();
 
-#define LSG_HIP(call)                                                                          \
+// ret: what the caller returns on failure (-1, or its own cleanup as in `done(-1)`); text: the call as written (stringized by the
+// two macros below, so that macros inside the call print by their names in both)
+#define LSG_HIP_AS_(call, text, ret)                                                           \
     do {                                                                                       \
         hipError_t e_ = (call);                                                                \
         if (e_ != hipSuccess) {                                                                \
-            lsg::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return -1;                                                                         \
+            lsg::set_error("%s failed: %s (%s:%d)", text, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return ret;                                                                        \
         }                                                                                      \
     } while (0)
+#define LSG_HIP_OR(call, ret) LSG_HIP_AS_(call, #call, ret)
+#define LSG_HIP(call) LSG_HIP_AS_(call, #call, -1)
 
 // Grow-only device buffer.
 struct DevBuf {

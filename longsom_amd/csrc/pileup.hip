@@ -25,7 +25,7 @@
 // More than two cell types: one resolve + walk pass per pair of cell types.  No global atomics on the event path, integer arithmetic
 // only (HBM- and issue-bound; no MFMA).
 #include "lsg_ctx.h"
-#include <hipcub/hipcub.hpp>
+#include "cub_tmp.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -336,15 +336,6 @@ static int tune_int(const char* name, int dflt) {
     const int x = atoi(v);
     return x > 0 && x <= 64 ? x : dflt;
 }
-
-#define SCAN_U32(in, out, n)                                                                              \
-    do {                                                                                                  \
-        size_t tb_ = 0;                                                                                   \
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_, (in), (out), (int)(n), st));              \
-        if (c->d_cub_tmp.reserve(tb_ + 256)) return -1;                                                   \
-        tb_ = c->d_cub_tmp.cap;                                                                           \
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb_, (in), (out), (int)(n), st));       \
-    } while (0)
 
 // ================================================================================================
 // A count over the tile store.
@@ -2103,7 +2094,7 @@ int unit_row_offsets(lsg_ctx* c, int ct, const uint32_t** off_out) {
     uint32_t* cnt = c->d_ne_rowoff.as<uint32_t>();
     uint32_t* off = cnt + (n_ne + 2);
     hipLaunchKernelGGL(k_unit_rowcount, dim3((n_ne + 256) / 256), dim3(256), 0, st, c->d_ne_units.as<uint32_t>(), c->d_ne_mask.as<uint64_t>(), n_ne, c->n_ct, ct, cnt);
-    SCAN_U32(cnt, off, n_ne + 1);
+    if (exclusive_sum(c->d_cub_tmp, cnt, off, n_ne + 1, st)) return -1;
     *off_out = off;
     return 0;
 }

@@ -18,7 +18,7 @@
 // store is the only resident copy (lsg_set_keep_reads keeps them for tests).  The plan of a count over the store (jobs, units, slabs:
 // ensure_plan) depends on the number of cell types only.
 #include "lsg_ctx.h"
-#include <hipcub/hipcub.hpp>
+#include "cub_tmp.h"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -748,15 +748,6 @@ __global__ __launch_bounds__(TMG_WAVES * 64) void k_tm_gather(const uint16_t* ev
     }
 }
 
-#define SCAN_U32(in, out, n)                                                                              \
-    do {                                                                                                  \
-        size_t tb_ = 0;                                                                                   \
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_, (in), (out), (int)(n), st));              \
-        if (c->d_cub_tmp.reserve(tb_ + 256)) return -1;                                                   \
-        tb_ = c->d_cub_tmp.cap;                                                                           \
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb_, (in), (out), (int)(n), st));       \
-    } while (0)
-
 enum { BT_KEY_A = 0, BT_KEY_B, BT_VAL_A, BT_VAL_B, BT_PEX, BT_NETILE, BT_SEG_BEGIN, BT_SEG_END, BT_TMP, BT_PER_TILE, BT_OFFS, BT_SPAN, BT_CURSOR, BT_LPT, BT_COPY_TMP, BT_N };
 
 void drop_store(lsg_ctx* c) {
@@ -875,11 +866,12 @@ static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, cons
     uint32_t* blk_off = c->tm[TM_BLK_OFF].as<uint32_t>();
     unsigned long long* d_sum = c->d_scalars.as<unsigned long long>() + 8;
     {
+        auto reduce_max_cb = [&](void* p, size_t& b, int64_t n) { return hipcub::DeviceReduce::Max(p, b, in.read_cb, reinterpret_cast<int32_t*>(d_small + 2), (int)n, st); };
         size_t tb = 0;
-        LSG_HIP(hipcub::DeviceReduce::Max(nullptr, tb, in.read_cb, reinterpret_cast<int32_t*>(d_small + 2), (int)(R > 0 ? R : 1), st));
+        LSG_HIP(reduce_max_cb(nullptr, tb, R > 0 ? R : 1));
         if (tmp.reserve(tb + 256 + 64 * 1024)) return -1;
         tb = tmp.cap;
-        if (R > 0) LSG_HIP(hipcub::DeviceReduce::Max(tmp.p, tb, in.read_cb, reinterpret_cast<int32_t*>(d_small + 2), (int)R, st));
+        if (R > 0) LSG_HIP(reduce_max_cb(tmp.p, tb, R));
     }
     {   // everything that follows from the range marks, in five launches (k_tt_*): the sizes below reach the host in the load's ONE early
         // look (the scatter, the sort and the gather are then queued without waiting for one another)
@@ -978,12 +970,13 @@ static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, cons
     const uint32_t* lpt_tiles = nullptr;
     // (the scratch is BT_COPY_TMP, sized below before anything is queued on the copy stream; on the main stream - the fall-back - the
     // copy stream has been waited for)
+    auto scan_blk_tiles = [&](void* p, size_t& b, hipStream_t s_) { uint32_t* bt_ = c->tm[TM_BLK_TILE].as<uint32_t>(); return hipcub::DeviceScan::InclusiveScan(p, b, bt_, bt_, hipcub::Max(), (int)nblk, s_); };
     auto blk_tiles = [&](hipStream_t s_) -> int {
         uint32_t* bt_ = c->tm[TM_BLK_TILE].as<uint32_t>();
         LSG_HIP(hipMemsetAsync(bt_, 0, (size_t)nblk * 4, s_));
         hipLaunchKernelGGL(k_tm_blk_mark, dim3((T + 255) / 256), dim3(256), 0, s_, c->d_tile_cap.as<uint32_t>(), blk_off, T, bt_);
         size_t tb = c->bt[BT_COPY_TMP].cap;
-        LSG_HIP(hipcub::DeviceScan::InclusiveScan(c->bt[BT_COPY_TMP].p, tb, bt_, bt_, hipcub::Max(), (int)nblk, s_));
+        LSG_HIP(scan_blk_tiles(c->bt[BT_COPY_TMP].p, tb, s_));
         LSG_HIP(hipEventRecord(c->ev_blk, s_));
         blk_tiles_made = true;
         return 0;
@@ -994,11 +987,11 @@ static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, cons
         const size_t lpt_pitch = ((size_t)n_netile + 64) & ~(size_t)63;            // (every array on a 256-byte boundary)
         if (lpt && lk.reserve(lpt_pitch * 4 * 3)) return -1;
         uint32_t* k_in = lk.as<uint32_t>(); uint32_t* k_out = k_in + lpt_pitch; uint32_t* t_out = k_out + lpt_pitch;
-        uint32_t* bt_ = c->tm[TM_BLK_TILE].as<uint32_t>();
+        auto sort_lpt = [&](void* p, size_t& b) { return hipcub::DeviceRadixSort::SortPairsDescending(p, b, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs); };
         // (the scratch of both is sized BEFORE either is queued: growing a buffer frees it, and work queued on this stream may still be reading it)
         size_t tb_lpt = 0, tb_blk = 0;
-        if (lpt) LSG_HIP(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb_lpt, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs));
-        LSG_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb_blk, bt_, bt_, hipcub::Max(), (int)nblk, bs));
+        if (lpt) LSG_HIP(sort_lpt(nullptr, tb_lpt));
+        LSG_HIP(scan_blk_tiles(nullptr, tb_blk, bs));
         // (... and of the sort of the shallow tiles, which runs on this stream beside the deep tiles' sort: below)
         size_t tb_sort2 = 0;
         if (n_netile) {
@@ -1017,7 +1010,7 @@ static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, cons
             // shifted by k_tile_caps and sorted from bit 0: rocprim 7.2's radix sort with begin_bit > 0 returns wrong pairs below ~1M items.
             hipLaunchKernelGGL(k_tile_caps, dim3((n_netile + 255) / 256), dim3(256), 0, bs, c->bt[BT_NETILE].as<uint32_t>(), n_netile, c->d_tile_cap.as<uint32_t>(), k_in);
             size_t tb = c->bt[BT_COPY_TMP].cap;
-            LSG_HIP(hipcub::DeviceRadixSort::SortPairsDescending(scratch, tb, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs));
+            LSG_HIP(sort_lpt(scratch, tb));
             LSG_HIP(hipEventRecord(c->ev_lpt, bs));
             lpt_tiles = t_out;
         }
@@ -1321,9 +1314,9 @@ static int plan_tiles(lsg_ctx* c, hipStream_t st) {
     uint32_t job_tgt = TM_JOB_TGT;
     { const uint64_t per = N / ((uint64_t)c->n_cus * 14 * 4); if (per < job_tgt) job_tgt = (uint32_t)(per < 768 ? 768 : per); }
     hipLaunchKernelGGL(k_tm_tiles, dim3((T + 256) / 256), dim3(256), 0, st, c->d_tile_cap.as<uint32_t>(), T, c->n_ct, job_tgt, 1u << c->wsh, ne, nj, slabs, multi);
-    SCAN_U32(ne, ne_off, T + 1); SCAN_U32(nj, job_off, T + 1); SCAN_U32(slabs, slab_off, T + 1); SCAN_U32(multi, multi_off, T + 1);
+    uint32_t* cnts[4] = {ne, nj, slabs, multi}; uint32_t* srcs[4] = {ne_off, job_off, slab_off, multi_off};
+    for (int i = 0; i < 4; ++i) if (exclusive_sum(c->d_cub_tmp, cnts[i], srcs[i], T + 1, st)) return -1;
     LSG_HIP(hipMemsetAsync(d_misc, 0, 8, st));
-    uint32_t* srcs[4] = {ne_off, job_off, slab_off, multi_off};
     for (int i = 0; i < 4; ++i) LSG_HIP(hipMemcpyAsync(&c->plan1_tot[i], srcs[i] + T, 4, hipMemcpyDeviceToHost, st));
     LSG_HIP(hipStreamSynchronize(st));
     const uint32_t n_net = c->plan1_tot[0], njobs = c->plan1_tot[1], n_mt = c->plan1_tot[3];
@@ -1365,7 +1358,7 @@ static int plan_jobs(lsg_ctx* c, bool finish, const uint64_t* skey, int cb_bits)
         hipcub::CountingInputIterator<uint32_t> iota(0);
         TmJobWork wf{c->tm[TM_JOBS].as<TmJob>()};
         hipcub::TransformInputIterator<uint32_t, TmJobWork, hipcub::CountingInputIterator<uint32_t>> it(iota, wf);
-        SCAN_U32(it, pex.as<uint32_t>(), njobs);
+        if (exclusive_sum(c->d_cub_tmp, it, pex.as<uint32_t>(), njobs, st)) return -1;
         hipLaunchKernelGGL(k_tm_chunks, dim3((njobs + 255) / 256), dim3(256), 0, st, pex.as<uint32_t>(), njobs, chunk_work, c->tm[TM_CHUNKS].as<uint32_t>(), d_misc + 1);
     }
     LSG_HIP(hipMemcpyAsync(c->plan_misc, d_misc, 8, hipMemcpyDeviceToHost, st));

@@ -2,7 +2,7 @@
 // bench's 10M-read / 1.2e10-event configuration never crosses PCIe.  Not on the timed path.
 #include "lsg_ctx.h"
 #include "synth_model.h"
-#include <hipcub/hipcub.hpp>
+#include "cub_tmp.h"
 
 namespace lsg {
 
@@ -122,14 +122,13 @@ int lsg_synth_generate(lsg_ctx* c, const lsg_synth_model* hm, lsg_reads* out) {
     hipLaunchKernelGGL(k_synth_header, dim3((unsigned)((R + 1 + 255) / 256)), dim3(256), 0, st, m, o_tid.as<int32_t>(),
                        o_pos.as<int32_t>(), o_flag.as<uint16_t>(), o_mapq.as<uint8_t>(), o_cb.as<int32_t>(),
                        evcnt.as<int64_t>(), segcnt.as<uint32_t>());
-    size_t t1 = 0, t2 = 0;
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t1, evcnt.as<int64_t>(), evoff.as<int64_t>(), (int)(R + 1), st));
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, segcnt.as<uint32_t>(), segoff.as<uint32_t>(), (int)(R + 1), st));
-    if (tmpb.reserve((t1 > t2 ? t1 : t2) + 16)) return -1;
-    size_t t = tmpb.cap;
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(tmpb.p, t, evcnt.as<int64_t>(), evoff.as<int64_t>(), (int)(R + 1), st));
-    t = tmpb.cap;
-    LSG_HIP(hipcub::DeviceScan::ExclusiveSum(tmpb.p, t, segcnt.as<uint32_t>(), segoff.as<uint32_t>(), (int)(R + 1), st));
+    if (with_cub_tmp(tmpb, "hipcub::DeviceScan::ExclusiveSum", [&](void* p, size_t& bytes) {      // both scans with one buffer, sized for the larger
+            size_t t1 = bytes, t2 = bytes;
+            hipError_t e = hipcub::DeviceScan::ExclusiveSum(p, t1, evcnt.as<int64_t>(), evoff.as<int64_t>(), (int)(R + 1), st);
+            if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(p, t2, segcnt.as<uint32_t>(), segoff.as<uint32_t>(), (int)(R + 1), st);
+            bytes = t1 > t2 ? t1 : t2;
+            return e;
+        })) return -1;
     int64_t E = 0; uint32_t S = 0;
     LSG_HIP(hipMemcpyAsync(&E, evoff.as<int64_t>() + R, 8, hipMemcpyDeviceToHost, st));
     LSG_HIP(hipMemcpyAsync(&S, segoff.as<uint32_t>() + R, 4, hipMemcpyDeviceToHost, st));

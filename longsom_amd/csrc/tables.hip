@@ -13,13 +13,13 @@
 #include "lsg_ctx.h"
 #include "call_rec.h"
 #include "text_sink.h"
+#include "text_table.h"
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 #include <fcntl.h>
 #include <unistd.h>
-#include <hipcub/hipcub.hpp>
 
 namespace lsg {
 int run_export_rows(lsg_ctx* c, int ct, DevBuf& dk, DevBuf& dr, DevBuf& dc);
@@ -304,6 +304,11 @@ __global__ void k_contig_shift(const int64_t* lo, const uint64_t* off, const int
         base += e - b;
     }
 }
+// the contig step of finish_places for rows whose keys `a` holds
+void contig_order(const FmtArgs& a, const RowPlaces& r, const int32_t* order, hipStream_t st) {
+    hipLaunchKernelGGL(k_contig_lo, dim3((unsigned)(a.n_contigs / 64 + 1)), dim3(64), 0, st, a, r.lo);
+    hipLaunchKernelGGL(k_contig_shift, dim3(1), dim3(1), 0, st, r.lo, r.off, order, a.n_contigs, r.shift);
+}
 
 // ---- what step 3 wants to know about the step-2 table, read off its text where it lies ---------------------------------------------
 // (calling.step3 parses only the rows that survive its FILTER patterns, given the kinds of cell every column holds over ALL rows: the
@@ -461,10 +466,6 @@ __global__ __launch_bounds__(256) void k_text_copy_rows(TextRows t, const uint32
     for (uint32_t q = 0; q < len2[i]; ++q) w[q] = r[q];
 }
 
-struct Widen { __host__ __device__ __forceinline__ uint64_t operator()(const uint32_t& v) const { return (uint64_t)v; } };
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 std::vector<std::string> split_names(const char* joined, int n) {
     std::vector<std::string> out;
     const char* p = joined;
@@ -483,7 +484,7 @@ int run_set_table_names(lsg_ctx* c, int32_t n_contigs, const char* contig_names,
     if (n_contigs != c->n_contigs) { set_error("lsg_set_table_names: %d contig names for %d contigs (lsg_set_contigs)", n_contigs, c->n_contigs); return -2; }
     if (n_ct < 1 || n_ct > LSG_MAX_CELLTYPES) { set_error("lsg_set_table_names: n_celltypes %d not in [1,%d]", n_ct, LSG_MAX_CELLTYPES); return -2; }
     const auto cn = split_names(contig_names, n_contigs), tn = split_names(ct_names, n_ct);
-    // one buffer: contig offsets | cell-type offsets | contigs in Python string order | the names' bytes
+    // one buffer: contig offsets, cell-type offsets, contigs in Python string order, the names' bytes
     std::vector<uint32_t> coff(n_contigs + 1, 0), toff(n_ct + 1, 0);
     std::string ctxt, ttxt;
     for (int i = 0; i < n_contigs; ++i) { ctxt += cn[(size_t)i]; coff[(size_t)i + 1] = (uint32_t)ctxt.size(); }
@@ -491,17 +492,11 @@ int run_set_table_names(lsg_ctx* c, int32_t n_contigs, const char* contig_names,
     std::vector<int32_t> order(n_contigs);
     for (int i = 0; i < n_contigs; ++i) order[(size_t)i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cn[(size_t)x] < cn[(size_t)y]; });
-    const size_t at_ct_off = (size_t)(n_contigs + 1) * 4, at_order = at_ct_off + (size_t)(n_ct + 1) * 4, at_ctxt = at_order + (size_t)n_contigs * 4,
-                 at_ttxt = at_ctxt + ctxt.size(), total = at_ttxt + ttxt.size();
-    std::vector<char> host(total + 8, 0);
-    memcpy(host.data(), coff.data(), coff.size() * 4);
-    memcpy(host.data() + at_ct_off, toff.data(), toff.size() * 4);
-    if (n_contigs) memcpy(host.data() + at_order, order.data(), order.size() * 4);
-    memcpy(host.data() + at_ctxt, ctxt.data(), ctxt.size());
-    memcpy(host.data() + at_ttxt, ttxt.data(), ttxt.size());
-    if (c->tab_names.reserve(host.size())) return -1;
-    LSG_HIP(hipMemcpyAsync(c->tab_names.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
-    LSG_HIP(hipStreamSynchronize(c->stream));
+    HostBlob b;
+    b.add(coff.data(), coff.size() * 4);                 // (at 0: FmtArgs::contig_off is the buffer's start)
+    const size_t at_ct_off = b.add(toff.data(), toff.size() * 4), at_order = b.add(order.data(), order.size() * 4), at_ctxt = b.add(ctxt.data(), ctxt.size()),
+                 at_ttxt = b.add(ttxt.data(), ttxt.size());
+    if (b.upload(c->tab_names, c->stream)) return -1;
     c->tab_n_contigs = n_contigs; c->tab_n_ct = n_ct;
     c->tab_ct_off_at = (uint32_t)at_ct_off; c->tab_order_at = (uint32_t)at_order; c->tab_contig_txt_at = (uint32_t)at_ctxt; c->tab_ct_txt_at = (uint32_t)at_ttxt;
     return 0;
@@ -556,39 +551,14 @@ int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     c->tab_scratch_table = -1;
     if (a.n == 0) { c->tab_bytes[table] = 0; return 0; }
     if (a.n >= (int64_t)1 << 31) { set_error("lsg_format_table: %lld rows", (long long)a.n); return -2; }
-    // scratch: len[n + 1] | off[n + 1] | lo[n_contigs + 1] | shift[n_contigs]
-    const size_t at_off = align_up((size_t)(a.n + 1) * 4, 256), at_lo = at_off + align_up((size_t)(a.n + 1) * 8, 256),
-                 at_shift = at_lo + align_up((size_t)(c->n_contigs + 1) * 8, 256), total = at_shift + (size_t)(c->n_contigs + 1) * 8;
-    if (c->tab_scratch.reserve(total)) return -1;
-    char* sc = c->tab_scratch.as<char>();
-    a.len = reinterpret_cast<uint32_t*>(sc);
-    uint64_t* off = reinterpret_cast<uint64_t*>(sc + at_off);
-    int64_t* lo = reinterpret_cast<int64_t*>(sc + at_lo);
-    int64_t* shift = reinterpret_cast<int64_t*>(sc + at_shift);
-    a.off = off; a.shift = shift;
+    RowPlaces r;
+    if (row_places(c->tab_scratch, a.n, c->n_contigs, r)) return -1;
+    a.len = r.len; a.off = r.off; a.shift = r.shift;
     const unsigned blocks = (unsigned)((a.n + 1 + 255) / 256);
     hipLaunchKernelGGL(k_row_len, dim3(blocks), dim3(256), 0, st, a);
-    {
-        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> in(a.len, Widen());
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, off, (int)(a.n + 1), st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, in, off, (int)(a.n + 1), st));
-    }
-    hipLaunchKernelGGL(k_contig_lo, dim3((unsigned)(c->n_contigs / 64 + 1)), dim3(64), 0, st, a, lo);
-    hipLaunchKernelGGL(k_contig_shift, dim3(1), dim3(1), 0, st, lo, off, order, c->n_contigs, shift);
-    LSG_HIP(hipMemcpyAsync(c->h_pin, off + a.n, 8, hipMemcpyDeviceToHost, st));
-    LSG_HIP(hipStreamSynchronize(st));
-    const int64_t bytes = (int64_t)c->h_pin[0];
-    if (bytes > 0) {
-        if (c->tab_text[table].reserve((size_t)bytes)) return -1;
-        a.text = c->tab_text[table].as<char>();
-        hipLaunchKernelGGL(k_row_put, dim3(blocks), dim3(256), 0, st, a);
-        LSG_HIP(hipGetLastError());
-        LSG_HIP(hipStreamSynchronize(st));
-    }
-    c->tab_bytes[table] = bytes;
+    int64_t bytes = 0;
+    if (finish_places(c, r, &bytes, [&] { contig_order(a, r, order, st); return 0; })) return -1;
+    if (print_table(c, table, bytes, [&](char* text) { a.text = text; hipLaunchKernelGGL(k_row_put, dim3(blocks), dim3(256), 0, st, a); })) return -1;
     c->tab_scratch_table = table; c->tab_scratch_rows = a.n;      // (the rows' places stay in the scratch: lsg_step2_summary reads the text by them)
     if (n_bytes) *n_bytes = bytes;
     return 0;
@@ -607,32 +577,14 @@ int run_step2_allele_queries(lsg_ctx* c, int64_t* keys_out, int64_t capacity, in
     FmtArgs a{};
     a.kind = K_KEPT; a.n_ct = c->n_ct; a.n_contigs = c->n_contigs; a.n = n;
     a.sites = c->d_calls.as<SiteRec>(); a.cands = c->ws[WS_CALL_CANDS].as<CandCt>();
-    // scratch: len[n + 1] | off[n + 1] | lo[n_contigs + 1] | shift[n_contigs + 1]
-    const size_t at_off = align_up((size_t)(n + 1) * 4, 256), at_lo = at_off + align_up((size_t)(n + 1) * 8, 256),
-                 at_shift = at_lo + align_up((size_t)(c->n_contigs + 1) * 8, 256), total = at_shift + (size_t)(c->n_contigs + 1) * 8;
-    if (c->tab_scratch2.reserve(total)) return -1;
-    char* sc = c->tab_scratch2.as<char>();
-    a.len = reinterpret_cast<uint32_t*>(sc);
-    uint64_t* off = reinterpret_cast<uint64_t*>(sc + at_off);
-    int64_t* lo = reinterpret_cast<int64_t*>(sc + at_lo);
-    int64_t* shift = reinterpret_cast<int64_t*>(sc + at_shift);
-    a.off = off; a.shift = shift;
+    RowPlaces r;
+    if (row_places(c->tab_scratch2, n, c->n_contigs, r)) return -1;
+    a.len = r.len; a.off = r.off; a.shift = r.shift;
     const unsigned blocks = (unsigned)((n + 1 + 255) / 256);
     hipLaunchKernelGGL(k_query_len, dim3(blocks), dim3(256), 0, st, a);
-    {
-        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> in(a.len, Widen());
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, off, (int)(n + 1), st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, in, off, (int)(n + 1), st));
-    }
     const int32_t* order = reinterpret_cast<const int32_t*>(c->tab_names.as<char>() + c->tab_order_at);
-    hipLaunchKernelGGL(k_contig_lo, dim3((unsigned)(c->n_contigs / 64 + 1)), dim3(64), 0, st, a, lo);
-    hipLaunchKernelGGL(k_contig_shift, dim3(1), dim3(1), 0, st, lo, off, order, c->n_contigs, shift);
-    LSG_HIP(hipMemcpyAsync(c->h_pin, off + n, 8, hipMemcpyDeviceToHost, st));
-    LSG_HIP(hipStreamSynchronize(st));
-    const int64_t k = (int64_t)c->h_pin[0];
+    int64_t k = 0;
+    if (finish_places(c, r, &k, [&] { contig_order(a, r, order, st); return 0; })) return -1;
     *n_out = k;
     if (!keys_out || k == 0) return 0;
     if (k > capacity) { set_error("lsg_step2_allele_queries: capacity %lld < %lld keys", (long long)capacity, (long long)k); return -2; }
@@ -658,47 +610,26 @@ int run_step2_summary(lsg_ctx* c, int32_t n_cols, uint8_t* kinds, int64_t* n_sur
     if (c->tab_scratch_table != LSG_TABLE_STEP2 || c->tab_scratch_rows != c->n_sites || !c->called) { set_error("lsg_step2_summary: must follow the format of LSG_TABLE_STEP2 directly"); return -2; }
     hipStream_t st = c->stream;
     const int64_t n = c->tab_scratch_rows;
-    const size_t at_off = align_up((size_t)(n + 1) * 4, 256), at_lo = at_off + align_up((size_t)(n + 1) * 8, 256),
-                 at_shift = at_lo + align_up((size_t)(c->n_contigs + 1) * 8, 256);
-    char* sc = c->tab_scratch.as<char>();
-    TextRows t{c->tab_text[LSG_TABLE_STEP2].as<char>(), reinterpret_cast<const uint32_t*>(sc), reinterpret_cast<const uint64_t*>(sc + at_off),
-               reinterpret_cast<const int64_t*>(sc + at_shift), c->d_calls.as<SiteRec>(), n};
-    const int64_t* lo = reinterpret_cast<const int64_t*>(sc + at_lo);
-    // second scratch: kinds[64] | len2[n + 1] | off2[n + 1] | shift2[n_contigs + 1]
-    const size_t b_len = 256, b_off = b_len + align_up((size_t)(n + 1) * 4, 256), b_shift = b_off + align_up((size_t)(n + 1) * 8, 256), b_total = b_shift + (size_t)(c->n_contigs + 1) * 8;
-    if (c->tab_scratch2.reserve(b_total)) return -1;
-    char* s2 = c->tab_scratch2.as<char>();
-    uint32_t* d_kinds = reinterpret_cast<uint32_t*>(s2);
-    uint32_t* len2 = reinterpret_cast<uint32_t*>(s2 + b_len);
-    uint64_t* off2 = reinterpret_cast<uint64_t*>(s2 + b_off);
-    int64_t* shift2 = reinterpret_cast<int64_t*>(s2 + b_shift);
+    RowPlaces r, r2;
+    row_places(c->tab_scratch, n, c->n_contigs, r, false);            // where run_format_table left the rows' places
+    TextRows t{c->tab_text[LSG_TABLE_STEP2].as<char>(), r.len, r.off, r.shift, c->d_calls.as<SiteRec>(), n};
+    // second scratch: kinds[64], then the survivors' places (their contigs start where the table's do: its lo)
+    if (row_places(c->tab_scratch2, n, c->n_contigs, r2, true, 256)) return -1;
+    uint32_t* d_kinds = c->tab_scratch2.as<uint32_t>();
     LSG_HIP(hipMemsetAsync(d_kinds, 0, 256, st));
     const unsigned blocks = (unsigned)((n + 1 + 255) / 256);
     hipLaunchKernelGGL(k_text_kinds, dim3(blocks), dim3(256), 0, st, t, (int)n_cols, d_kinds);
-    hipLaunchKernelGGL(k_text_survivors, dim3(blocks), dim3(256), 0, st, t, len2);
-    {
-        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> in(len2, Widen());
-        size_t tb = 0;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, off2, (int)(n + 1), st));
-        if (c->d_cub_tmp.reserve(tb + 256)) return -1;
-        tb = c->d_cub_tmp.cap;
-        LSG_HIP(hipcub::DeviceScan::ExclusiveSum(c->d_cub_tmp.p, tb, in, off2, (int)(n + 1), st));
-    }
+    hipLaunchKernelGGL(k_text_survivors, dim3(blocks), dim3(256), 0, st, t, r2.len);
     const int32_t* order = reinterpret_cast<const int32_t*>(c->tab_names.as<char>() + c->tab_order_at);
-    hipLaunchKernelGGL(k_contig_shift, dim3(1), dim3(1), 0, st, lo, off2, order, c->n_contigs, shift2);
     uint32_t h_kinds[64];
-    LSG_HIP(hipMemcpyAsync(h_kinds, d_kinds, 256, hipMemcpyDeviceToHost, st));
-    LSG_HIP(hipMemcpyAsync(c->h_pin, off2 + n, 8, hipMemcpyDeviceToHost, st));
-    LSG_HIP(hipStreamSynchronize(st));
+    int64_t bytes = 0;
+    if (finish_places(c, r2, &bytes, [&] {
+            hipLaunchKernelGGL(k_contig_shift, dim3(1), dim3(1), 0, st, r.lo, r2.off, order, c->n_contigs, r2.shift);
+            LSG_HIP(hipMemcpyAsync(h_kinds, d_kinds, 256, hipMemcpyDeviceToHost, st));
+            return 0;
+        })) return -1;
     for (int q = 0; q < n_cols; ++q) kinds[q] = (uint8_t)h_kinds[q];
-    const int64_t bytes = (int64_t)c->h_pin[0];
-    if (bytes > 0) {
-        if (c->tab_text[LSG_TABLE_STEP3_ROWS].reserve((size_t)bytes)) return -1;
-        hipLaunchKernelGGL(k_text_copy_rows, dim3(blocks), dim3(256), 0, st, t, len2, off2, shift2, c->tab_text[LSG_TABLE_STEP3_ROWS].as<char>());
-        LSG_HIP(hipGetLastError());
-        LSG_HIP(hipStreamSynchronize(st));
-    }
-    c->tab_bytes[LSG_TABLE_STEP3_ROWS] = bytes;
+    if (print_table(c, LSG_TABLE_STEP3_ROWS, bytes, [&](char* text) { hipLaunchKernelGGL(k_text_copy_rows, dim3(blocks), dim3(256), 0, st, t, r2.len, r2.off, r2.shift, text); })) return -1;
     if (n_survivor_bytes) *n_survivor_bytes = bytes;
     return 0;
 }

@@ -1,5 +1,6 @@
-// The sinks and number printers of the tables printed on the device (tables.hip, cellgeno.hip): a row is printed twice, first into a
-// sink that only counts (its length), then into one that stores (its bytes).
+// The sinks and number printers of the tables printed on the device (tables.hip, cellgeno.hip, genecounts.hip): a row is printed twice,
+// first into a sink that only counts (its length), then into one that stores (its bytes).  What the host does between the two kernels -
+// the rows' places from their lengths, the table's buffer - is text_table.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -165,6 +165,54 @@ def test_contig_order_context_edges_and_rounding_ties(engine, tmp_path):
     assert len(surv) > 0 and any(l.startswith(b"chrM\t") for l in surv.split(b"\n"))
 
 
+@pytest.mark.parametrize("n_rows", [1, 255, 256, 257])
+def test_tables_at_the_edge_of_a_block_of_rows(engine, tmp_path, n_rows):
+    """the length kernels write n + 1 slots, 256 to a block, the put kernels n rows: their grids grow at n = 256 and n = 257.  Both cell
+    types hold the same n sites (so the merged and step-1 tables have n rows too), or the second holds none (n = 256: its count table is
+    empty, and no site reaches min_cell_types); contigs in another order than their names', one of them without a row"""
+    from longsom_amd import calling
+    rng = np.random.default_rng(256)
+    lens, names, ct_names = [700, 500, 90, 600], ["chr2", "chr10", "chr3", "chr1"], ["Cancer", "Non-Cancer"]
+    seqs = [rng.choice(np.frombuffer(b"ACGT", np.uint8), L) for L in lens]
+    engine.set_contigs(lens)
+    for t, s in enumerate(seqs):
+        engine.load_reference(t, s)
+    where = np.asarray([(t << 32) | pos for t in (0, 1, 3) for pos in range(lens[t])], np.int64)
+    keys = np.sort(rng.choice(where, n_rows, replace=False))
+    cls_of = {ord("A"): 0, ord("C"): 1, ord("T"): 2, ord("G"): 3}
+
+    def rows_of(keys):
+        rows = np.zeros((len(keys), 42), np.uint32)
+        for r, k in zip(rows, keys):
+            rc = cls_of[int(seqs[int(k >> 32)][int(k & 0xFFFFFFFF)])]
+            bc = np.zeros(8, np.int64)
+            bc[rc] = rng.integers(15, 60)
+            for alt in rng.permutation([c for c in range(4) if c != rc])[:rng.integers(0, 3)]:
+                bc[alt] = rng.integers(1, 12)
+            cc = np.minimum(bc, rng.integers(1, 9, 8)) * (bc > 0)
+            r[0] = bc.sum(); r[1] = max(5, int(cc.max()) + 3); r[2:10] = cc; r[10:18] = bc; r[18:26] = bc * 30; r[26:34] = bc // 2; r[34:42] = bc - bc // 2
+        return rows
+    second = keys[:0] if n_rows == 256 else keys
+    engine.load_counts([keys, second], [rows_of(keys), rows_of(second)])
+    n_sites, n_cand = engine.call_step1(CallParams.longsom_defaults(min_cell_types=2))
+    assert n_sites == n_rows
+    calls = engine.fetch_calls()
+    per_ct = [engine.fetch_counts(ct) for ct in range(2)]
+    want = host_tables(str(tmp_path), per_ct, calls, names, ct_names)
+    got = device_tables(engine, names, ct_names, 2, str(tmp_path))
+    same_tables(got, want)
+    if n_rows == 256:
+        assert got[1] == b"" and engine.format_table(1) == 0
+    assert len(want[0].split(b"\n")) == n_rows + 1 and len(want[4].split(b"\n")) == n_rows + 1
+    step2_on_device_equals_host(engine, names, ct_names, want[6], [np.zeros(0, np.int64)] * 3)
+    # the allele queries: the one-base-ALT rows of the kept table (the host's text of it), in its order
+    one = [f for f in (l.split("\t") for l in want[6].decode().split("\n") if l) if len(f[4]) == 1]
+    q = engine.step2_allele_queries()
+    assert len(q) == len(one)
+    if one:
+        assert q.tolist() == calling.pack_allele_keys([names.index(f[0]) for f in one], [int(f[1]) for f in one], "".join(f[3] for f in one), "".join(f[4] for f in one)).tolist()
+
+
 def test_tables_of_a_counted_sample(engine, tmp_path):
     """rows the count itself wrote (blocked planes, narrow and wide blocks) for a synthetic sample over the hg38 contig table"""
     from longsom_amd import synth
