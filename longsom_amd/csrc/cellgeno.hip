@@ -272,7 +272,7 @@ int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_dep
     if (int rc = check_tail_params(who, alpha2, beta2, pvalue)) return rc;
     if (c->n_contigs <= 0) { set_error("%s: no contigs set", who); return -2; }
     if (c->n_cb <= 0) { set_error("%s: no barcodes set", who); return -2; }
-    if (c->store_skipped) { set_error("%s: the load kept no store (lsg_set_store_policy): load the reads again with LSG_STORE_KEEP", who); return -2; }
+    if (!keeps_store(c->load_form)) { set_error("%s: the load kept no store (lsg_set_store_policy): load the reads again with LSG_STORE_KEEP", who); return -2; }
     if (!c->tm_valid) { set_error("%s: no reads loaded", who); return -2; }
     for (int64_t i = 1; i < n_sites; ++i)
         if (site_keys[i] <= site_keys[i - 1]) { set_error("%s: site keys must be strictly ascending", who); return -2; }

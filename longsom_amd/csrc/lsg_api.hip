@@ -304,7 +304,7 @@ int lsg_set_load_filter(lsg_ctx* c, int32_t min_mq, uint32_t flag_exclude, int32
 
 // the resident store holds only reads that passed the load filter: a count (or a genotyping pass) that would admit more is refused
 static int check_load_filter(lsg_ctx* c, const char* who, int32_t min_mq, uint32_t flag_exclude, int32_t ignore_orphans) {
-    if (min_mq < c->st_min_mq || (c->st_flag_exclude & ~flag_exclude) != 0 || (c->st_ignore_orphans && !ignore_orphans)) {
+    if (!count_within_load_filter(ReadFilter{min_mq, flag_exclude, ignore_orphans}, ReadFilter{c->st_min_mq, c->st_flag_exclude, c->st_ignore_orphans})) {
         set_error("%s: these read filters (min_mq %d, flag_exclude 0x%x, ignore_orphans %d) admit reads the load filter dropped (min_mq %d, flag_exclude 0x%x, ignore_orphans %d): "
                   "load the reads again under a filter no stricter than the counts' (lsg_set_load_filter)", who, min_mq, flag_exclude, ignore_orphans,
                   c->st_min_mq, c->st_flag_exclude, c->st_ignore_orphans);
@@ -383,7 +383,7 @@ int lsg_pileup_count(lsg_ctx* c, const lsg_count_params* params, int64_t* n_rows
     if (int rc = check_load_filter(c, "lsg_pileup_count", params->min_mq, params->flag_exclude, params->ignore_orphans)) return rc;
     // the load made this very count while it built the store (lsg_set_count_at_load): it is handed out once, a later call counts again
     // (a load that kept no store: its count is all there is, and stays until something invalidates it)
-    const bool have = c->counted && (c->counted_at_load || c->store_skipped) && memcmp(params, &c->last_params, sizeof(*params)) == 0;
+    const bool have = c->counted && (c->counted_at_load || !keeps_store(c->load_form)) && memcmp(params, &c->last_params, sizeof(*params)) == 0;
     c->counted_at_load = false;
     if (!have) { int rc = run_count(c, params); if (rc) return rc; }
     if (n_rows) for (int i = 0; i < c->n_ct; ++i) n_rows[i] = c->n_rows[i];
@@ -440,7 +440,7 @@ int lsg_get_count_stats(lsg_ctx* c, lsg_count_stats* out) {
 
 int lsg_get_layout_info(lsg_ctx* c, int32_t* path, double* build_ms, int64_t* store_bytes) {
     if (!c) { set_error("lsg_get_layout_info: NULL handle"); return -2; }
-    if (path) *path = c->store_skipped ? (c->wsh ? 6 : c->line_loads ? 5 : 4) : c->load_was_fused ? 3 : 2;       // 3: the load's gather also made the first count (lsg_set_count_at_load)
+    if (path) *path = (int32_t)c->load_form;       // (load_form.h: 3: the load's gather also made the first count, lsg_set_count_at_load; 4-6: it kept no store)
     if (build_ms) *build_ms = c->layout_build_ms;
     if (store_bytes) {
         int64_t b = 0;

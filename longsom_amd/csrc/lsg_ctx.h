@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/longsom_hip.h"
 #include "../../include/longsom_synth.h"
+#include "load_form.h"
 
 namespace lsg {
 
@@ -185,9 +186,13 @@ int live_read_bound_all(lsg_ctx* c);
 __global__ void k_read_end(const uint32_t* seg_read, const int32_t* seg_start, const int32_t* seg_len, int64_t n_segs, int32_t* read_end);      // layout.hip
 __global__ void k_read_end_init(const int32_t* read_pos, int64_t n_reads, int32_t* read_end);
 int depth_cap_drops(lsg_ctx* c, const lsg_count_params* p);   // layout.hip: htslib's max_depth rule -> d_read_drop (or none)
-struct GatherCountSrc { const uint16_t* events; int64_t n_events; const uint64_t* key; const uint32_t* rdv; int32_t cb_bits; int32_t src_shift; int32_t wsh; };
+struct GatherCountSrc { const uint16_t* events; int64_t n_events; const uint64_t* key; const uint32_t* rdv; int32_t cb_bits; int32_t src_shift; };
 int unit_row_offsets(lsg_ctx* c, int ct, const uint32_t** off);      // pileup.hip: per unit, the first of its rows in the cell type's genomic row order
-int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc& src, bool direct);      // pileup.hip: the load's gather and the first count in one pass (k_tm_gather_count), or the count alone from the caller's events (k_tm_count_direct)
+int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc& src, LoadForm form);      // pileup.hip: the load's gather and the first count in one pass (LOAD_FUSED: k_tm_gather_count), or the count alone from the caller's events (k_tm_count_direct, k_tm_count_win)
+// The load's words in d_scalars (64-bit slots; the count's own, SC_* in pileup.hip, take the block over afterwards), and where the early look's
+// two copies land in h_pin
+enum { LS_QHEAD = 0, LS_BAD = 2, LS_EVENTS = 3, LS_SMALL = 4 /* four 32-bit words: store.hip d_small */, LS_TOTAL = 8 /* entries, 64 bits */, LS_WORDS = 9 };
+enum { HP_LOOK = 0, HP_NBLK = 16 };
 }
 
 struct lsg_ctx {
@@ -244,19 +249,15 @@ struct lsg_ctx {
     // lsg_set_count_at_load: the next load also makes the first count under these parameters, in the pass that builds the store
     bool cal_enabled = false; lsg_count_params cal_params{};
     bool counted_at_load = false;         // the resident count is that one and nobody has asked for it yet
-    bool load_was_fused = false;          // the last load built its store in the pass that counted (lsg_get_layout_info path 3)
     bool tm_valid = false;
     int32_t store_policy = 0;             // lsg_set_store_policy: LSG_STORE_KEEP / LSG_STORE_SKIP_WHEN_COUNTED
-    bool store_skipped = false;           // the last load made its count and kept no store: what needs one fails
+    lsg::LoadForm load_form = lsg::LOAD_STORE;      // the last load's form (load_form.h; lsg_get_layout_info's path): a load that kept no store has made its count, and what needs a store fails
     double layout_build_ms = 0;           // wall time of the last build (lsg_get_layout_info)
     float build_ms[4] = {0, 0, 0, 0};     // HIP-event times of the last build: capacities + scatter, sort, fill, gather
     int64_t max_live_reads = -1;          // layout.hip: bound on the reads live at once in the reference's pileup buffer (-1 = stale)
     int64_t max_live_all = -1;            // the same over all reads with a barcode: table-independent, cached per load
-    int32_t wsh = 0;                      // build_store: the bins of the last load's entries - 0: the 64-position tiles, 1: 128-position windows (a load that kept no store)
     int32_t events_layout = 0;            // lsg_set_events_layout: what the caller says about the events of the next loads (LSG_LAYOUT_*)
     const void* hint_phased_events = nullptr;      // the events array this library's own producer (synth.hip, ingest.hip) last laid out phased modulo 128
-    bool src_phased = false;              // build_store: the last load's events were tile-phased (LSG_LAYOUT_PHASED): an entry = one 128-byte line
-    bool line_loads = false;              // pileup.hip run_gather_count: the last direct count fetched every entry as its one 128-byte line (tile-phased events)
     int64_t max_live_exact = -1;          // per cell type at position resolution (asked only when the tile-level bounds cannot rule the cap out)
     lsg::DevBuf d_read_drop;              // layout.hip: per read, the pileup's max_depth rule under the last count's parameters: 1 = dropped in every window it overlaps, 2 = in some (d_drop_pairs)
     lsg::DevBuf d_drop_pairs; int64_t n_drop_pairs = 0;      // sorted (read << 32 | window of its contig) of the reads dropped in some windows only

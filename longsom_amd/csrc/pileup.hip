@@ -42,6 +42,8 @@ constexpr int ARENA = 256;           // rows reserved per wave per allocation: t
 enum { SC_COLS = 8, SC_OVERFLOW = 9, SC_READS = 10, SC_SEGS = 11, SC_EVENTS = 12, SC_ROWS_DEEP = 15,
        SC_ROWS = 16, SC_ROWS_SRC = 28, SC_NENT = 38, SC_QWALK = 48,
        SC_ROWALLOC = 160, SC_ROWALLOC_STRIDE = 16, SC_COUNT = SC_ROWALLOC + SC_ROWALLOC_STRIDE * LSG_MAX_CELLTYPES };   // ROWS_SRC[4]: 1 the four forms of the count (k_tm_walk, k_tm_gather_count, k_tm_count_direct, k_tm_count_win), 2 nobody (a wide job's sums go to a slab), 3 k_finalize_multi
+// (the load's words, LS_* in lsg_ctx.h, lie in the same block: a count zeroes all of it, after the load's early look has read them)
+static_assert(LS_WORDS <= SC_COUNT && LS_TOTAL < SC_QWALK, "the load's words lie inside the block a count zeroes, below the queue words");
 
 struct CountArgs {
     // reads
@@ -317,7 +319,7 @@ static void fill_args(lsg_ctx* c, const lsg_count_params* p, CountArgs& a) {
     a.drop_pairs = c->has_drops && c->n_drop_pairs ? c->d_drop_pairs.as<unsigned long long>() : nullptr; a.n_drop_pairs = c->n_drop_pairs;
     a.tile_base = c->d_tile_base.as<uint32_t>(); a.window = c->st_window;
     // every stored read passed the load filter: a count under exactly that filter, with nothing dropped, admits them all
-    const bool all_in = !c->has_drops && p->min_mq <= c->st_min_mq && (p->flag_exclude & ~c->st_flag_exclude) == 0 && (!p->ignore_orphans || c->st_ignore_orphans);
+    const bool all_in = !c->has_drops && count_admits_every_stored_read(ReadFilter{p->min_mq, p->flag_exclude, p->ignore_orphans}, ReadFilter{c->st_min_mq, c->st_flag_exclude, c->st_ignore_orphans});
     a.adm = all_in ? nullptr : c->d_read_adm.as<unsigned long long>();
     a.ne_units = c->d_ne_units.as<uint32_t>(); a.ne_nslot = c->ws[WS_NE_NSLOT].as<uint32_t>();
     a.ne_acc = c->ws[WS_NE_ACC].as<uint32_t>(); a.ne_geom = c->ws[WS_NE_GEOM].as<int2>();
@@ -1868,7 +1870,7 @@ static int count_prepare(lsg_ctx* c, const lsg_count_params* p, CountLaunch& L) 
             const uint64_t by_depth = (uint64_t)c->rd.n_events / (uint64_t)p->min_dp + 64;
             if (by_depth < want_rows) want_rows = by_depth;
         }
-        const uint64_t emitters = (uint64_t)L.grid_walk * TMW_WAVES * 2 + L.grid_fin + (uint64_t)c->n_cus * 4 + (c->wsh ? (uint64_t)c->n_cus * 16 * TMW_WAVES * 4 : 0u);      // (the windows' count: four arenas a wave)
+        const uint64_t emitters = (uint64_t)L.grid_walk * TMW_WAVES * 2 + L.grid_fin + (uint64_t)c->n_cus * 4 + (bins_windows(c->load_form) ? (uint64_t)c->n_cus * 16 * TMW_WAVES * 4 : 0u);      // (the windows' count: four arenas a wave)
         uint64_t arena = want_rows / (emitters * 8) / ARENA * ARENA;
         c->arena = (uint32_t)(arena < (uint64_t)ARENA ? (uint64_t)ARENA : (arena > 8ull * ARENA ? 8ull * ARENA : arena));
         want_rows += emitters * c->arena + 64;
@@ -1966,8 +1968,10 @@ static int count_finish(lsg_ctx* c, const lsg_count_params* p, CountLaunch& L) {
 
 // The fused pass of a load (store.hip build_store when lsg_set_count_at_load is on): the plan is made (its chunk and wide-job counters
 // still on the device), the sort's output lies in src; queues everything a count queues around k_tm_gather_count and ends with the
-// count's one synchronisation.  At most two cell types (one pass), no depth-cap drops (the caller has checked the bound).
-int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc& src, bool direct) {
+// count's one synchronisation.  At most two cell types (one pass), no depth-cap drops (the caller has checked the bound).  `form` is the
+// load's settled one (load_form.h): it says which range kernel counts and where the wide jobs' entries come from.
+int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc& src, LoadForm form) {
+    const bool direct = !keeps_store(form), windows = bins_windows(form);
     hipStream_t st = c->stream;
     c->has_drops = false; c->n_depth_dropped = 0;
     CountLaunch L;
@@ -1975,7 +1979,11 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
     TgArgs tg{};
     tg.events = src.events; tg.n_events = src.n_events; tg.key = src.key; tg.rdv = src.rdv; tg.cb_bits = src.cb_bits;
     tg.src_mask = (1ull << ((src.rdv ? 52 : 50) - src.cb_bits)) - 1ull; tg.src_shift = src.src_shift;
-    if (!src.rdv && (!direct || L.a.adm)) return 1;      // (keys alone carry no read index: a count that looks reads up is made from a load that kept them; build_store loads again)
+    // keys alone carry no read index, and the windows' count reads keys alone, 8-bit quality thresholds and 256-byte blocks: load_settle
+    // gives no other load these forms
+    if ((!src.rdv && (!direct || L.a.adm)) || (windows && (src.rdv || p->min_bq < 1 || p->min_bq > 255 || src.src_shift != 7))) {
+        set_error("lsg_load_reads: internal error: the load's form (%d) does not fit its count", (int)form); return -1;
+    }
     tg.tile_off = c->d_tile_off.as<uint32_t>(); tg.blk_off = c->tm[TM_BLK_OFF].as<uint32_t>();
     tg.s0 = c->tm[TM_S0].as<uint32_t>(); tg.b8 = c->tm[TM_B].as<uint8_t>(); tg.rd = c->tm[TM_RD].as<uint32_t>();
     tg.store = c->tm[TM_STORE].as<uint4>(); tg.ext = c->tm[TM_EXT].as<uint16_t>();
@@ -1986,7 +1994,6 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
     stage("count prepared");
     LSG_HIP(hipEventRecord(c->ev[1], st)); LSG_HIP(hipEventRecord(c->ev[3], st));
     // which range kernel counts, and which entry source its wide jobs are left to
-    enum { GATHER, TILES, WINDOWS } form = !direct ? GATHER : (src.wsh ? WINDOWS : TILES);
     const char* what = "k_tm_gather_count";
     if (direct) {
         // no store (lsg_set_store_policy): the XCDs' job queues
@@ -1994,20 +2001,17 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
         LSG_HIP(hipMemsetAsync(c->d_xcd_queues.p, 0, 8 * 128, st));
         tg.queues = c->d_xcd_queues.as<unsigned long long>();
     }
-    if (form == WINDOWS) {
+    if (windows) {
         // entries binned by 128-position windows (store.hip build_store): one 256-byte block per entry; 17 KB of LDS a workgroup: 9 per CU
-        if (tg.rdv || L.a.adm || p->min_bq < 1 || p->min_bq > 255 || tg.src_shift != 7) return 1;      // (build_store makes such a load by tiles)
         tg.src_mask = (1ull << (48 - src.cb_bits)) - 1ull;      // (seven bits each for the first position and the events - 1)
-        c->line_loads = true;
         const unsigned gridw = (unsigned)(c->n_cus * tune_int("LSG_GRID_TW", 9));
         hipLaunchKernelGGL(k_tm_count_win, dim3(gridw), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
         what = "k_tm_count_win";
-    } else if (form == TILES) {
+    } else if (direct) {
         // 80 registers per lane: 6 waves per SIMD = 12 workgroups per CU (8: 9.3 ms, 10: 8.5, 12: 8.2)
         const unsigned grid = (unsigned)(c->n_cus * tune_int("LSG_GRID_TD", 12));
         // tile-phased events: an entry is fetched as its one 128-byte line (tm_add<.., true>: the quality compare reads the event's low byte)
-        const bool al = tg.src_shift == 6 && p->min_bq >= 1 && p->min_bq <= 255;
-        c->line_loads = al;
+        const bool al = form == LOAD_LINES;
         if (tg.rdv && al) hipLaunchKernelGGL((k_tm_count_direct<false, true>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
         else if (tg.rdv) hipLaunchKernelGGL((k_tm_count_direct<false, false>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
         else if (al) hipLaunchKernelGGL((k_tm_count_direct<true, true>), dim3(grid), dim3(TMW_WAVES * 64), 0, st, L.a, L.tm, tg);
@@ -2025,8 +2029,8 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
     // where the range kernel took its entries (it ends at once when the plan has none)
     const dim3 grid_wide((unsigned)(c->n_cus * 2));
     const uint32_t* n_wide = c->d_plan_misc;
-    if (form == WINDOWS) hipLaunchKernelGGL(k_tm_walk_wide<WideFromKeys<1>>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromKeys<1>{tg}, n_wide);
-    else if (form == TILES) hipLaunchKernelGGL(k_tm_walk_wide<WideFromKeys<0>>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromKeys<0>{tg}, n_wide);
+    if (windows) hipLaunchKernelGGL(k_tm_walk_wide<WideFromKeys<1>>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromKeys<1>{tg}, n_wide);
+    else if (direct) hipLaunchKernelGGL(k_tm_walk_wide<WideFromKeys<0>>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromKeys<0>{tg}, n_wide);
     else hipLaunchKernelGGL(k_tm_walk_wide<WideFromStore>, grid_wide, dim3(64), 0, st, L.a, L.tm, WideFromStore{1}, n_wide);
     stage("wide walk");
     return count_finish(c, p, L);
@@ -2035,10 +2039,9 @@ int run_gather_count(lsg_ctx* c, const lsg_count_params* p, const GatherCountSrc
 int run_count(lsg_ctx* c, const lsg_count_params* p) {
     if (c->n_contigs <= 0) { set_error("lsg_pileup_count: no contigs set"); return -2; }
     if (c->n_ct <= 0) { set_error("lsg_pileup_count: no barcodes set"); return -2; }
-    if (c->store_skipped) { set_error("lsg_pileup_count: the load kept no store (lsg_set_store_policy): only the count it made is there - load the reads again to count with other parameters, tables or regions"); return -2; }
+    if (!keeps_store(c->load_form)) { set_error("lsg_pileup_count: the load kept no store (lsg_set_store_policy): only the count it made is there - load the reads again to count with other parameters, tables or regions"); return -2; }
     if (!c->tm_valid) { set_error("lsg_pileup_count: no reads loaded"); return -2; }
-    for (int t = 0; t < c->n_contigs; ++t)
-        if (!c->ref_ptr[t]) { set_error("lsg_pileup_count: reference of contig %d not loaded", t); return -2; }
+    if (const int t = first_missing_reference(c->ref_ptr.data(), c->n_contigs); t >= 0) { set_error("lsg_pileup_count: reference of contig %d not loaded", t); return -2; }
     if (int rc = ensure_plan(c)) return rc;
     if (depth_cap_drops(c, p)) return -1;           // free unless some cell type's pileup buffer can reach max_depth (cached bound)
     CountLaunch L;

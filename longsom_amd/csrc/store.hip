@@ -754,7 +754,7 @@ void drop_store(lsg_ctx* c) {
     c->tm_valid = false; c->plan_n_ct = 0; c->plan1_n_ct = 0; c->tm_n = 0; c->tm_events = 0; c->tm_np = 0; c->tm_nblk = 0; c->tm_njobs = 0; c->tm_nchunks = 0;
     c->tm_n_ne = 0; c->tm_n_multi = 0; c->tm_n_slabs = 0; c->tm_n_wide = 0;
     c->max_live_reads = -1; c->max_live_all = -1; c->max_live_exact = -1; c->has_drops = false;
-    c->counted = c->called = false; c->counted_at_load = false; c->load_was_fused = false; c->store_skipped = false;
+    c->counted = c->called = false; c->counted_at_load = false; c->load_form = LOAD_STORE;
 }
 
 // the build's temporaries stay in the context (grow-only): allocating ~9 GB per load costs more wall time than the build's kernels —
@@ -766,7 +766,7 @@ static void settle_temporaries(lsg_ctx* c) {
     if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) return;
     // (a load that kept no store holds little else: its temporaries stay while a quarter of the device is free - giving 46 GB back and
     // asking for them again cost C4's next load 3.8 s)
-    const bool tight = c->store_skipped ? mem_free < mem_total / 4 : (held > mem_total / 8 || mem_free < mem_total / 8);
+    const bool tight = !keeps_store(c->load_form) ? mem_free < mem_total / 4 : (held > mem_total / 8 || mem_free < mem_total / 8);
     if (tight) { for (auto& b : c->bt) b.release(); c->ws[WS_SEG_INFO].release(); c->plan1_n_ct = 0; }      // (the plan's tile-level half lived there: the first count makes it again)
 }
 
@@ -786,10 +786,6 @@ static hipError_t lsg_segmented_sort(Args&&... args) { return rocprim::segmented
 template <unsigned RB, unsigned BS, unsigned IPT, class... Args>
 static hipError_t lsg_segmented_sort_keys(Args&&... args) { return rocprim::segmented_radix_sort_keys<LsgSortConfig<RB, BS, IPT>>(std::forward<Args>(args)...); }
 
-// Can the load make the count itself (lsg_set_count_at_load: at most two cell types, barcodes set, the copy stream for the plan)?  The gate
-// of every form of the load below that counts; each form adds conditions of its own.
-static bool count_in_load(const lsg_ctx* c) { return c->cal_enabled && c->n_ct >= 1 && c->n_ct <= 2 && c->n_cb > 0 && c->copy_stream; }
-
 // (diagnostic, LSG_TILE_HIST: how the entries spread over tile sizes; C2: DESIGN.md section 9)
 static int print_tile_hist(const lsg_ctx* c, uint32_t T) {
     std::vector<uint32_t> caps(T);
@@ -802,71 +798,97 @@ static int print_tile_hist(const lsg_ctx* c, uint32_t T) {
     return 0;
 }
 
-// The forms of a load, leanest first.  A load that cannot keep the form it was started in returns the rung to start again on
-// (build_store), always a lower one: windows and keys alone, tiles and keys alone, tiles and values.
-enum LoadRung { RUNG_WINDOWS = 1, RUNG_TILE_KEYS, RUNG_TILE_VALUES };
+// The k_tt_* launches' scratch: four parts of d_cub_tmp, a record per chunk in each
+enum { TT_PART_AGG1 = 0, TT_PART_AGG2, TT_PART_IN2, TT_PART_DIN, TT_PARTS };
+constexpr size_t TT_PART_BYTES = 16 * 1024;
+static_assert(TT_MAX_CHUNKS * sizeof(TtAgg1) <= TT_PART_BYTES && TT_MAX_CHUNKS * sizeof(TtAgg2) <= TT_PART_BYTES && TT_MAX_CHUNKS * sizeof(int32_t) <= TT_PART_BYTES,
+              "a record per chunk fits its part of the k_tt_* scratch");
+static_assert(LS_WORDS <= HP_NBLK, "the early look's two copies land apart in the pinned block");
 
-static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int64_t* seg_ev_off, const lsg_reads* src, int rung) {
-    drop_store(c);
-    hipStream_t st = c->stream;
+// One attempt at a load (build_once): the inputs, what the early look said, the form (load_form.h) and the buffers in play.
+struct LoadBuild {
+    lsg_ctx* c; hipStream_t st;
+    const uint16_t* events; int64_t n_events; const lsg_reads* in; int rung;
+    std::chrono::steady_clock::time_point t_wall;
+    BuildArgs a; unsigned g_bin;
+    LoadFacts f; LoadWant want; LoadSettled form;
+    uint32_t T;                                      // bins: tiles, or windows of two
+    uint64_t N; uint32_t nblk, n_netile; int bits;   // the early look: entries, blocks, non-empty bins, the barcode bits of the sort key
+    uint32_t* blk_off; uint32_t* d_small;            // d_small: [0] max entries of a tile, [1] non-empty tiles, [2] largest barcode id, [3] the live-reads bound
+    const uint32_t* lpt_tiles;                       // the non-empty bins deepest first (more than one), or null
+    bool done;                                       // the attempt ended early (an empty load, a count that needed no store): nothing more to queue
+    bool blk_tiles_made, tiles_planned, planned;
+    uint64_t* key_in() const { return c->bt[BT_KEY_A].as<uint64_t>(); }
+    uint64_t* key_out() const { return c->bt[BT_KEY_B].as<uint64_t>(); }
+    uint32_t* val_in() const { return c->bt[BT_VAL_A].as<uint32_t>(); }
+    uint32_t* val_out() const { return c->bt[BT_VAL_B].as<uint32_t>(); }
+};
+
+static int load_empty(LoadBuild& b) {              // nothing to store: an empty store is a store
+    b.c->layout_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b.t_wall).count();
+    b.c->tm_valid = true; b.done = true;
+    return 0;
+}
+
+// ---- 0. what the attempt wants, the zeroed tables, the kernels' arguments
+static int load_begin(LoadBuild& b, const int64_t* seg_ev_off) {
+    lsg_ctx* c = b.c; hipStream_t st = b.st;
     const int64_t S = c->rd.n_segs, R = c->rd.n_reads;
-    // (the pass that counts takes 64 .. 2^39 events; the plan's tile-level half and the depth cap's bounds need the gate alone)
-    const bool counts = count_in_load(c) && n_events >= 64 && n_events < (1ll << 39);
-    const bool skip_store = c->cal_enabled && c->store_policy == LSG_STORE_SKIP_WHEN_COUNTED;
-    // WINDOWS.  A load that will keep no store and sort keys alone (below), over events its producer says are phased modulo 128
-    // (lsg_set_events_layout; this library's own producers say so themselves), bins its entries by 128-position windows - tiles (2 w, 2 w + 1) -
-    // instead of tiles: 0.58 x as many entries through the scatter and the sort, and every entry one aligned 256-byte block for the count
-    // (k_tm_count_win).  Everything here that is "per tile" is then per window (T bins); the count's units stay the tiles'.  Should the early
-    // look say otherwise (events not phased after all, a depth cap that could fire, ...), the load starts again by tiles (RUNG_TILE_KEYS).
-    const bool win = rung == RUNG_WINDOWS && skip_store && counts && n_events >= 128 &&
-                     (c->events_layout == LSG_LAYOUT_PHASED || (c->hint_phased_events && c->hint_phased_events == (const void*)events)) && ((uintptr_t)events & 255u) == 0 && c->plp_window >= 128 &&
-                     c->cal_params.min_bq >= 1 && c->cal_params.min_bq <= 255 && (c->n_tiles & 1u) == 0;
-    const int wsh = win ? 1 : 0;
-    c->wsh = wsh;
-    const uint32_t T = c->n_tiles >> wsh;
-    const auto t_wall = std::chrono::steady_clock::now();
-    auto finish = [&]() {
-        c->layout_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall).count();
-        c->tm_valid = true;
-        return 0;
-    };
+    const lsg_count_params& q = c->cal_params;
+    LoadFacts& f = b.f;
+    f.rung = b.rung; f.cal_enabled = c->cal_enabled; f.skip_policy = c->store_policy == LSG_STORE_SKIP_WHEN_COUNTED;
+    f.n_ct = c->n_ct; f.n_cb = c->n_cb; f.copy_stream = c->copy_stream != nullptr; f.n_events = b.n_events;
+    f.says_phased = c->events_layout == LSG_LAYOUT_PHASED || (c->hint_phased_events && c->hint_phased_events == (const void*)b.events);
+    f.events_addr = (uintptr_t)b.events; f.plp_window = c->plp_window; f.min_bq = q.min_bq; f.n_tiles = c->n_tiles;
+    f.load_filter = ReadFilter{c->lf_min_mq, c->lf_flag_exclude, c->lf_ignore_orphans}; f.count_filter = ReadFilter{q.min_mq, q.flag_exclude, q.ignore_orphans};
+    f.refs_loaded = references_loaded(c->ref_ptr.data(), c->n_contigs);
+    f.test_keys_only_refused = getenv("LSG_TEST_KEYS_ONLY_REFUSED") != nullptr;
+    b.want = load_want(f);
+    const int wsh = b.want.wsh;
+    const uint32_t T = b.T = b.want.n_bins;
+    b.t_wall = std::chrono::steady_clock::now();
     for (auto& v : c->build_ms) v = 0;
     c->st_min_mq = c->lf_min_mq; c->st_flag_exclude = c->lf_flag_exclude; c->st_ignore_orphans = c->lf_ignore_orphans;
     if (c->d_tile_cap.reserve(((size_t)T + 2) * 4) || c->d_tile_off.reserve(((size_t)T + 2) * 4) || c->d_scalars.reserve(512 * 8)) return -1;
     LSG_HIP(hipMemsetAsync(c->d_tile_cap.p, 0, ((size_t)T + 2) * 4, st));
     LSG_HIP(hipMemsetAsync(c->d_tile_off.p, 0, ((size_t)T + 2) * 4, st));
-    if (S <= 0 || T == 0) { LSG_HIP(hipStreamSynchronize(st)); return finish(); }
+    if (S <= 0 || T == 0) { LSG_HIP(hipStreamSynchronize(st)); return load_empty(b); }
     if (c->ws[WS_SEG_INFO].reserve(((size_t)S + 1) * 8)) return -1;
-    LSG_HIP(hipMemsetAsync(c->d_scalars.p, 0, 64, st));
-    BuildArgs a{};
-    a.n_reads = R; a.n_segs = S; a.n_events = n_events;
-    const lsg_reads& in = src ? *src : c->rd;          // (same contents: the handle's copies of a caller's device arrays may still be travelling on the copy stream)
+    unsigned long long* sc = c->d_scalars.as<unsigned long long>();
+    LSG_HIP(hipMemsetAsync(sc, 0, LS_TOTAL * 8, st));
+    BuildArgs& a = b.a;
+    a.n_reads = R; a.n_segs = S; a.n_events = b.n_events;
+    const lsg_reads& in = *b.in;
     a.read_tid = in.read_tid; a.read_flag = in.read_flag; a.read_mapq = in.read_mapq; a.read_cb = in.read_cb;
     a.seg_read = in.seg_read; a.seg_start = in.seg_start; a.seg_len = in.seg_len; a.seg_ev_off = seg_ev_off;
     a.tile_base = c->d_tile_base.as<uint32_t>(); a.contig_len = c->d_contig_len.as<int64_t>(); a.n_contigs = c->n_contigs; a.n_tiles = T;
     a.seg_info = c->ws[WS_SEG_INFO].as<uint2>(); a.tile_cap = c->d_tile_cap.as<uint32_t>();
     a.lf_min_mq = c->lf_min_mq; a.lf_flag_exclude = c->lf_flag_exclude; a.lf_ignore_orphans = c->lf_ignore_orphans;
     a.window = c->plp_window; c->st_window = c->plp_window; a.wsh = wsh;
-    a.qhead = c->d_scalars.as<unsigned long long>(); a.bad = reinterpret_cast<uint32_t*>(c->d_scalars.as<unsigned long long>() + 2);
-    a.n_ev = c->d_scalars.as<unsigned long long>() + 3;
+    a.qhead = sc + LS_QHEAD; a.bad = reinterpret_cast<uint32_t*>(sc + LS_BAD); a.n_ev = sc + LS_EVENTS;
     if (c->bt[BT_SPAN].reserve(((size_t)T + 2) * 4)) return -1;
     LSG_HIP(hipMemsetAsync(c->bt[BT_SPAN].p, 0, ((size_t)T + 2) * 4, st));
     a.span_diff = c->bt[BT_SPAN].as<int32_t>();
-    uint32_t* d_small = reinterpret_cast<uint32_t*>(c->d_scalars.as<unsigned long long>() + 4);      // [0] max entries of a tile, [1] non-empty tiles, [2] largest barcode id, [3] the live-reads bound
-    DevBuf& tmp = c->bt[BT_TMP];
+    b.d_small = reinterpret_cast<uint32_t*>(sc + LS_SMALL);
     LSG_HIP(hipEventRecord(c->evb[0], st));
-    // ---- 1. static admission + capacities
+    return 0;
+}
+
+// ---- 1. static admission + capacities, and the load's ONE early look at the device
+static int load_measure(LoadBuild& b) {
+    lsg_ctx* c = b.c; hipStream_t st = b.st; BuildArgs& a = b.a;
+    const int64_t S = a.n_segs, R = a.n_reads; const uint32_t T = b.T;
+    DevBuf& tmp = c->bt[BT_TMP];
     unsigned g_seg = (unsigned)((S + 256 * SEG_U - 1) / (256 * SEG_U)); if (g_seg > (unsigned)(c->n_cus * 16)) g_seg = (unsigned)(c->n_cus * 16);
-    unsigned g_bin = (unsigned)((S + 256 * BIN_SUPER - 1) / (256 * BIN_SUPER)); if (g_bin > (unsigned)(c->n_cus * 8)) g_bin = (unsigned)(c->n_cus * 8);
+    b.g_bin = (unsigned)((S + 256 * BIN_SUPER - 1) / (256 * BIN_SUPER)); if (b.g_bin > (unsigned)(c->n_cus * 8)) b.g_bin = (unsigned)(c->n_cus * 8);
     if (c->bt[BT_PER_TILE].reserve(((size_t)T + 2) * 4)) return -1;
     LSG_HIP(hipMemsetAsync(c->bt[BT_PER_TILE].p, 0, ((size_t)T + 2) * 4, st));
     a.cap_diff = c->bt[BT_PER_TILE].as<int32_t>();
     hipLaunchKernelGGL(k_seg_static, dim3(g_seg), dim3(256), 0, st, a);
     if (c->bt[BT_NETILE].reserve(((size_t)T + 2) * 4) || c->tm[TM_BLK_OFF].reserve(((size_t)T + 2) * 4)) return -1;
-    uint32_t* blk_off = c->tm[TM_BLK_OFF].as<uint32_t>();
-    unsigned long long* d_sum = c->d_scalars.as<unsigned long long>() + 8;
+    b.blk_off = c->tm[TM_BLK_OFF].as<uint32_t>();
     {
-        auto reduce_max_cb = [&](void* p, size_t& b, int64_t n) { return hipcub::DeviceReduce::Max(p, b, in.read_cb, reinterpret_cast<int32_t*>(d_small + 2), (int)n, st); };
+        auto reduce_max_cb = [&](void* p, size_t& n_, int64_t n) { return hipcub::DeviceReduce::Max(p, n_, b.in->read_cb, reinterpret_cast<int32_t*>(b.d_small + 2), (int)n, st); };
         size_t tb = 0;
         LSG_HIP(reduce_max_cb(nullptr, tb, R > 0 ? R : 1));
         if (tmp.reserve(tb + 256 + 64 * 1024)) return -1;
@@ -875,185 +897,209 @@ static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, cons
     }
     {   // everything that follows from the range marks, in five launches (k_tt_*): the sizes below reach the host in the load's ONE early
         // look (the scatter, the sort and the gather are then queued without waiting for one another)
-        if (c->d_cub_tmp.reserve(64 * 1024)) return -1;
+        if (c->d_cub_tmp.reserve(TT_PARTS * TT_PART_BYTES)) return -1;
         TtArgs ta{};
         ta.cap_diff = a.cap_diff; ta.span_diff = a.span_diff; ta.T = T;
         const uint64_t per = ((uint64_t)T + 1 + TT_MAX_CHUNKS - 1) / TT_MAX_CHUNKS;
         ta.chunk = (uint32_t)((per + TT_SUB - 1) / TT_SUB * TT_SUB);
         ta.n_chunks = (uint32_t)(((uint64_t)T + 1 + ta.chunk - 1) / ta.chunk);
         char* scratch = reinterpret_cast<char*>(c->d_cub_tmp.p);          // (a buffer nothing else on this stream holds across these launches)
-        ta.agg1 = reinterpret_cast<TtAgg1*>(scratch); ta.agg2 = reinterpret_cast<TtAgg2*>(scratch + 16 * 1024); ta.in2 = reinterpret_cast<TtAgg2*>(scratch + 32 * 1024);
-        ta.din = reinterpret_cast<int32_t*>(scratch + 48 * 1024);
-        ta.cap = c->d_tile_cap.as<uint32_t>(); ta.tile_off = c->d_tile_off.as<uint32_t>(); ta.blk_off = blk_off; ta.netile = c->bt[BT_NETILE].as<uint32_t>();
-        ta.d_small = d_small; ta.d_sum = d_sum;
+        ta.agg1 = reinterpret_cast<TtAgg1*>(scratch + TT_PART_AGG1 * TT_PART_BYTES); ta.agg2 = reinterpret_cast<TtAgg2*>(scratch + TT_PART_AGG2 * TT_PART_BYTES);
+        ta.in2 = reinterpret_cast<TtAgg2*>(scratch + TT_PART_IN2 * TT_PART_BYTES); ta.din = reinterpret_cast<int32_t*>(scratch + TT_PART_DIN * TT_PART_BYTES);
+        ta.cap = c->d_tile_cap.as<uint32_t>(); ta.tile_off = c->d_tile_off.as<uint32_t>(); ta.blk_off = b.blk_off; ta.netile = c->bt[BT_NETILE].as<uint32_t>();
+        ta.d_small = b.d_small; ta.d_sum = c->d_scalars.as<unsigned long long>() + LS_TOTAL;
         hipLaunchKernelGGL(k_tt_marks, dim3(ta.n_chunks), dim3(TT_THREADS), 0, st, ta);
         hipLaunchKernelGGL(k_tt_scan1, dim3(1), dim3(TT_MAX_CHUNKS), 0, st, ta);
         hipLaunchKernelGGL(k_tt_caps, dim3(ta.n_chunks), dim3(TT_THREADS), 0, st, ta);
         hipLaunchKernelGGL(k_tt_scan2, dim3(1), dim3(TT_MAX_CHUNKS), 0, st, ta);
         hipLaunchKernelGGL(k_tt_offsets, dim3(ta.n_chunks), dim3(TT_THREADS), 0, st, ta);
     }
-    uint32_t total = 0, bad = 0, n_netile = 0, nblk = 0; int32_t max_cb = 0, max_live = 0;
-    unsigned long long n_ev = 0, sum = 0;
     // the load's first look at the device: the sizes of everything that follows, in TWO small copies to pinned memory (the scalars'
     // block, and the number of blocks where the scan left it) - seven separate copies were seven commands of ~20 us each on the stream
-    LSG_HIP(hipMemcpyAsync(c->h_pin, c->d_scalars.p, 9 * 8, hipMemcpyDeviceToHost, st));
-    LSG_HIP(hipMemcpyAsync(c->h_pin + 16, blk_off + T, 4, hipMemcpyDeviceToHost, st));
+    LSG_HIP(hipMemcpyAsync(c->h_pin + HP_LOOK, c->d_scalars.p, LS_WORDS * 8, hipMemcpyDeviceToHost, st));
+    LSG_HIP(hipMemcpyAsync(c->h_pin + HP_NBLK, b.blk_off + T, 4, hipMemcpyDeviceToHost, st));
     LSG_HIP(hipStreamSynchronize(st));
-    {
-        const unsigned long long* hp = c->h_pin;
-        const uint32_t* hs = reinterpret_cast<const uint32_t*>(hp + 4);      // d_small[0..3]
-        bad = (uint32_t)hp[2]; n_ev = hp[3]; n_netile = hs[1]; max_cb = R > 0 ? (int32_t)hs[2] : 0; max_live = (int32_t)hs[3]; sum = hp[8];
-        nblk = (uint32_t)hp[16];
-    }
-    // tile-phased events (LSG_LAYOUT_PHASED): every entry lies inside one aligned 128-byte line of the caller's array; the key carries the line
-    // (k_seg_static looked at the phase modulo the bins' width: 64, or 128 for windows)
-    if (win && (bad & 4u) && !(bad & 3u)) return RUNG_TILE_KEYS;
-    const int src_shift = !(bad & 4u) && ((uintptr_t)events & (wsh ? 255u : 127u)) == 0 ? 6 + wsh : 0;
-    c->src_phased = src_shift != 0;
-    if (bad & 2u) { set_error("lsg_load_reads: a segment's read index lies outside the read arrays"); return -2; }
-    if (bad & 1u) { set_error("lsg_load_reads: a segment's event range lies outside the events array"); return -2; }
+    return 0;
+}
+
+// ---- 2. what the early look says: a restart, a refusal, an empty load - or the sizes of everything that follows
+static int load_validate(LoadBuild& b) {
+    lsg_ctx* c = b.c;
+    const unsigned long long* hp = c->h_pin + HP_LOOK;
+    const uint32_t* hs = reinterpret_cast<const uint32_t*>(hp + LS_SMALL);      // d_small[0..3]
+    const int32_t max_cb = b.a.n_reads > 0 ? (int32_t)hs[2] : 0, max_live = (int32_t)hs[3];
+    const unsigned long long n_ev = hp[LS_EVENTS], sum = hp[LS_TOTAL];
+    b.f.bad = (uint32_t)hp[LS_BAD]; b.n_netile = hs[1]; b.nblk = (uint32_t)c->h_pin[HP_NBLK];
+    if (look_refutes_windows(b.want, b.f.bad)) return RUNG_TILE_KEYS;
+    if (b.f.bad & LOOK_BAD_READ) { set_error("lsg_load_reads: a segment's read index lies outside the read arrays"); return -2; }
+    if (b.f.bad & LOOK_BAD_EVENTS) { set_error("lsg_load_reads: a segment's event range lies outside the events array"); return -2; }
     if (sum >= 0x7FFFFFF0ull) { set_error("lsg_load_reads: %llu tile entries exceed the 31-bit entry index; load the reads in windows", sum); return -2; }
-    total = (uint32_t)sum;
-    const uint64_t N = total;
-    c->tm_n = N; c->tm_events = (int64_t)n_ev;
+    b.N = (uint32_t)sum;
+    c->tm_n = b.N; c->tm_events = (int64_t)n_ev;
     c->max_live_all = max_live > 0 ? max_live : 0;
-    if (N == 0) return finish();
-    if (getenv("LSG_TILE_HIST")) { if (int rc = print_tile_hist(c, T)) return rc; }
-    // ---- 2. scatter (queued BEFORE the copy stream's work below: those two dozen launches are 0.3 ms of host time the scatter need not wait for)
+    if (b.N == 0) return load_empty(b);
+    if (getenv("LSG_TILE_HIST")) { if (int rc = print_tile_hist(c, b.T)) return rc; }
     int bits = 1; while (bits < 24 && (1ll << bits) <= (long long)max_cb) ++bits;      // the barcode bits of the sort key
-    DevBuf &key_a = c->bt[BT_KEY_A], &key_b = c->bt[BT_KEY_B], &val_a = c->bt[BT_VAL_A], &val_b = c->bt[BT_VAL_B];
-    if ((n_events >> src_shift) >= (1ll << (52 - bits - 2 * wsh))) {
-        set_error("lsg_load_reads: %lld events with %d-bit barcode ids do not fit the packed sort key (events < 2^%d): load the reads in windows", (long long)n_events, bits, 52 - bits + src_shift);
+    b.bits = b.f.bits = bits;
+    const int src_shift = load_src_shift(b.f, b.want);
+    if (!source_fits_key(b.f, b.want, src_shift, false)) {
+        set_error("lsg_load_reads: %lld events with %d-bit barcode ids do not fit the packed sort key (events < 2^%d): load the reads in windows", (long long)b.n_events, bits, 52 - bits + src_shift);
         return -2;
     }
-    // A load that is counted once, without a store, by a count that admits every stored read (the filters of the load) and whose depth cap
-    // cannot fire needs nothing of an entry's value but two flags: they ride in the key (bits 62, 63, above a source field two bits
-    // narrower) and the scatter, the sort and the count move 8 bytes an entry instead of 12.  Should the count not be made that way after
-    // all (its rows outgrow their buffer), the load starts again with values (RUNG_TILE_VALUES).
-    bool keys_only = rung <= RUNG_TILE_KEYS && skip_store && counts && (n_events >> src_shift) < (1ll << (50 - bits - 2 * wsh));
-    // Can the depth cap of the count this load is to make fire at all?  The all-reads bound per tile (window) came with the early look; when it
-    // cannot say no, the per-position bound of this table's cell types decides (layout.hip: ~10 ms at C4, whose tiles hold more than 200 000
-    // reads that no position does) - here, before the scatter, because a count whose cap cannot fire may sort keys alone.
-    bool cap_out = true;
+    return 0;
+}
+
+// ---- 3. Can the depth cap of the count this load is to make fire at all?  The all-reads bound per tile (window) came with the early look; when it
+// cannot say no, the per-position bound of this table's cell types decides (layout.hip: ~10 ms at C4, whose tiles hold more than 200 000
+// reads that no position does) - here, before the scatter, because a count whose cap cannot fire may sort keys alone.
+static int load_cap_out(LoadBuild& b) {
+    lsg_ctx* c = b.c;
+    b.f.cap_out = true;
     if (c->cal_enabled && c->cal_params.max_depth > 0 && c->max_live_all + 1 > (int64_t)c->cal_params.max_depth) {
-        cap_out = false;
-        if (count_in_load(c)) {
+        b.f.cap_out = false;
+        if (count_in_load(b.f)) {
             LSG_HIP(hipStreamSynchronize(c->copy_stream));          // (the handle's copies of the read arrays, which the bounds read, are made there)
             if (live_read_bound(c)) return -1;                      // first the tiles again, per cell type of this table (C4: 135 343 against 225 294 over all reads)
-            cap_out = c->max_live_reads + 1 <= (int64_t)c->cal_params.max_depth;
-            if (!cap_out) {
+            b.f.cap_out = c->max_live_reads + 1 <= (int64_t)c->cal_params.max_depth;
+            if (!b.f.cap_out) {
                 if (live_read_bound_exact(c)) return -1;
-                cap_out = c->max_live_exact <= (int64_t)c->cal_params.max_depth;
+                b.f.cap_out = c->max_live_exact <= (int64_t)c->cal_params.max_depth;
             }
         }
     }
-    if (keys_only) {
-        const lsg_count_params& q = c->cal_params;
-        if (q.min_mq != c->st_min_mq || q.flag_exclude != c->st_flag_exclude || (q.ignore_orphans != 0) != (c->st_ignore_orphans != 0)) keys_only = false;
-        if (!cap_out) keys_only = false;
-        for (int t = 0; t < c->n_contigs && keys_only; ++t) if (!c->ref_ptr[t]) keys_only = false;
-    }
-    if (win && !keys_only) return RUNG_TILE_KEYS;
-    if (keys_only && getenv("LSG_TIMING")) fprintf(stderr, "[lsg] load: keys alone through the scatter and the sort (8 bytes an entry)%s\n", win ? ", entries binned by 128-position windows" : "");
-    if (key_a.reserve(N * 8 + 16) || key_b.reserve(N * 8 + 16) || (!keys_only && (val_a.reserve(N * 4 + 16) || val_b.reserve(N * 4 + 16))) ||
+    return 0;
+}
+
+// ---- 4. the form of this load (load_form.h), or the rung to start again on
+static int load_settle_form(LoadBuild& b) {
+    b.form = load_settle(b.f, b.want);
+    if (b.form.restart) return b.form.restart;
+    b.c->load_form = b.form.form;                  // (what the plan and the count's preparation read from here on; rows that outgrow their buffer change it once more)
+    if (b.form.keys_only && getenv("LSG_TIMING")) fprintf(stderr, "[lsg] load: keys alone through the scatter and the sort (8 bytes an entry)%s\n", b.want.win ? ", entries binned by 128-position windows" : "");
+    return 0;
+}
+
+// ---- 5. scatter (queued BEFORE the copy stream's work below: those two dozen launches are 0.3 ms of host time the scatter need not wait for)
+static int load_scatter(LoadBuild& b) {
+    lsg_ctx* c = b.c; hipStream_t st = b.st; BuildArgs& a = b.a;
+    const uint64_t N = b.N; const uint32_t T = b.T; const bool keys_only = b.form.keys_only;
+    if (c->bt[BT_KEY_A].reserve(N * 8 + 16) || c->bt[BT_KEY_B].reserve(N * 8 + 16) || (!keys_only && (c->bt[BT_VAL_A].reserve(N * 4 + 16) || c->bt[BT_VAL_B].reserve(N * 4 + 16))) ||
         c->bt[BT_CURSOR].reserve(((size_t)T + 2) * 4)) return -1;
     // (the cursors in a buffer of their own: the plan's tile-level half may be at work in BT_PER_TILE beside the scatter)
-    a.cursor = c->bt[BT_CURSOR].as<uint32_t>(); a.key = key_a.as<uint64_t>(); a.rdv = keys_only ? nullptr : val_a.as<uint32_t>(); a.cb_bits = bits; a.src_shift = src_shift;
+    a.cursor = c->bt[BT_CURSOR].as<uint32_t>(); a.key = b.key_in(); a.rdv = keys_only ? nullptr : b.val_in(); a.cb_bits = b.bits; a.src_shift = b.form.src_shift;
     LSG_HIP(hipMemcpyAsync(a.cursor, c->d_tile_off.p, ((size_t)T + 1) * 4, hipMemcpyDeviceToDevice, st));
-    LSG_HIP(hipMemsetAsync(c->d_scalars.p, 0, 8, st));
-    hipLaunchKernelGGL(k_bin, dim3(g_bin), dim3(BIN_THREADS), 0, st, a);
+    LSG_HIP(hipMemsetAsync(c->d_scalars.as<unsigned long long>() + LS_QHEAD, 0, 8, st));
+    hipLaunchKernelGGL(k_bin, dim3(b.g_bin), dim3(BIN_THREADS), 0, st, a);
     LSG_HIP(hipEventRecord(c->evb[1], st));
-    // ---- beside the scatter, on the copy stream: what follows from the capacities alone
-    if (c->tm[TM_BLK_TILE].reserve(((size_t)nblk + 2) * 4)) return -1;
-    bool blk_tiles_made = false;
+    return 0;
+}
+
+// The segmented sort of the bins' entries by barcode: keys alone or (key, value) pairs as the form says, over the segments [seg_begin[i],
+// seg_end[i]), on `s`, with `block` threads a workgroup in the block sort (512: keys alone only).  tmp null: the scratch's size.
+// (64-bit keys sorted on their barcode bits only, begin_bit 0 .. end_bit `bits`: the rest of the key is payload)
+// (one configuration: 7 bits per pass, 256 x 8 items in the block sort - the sweep over 512 / 1024 threads, 4-16 items and 8 bits per pass
+// that used to be selectable here found nothing faster, and cost a minute of compile time)
+static hipError_t sort_bins(const LoadBuild& b, void* tmp, size_t& tmp_n, uint32_t* seg_begin, uint32_t* seg_end, hipStream_t s, unsigned block = 256) {
+    uint64_t* ki = tmp ? b.key_in() : nullptr; uint64_t* ko = tmp ? b.key_out() : nullptr;
+    const unsigned N = (unsigned)b.N, n_seg = (unsigned)b.n_netile, bits = (unsigned)b.bits;
+    if (!b.form.keys_only) return lsg_segmented_sort<7, 256, 8>(tmp, tmp_n, ki, ko, tmp ? b.val_in() : (uint32_t*)nullptr, tmp ? b.val_out() : (uint32_t*)nullptr, N, n_seg, seg_begin, seg_end, 0u, bits, s, false);
+    if (block == 512) return lsg_segmented_sort_keys<7, 512, 8>(tmp, tmp_n, ki, ko, N, n_seg, seg_begin, seg_end, 0u, bits, s, false);
+    return lsg_segmented_sort_keys<7, 256, 8>(tmp, tmp_n, ki, ko, N, n_seg, seg_begin, seg_end, 0u, bits, s, false);
+}
+
+// the tile of every block (the re-counts' resolve and the plain gather read it; the fused pass does not), on `s`
+// (the scratch is BT_COPY_TMP, sized by load_side_work before anything is queued on the copy stream; on the main stream - the fall-back - the
+// copy stream has been waited for)
+static hipError_t scan_blk_tiles(const LoadBuild& b, void* p, size_t& n, hipStream_t s) {
+    uint32_t* bt_ = b.c->tm[TM_BLK_TILE].as<uint32_t>();
+    return hipcub::DeviceScan::InclusiveScan(p, n, bt_, bt_, hipcub::Max(), (int)b.nblk, s);
+}
+static int blk_tiles(LoadBuild& b, hipStream_t s) {
+    lsg_ctx* c = b.c;
+    uint32_t* bt_ = c->tm[TM_BLK_TILE].as<uint32_t>();
+    LSG_HIP(hipMemsetAsync(bt_, 0, (size_t)b.nblk * 4, s));
+    hipLaunchKernelGGL(k_tm_blk_mark, dim3((b.T + 255) / 256), dim3(256), 0, s, c->d_tile_cap.as<uint32_t>(), b.blk_off, b.T, bt_);
+    size_t tb = c->bt[BT_COPY_TMP].cap;
+    LSG_HIP(scan_blk_tiles(b, c->bt[BT_COPY_TMP].p, tb, s));
+    LSG_HIP(hipEventRecord(c->ev_blk, s));
+    b.blk_tiles_made = true;
+    return 0;
+}
+
+// ---- 6. beside the scatter, on the copy stream: what follows from the capacities alone
+static int load_side_work(LoadBuild& b) {
+    lsg_ctx* c = b.c;
+    const uint32_t n_netile = b.n_netile;
+    if (c->tm[TM_BLK_TILE].reserve(((size_t)b.nblk + 2) * 4)) return -1;
     const bool lpt = n_netile > 1;
-    const uint32_t* lpt_tiles = nullptr;
-    // (the scratch is BT_COPY_TMP, sized below before anything is queued on the copy stream; on the main stream - the fall-back - the
-    // copy stream has been waited for)
-    auto scan_blk_tiles = [&](void* p, size_t& b, hipStream_t s_) { uint32_t* bt_ = c->tm[TM_BLK_TILE].as<uint32_t>(); return hipcub::DeviceScan::InclusiveScan(p, b, bt_, bt_, hipcub::Max(), (int)nblk, s_); };
-    auto blk_tiles = [&](hipStream_t s_) -> int {
-        uint32_t* bt_ = c->tm[TM_BLK_TILE].as<uint32_t>();
-        LSG_HIP(hipMemsetAsync(bt_, 0, (size_t)nblk * 4, s_));
-        hipLaunchKernelGGL(k_tm_blk_mark, dim3((T + 255) / 256), dim3(256), 0, s_, c->d_tile_cap.as<uint32_t>(), blk_off, T, bt_);
+    hipStream_t bs = c->copy_stream;
+    DevBuf& lk = c->bt[BT_LPT];
+    const size_t lpt_pitch = ((size_t)n_netile + 64) & ~(size_t)63;            // (every array on a 256-byte boundary)
+    if (lpt && lk.reserve(lpt_pitch * 4 * 3)) return -1;
+    uint32_t* k_in = lk.as<uint32_t>(); uint32_t* k_out = k_in + lpt_pitch; uint32_t* t_out = k_out + lpt_pitch;
+    auto sort_lpt = [&](void* p, size_t& n) { return hipcub::DeviceRadixSort::SortPairsDescending(p, n, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs); };
+    // (the scratch of both is sized BEFORE either is queued: growing a buffer frees it, and work queued on this stream may still be reading it)
+    size_t tb_lpt = 0, tb_blk = 0;
+    if (lpt) LSG_HIP(sort_lpt(nullptr, tb_lpt));
+    LSG_HIP(scan_blk_tiles(b, nullptr, tb_blk, bs));
+    // (... and of the sort of the shallow tiles, which runs on this stream beside the deep tiles' sort: load_sort)
+    size_t tb_sort2 = 0;
+    if (n_netile) LSG_HIP(sort_bins(b, nullptr, tb_sort2, nullptr, nullptr, bs));
+    size_t tb_max = tb_lpt > tb_blk ? tb_lpt : tb_blk;
+    if (tb_sort2 > tb_max) tb_max = tb_sort2;
+    if (c->bt[BT_COPY_TMP].reserve(tb_max + 256)) return -1;
+    if (lpt) {
+        // The sort's segments deepest first: rocprim gives every segment beyond its block sort to ONE workgroup, and the deepest tiles
+        // (chrM: the last contig) would start last - their workgroups' tail is then hidden behind the rest.  A stable radix sort of the
+        // non-empty tiles by capacity >> 11 (what lies above the block sort's 2048: the shallower ones keep their order).  The keys are
+        // shifted by k_tile_caps and sorted from bit 0: rocprim 7.2's radix sort with begin_bit > 0 returns wrong pairs below ~1M items.
+        hipLaunchKernelGGL(k_tile_caps, dim3((n_netile + 255) / 256), dim3(256), 0, bs, c->bt[BT_NETILE].as<uint32_t>(), n_netile, c->d_tile_cap.as<uint32_t>(), k_in);
         size_t tb = c->bt[BT_COPY_TMP].cap;
-        LSG_HIP(scan_blk_tiles(c->bt[BT_COPY_TMP].p, tb, s_));
-        LSG_HIP(hipEventRecord(c->ev_blk, s_));
-        blk_tiles_made = true;
-        return 0;
-    };
-    {
-        hipStream_t bs = c->copy_stream;
-        DevBuf& lk = c->bt[BT_LPT];
-        const size_t lpt_pitch = ((size_t)n_netile + 64) & ~(size_t)63;            // (every array on a 256-byte boundary)
-        if (lpt && lk.reserve(lpt_pitch * 4 * 3)) return -1;
-        uint32_t* k_in = lk.as<uint32_t>(); uint32_t* k_out = k_in + lpt_pitch; uint32_t* t_out = k_out + lpt_pitch;
-        auto sort_lpt = [&](void* p, size_t& b) { return hipcub::DeviceRadixSort::SortPairsDescending(p, b, k_in, k_out, c->bt[BT_NETILE].as<uint32_t>(), t_out, (int)n_netile, 0, 21, bs); };
-        // (the scratch of both is sized BEFORE either is queued: growing a buffer frees it, and work queued on this stream may still be reading it)
-        size_t tb_lpt = 0, tb_blk = 0;
-        if (lpt) LSG_HIP(sort_lpt(nullptr, tb_lpt));
-        LSG_HIP(scan_blk_tiles(nullptr, tb_blk, bs));
-        // (... and of the sort of the shallow tiles, which runs on this stream beside the deep tiles' sort: below)
-        size_t tb_sort2 = 0;
-        if (n_netile) {
-            if (keys_only) LSG_HIP((lsg_segmented_sort_keys<7, 256, 8>(nullptr, tb_sort2, (uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned)N, (unsigned)n_netile, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (unsigned)bits, bs, false)));
-            else LSG_HIP((lsg_segmented_sort<7, 256, 8>(nullptr, tb_sort2, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned)N, (unsigned)n_netile,
-                                                        (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (unsigned)bits, bs, false)));
-        }
-        size_t tb_max = tb_lpt > tb_blk ? tb_lpt : tb_blk;
-        if (tb_sort2 > tb_max) tb_max = tb_sort2;
-        if (c->bt[BT_COPY_TMP].reserve(tb_max + 256)) return -1;
-        void* scratch = c->bt[BT_COPY_TMP].p;
-        if (lpt) {
-            // The sort's segments deepest first: rocprim gives every segment beyond its block sort to ONE workgroup, and the deepest tiles
-            // (chrM: the last contig) would start last - their workgroups' tail is then hidden behind the rest.  A stable radix sort of the
-            // non-empty tiles by capacity >> 11 (what lies above the block sort's 2048: the shallower ones keep their order).  The keys are
-            // shifted by k_tile_caps and sorted from bit 0: rocprim 7.2's radix sort with begin_bit > 0 returns wrong pairs below ~1M items.
-            hipLaunchKernelGGL(k_tile_caps, dim3((n_netile + 255) / 256), dim3(256), 0, bs, c->bt[BT_NETILE].as<uint32_t>(), n_netile, c->d_tile_cap.as<uint32_t>(), k_in);
-            size_t tb = c->bt[BT_COPY_TMP].cap;
-            LSG_HIP(sort_lpt(scratch, tb));
-            LSG_HIP(hipEventRecord(c->ev_lpt, bs));
-            lpt_tiles = t_out;
-        }
-        // the tile of every block (the re-counts' resolve and the plain gather read it; the fused pass does not) - left out when the load is
-        // to keep no store (should it build one after all, blk_tiles() runs then)
-        if (!skip_store) { if (int rc = blk_tiles(bs)) return rc; }
+        LSG_HIP(sort_lpt(c->bt[BT_COPY_TMP].p, tb));
+        LSG_HIP(hipEventRecord(c->ev_lpt, bs));
+        b.lpt_tiles = t_out;
     }
-    // The plan's tile-level half (units, jobs and slabs per bin and their totals: it reads the capacities only) on the copy stream NOW, beside
-    // the scatter - it ends in a host round trip that used to wait for the shallow bins' sort on that stream (0.25 ms of nothing between the
-    // sort and the count for a rank's eighth of a sample) - whenever the load is to make its count
-    const bool tiles_planned = count_in_load(c);
-    if (tiles_planned) {
-        if (int rc = plan_tiles(c, c->copy_stream)) return rc;
-        plan_finish_tiles(c);
+    // the tile of every block - left out when the load is to keep no store (should it build one after all, load_reserve_store makes them)
+    if (!b.want.skip_store) { if (int rc = blk_tiles(b, bs)) return rc; }
+    return 0;
+}
+
+// ---- 7. The plan's tile-level half (units, jobs and slabs per bin and their totals: it reads the capacities only) on the copy stream NOW, beside
+// the scatter - it ends in a host round trip that used to wait for the shallow bins' sort on that stream (0.25 ms of nothing between the
+// sort and the count for a rank's eighth of a sample) - whenever the load is to make its count
+static int load_plan_tiles(LoadBuild& b) {
+    b.tiles_planned = count_in_load(b.f);
+    if (b.tiles_planned) {
+        if (int rc = plan_tiles(b.c, b.c->copy_stream)) return rc;
+        plan_finish_tiles(b.c);
     }
-    // ---- 3. every tile's entries by barcode
+    return 0;
+}
+
+// ---- 8. every tile's entries by barcode: the deep tiles on the main stream, the shallow ones beside them on the copy stream
+static int load_sort(LoadBuild& b) {
+    lsg_ctx* c = b.c; hipStream_t st = b.st;
+    const uint32_t n_netile = b.n_netile;
     if (n_netile) {
         // (begin / end of the deep tiles' sort, then of the shallow tiles' sort: four arrays of n_netile + 1 in the two buffers)
         const size_t seg_pitch = ((size_t)n_netile + 64) & ~(size_t)63;
         if (c->bt[BT_SEG_BEGIN].reserve(seg_pitch * 8) || c->bt[BT_SEG_END].reserve(seg_pitch * 8)) return -1;
         uint32_t* sb1 = c->bt[BT_SEG_BEGIN].as<uint32_t>(); uint32_t* se1 = c->bt[BT_SEG_END].as<uint32_t>();
         uint32_t* sb2 = sb1 + seg_pitch; uint32_t* se2 = se1 + seg_pitch;
-        if (lpt) LSG_HIP(hipStreamWaitEvent(st, c->ev_lpt, 0));
-        hipLaunchKernelGGL(k_seg_bounds, dim3((n_netile + 255) / 256), dim3(256), 0, st, lpt ? lpt_tiles : c->bt[BT_NETILE].as<uint32_t>(), n_netile, c->d_tile_off.as<uint32_t>(), sb1, se1, sb2, se2);
+        if (b.lpt_tiles) LSG_HIP(hipStreamWaitEvent(st, c->ev_lpt, 0));
+        hipLaunchKernelGGL(k_seg_bounds, dim3((n_netile + 255) / 256), dim3(256), 0, st, b.lpt_tiles ? b.lpt_tiles : c->bt[BT_NETILE].as<uint32_t>(), n_netile, c->d_tile_off.as<uint32_t>(), sb1, se1, sb2, se2);
         LSG_HIP(hipEventRecord(c->ev_copy, st));      // (the second sort, queued below, starts here)
+        // (a small load - a rank's share of a sharded sample - is bound by ONE workgroup working through its deepest tile, 2048 entries
+        // an iteration: 512 threads take 4096 - C2 in eight shards 0.71 -> 0.42-0.55 ms, in four 0.76 -> 0.69; 1024 threads gain on the
+        // deepest tiles and lose on all others; a whole sample is bound by throughput, where the small workgroups win)
+        // (C2: 23 M entries a rank in eight shards, 46 M in four, 92 M in two - where the big workgroups already lose)
+        const unsigned block = b.N < (64ull << 20) ? 512 : 256;
+        DevBuf& tmp = c->bt[BT_TMP];
         size_t tb = 0;
-        // (64-bit keys sorted on their barcode bits only, begin_bit 0 .. end_bit `bits`: the rest of the key is payload)
-        // (one configuration: 7 bits per pass, 256 x 8 items in the block sort - the sweep over 512 / 1024 threads, 4-16 items and 8 bits per pass
-        // that used to be selectable here found nothing faster, and cost a minute of compile time)
-        const bool big_blocks = N < (64ull << 20);       // (C2: 23 M entries a rank in eight shards, 46 M in four, 92 M in two - where the big workgroups already lose)
-        auto sort = [&](void* tmp_p, size_t& tmp_n) {
-            // (a small load - a rank's share of a sharded sample - is bound by ONE workgroup working through its deepest tile, 2048 entries
-            // an iteration: 512 threads take 4096 - C2 in eight shards 0.71 -> 0.42-0.55 ms, in four 0.76 -> 0.69; 1024 threads gain on the
-            // deepest tiles and lose on all others; a whole sample is bound by throughput, where the small workgroups win)
-            if (keys_only && big_blocks) return lsg_segmented_sort_keys<7, 512, 8>(tmp_p, tmp_n, key_a.as<uint64_t>(), key_b.as<uint64_t>(), (unsigned)N, (unsigned)n_netile, sb1, se1, 0u, (unsigned)bits, st, false);
-            if (keys_only) return lsg_segmented_sort_keys<7, 256, 8>(tmp_p, tmp_n, key_a.as<uint64_t>(), key_b.as<uint64_t>(), (unsigned)N, (unsigned)n_netile, sb1, se1, 0u, (unsigned)bits, st, false);
-            return lsg_segmented_sort<7, 256, 8>(tmp_p, tmp_n, key_a.as<uint64_t>(), key_b.as<uint64_t>(), val_a.as<uint32_t>(), val_b.as<uint32_t>(), (unsigned)N, (unsigned)n_netile,
-                                                 sb1, se1, 0u, (unsigned)bits, st, false);
-        };
-        LSG_HIP(sort(nullptr, tb));
+        LSG_HIP(sort_bins(b, nullptr, tb, sb1, se1, st, block));
         if (tmp.reserve(tb + 256)) return -1;
         tb = tmp.cap;
-        LSG_HIP(sort(tmp.p, tb));
+        LSG_HIP(sort_bins(b, tmp.p, tb, sb1, se1, st, block));
         // rocprim runs its three kernels (a block per segment beyond 256 entries: 2.7 ms at C2; the warp sorts of the segments up to 256 and up
         // to 64: 0.55 ms) one after the other, and the first one's tail leaves most of the chip idle: the shallow tiles are sorted on the copy
         // stream beside it (same output arrays, disjoint segments, scratch of its own); queued AFTER the deep tiles' sort so that the
@@ -1061,107 +1107,125 @@ static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, cons
         hipStream_t bs = c->copy_stream;
         LSG_HIP(hipStreamWaitEvent(bs, c->ev_copy, 0));
         size_t tb2 = c->bt[BT_COPY_TMP].cap;
-        if (keys_only) LSG_HIP((lsg_segmented_sort_keys<7, 256, 8>(c->bt[BT_COPY_TMP].p, tb2, key_a.as<uint64_t>(), key_b.as<uint64_t>(), (unsigned)N, (unsigned)n_netile, sb2, se2, 0u, (unsigned)bits, bs, false)));
-        else LSG_HIP((lsg_segmented_sort<7, 256, 8>(c->bt[BT_COPY_TMP].p, tb2, key_a.as<uint64_t>(), key_b.as<uint64_t>(), val_a.as<uint32_t>(), val_b.as<uint32_t>(), (unsigned)N, (unsigned)n_netile,
-                                                    sb2, se2, 0u, (unsigned)bits, bs, false)));
+        LSG_HIP(sort_bins(b, c->bt[BT_COPY_TMP].p, tb2, sb2, se2, bs));
         LSG_HIP(hipEventRecord(c->ev_lpt, bs));            // (the event of the tiles' order: waited for above, free again)
         LSG_HIP(hipStreamWaitEvent(st, c->ev_lpt, 0));      // both halves of the order are there
     }
     LSG_HIP(hipEventRecord(c->evb[2], st));
-    // ---- 4. blocks and the per-entry words (the blocks' offsets and their number came with the load's early look)
-    const uint64_t np = (uint64_t)nblk * 8;
-    c->tm_np = np; c->tm_nblk = nblk;
-    auto reserve_store = [&]() -> int {
+    // (the blocks' offsets and their number came with the load's early look)
+    c->tm_np = (uint64_t)b.nblk * 8; c->tm_nblk = b.nblk;
+    LSG_HIP(hipEventRecord(c->evb[3], st));
+    return 0;
+}
+
+static void load_stage(const LoadBuild& b, const char* what) {
+    if (!getenv("LSG_DEBUG_SYNC")) return;
+    const hipError_t e = hipStreamSynchronize(b.st); fprintf(stderr, "[lsg] fused load: %s: %s\n", what, hipGetErrorString(e)); fflush(stderr);
+}
+// the plan of a load that counts: its tile-level half was made on the copy stream while the scatter and the sort were at work
+// (tiles_planned), its job-level half behind the sort - the jobs are cut at run starts read from the sorted keys
+static int load_plan_jobs(LoadBuild& b) {
+    load_stage(b, "scatter + sort + block tables");
+    if (int rc = plan_jobs(b.c, false, b.key_out(), b.bits)) return rc;
+    load_stage(b, "plan");
+    return 0;
+}
+static GatherCountSrc gather_count_src(const LoadBuild& b) {
+    return GatherCountSrc{b.events, b.n_events, b.key_out(), b.form.keys_only ? nullptr : b.val_out(), b.bits, b.form.src_shift};
+}
+
+// ---- 10. the one close: the phases' times, the temporaries, the wall time; a load that keeps a store says so
+static int load_close(LoadBuild& b) {
+    lsg_ctx* c = b.c;
+    for (int i = 0; i < 4; ++i) { float ms = 0; if (hipEventElapsedTime(&ms, c->evb[i], c->evb[i + 1]) == hipSuccess) c->build_ms[i] = ms; }
+    settle_temporaries(c);
+    if (keeps_store(c->load_form)) {
+        if (getenv("LSG_TIMING"))
+            fprintf(stderr, "[lsg] tile store: %llu entries, %u blocks (%.2f GB): capacities + scatter %.2f, sort %.2f, fill %.2f, gather %.2f ms\n",
+                    (unsigned long long)b.N, b.nblk, (double)b.nblk * 1024 / 1e9, c->build_ms[0], c->build_ms[1], c->build_ms[2], c->build_ms[3]);
+        c->tm_valid = true;
+    }
+    c->layout_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b.t_wall).count();
+    b.done = true;
+    return 0;
+}
+
+// ---- 9a. A load that is counted once and never again (lsg_set_store_policy): the count alone, from the caller's events through the
+// sort's output - no blocks, no per-entry words.  What needs a store afterwards is refused until the next load.
+static int load_count_no_store(LoadBuild& b) {
+    lsg_ctx* c = b.c;
+    if (int rc = load_plan_jobs(b)) return rc;
+    b.planned = true;
+    const int rc = run_gather_count(c, &c->cal_params, gather_count_src(b), b.form.form);
+    LSG_HIP(hipStreamSynchronize(b.st));
+    if (hipGetLastError() != hipSuccess) { set_error("lsg_load_reads: the count pass failed"); return -1; }
+    if (rc < 0 && rc != -3) return rc;                        // a failure (allocation, HIP) is one: only rows that outgrew their buffer (-3) load again
+    if (rc == 0) {
+        plan_finish(c);
+        LSG_HIP(hipStreamSynchronize(c->copy_stream));     // (the blocks' tiles: nobody reads them, nothing may still be writing them)
+        c->counted_at_load = true;
+        return load_close(b);                                 // (tm_valid stays false: there is no store)
+    }
+    c->counted = false;                                       // rows outgrew their buffer: the store is built after all, the count is made on request - or the load starts again
+    b.form = load_rows_outgrew(b.want, b.form);
+    c->load_form = b.form.form;
+    return b.form.restart;
+}
+
+// ---- the blocks and the per-entry words
+static int load_reserve_store(LoadBuild& b) {
+    lsg_ctx* c = b.c; hipStream_t st = b.st;
+    const uint32_t nblk = b.nblk; const uint64_t np = c->tm_np;
     if (c->tm[TM_S0].reserve((np + 16) * 4) || c->tm[TM_B].reserve(np + 16) ||
         c->tm[TM_RD].reserve((np + 16) * 4) || c->tm[TM_META].reserve((np + 8 * (TM_GROUP + 1)) * 4) ||
         c->tm[TM_BLK_TILE].reserve(((size_t)nblk + 2) * 4) || c->tm[TM_EXT].reserve(((size_t)nblk + TM_GROUP + 2) * 2)) return -1;
     LSG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->tm[TM_S0].as<uint32_t>() + np), (int)TM_PAD_S0, 16, st));       // (what the walk's group loads and the run flags' neighbours see past the end)
     LSG_HIP(hipMemsetAsync(c->tm[TM_B].as<uint8_t>() + np, 0, 16, st));
-    // ---- 5. the per-entry words and the events.  The blocks are the load's largest allocation (C4: 124 GB beside 106 GB of the caller's
-    // events): they are reserved once and kept; when the device is nearly full what the build no longer needs goes first
+    // The blocks are the load's largest allocation (C4: 124 GB beside 106 GB of the caller's events): they are reserved once and kept;
+    // when the device is nearly full what the build no longer needs goes first
     if (c->tm[TM_STORE].cap < ((size_t)nblk + TM_GROUP) * 1024) {
         size_t mem_free = 0, mem_total = 0;
         if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && ((size_t)nblk + TM_GROUP) * 1088 + (mem_total >> 5) > mem_free) {
             LSG_HIP(hipStreamSynchronize(st));
-            key_a.release(); val_a.release(); c->ws[WS_SEG_INFO].release(); c->bt[BT_SPAN].release(); c->bt[BT_PEX].release(); c->bt[BT_OFFS].release();
+            c->bt[BT_KEY_A].release(); c->bt[BT_VAL_A].release(); c->ws[WS_SEG_INFO].release(); c->bt[BT_SPAN].release(); c->bt[BT_PEX].release(); c->bt[BT_OFFS].release();
         }
         if (c->tm[TM_STORE].reserve(((size_t)nblk + TM_GROUP) * 1024)) return -1;
     }
-    return 0;
-    };
-    LSG_HIP(hipEventRecord(c->evb[3], st));
-    // The first count in the same pass (lsg_set_count_at_load): when its parameters and the barcode table are known now, the depth cap
-    // cannot fire (the all-reads bound came with the early look) and one pass covers the cell types, the gather below is replaced by
-    // pileup.hip's k_tm_gather_count, which builds the same store and counts while each block is in registers.
-    bool fused = counts;
-    if (fused) {
-        const lsg_count_params& q = c->cal_params;
-        if (q.min_mq < c->st_min_mq || (c->st_flag_exclude & ~q.flag_exclude) != 0 || (c->st_ignore_orphans && !q.ignore_orphans)) fused = false;       // (the count would be refused)
-        if (fused && !cap_out) fused = false;                     // the depth cap might fire (decided before the scatter, above): the count is left to lsg_pileup_count
-        for (int t = 0; t < c->n_contigs && fused; ++t) if (!c->ref_ptr[t]) fused = false;
-    }
-    const bool dbg = getenv("LSG_DEBUG_SYNC") != nullptr;
-    auto stage = [&](const char* what) { if (dbg) { const hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "[lsg] fused load: %s: %s\n", what, hipGetErrorString(e)); fflush(stderr); } };
-    // the plan: its tile-level half was made on the copy stream while the scatter and the sort were at work (tiles_planned: a load that
-    // counts), its job-level half behind the sort - the jobs are cut at run starts read from the sorted keys
-    auto fused_plan = [&]() -> int {
-        stage("scatter + sort + block tables");
-        c->tm_np = np; c->tm_nblk = nblk;
-        if (int rc = plan_jobs(c, false, key_b.as<uint64_t>(), bits)) return rc;
-        stage("plan");
-        return 0;
-    };
-    const GatherCountSrc gsrc{events, n_events, key_b.as<uint64_t>(), keys_only ? nullptr : val_b.as<uint32_t>(), bits, src_shift, wsh};
-    bool planned = false;
-    if (win && !fused) return RUNG_TILE_KEYS;
-    if (keys_only && getenv("LSG_TEST_KEYS_ONLY_REFUSED")) return win ? RUNG_TILE_KEYS : RUNG_TILE_VALUES;      // (test hook: the way a refused count of keys alone takes)
-    if (fused && skip_store) {
-        // A load that is counted once and never again (lsg_set_store_policy): the count alone, from the caller's events through the
-        // sort's output - no blocks, no per-entry words.  What needs a store afterwards is refused until the next load.
-        if (int rc = fused_plan()) return rc;
-        planned = true;
-        const int rc = run_gather_count(c, &c->cal_params, gsrc, true);
-        LSG_HIP(hipStreamSynchronize(st));
-        if (hipGetLastError() != hipSuccess) { set_error("lsg_load_reads: the count pass failed"); return -1; }
-        if (rc < 0 && rc != -3) return rc;                        // a failure (allocation, HIP) is one: only rows that outgrew their buffer (-3) or a refused count of keys alone (1) load again
-        if (rc == 0) {
-            plan_finish(c);
-            LSG_HIP(hipStreamSynchronize(c->copy_stream));     // (the blocks' tiles: nobody reads them, nothing may still be writing them)
-            c->load_was_fused = true; c->counted_at_load = true; c->store_skipped = true;
-            for (int i = 0; i < 4; ++i) { float ms = 0; if (hipEventElapsedTime(&ms, c->evb[i], c->evb[i + 1]) == hipSuccess) c->build_ms[i] = ms; }
-            settle_temporaries(c);
-            c->layout_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall).count();
-            return 0;                                             // (tm_valid stays false: there is no store)
-        }
-        c->counted = false;                                       // rows outgrew their buffer: the store is built after all, the count is made on request
-        fused = false;
-    }
-    if (win) return RUNG_TILE_KEYS;                          // (the windows' count was not made: rows outgrew their buffer, a count that is not the load's ...)
-    if (keys_only) return RUNG_TILE_VALUES;                  // (a load of keys alone that is not counted that way after all)
-    if (int rc = reserve_store()) return rc;
-    if (!blk_tiles_made) {                                       // (a load that was to keep no store builds one after all)
+    if (!b.blk_tiles_made) {                                     // (a load that was to keep no store builds one after all)
         LSG_HIP(hipStreamSynchronize(c->copy_stream));
-        if (int rc = blk_tiles(st)) return rc;
+        if (int rc = blk_tiles(b, st)) return rc;
     }
-    if (fused) {
-        if (int rc = fused_plan()) return rc;
-        c->tm_valid = true;                                   // (what the count's preparation looks at; the blocks are written by the pass itself)
-        int rc = run_gather_count(c, &c->cal_params, gsrc, false);
-        LSG_HIP(hipStreamSynchronize(st));
-        if (hipGetLastError() != hipSuccess) { c->tm_valid = false; set_error("lsg_load_reads: the fused gather + count pass failed"); return -1; }
-        if (rc < 0 && rc != -3) { c->tm_valid = false; return rc; }      // (as above: -3 = the rows outgrew their buffer, the store is whole and counted on request)
-        plan_finish(c);
-        c->load_was_fused = true;
-        c->counted_at_load = rc == 0;                         // (a count that could not be kept - rows outgrew their buffer - is made again on request; the store is whole either way)
-        if (rc) c->counted = false;
-    } else {
+    return 0;
+}
+
+// ---- 9b. the store written by the pass that counts (pileup.hip's k_tm_gather_count)
+static int load_gather_count(LoadBuild& b) {
+    lsg_ctx* c = b.c;
+    if (int rc = load_reserve_store(b)) return rc;
+    if (int rc = load_plan_jobs(b)) return rc;
+    c->tm_valid = true;                                   // (what the count's preparation looks at; the blocks are written by the pass itself)
+    const int rc = run_gather_count(c, &c->cal_params, gather_count_src(b), b.form.form);
+    LSG_HIP(hipStreamSynchronize(b.st));
+    if (hipGetLastError() != hipSuccess) { c->tm_valid = false; set_error("lsg_load_reads: the fused gather + count pass failed"); return -1; }
+    if (rc < 0 && rc != -3) { c->tm_valid = false; return rc; }      // (-3 = the rows outgrew their buffer, the store is whole and counted on request)
+    plan_finish(c);
+    c->counted_at_load = rc == 0;                         // (a count that could not be kept - rows outgrew their buffer - is made again on request; the store is whole either way)
+    if (rc) c->counted = false;
+    return 0;
+}
+
+// ---- 9c. the plain gather, the plan beside it
+static int load_gather(LoadBuild& b) {
+    lsg_ctx* c = b.c; hipStream_t st = b.st;
+    const uint32_t nblk = b.nblk;
+    if (int rc = load_reserve_store(b)) return rc;
     LSG_HIP(hipStreamWaitEvent(st, c->ev_blk, 0));                  // (the blocks' tiles, made on the copy stream)
-    const bool plan_early = c->n_ct > 0 && c->copy_stream && c->ev_copy && !planned;      // (planned: a count without a store was tried and its rows did not fit)
+    const bool plan_early = c->n_ct > 0 && c->copy_stream && c->ev_copy && !b.planned;      // (planned: a count without a store was tried and its rows did not fit)
     if (plan_early) LSG_HIP(hipEventRecord(c->ev_copy, st));       // everything the gather waits for is what the plan's tile-level half waits for
     {
         const dim3 grid((unsigned)(((((uint64_t)nblk + TMG_BLOCKS - 1) / TMG_BLOCKS + TMG_WAVES - 1) / TMG_WAVES + 7) / 8 * 8));
         hipLaunchKernelGGL(k_tm_gather, grid, dim3(TMG_WAVES * 64), 0, st,
-                           events, n_events, key_b.as<uint64_t>(), val_b.as<uint32_t>(), bits, src_shift, c->d_tile_off.as<uint32_t>(), blk_off, c->tm[TM_BLK_TILE].as<uint32_t>(), nblk,
+                           b.events, b.n_events, b.key_out(), b.val_out(), b.bits, b.form.src_shift, c->d_tile_off.as<uint32_t>(), b.blk_off, c->tm[TM_BLK_TILE].as<uint32_t>(), nblk,
                            c->tm[TM_S0].as<uint32_t>(), c->tm[TM_B].as<uint8_t>(), c->tm[TM_RD].as<uint32_t>(),
                            c->tm[TM_STORE].as<uint4>(), c->tm[TM_EXT].as<uint16_t>());
     }
@@ -1170,23 +1234,36 @@ static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, cons
     int plan_rc = 0;
     if (plan_early) {       // beside the gather, on the copy stream: a dozen small kernels and two host round trips that the first count would otherwise pay
         LSG_HIP(hipStreamWaitEvent(c->copy_stream, c->ev_copy, 0));
-        plan_rc = tiles_planned ? 0 : plan_tiles(c, c->copy_stream);
-        if (!plan_rc) {        // ... and its job-level half right behind the gather: the load's last synchronisation is the plan's too
-            c->tm_np = np; c->tm_nblk = nblk;
-            plan_rc = plan_jobs(c, false);
-        }
+        plan_rc = b.tiles_planned ? 0 : plan_tiles(c, c->copy_stream);
+        if (!plan_rc) plan_rc = plan_jobs(c, false);        // ... and its job-level half right behind the gather: the load's last synchronisation is the plan's too
     }
     LSG_HIP(hipStreamSynchronize(st));
     if (plan_early) LSG_HIP(hipStreamSynchronize(c->copy_stream));
     if (plan_rc) return plan_rc;
-    if (plan_early || planned) plan_finish(c);
-    }
-    for (int i = 0; i < 4; ++i) { float ms = 0; if (hipEventElapsedTime(&ms, c->evb[i], c->evb[i + 1]) == hipSuccess) c->build_ms[i] = ms; }
-    settle_temporaries(c);
-    if (getenv("LSG_TIMING"))
-        fprintf(stderr, "[lsg] tile store: %llu entries, %u blocks (%.2f GB): capacities + scatter %.2f, sort %.2f, fill %.2f, gather %.2f ms\n",
-                (unsigned long long)N, nblk, (double)nblk * 1024 / 1e9, c->build_ms[0], c->build_ms[1], c->build_ms[2], c->build_ms[3]);
-    return finish();
+    if (plan_early || b.planned) plan_finish(c);
+    return 0;
+}
+
+// One attempt: the phases in the order their work is queued on the two streams.  0: loaded; < 0: refused; > 0: the rung to start again on.
+static int build_once(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int64_t* seg_ev_off, const lsg_reads* src, int rung) {
+    drop_store(c);
+    LoadBuild b{};
+    b.c = c; b.st = c->stream; b.events = events; b.n_events = n_events; b.rung = rung;
+    b.in = src ? src : &c->rd;          // (same contents: the handle's copies of a caller's device arrays may still be travelling on the copy stream)
+    int rc;
+    if ((rc = load_begin(b, seg_ev_off)) || b.done) return rc;
+    if ((rc = load_measure(b))) return rc;
+    if ((rc = load_validate(b)) || b.done) return rc;
+    if ((rc = load_cap_out(b))) return rc;
+    if ((rc = load_settle_form(b))) return rc;
+    if ((rc = load_scatter(b))) return rc;
+    if ((rc = load_side_work(b))) return rc;
+    if ((rc = load_plan_tiles(b))) return rc;
+    if ((rc = load_sort(b))) return rc;
+    if (b.form.refused) return b.form.refused;
+    if (b.form.fused && !keeps_store(b.form.form)) { if ((rc = load_count_no_store(b)) || b.done) return rc; }
+    if ((rc = b.form.fused ? load_gather_count(b) : load_gather(b))) return rc;
+    return load_close(b);
 }
 
 int build_store(lsg_ctx* c, const uint16_t* events, int64_t n_events, const int64_t* seg_ev_off, const lsg_reads* src) {
@@ -1302,7 +1379,8 @@ __global__ void k_tm_chunks(const uint32_t* pex, uint32_t njobs, uint32_t chunk_
 // size.  It reads the tiles' capacities only, so the load makes it on the copy stream BESIDE its gather (which then is all the device
 // is waiting for) when the number of cell types is already known; else the first count makes it.
 static int plan_tiles(lsg_ctx* c, hipStream_t st) {
-    const uint32_t T = c->n_tiles >> c->wsh;      // (bins: tiles, or windows of two)
+    const int wsh = bin_shift(c->load_form);
+    const uint32_t T = c->n_tiles >> wsh;      // (bins: tiles, or windows of two)
     const uint64_t N = c->tm_n;
     DevBuf &per_tile = c->bt[BT_PER_TILE], &offs = c->bt[BT_OFFS];
     if (per_tile.reserve((size_t)(T + 2) * 4 * 4) || offs.reserve((size_t)(T + 2) * 4 * 4 + 64)) return -1;
@@ -1313,7 +1391,7 @@ static int plan_tiles(lsg_ctx* c, hipStream_t st) {
     // resident pair of waves should still get several
     uint32_t job_tgt = TM_JOB_TGT;
     { const uint64_t per = N / ((uint64_t)c->n_cus * 14 * 4); if (per < job_tgt) job_tgt = (uint32_t)(per < 768 ? 768 : per); }
-    hipLaunchKernelGGL(k_tm_tiles, dim3((T + 256) / 256), dim3(256), 0, st, c->d_tile_cap.as<uint32_t>(), T, c->n_ct, job_tgt, 1u << c->wsh, ne, nj, slabs, multi);
+    hipLaunchKernelGGL(k_tm_tiles, dim3((T + 256) / 256), dim3(256), 0, st, c->d_tile_cap.as<uint32_t>(), T, c->n_ct, job_tgt, 1u << wsh, ne, nj, slabs, multi);
     uint32_t* cnts[4] = {ne, nj, slabs, multi}; uint32_t* srcs[4] = {ne_off, job_off, slab_off, multi_off};
     for (int i = 0; i < 4; ++i) if (exclusive_sum(c->d_cub_tmp, cnts[i], srcs[i], T + 1, st)) return -1;
     LSG_HIP(hipMemsetAsync(d_misc, 0, 8, st));
@@ -1336,19 +1414,20 @@ static int plan_tiles(lsg_ctx* c, hipStream_t st) {
 static int plan_jobs(lsg_ctx* c, bool finish, const uint64_t* skey, int cb_bits) {
     hipStream_t st = c->stream;
     const RunSrc rs{c->tm[TM_S0].as<uint32_t>(), skey, skey ? (1u << cb_bits) - 1u : 0u};
-    const uint32_t T = c->n_tiles >> c->wsh;
+    const int wsh = bin_shift(c->load_form);
+    const uint32_t T = c->n_tiles >> wsh;
     DevBuf &per_tile = c->bt[BT_PER_TILE], &offs = c->bt[BT_OFFS];
     uint32_t* nj = per_tile.as<uint32_t>() + (T + 2);
     uint32_t* ne_off = offs.as<uint32_t>(); uint32_t* job_off = ne_off + (T + 2); uint32_t* slab_off = job_off + (T + 2); uint32_t* multi_off = slab_off + (T + 2);
     uint32_t* d_misc = multi_off + (T + 2);          // [0] wide jobs, [1] chunks
     const uint32_t* tot = c->plan1_tot;
     const uint32_t njobs = tot[1], n_mt = tot[3];
-    hipLaunchKernelGGL(k_tm_jobs, dim3((T + 255) / 256), dim3(256), 0, st, c->d_tile_base.as<uint32_t>(), c->n_contigs, c->n_ct, c->wsh, rs, c->d_tile_off.as<uint32_t>(),
+    hipLaunchKernelGGL(k_tm_jobs, dim3((T + 255) / 256), dim3(256), 0, st, c->d_tile_base.as<uint32_t>(), c->n_contigs, c->n_ct, wsh, rs, c->d_tile_off.as<uint32_t>(),
                        c->d_tile_cap.as<uint32_t>(), c->tm[TM_BLK_OFF].as<uint32_t>(), ne_off, nj, job_off, slab_off, multi_off, T,
                        c->tm[TM_JOBS].as<TmJob>(), c->tm[TM_NE_UNITS].as<uint32_t>(), c->tm[TM_NE_GEOM].as<int2>(), c->tm[TM_NE_NSLOT].as<uint32_t>(),
                        c->tm[TM_NE_ACC].as<uint32_t>(), c->tm[TM_MULTI].as<uint32_t>(), d_misc);
-    if (n_mt) hipLaunchKernelGGL(k_tm_jobs_multi, dim3(n_mt >> c->wsh), dim3(64), 0, st, c->n_ct, c->wsh, rs, c->d_tile_off.as<uint32_t>(), c->d_tile_cap.as<uint32_t>(), c->tm[TM_BLK_OFF].as<uint32_t>(),
-                                 ne_off, nj, job_off, slab_off, c->tm[TM_MULTI].as<uint32_t>(), c->tm[TM_NE_UNITS].as<uint32_t>(), c->tm[TM_NE_GEOM].as<int2>(), n_mt >> c->wsh, c->tm[TM_JOBS].as<TmJob>(), d_misc);
+    if (n_mt) hipLaunchKernelGGL(k_tm_jobs_multi, dim3(n_mt >> wsh), dim3(64), 0, st, c->n_ct, wsh, rs, c->d_tile_off.as<uint32_t>(), c->d_tile_cap.as<uint32_t>(), c->tm[TM_BLK_OFF].as<uint32_t>(),
+                                 ne_off, nj, job_off, slab_off, c->tm[TM_MULTI].as<uint32_t>(), c->tm[TM_NE_UNITS].as<uint32_t>(), c->tm[TM_NE_GEOM].as<int2>(), n_mt >> wsh, c->tm[TM_JOBS].as<TmJob>(), d_misc);
     {   // static work-balanced chunks of the job list; every workgroup of the walk should get several: a small load is cut finer
         DevBuf& pex = c->bt[BT_PEX];
         const uint64_t total_work = c->tm_np + (uint64_t)njobs * TM_JOB_W0;
