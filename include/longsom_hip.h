@@ -365,7 +365,7 @@ enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG
 /* Tables added since continue the numbering where enum lsg_table ends, so that none of its values moves - LSG_TABLE_SLOTS, the number
  * of tables its callers were built against, among them.  LSG_TABLE_ALL_SLOTS bounds every table index lsg_format_table,
  * lsg_copy_table, lsg_append_table and lsg_free_table serve. */
-enum lsg_table_more { LSG_TABLE_GENE_COUNTS = LSG_TABLE_SLOTS, LSG_TABLE_ALL_SLOTS };
+enum lsg_table_more { LSG_TABLE_GENE_COUNTS = LSG_TABLE_SLOTS, LSG_TABLE_HCCV2, LSG_TABLE_HCCV3, LSG_TABLE_HCCV_PASS, LSG_TABLE_ALL_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -386,6 +386,47 @@ int lsg_append_table(lsg_ctx* ctx, int32_t table, const char* path);
 int lsg_step2_summary(lsg_ctx* ctx, int32_t n_cols, uint8_t* kinds, int64_t* n_survivor_bytes);
 /* Frees one table's text (table < 0: every table's, and the flat row copies they were printed from). */
 int lsg_free_table(lsg_ctx* ctx, int32_t table);
+
+/* ---- the high-confidence cancer variant filter over the step-2 table's text (csrc/hccv.hip, csrc/hccv_core.h) ---------------------
+ * HCCV_SNV of CellTypeReannotation/HighConfidenceCancerVariants.py:8-88 with MultiAllelic_filtering (:90-163), DP_filtering (:200-209)
+ * and MCF_filtering (:212-255), decided and printed row by row where the table's text lies - the step between the two passes of the
+ * cell-type re-annotation, which reads the whole pass-1 step-2 table.  The rows of <out>.HCCV.tsv2 become table LSG_TABLE_HCCV2, those
+ * of <out>.HCCV.tsv3 LSG_TABLE_HCCV3 (every non-chrM row in input order, then the chrM rows: pd.concat, :75), the rows of .tsv3 whose
+ * verdict is PASS LSG_TABLE_HCCV_PASS (a few hundred: the caller applies the cluster test, :165-197, to them).  Rows only; the header
+ * lines are the caller's.  lsg_copy_table / lsg_append_table / lsg_free_table serve the three like any table.
+ *   col[]          where the header line has #CHROM Start REF ALT FILTER Cell_types Dp Nc Bc Cc VAF MCF Cancer Non-Cancer, of n_cols <= 64
+ *   two_delta_vaf  2 * delta_vaf as the caller's arithmetic gives it (the comparison is the reference's, operation for operation)
+ * A row that cannot be decided as pandas and the reference's Python would decide it makes the whole call undecided: info->n_undecided
+ * > 0 with the smallest such row's ordinal and its reason, no table is made, and the caller runs the reference's frame code over the
+ * whole table.  Nothing is guessed.  info->kinds: as lsg_step2_summary's, filled by lsg_hccv_filter_text only. */
+#define LSG_HCCV_COLS 14
+enum lsg_hccv_reason { LSG_HCCV_OK = 0,
+                       LSG_HCCV_SHORT_ROW,      /* fewer fields than the header has columns */
+                       LSG_HCCV_LONG_ROW,       /* more */
+                       LSG_HCCV_ODD_TEXT,       /* a quote, a carriage return or a '#' in the row, or an empty line */
+                       LSG_HCCV_MISSING,        /* #CHROM, Start, ALT, FILTER or a needed cell-type column is a missing cell */
+                       LSG_HCCV_NUMBER,         /* a needed field is not the number it should be (or a division by zero follows from it) */
+                       LSG_HCCV_MAX_ZERO,       /* a multi-allelic row without a non-reference read in the cancer column */
+                       LSG_HCCV_CELL_TYPES,     /* no cell type, more than two, or two of which neither is Cancer */
+                       LSG_HCCV_TOO_LONG };     /* a FILTER of more than 256 bytes to strip */
+typedef struct {
+    int32_t n_cols; int32_t col[LSG_HCCV_COLS];
+    int32_t pad_;
+    double min_dp, delta_vaf, two_delta_vaf, delta_mcf;
+} lsg_hccv_params;
+typedef struct {
+    int64_t rows_in, rows_tsv2, rows_tsv3, rows_pass;
+    int64_t bytes_tsv2, bytes_tsv3, bytes_pass;
+    int64_t n_undecided, first_undecided;       /* rows that could not be decided, the smallest ordinal among them (-1: none) */
+    int32_t reason;                             /* lsg_hccv_reason of that row */
+    float ms_rows, ms_decide, ms_print;         /* HIP-event times: the newline pass and compaction, the decide-and-measure kernel, the print kernel */
+    uint8_t kinds[64];
+} lsg_hccv_info;
+/* Over the resident text of LSG_TABLE_STEP2 (lsg_format_table first; the text and lsg_step2_summary's table are left as they are). */
+int lsg_hccv_filter(lsg_ctx* ctx, const lsg_hccv_params* params, lsg_hccv_info* info);
+/* Over a table in host memory: the data rows of a step-2 file, leading lines that start with '#' skipped; uploaded through pinned
+ * staging, row starts found on the device. */
+int lsg_hccv_filter_text(lsg_ctx* ctx, const char* text, int64_t n_bytes, const lsg_hccv_params* params, lsg_hccv_info* info);
 
 /* ---- FASTQ for the fusion caller, printed on the device (csrc/fastq.hip) ---------------------------
  * A BAM's records as the FASTQ text ctat-LR-fusion reads, into table LSG_TABLE_FASTQ (lsg_copy_table / lsg_append_table / lsg_free_table

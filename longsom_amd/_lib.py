@@ -148,6 +148,20 @@ class GeneCountInfo(C.Structure):
     ]
 
 
+class HccvParams(C.Structure):
+    """lsg_hccv_params: where the header has the fourteen columns the filter reads (reanno.HCCV_COLUMNS), and its thresholds"""
+    _fields_ = [("n_cols", C.c_int32), ("col", C.c_int32 * 14), ("pad_", C.c_int32),
+                ("min_dp", C.c_double), ("delta_vaf", C.c_double), ("two_delta_vaf", C.c_double), ("delta_mcf", C.c_double)]
+
+
+class HccvInfo(C.Structure):
+    """lsg_hccv_info (lsg_hccv_filter / lsg_hccv_filter_text / lsio_hccv_rows)"""
+    _fields_ = [("rows_in", C.c_int64), ("rows_tsv2", C.c_int64), ("rows_tsv3", C.c_int64), ("rows_pass", C.c_int64),
+                ("bytes_tsv2", C.c_int64), ("bytes_tsv3", C.c_int64), ("bytes_pass", C.c_int64),
+                ("n_undecided", C.c_int64), ("first_undecided", C.c_int64), ("reason", C.c_int32),
+                ("ms_rows", C.c_float), ("ms_decide", C.c_float), ("ms_print", C.c_float), ("kinds", C.c_uint8 * 64)]
+
+
 FASTQ_OK, FASTQ_NO_CB, FASTQ_CB_TYPE, FASTQ_UB_TYPE, FASTQ_NM_TYPE, FASTQ_NH_TYPE = -1, 0, 1, 2, 3, 4
 
 
@@ -198,6 +212,8 @@ SIGNATURES = {
     "lsg_append_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_char_p]),
     "lsg_free_table": (C.c_int, [C.c_void_p, C.c_int32]),
     "lsg_step2_summary": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "lsg_hccv_filter": (C.c_int, [C.c_void_p, C.POINTER(HccvParams), C.POINTER(HccvInfo)]),
+    "lsg_hccv_filter_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(HccvParams), C.POINTER(HccvInfo)]),
     "lsg_load_posset": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32]),
     "lsg_probe_posset": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "lsg_load_alleleset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

@@ -350,15 +350,27 @@ def calling_step3(argv=None):
 
 
 def hccv(argv=None):
-    """HighConfidenceCancerVariants.py --SNVs --outfile PREFIX --min_dp --deltaVAF --deltaMCF [--clust_dist]  (:259-267)."""
+    """HighConfidenceCancerVariants.py --SNVs --outfile PREFIX --min_dp --deltaVAF --deltaMCF [--clust_dist]  (:259-267).
+    Flags of this script alone: --device N decides and prints the rows on GPU N (the table is uploaded), --native with the host twin of the
+    same row code; without either the pandas form runs, as before.  A table the row code does not decide runs through the pandas form."""
     from . import reanno
     ap = argparse.ArgumentParser(description="High-confidence cancer variants for the cell-type re-annotation")
     ap.add_argument("--SNVs", required=True); ap.add_argument("--outfile", required=True)
     ap.add_argument("--min_dp", type=float, required=True); ap.add_argument("--deltaVAF", type=float, required=True)
     ap.add_argument("--deltaMCF", type=float, required=True); ap.add_argument("--clust_dist", type=int, default=10000)
+    how = ap.add_mutually_exclusive_group()
+    how.add_argument("--device", type=int, default=None); how.add_argument("--native", action="store_true")
     a = ap.parse_args(argv)
     print("\n- High Confidence Cancer Variants calling\n")
-    reanno.hccv_filter(a.SNVs, a.outfile, a.min_dp, a.deltaVAF, a.deltaMCF, a.clust_dist)
+    args = (a.SNVs, a.outfile, a.min_dp, a.deltaVAF, a.deltaMCF, a.clust_dist)
+    if a.device is not None:
+        from .engine import Engine
+        with Engine(a.device) as eng:
+            reanno.hccv_filter_device(eng, *args)
+    elif a.native:
+        reanno.hccv_filter_native(*args)
+    else:
+        reanno.hccv_filter(*args)
 
 
 def single_cell_genotype(argv=None):

@@ -23,6 +23,8 @@ int run_copy_table(lsg_ctx* c, int32_t table, char* dst, int64_t capacity);
 int run_append_table(lsg_ctx* c, int32_t table, const char* path);
 int run_free_table(lsg_ctx* c, int32_t table);
 int run_step2_summary(lsg_ctx* c, int32_t n_cols, uint8_t* kinds, int64_t* n_survivor_bytes);
+int run_hccv_filter(lsg_ctx* c, const lsg_hccv_params* p, lsg_hccv_info* info);
+int run_hccv_filter_text(lsg_ctx* c, const char* text, int64_t n_bytes, const lsg_hccv_params* p, lsg_hccv_info* info);
 int run_genotype(lsg_ctx* c, const lsg_genotype_params* p, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
                  uint32_t* dp, uint32_t* alt, int on_device, int32_t max_depth, int64_t n_groups, const int64_t* group_off);
 int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_depth, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
@@ -122,6 +124,7 @@ void lsg_destroy(lsg_ctx* c) {
     c->bnpcs.release();
     c->bb.release();
     c->gc.release();
+    c->hccv.release();
     c->tab_names.release();
     for (auto& b : c->ws) b.release();
     for (auto& b : c->tm) b.release();
@@ -501,6 +504,16 @@ int lsg_step2_summary(lsg_ctx* c, int32_t n_cols, uint8_t* kinds, int64_t* n_sur
     if (!c || !kinds) { set_error("lsg_step2_summary: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
     return run_step2_summary(c, n_cols, kinds, n_survivor_bytes);
+}
+int lsg_hccv_filter(lsg_ctx* c, const lsg_hccv_params* params, lsg_hccv_info* info) {
+    if (!c || !params || !info) { set_error("lsg_hccv_filter: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_hccv_filter(c, params, info);
+}
+int lsg_hccv_filter_text(lsg_ctx* c, const char* text, int64_t n_bytes, const lsg_hccv_params* params, lsg_hccv_info* info) {
+    if (!c || !text || n_bytes < 0 || !params || !info) { set_error("lsg_hccv_filter_text: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_hccv_filter_text(c, text, n_bytes, params, info);
 }
 int lsg_free_table(lsg_ctx* c, int32_t table) {
     if (!c) { set_error("lsg_free_table: bad arguments"); return -2; }

@@ -141,6 +141,13 @@ struct GeneCounts {
     void release() { for (DevBuf* b : {&iv, &row_of_gene, &matrix, &tallies, &state, &small, &text, &scratch}) b->release(); ann_valid = mat_valid = text_valid = false; n_iv = 0; n_genes = n_rows = n_cb = n_cols = 0; }
 };
 
+// hccv.hip: an uploaded table's text, the newline pass's pieces, the rows' starts, per row its length and flags (and the call's few
+// counters), the places of the rows in the five scans of lsg_hccv_filter
+struct Hccv {
+    DevBuf text, pieces, starts, rows, places[5];
+    void release() { for (DevBuf* b : {&text, &pieces, &starts, &rows}) b->release(); for (DevBuf& b : places) b.release(); }
+};
+
 // workspace buffers (lsg_ctx::ws)
 enum { WS_NE_NSLOT = 0, WS_NE_ACC, WS_NE_GEOM, WS_MULTI_LIST, WS_MACC, WS_EXPORT_K, WS_EXPORT_R,
        WS_EXPORT_C, WS_CALL_FLAGS, WS_CALL_SEL, WS_CALL_CANDS, WS_CALL_TASKS, WS_SEG_INFO };
@@ -302,6 +309,7 @@ struct lsg_ctx {
     lsg::Bnpcs bnpcs;                     // bnpc_sampler.hip: the sampler's chains
     lsg::Bbfit bb;                        // bbfit.hip: the beta-binomial fit's histograms
     lsg::GeneCounts gc;                   // genecounts.hip: the annotation's intervals and the cell-by-gene matrix
+    lsg::Hccv hccv;                       // hccv.hip: the scratch of the high-confidence cancer variant filter
 
     lsg::PosSet posset[3];
     lsg::PosSet alleleset; bool alleleset_loaded = false;      // lsg_load_alleleset: step 2's gnomAD alleles (loaded with n = 0: a source that hits nothing)

@@ -314,20 +314,7 @@ void contig_order(const FmtArgs& a, const RowPlaces& r, const int32_t* order, hi
 // (calling.step3 parses only the rows that survive its FILTER patterns, given the kinds of cell every column holds over ALL rows: the
 // host finds both with passes over the table's gigabytes, hostio/tsvstep3.cpp lsio_step3_column_kinds and tsvscan.cpp; these are the
 // same rules over the same bytes, one thread per row.)
-__device__ __forceinline__ bool text_eq(const char* f, int n, const char* lit, int m) {
-    if (n != m) return false;
-    for (int i = 0; i < n; ++i) if (f[i] != lit[i]) return false;
-    return true;
-}
-#define TEXT_IS(f, n, lit) text_eq(f, n, lit, (int)sizeof(lit) - 1)
-// the strings pandas.read_csv takes for a missing value (tsvstep3.cpp is_na)
-__device__ bool text_is_na(const char* f, int n) {
-    if (n == 0) return true;
-    if (n > 8) return false;
-    return TEXT_IS(f, n, "#N/A") || TEXT_IS(f, n, "#N/A N/A") || TEXT_IS(f, n, "#NA") || TEXT_IS(f, n, "-1.#IND") || TEXT_IS(f, n, "-1.#QNAN") || TEXT_IS(f, n, "-NaN") ||
-           TEXT_IS(f, n, "-nan") || TEXT_IS(f, n, "1.#IND") || TEXT_IS(f, n, "1.#QNAN") || TEXT_IS(f, n, "<NA>") || TEXT_IS(f, n, "N/A") || TEXT_IS(f, n, "NA") ||
-           TEXT_IS(f, n, "NULL") || TEXT_IS(f, n, "NaN") || TEXT_IS(f, n, "None") || TEXT_IS(f, n, "n/a") || TEXT_IS(f, n, "nan") || TEXT_IS(f, n, "null");
-}
+using lsgt::text_is_na;      // (text_core.h: the cell tests a host program shares)
 __device__ __forceinline__ bool is_dig(char c) { return c >= '0' && c <= '9'; }
 __device__ __forceinline__ bool is_xdig(char c) { return is_dig(c) || (c >= 'a' && c <= 'f') || (c >= 'A' && c <= 'F'); }
 __device__ __forceinline__ char lower(char c) { return (c >= 'A' && c <= 'Z') ? (char)(c + 32) : c; }
@@ -399,9 +386,9 @@ __device__ int text_kind(const char* f, int n) {
 }
 
 struct TextRows {                                      // the rows of a formatted table: row i = text[off[i] + shift[tid of row i] ..) of len[i] bytes (0: no row)
-    const char* text; const uint32_t* len; const uint64_t* off; const int64_t* shift; const SiteRec* sites; int64_t n;
+    const char* text; const uint32_t* len; const uint64_t* off; const int64_t* shift; const SiteRec* sites; int64_t n;      // (sites = nullptr: rows in the text's own order, no shift)
 };
-__device__ __forceinline__ const char* row_text(const TextRows& t, int64_t i) { return t.text + (int64_t)t.off[i] + t.shift[(int)(t.sites[i].key >> 32)]; }
+__device__ __forceinline__ const char* row_text(const TextRows& t, int64_t i) { return t.text + (int64_t)t.off[i] + (t.sites ? t.shift[(int)(t.sites[i].key >> 32)] : 0); }
 
 // per column, the OR of the kinds of its cells over every row (a '#' cuts the row as pandas' comment="#" does; columns past the row's
 // last field hold a missing value)
@@ -431,11 +418,6 @@ __global__ __launch_bounds__(256) void k_text_kinds(TextRows t, int n_cols, uint
     if (threadIdx.x < n_cols && sh[threadIdx.x]) atomicOr(&kinds[threadIdx.x], sh[threadIdx.x]);
 }
 
-__device__ bool text_contains(const char* f, int n, const char* lit, int m) {
-    for (int i = 0; i + m <= n; ++i) { int j = 0; while (j < m && f[i + j] == lit[j]) ++j; if (j == m) return true; }
-    return false;
-}
-#define TEXT_HAS(f, n, lit) text_contains(f, n, lit, (int)sizeof(lit) - 1)
 // the rows step 3 can keep (calling._step3_survivors): FILTER free of the patterns of BaseCellCalling.step3.py:49-52 (chrM rows:
 // "Min|LR|gnomAD|LC|RNA") / :60-84 (the others), Cell_types (field 6) not "Non-Cancer"; a row of fewer than 7 fields is not kept
 __global__ __launch_bounds__(256) void k_text_survivors(TextRows t, uint32_t* len2) {
@@ -562,6 +544,13 @@ int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     c->tab_scratch_table = table; c->tab_scratch_rows = a.n;      // (the rows' places stay in the scratch: lsg_step2_summary reads the text by them)
     if (n_bytes) *n_bytes = bytes;
     return 0;
+}
+
+// k_text_kinds over rows that lie in the text's own order (hccv.hip: a table the caller uploaded): row i = text[off[i] ..) of len[i] bytes,
+// its newline counted; kinds = 64 zeroed words on the device
+void launch_text_kinds(const char* text, const uint32_t* len, const uint64_t* off, int64_t n, int n_cols, uint32_t* kinds, hipStream_t st) {
+    const TextRows t{text, len, off, nullptr, nullptr, n};
+    hipLaunchKernelGGL(k_text_kinds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t, n_cols, kinds);
 }
 
 // Count, then compact: the keys' places come from the same scan and contig shifts as a table's rows, with every query one unit long
@@ -698,6 +687,7 @@ int run_free_table(lsg_ctx* c, int32_t table) {
     if (table < 0) {
         for (int ct = 0; ct < LSG_MAX_CELLTYPES; ++ct) { c->tab_keys[ct].release(); c->tab_refs[ct].release(); c->tab_rows[ct].release(); c->tab_rows_serial[ct] = 0; }
         c->tab_scratch.release(); c->tab_scratch2.release(); c->tab_scratch_table = -1;
+        c->hccv.release();
     }
     return 0;
 }

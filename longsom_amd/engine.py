@@ -536,6 +536,23 @@ class Engine:
     def free_table(self, table: int = -1) -> None:
         _lib.check(self._lib.lsg_free_table(self._h, int(table)), "lsg_free_table")
 
+    # ---- the high-confidence cancer variant filter over a step-2 table's text (csrc/hccv.hip; reanno.hccv_filter_device drives it) ----
+    TABLE_HCCV2, TABLE_HCCV3, TABLE_HCCV_PASS = 18, 19, 20
+
+    def hccv_filter(self, params):
+        """After format_table(TABLE_STEP2): its rows through HighConfidenceCancerVariants.py's row rules (an _lib.HccvParams) into
+        TABLE_HCCV2 (.HCCV.tsv2's rows), TABLE_HCCV3 (.HCCV.tsv3's) and TABLE_HCCV_PASS (its PASS rows); returns the _lib.HccvInfo.
+        info.n_undecided > 0: no table was made, the table is for reanno.hccv_filter."""
+        info = _lib.HccvInfo()
+        _lib.check(self._lib.lsg_hccv_filter(self._h, C.byref(params), C.byref(info)), "lsg_hccv_filter")
+        return info
+
+    def hccv_filter_text(self, text: bytes, params):
+        """The same over a step-2 table in host memory (leading '#' lines skipped); info.kinds = the kinds of cell of its columns."""
+        info = _lib.HccvInfo()
+        _lib.check(self._lib.lsg_hccv_filter_text(self._h, text, len(text), C.byref(params), C.byref(info)), "lsg_hccv_filter_text")
+        return info
+
     def load_posset(self, kind: int, keys, on_device: bool = False, n: Optional[int] = None):
         if on_device:
             _lib.check(self._lib.lsg_load_posset(self._h, kind, C.c_void_p(int(keys)), int(n), 1), "lsg_load_posset")

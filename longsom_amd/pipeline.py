@@ -60,6 +60,16 @@ class SnvParams:
 
 
 @dataclass
+class HccvRequest:
+    """run_chain(hccv=...): HighConfidenceCancerVariants.py's arguments, for the filter made on the device while the step-2 text is resident"""
+    out_prefix: str
+    min_dp: float = 20
+    delta_vaf: float = 0.1
+    delta_mcf: float = 0.4
+    clust_dist: int = 10000
+
+
+@dataclass
 class SnvOutputs:
     report: str
     counts: Dict[str, str]
@@ -72,6 +82,8 @@ class SnvOutputs:
     row_digests: Optional[dict] = None     # SnvParams.row_digests: rows, columns and xxhash of (keys, reference bases, counters) per cell type, as tools/oracle_hashes.py writes them
     _pending: list = field(default_factory=list, repr=False, compare=False)
     resident: Optional[dict] = field(default=None, repr=False, compare=False)      # a rank's region and decode summary (sharded two-pass loop)
+    hccv: str = ""                         # run_chain(hccv=...): the .HCCV.tsv the device made from the resident step-2 text ("": it made none)
+    hccv_report: Optional[dict] = field(default=None, repr=False, compare=False)      # ... and reanno.hccv_filter_device's report of that call
 
     @classmethod
     def under(cls, out_dir: str, sample_id: str, celltype_names, last: str = "step3", make_dirs: bool = False) -> "SnvOutputs":
@@ -378,10 +390,12 @@ def _device_tables(eng, out: "SnvOutputs", contig_names, celltype_names, sample_
 
 def run_chain(res: Resident, celltype_of: np.ndarray, celltype_names: List[str], report: Dict[str, int], out_dir: str, sample_id: str,
               params: SnvParams, editing: Optional[str] = None, pon_sr: Optional[str] = None, pon_lr: Optional[str] = None,
-              gnomad_af_json: Optional[str] = None, step3: bool = True) -> SnvOutputs:
+              gnomad_af_json: Optional[str] = None, step3: bool = True, hccv: Optional[HccvRequest] = None) -> SnvOutputs:
     """SplitBam report -> BaseCellCounter -> MergeCounts -> BaseCellCalling step 1-3 for one barcode -> cell-type table over the
     resident reads (celltype_of[barcode id] = index into celltype_names, 255 = barcode not listed).  step3=False stops after
-    step 2, as pass 1 of the reference does (rules/CellTypeReannotation.smk has no step-3 rule: HCCV reads calling.step2.tsv)."""
+    step 2, as pass 1 of the reference does (rules/CellTypeReannotation.smk has no step-3 rule: HCCV reads calling.step2.tsv).
+    hccv: where the device prints the step-2 table itself, the high-confidence cancer variant filter runs over that text while it is
+    resident (SnvOutputs.hccv names its file; "" when this run's step 2 was the host's, or the table is one for reanno.hccv_filter)."""
     eng, contig_names = res.engine, res.contig_names
     # Step 2 with --min_distance 0 (LongSom's own setting) tags rows by position sets and by gnomAD alleles and blanks NA cells: the device
     # prints that table itself and tells step 3 what it needs of it (_device_steps23); any other step 2 - a distance filter, a
@@ -399,7 +413,7 @@ def run_chain(res: Resident, celltype_of: np.ndarray, celltype_names: List[str],
                                 last="step3" if step3 else "step2")
     try:
         if device23:
-            return _device_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3, gnomad)
+            return _device_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3, gnomad, hccv)
         return _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad, step3)
     except BaseException:
         try:                                   # (the writers stream from the engine: nobody may close it under them)
@@ -409,7 +423,7 @@ def run_chain(res: Resident, celltype_of: np.ndarray, celltype_names: List[str],
         raise
 
 
-def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3, gnomad=None):
+def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, pon_sr, pon_lr, step3, gnomad=None, hccv=None):
     """Steps 2 and 3 of run_chain with the step-2 table printed on the device (Engine.TABLE_STEP2: csrc/tables.hip): its text goes from
     the device straight into its file; the host sees the kinds of cell of its columns and the rows step 3 can keep
     (Engine.step2_summary), which is all calling.step3 reads of a table this large.  gnomad (calling.open_gnomad's): the alleles it tags
@@ -439,6 +453,16 @@ def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, po
     eng.free_table(eng.TABLE_STEP3_ROWS)
     out.start_background(lambda: eng.append_table(eng.TABLE_STEP2, out.step2))
     t["step2"] = time.time() - t0
+    if hccv is not None:
+        # the filter between the two passes of the re-annotation, over the same resident text (the table's file is still being written:
+        # a table the row code does not decide is left to the caller, who runs reanno.hccv_filter once the file is whole)
+        from . import reanno
+        t1 = time.time()
+        out.hccv_report = {}
+        os.makedirs(os.path.dirname(hccv.out_prefix) or ".", exist_ok=True)
+        out.hccv = reanno.hccv_filter_device(eng, out.step2, hccv.out_prefix, hccv.min_dp, hccv.delta_vaf, hccv.delta_mcf, hccv.clust_dist, resident=True, head=hdr,
+                                             kinds=kinds, fallback=False, report=out.hccv_report) or ""
+        t["hccv_device"] = time.time() - t1
     try:
         if step3:
             _write_step3(out, survivors, params, t, all_kinds=kinds, full_text=lambda: eng.table_bytes(eng.TABLE_STEP2, n2, prefix=hdr), survivors_only=True)
@@ -933,12 +957,17 @@ def run_reannotation(bam: str, barcodes_tsv: str, ref_fasta: str, out_dir: str, 
     try:
         res = load_sample(bam, barcodes_tsv, ref_fasta, eng, rp.chain.min_mapping_quality, keep_unlisted=True)      # (the genotyping pileup's buffer holds every read)
         d1 = os.path.join(out_dir, "CellTypeReannotation")
+        # The HCCV filter runs on the device over the step-2 text while run_chain holds it resident (LONGSOM_HOST_HCCV=1, a step 2 made on
+        # the host, or a table the row code leaves undecided: reanno.hccv_filter over the file, as before)
+        hccv_args = (rp.hccv_min_depth, rp.hccv_delta_vaf, rp.hccv_delta_mcf, rp.hccv_clust_dist)
+        want = None if os.environ.get("LONGSOM_HOST_HCCV", "0") == "1" else HccvRequest(os.path.join(d1, "HCCV", sample_id), *hccv_args)
         p1 = run_chain(res, res.table.celltype_of, res.table.celltype_names, res.dec.report, d1, sample_id, rp.chain, editing, pon_sr, pon_lr, gnomad_af_json,
-                       step3=pass1_step3)
+                       step3=pass1_step3, hccv=want)
         t0 = time.time()
         os.makedirs(os.path.join(d1, "HCCV"), exist_ok=True)
-        hccv = reanno.hccv_filter(p1.step2, os.path.join(d1, "HCCV", sample_id), rp.hccv_min_depth, rp.hccv_delta_vaf, rp.hccv_delta_mcf, rp.hccv_clust_dist)
-        t["hccv"] = time.time() - t0
+        hccv = p1.hccv or reanno.hccv_filter(p1.step2, os.path.join(d1, "HCCV", sample_id), *hccv_args)
+        t["hccv"] = time.time() - t0 + p1.timings.get("hccv_device", 0.0)
+        t["hccv_path"] = (p1.hccv_report or {}).get("path", "host") if p1.hccv else "host"      # (which of the two made the files)
         t0 = time.time()
         eng.set_barcodes(res.table.celltype_of, len(res.table.celltype_names))
         geno = os.path.join(d1, "HCCV", sample_id + ".SNVs.SingleCellGenotype.tsv")

@@ -247,6 +247,196 @@ def _hccv_filter_rowwise(step2_tsv: str, out_prefix: str, min_dp: float = 20, de
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The same filter with the rows decided and printed by the shared row code (csrc/hccv_core.h): on the host (liblongsom_io.so,
+# lsio_hccv_rows) or on the device (lsg_hccv_filter over the resident step-2 text, lsg_hccv_filter_text over an uploaded table)
+# ---------------------------------------------------------------------------------------------------------------------
+HCCV_COLUMNS = ("#CHROM", "Start", "REF", "ALT", "FILTER", "Cell_types", "Dp", "Nc", "Bc", "Cc", "VAF", "MCF", "Cancer", "Non-Cancer")
+HCCV_REASONS = ("decided", "short row", "long row", "quote, carriage return, '#' or empty line", "missing cell", "not a number", "MAX == 0", "cell types",
+                "FILTER too long")
+
+
+def _hccv_head(head_lines):
+    """(comment lines to copy, column names or None) from the lines a step-2 table starts with, as hccv_filter reads them"""
+    comments, cols = [], None
+    for line in head_lines:
+        if not line.startswith("#"):
+            break
+        if "#CHROM" in line:
+            cols = line.rstrip("\n").split("\t")
+        else:
+            comments.append(line)
+    return comments, cols
+
+
+def _hccv_params(cols, min_dp, delta_vaf, delta_mcf):
+    """lsg_hccv_params for a table with these columns; None when the row code is not for it (a column missing or named twice, > 64 columns)"""
+    from ._lib import HccvParams
+    if cols is None or len(cols) > 64 or len(set(cols)) != len(cols) or any(c not in cols for c in HCCV_COLUMNS) or any(ch in c for c in cols for ch in '"\r\n'):
+        return None
+    p = HccvParams()
+    p.n_cols = len(cols)
+    for k, name in enumerate(HCCV_COLUMNS):
+        p.col[k] = cols.index(name)
+    p.min_dp, p.delta_vaf, p.two_delta_vaf, p.delta_mcf = float(min_dp), float(delta_vaf), 2 * delta_vaf, float(delta_mcf)
+    return p
+
+
+class _HostRows:
+    """the host twin: lsio_hccv_rows over the table's bytes"""
+    name = "native"
+
+    def __init__(self, text: bytes):
+        self.text, self.out = text, None
+
+    def decide(self, params):
+        import ctypes as C
+        from . import hostio
+        from ._lib import HccvInfo, HccvParams
+        lib = hostio.load()
+        lib.lsio_hccv_rows.restype = C.c_int
+        lib.lsio_hccv_rows.argtypes = [C.c_char_p, C.c_int64, C.POINTER(HccvParams), C.POINTER(HccvInfo)] + [C.POINTER(C.c_void_p)] * 3
+        lib.lsio_hccv_last_error.restype = C.c_char_p
+        lib.lsio_free_text.argtypes = [C.c_void_p]
+        info, ptr = HccvInfo(), [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        if lib.lsio_hccv_rows(self.text, len(self.text), C.byref(params), C.byref(info), *[C.byref(x) for x in ptr]) != 0:
+            raise RuntimeError(lib.lsio_hccv_last_error().decode("utf-8", "replace"))
+        try:
+            sizes = (info.bytes_tsv2, info.bytes_tsv3, info.bytes_pass)
+            self.out = [C.string_at(x, n) if x.value else b"" for x, n in zip(ptr, sizes)]
+        finally:
+            for x in ptr:
+                lib.lsio_free_text(x)
+        return info
+
+    def append(self, which: int, path: str) -> None:
+        with open(path, "ab") as f:
+            f.write(self.out[which])
+
+    def pass_rows(self, info) -> bytes:
+        return self.out[2]
+
+    def close(self) -> None:
+        self.out = None
+
+
+class _DeviceRows:
+    """the device: the resident step-2 text (text None) or an uploaded table; the three row sets are the engine's tables"""
+
+    def __init__(self, engine, text=None):
+        self.eng, self.text = engine, text
+        self.name = "device-resident" if text is None else "device-uploaded"
+
+    def decide(self, params):
+        return self.eng.hccv_filter(params) if self.text is None else self.eng.hccv_filter_text(self.text, params)
+
+    def append(self, which: int, path: str) -> None:
+        self.eng.append_table((self.eng.TABLE_HCCV2, self.eng.TABLE_HCCV3)[which], path)
+
+    def pass_rows(self, info) -> bytes:
+        return self.eng.table_bytes(self.eng.TABLE_HCCV_PASS, int(info.bytes_pass))
+
+    def close(self) -> None:
+        for t in (self.eng.TABLE_HCCV2, self.eng.TABLE_HCCV3, self.eng.TABLE_HCCV_PASS):
+            self.eng.free_table(t)
+
+
+def _cluster_kept(pass_rows: bytes, n_cols: int, i_filter: int, clust_dist: int) -> bytes:
+    """tag_clustered_SNVs + modify_filter (:163-199) over the PASS rows: the rows that stay, unchanged (_cluster_tags tells which)"""
+    lines = pass_rows.decode().split("\n")[:-1]
+    fields = [l.split("\t") for l in lines]
+    index = pd.Series([f[n_cols] for f in fields], dtype=object)
+    flt = pd.Series([f[i_filter] for f in fields], dtype=object)
+    tagged = _cluster_tags(index, flt, clust_dist) if len(lines) else flt
+    return "".join(l + "\n" for l, f in zip(lines, tagged) if "dist" not in f).encode()
+
+
+def _hccv_drive(rows, head_lines, step2_tsv, out_prefix, min_dp, delta_vaf, delta_mcf, clust_dist, kinds=None, fallback=True, report=None):
+    """The driver the host twin and the device share: the head lines of the three files, .tsv2 and .tsv3 streamed from the row sets, the
+    final table from the PASS rows after the cluster test.  A table the row code does not decide - a row reported undecided, column kinds
+    whose printed form depends on the dtype pandas infers, a missing column, no row left - goes to hccv_filter as a whole (fallback=False:
+    nothing is written and None returned; the caller runs it).  report (a dict, filled in): "path" = rows.name or "fallback", "why", the
+    counts of the call."""
+    from . import tsvio
+    report = report if report is not None else {}
+    out = out_prefix + ".HCCV.tsv"
+
+    def give_up(why):
+        report.update(path="fallback", why=why)
+        if not fallback:
+            return None
+        return hccv_filter(step2_tsv, out_prefix, min_dp, delta_vaf, delta_mcf, clust_dist)
+    comments, cols = _hccv_head(head_lines)
+    params = _hccv_params(cols, min_dp, delta_vaf, delta_mcf)
+    if params is None:
+        return give_up("columns")
+    try:
+        info = rows.decide(params)
+        report.update(rows_in=int(info.rows_in), rows_tsv2=int(info.rows_tsv2), rows_tsv3=int(info.rows_tsv3), rows_pass=int(info.rows_pass),
+                      n_undecided=int(info.n_undecided), first_undecided=int(info.first_undecided), reason=int(info.reason),
+                      ms=(float(info.ms_rows), float(info.ms_decide), float(info.ms_print)))
+        if info.n_undecided:
+            return give_up("row %d: %s" % (info.first_undecided, HCCV_REASONS[info.reason]))
+        k = np.asarray(kinds, np.uint8) if kinds is not None else np.frombuffer(bytes(info.kinds), np.uint8)[:len(cols)]
+        if tsvio.kinds_dtype_sensitive(k):
+            return give_up("column kinds")
+        if info.rows_tsv2 == 0 or info.rows_tsv3 == 0:      # (the reference's frame operations on an empty frame decide what happens; no PASS row: a table of its head lines)
+            return give_up("no row left")
+        try:
+            final = _cluster_kept(rows.pass_rows(info), len(cols), cols.index("FILTER"), int(clust_dist))
+        except Exception:                                    # noqa: BLE001 - (an INDEX that does not split into three, a position that is no integer: the reference's error is the answer)
+            return give_up("cluster test")
+        with open(out, "w") as dst:
+            dst.writelines(comments)
+            dst.write(HCCV_INFO_LINE)
+        head2 = "\t".join(cols + ["INDEX", "DP_FILTER"])
+        for which, head in ((0, head2 + "\n"), (1, head2 + "\tHCCV_FILTER\n")):
+            with open(out + "23"[which], "a") as f:       # (DataFrame.to_csv(mode="a"), as the reference appends them)
+                f.write(head)
+            rows.append(which, out + "23"[which])
+        with open(out, "ab") as f:
+            f.write((head2 + "\tHCCV_FILTER\n").encode() + final)
+        report.update(path=rows.name, why="")
+        return out
+    finally:
+        rows.close()
+
+
+def _read_head(path: str):
+    lines = []
+    with open(path) as src:
+        for line in src:
+            lines.append(line)
+            if not line.startswith("#"):
+                break
+    return lines
+
+
+def hccv_filter_native(step2_tsv: str, out_prefix: str, min_dp: float = 20, delta_vaf: float = 0.1, delta_mcf: float = 0.4, clust_dist: int = 10000,
+                       report: Optional[dict] = None) -> str:
+    """hccv_filter with every row decided and printed by the host twin of the device's row code (lsio_hccv_rows, csrc/hccv_core.h): the same
+    three files, byte for byte; a table the row code does not decide runs through hccv_filter (report["path"] tells)."""
+    with open(step2_tsv, "rb") as f:
+        text = f.read()
+    return _hccv_drive(_HostRows(text), _read_head(step2_tsv), step2_tsv, out_prefix, min_dp, delta_vaf, delta_mcf, clust_dist, report=report)
+
+
+def hccv_filter_device(engine, step2_tsv: str, out_prefix: str, min_dp: float = 20, delta_vaf: float = 0.1, delta_mcf: float = 0.4, clust_dist: int = 10000,
+                       resident: bool = False, head: Optional[bytes] = None, kinds=None, fallback: bool = True, report: Optional[dict] = None):
+    """hccv_filter on the GPU.  resident=False: the file step2_tsv is uploaded (lsg_hccv_filter_text).  resident=True: the rows are the
+    engine's TABLE_STEP2 text as format_table left it (lsg_hccv_filter) - head is that table's head lines, kinds what step2_summary said
+    of its columns, and step2_tsv is read only by the fallback (fallback=False: None comes back instead, for a caller whose file is
+    still being written)."""
+    if resident:
+        if head is None or kinds is None:
+            raise ValueError("hccv_filter_device(resident=True) takes the table's head lines and its column kinds (Engine.step2_summary)")
+        return _hccv_drive(_DeviceRows(engine), head.decode().splitlines(True), step2_tsv, out_prefix, min_dp, delta_vaf, delta_mcf, clust_dist, kinds=kinds,
+                           fallback=fallback, report=report)
+    with open(step2_tsv, "rb") as f:
+        text = f.read()
+    return _hccv_drive(_DeviceRows(engine, text), _read_head(step2_tsv), step2_tsv, out_prefix, min_dp, delta_vaf, delta_mcf, clust_dist, fallback=fallback, report=report)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Per-cell genotyping of the HCCV sites
 # ---------------------------------------------------------------------------------------------------------------------
 def read_target_windows(variant_file: str, window: int = 50000) -> "OrderedDict[str, List[List[str]]]":
