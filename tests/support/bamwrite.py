@@ -51,12 +51,13 @@ def write_bam(path: str, contigs: Sequence[Tuple[str, int]], records: Sequence[d
     """records: dicts with tid, pos (0-based), name, flag, mapq, cigar, seq, qual (list of ints), tags; must already be
     coordinate sorted."""
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % c for c in contigs)
-    out = b"BAM\1" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(contigs))
+    parts = [b"BAM\1" + struct.pack("<I", len(text)) + text.encode() + struct.pack("<I", len(contigs))]
     for name, ln in contigs:
-        out += struct.pack("<I", len(name) + 1) + name.encode() + b"\0" + struct.pack("<I", ln)
+        parts.append(struct.pack("<I", len(name) + 1) + name.encode() + b"\0" + struct.pack("<I", ln))
     for r in records:
-        out += encode_record(r["tid"], r["pos"], r.get("name", "r"), r.get("flag", 0), r.get("mapq", 60), r["cigar"], r["seq"],
-                             r.get("qual", []), r.get("tags", {}))
+        parts.append(encode_record(r["tid"], r["pos"], r.get("name", "r"), r.get("flag", 0), r.get("mapq", 60), r["cigar"], r["seq"],
+                                   r.get("qual", []), r.get("tags", {})))
+    out = b"".join(parts)                      # joined once: appending to a bytes object copies it per record
     with open(path, "wb") as f:
         for i in range(0, len(out), 0xFF00):
             f.write(_bgzf_block(out[i:i + 0xFF00]))
