@@ -354,6 +354,7 @@ int lsg_export_calls(lsg_ctx* ctx, int32_t kind, void* dst_device, int64_t capac
  *   LSG_TABLE_BNPC_BIN / _VAF   the SNV rows of BnpC_input/<id>.BinaryMatrix.tsv and VAFMatrix.tsv (FormatInputBnpC.py:16-34; see lsg_cellgeno_filter)
  *   LSG_TABLE_FASTQ       the FASTQ records of a BAM for ctat-LR-fusion (FusionCalling/BamToFastq.py:9-42; made by lsg_bam_fastq below,
  *                         not by lsg_format_table)
+ *   LSG_TABLE_STEP3_ALL / _PASS   the rows of calling.step3.unfiltered.tsv and calling.step3.tsv (made by lsg_step3_filter below)
  *   LSG_TABLE_GENE_COUNTS the whole of <id>.counts.formated.txt, its header line included: the cell-by-gene read counts inferCNV reads
  *                         (rules featureCount + format_featureCount, rules/CNACalling.smk:29-75; see lsg_gene_counts below)
  * Rows only (the header lines are the caller's), in the reference's order: contigs in Python string order, positions ascending.
@@ -365,7 +366,8 @@ enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG
 /* Tables added since continue the numbering where enum lsg_table ends, so that none of its values moves - LSG_TABLE_SLOTS, the number
  * of tables its callers were built against, among them.  LSG_TABLE_ALL_SLOTS bounds every table index lsg_format_table,
  * lsg_copy_table, lsg_append_table and lsg_free_table serve. */
-enum lsg_table_more { LSG_TABLE_GENE_COUNTS = LSG_TABLE_SLOTS, LSG_TABLE_HCCV2, LSG_TABLE_HCCV3, LSG_TABLE_HCCV_PASS, LSG_TABLE_ALL_SLOTS };
+enum lsg_table_more { LSG_TABLE_GENE_COUNTS = LSG_TABLE_SLOTS, LSG_TABLE_HCCV2, LSG_TABLE_HCCV3, LSG_TABLE_HCCV_PASS,
+                      LSG_TABLE_STEP3_ALL, LSG_TABLE_STEP3_PASS, LSG_TABLE_ALL_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -408,7 +410,12 @@ enum lsg_hccv_reason { LSG_HCCV_OK = 0,
                        LSG_HCCV_NUMBER,         /* a needed field is not the number it should be (or a division by zero follows from it) */
                        LSG_HCCV_MAX_ZERO,       /* a multi-allelic row without a non-reference read in the cancer column */
                        LSG_HCCV_CELL_TYPES,     /* no cell type, more than two, or two of which neither is Cancer */
-                       LSG_HCCV_TOO_LONG };     /* a FILTER of more than 256 bytes to strip */
+                       LSG_HCCV_TOO_LONG,       /* a FILTER of more than 256 bytes to strip */
+                       /* lsg_step3_filter's own */
+                       LSG_STEP3_CHROM_COLON,   /* a ':' in #CHROM or in the ALT that INDEX takes: INDEX would not split into its three parts */
+                       LSG_STEP3_ALT,           /* an ALT whose first character is none of ACTG */
+                       LSG_STEP3_INDEX_LONG,    /* a clustered row's INDEX of more than LSG_STEP3_INDEX_MAX bytes */
+                       LSG_STEP3_POSITION };    /* a PASS row's Start is no plain integer: the cluster test would raise */
 typedef struct {
     int32_t n_cols; int32_t col[LSG_HCCV_COLS];
     int32_t pad_;
@@ -427,6 +434,41 @@ int lsg_hccv_filter(lsg_ctx* ctx, const lsg_hccv_params* params, lsg_hccv_info* 
 /* Over a table in host memory: the data rows of a step-2 file, leading lines that start with '#' skipped; uploaded through pinned
  * staging, row starts found on the device. */
 int lsg_hccv_filter_text(lsg_ctx* ctx, const char* text, int64_t n_bytes, const lsg_hccv_params* params, lsg_hccv_info* info);
+
+/* ---- step 3's final filters over the step-2 table's text (csrc/step3.hip, csrc/step3_core.h) --------------------------------------
+ * BaseCellCalling.step3.py:41-316, decided and printed row by row where the text lies: the Cell_types and FILTER drops, MultiAllelic_filtering
+ * (:163-231), chrM_filtering (:101-161), BC_CC_filtering (:233-251), BetaBino_filtering (:254-280) and the cluster tag (:283-306).  The
+ * rows of calling.step3.unfiltered.tsv become table LSG_TABLE_STEP3_ALL (every non-chrM row in input order, then the chrM rows:
+ * pd.concat), the rows whose STEP3FILTER is exactly PASS after the cluster tag LSG_TABLE_STEP3_PASS (calling.step3.tsv).  Rows only;
+ * the header lines are the caller's.  lsg_copy_table / lsg_append_table / lsg_free_table serve the two like any table.
+ * The cluster test needs a row's neighbours in string-sorted order: the call copies the PASS rows' (ordinal, INDEX) to the host - a few
+ * hundred -, sorts and tests them there, and sends the INDEX texts to tag back as sorted records of LSG_STEP3_INDEX_MAX + 1 bytes, which
+ * every kept row's lane searches for the INDEX it prints.
+ *   col[]   where the header line has #CHROM Start REF ALT FILTER Cell_types Dp Nc Bc Cc VAF MCF Cell_type_Filter Cancer Non-Cancer, of
+ *           n_cols <= 64 (Non-Cancer may be -1: a table of one cell type)
+ * An undecided row makes the whole call undecided exactly as lsg_hccv_filter's does (the same info fields, enum lsg_hccv_reason), and
+ * the caller runs calling.step3 over the same input.  info->kinds: as lsg_step2_summary's, filled by lsg_step3_filter_text only. */
+#define LSG_STEP3_COLS 15
+#define LSG_STEP3_INDEX_MAX 63
+typedef struct {
+    int32_t n_cols; int32_t col[LSG_STEP3_COLS];
+    double delta_vaf, delta_mcf;
+    int64_t min_ac_reads, min_ac_cells, clust_dist;
+} lsg_step3_params;
+typedef struct {
+    int64_t rows_in, rows_all, rows_pass;       /* data rows read, rows of the unfiltered table, rows of the final table */
+    int64_t rows_pass_unclustered, n_clustered; /* PASS rows before the cluster tag, INDEX texts the cluster test tags */
+    int64_t bytes_all, bytes_pass;
+    int64_t n_undecided, first_undecided;       /* rows that could not be decided, the smallest ordinal among them (-1: none) */
+    int32_t reason;                             /* lsg_hccv_reason of that row */
+    float ms_rows, ms_decide, ms_cluster, ms_print;   /* HIP-event times of the newline pass, the decide kernel and the print kernel; host time of the cluster round trip */
+    int32_t pad_;
+    uint8_t kinds[64];
+} lsg_step3_info;
+/* Over the resident rows of LSG_TABLE_STEP3_ROWS as lsg_step2_summary left them (which stay as they are). */
+int lsg_step3_filter(lsg_ctx* ctx, const lsg_step3_params* params, lsg_step3_info* info);
+/* Over a whole step-2 table in host memory: leading lines that start with '#' skipped, every drop applied. */
+int lsg_step3_filter_text(lsg_ctx* ctx, const char* text, int64_t n_bytes, const lsg_step3_params* params, lsg_step3_info* info);
 
 /* ---- FASTQ for the fusion caller, printed on the device (csrc/fastq.hip) ---------------------------
  * A BAM's records as the FASTQ text ctat-LR-fusion reads, into table LSG_TABLE_FASTQ (lsg_copy_table / lsg_append_table / lsg_free_table

@@ -162,6 +162,19 @@ class HccvInfo(C.Structure):
                 ("ms_rows", C.c_float), ("ms_decide", C.c_float), ("ms_print", C.c_float), ("kinds", C.c_uint8 * 64)]
 
 
+class Step3Params(C.Structure):
+    """lsg_step3_params: where the header has the fifteen columns step 3 reads (tsvio.STEP3_COLUMNS; Non-Cancer may be -1), and its thresholds"""
+    _fields_ = [("n_cols", C.c_int32), ("col", C.c_int32 * 15), ("delta_vaf", C.c_double), ("delta_mcf", C.c_double),
+                ("min_ac_reads", C.c_int64), ("min_ac_cells", C.c_int64), ("clust_dist", C.c_int64)]
+
+
+class Step3Info(C.Structure):
+    """lsg_step3_info (lsg_step3_filter / lsg_step3_filter_text / lsio_step3_core_rows)"""
+    _fields_ = [("rows_in", C.c_int64), ("rows_all", C.c_int64), ("rows_pass", C.c_int64), ("rows_pass_unclustered", C.c_int64), ("n_clustered", C.c_int64),
+                ("bytes_all", C.c_int64), ("bytes_pass", C.c_int64), ("n_undecided", C.c_int64), ("first_undecided", C.c_int64), ("reason", C.c_int32),
+                ("ms_rows", C.c_float), ("ms_decide", C.c_float), ("ms_cluster", C.c_float), ("ms_print", C.c_float), ("pad_", C.c_int32), ("kinds", C.c_uint8 * 64)]
+
+
 FASTQ_OK, FASTQ_NO_CB, FASTQ_CB_TYPE, FASTQ_UB_TYPE, FASTQ_NM_TYPE, FASTQ_NH_TYPE = -1, 0, 1, 2, 3, 4
 
 
@@ -214,6 +227,8 @@ SIGNATURES = {
     "lsg_step2_summary": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "lsg_hccv_filter": (C.c_int, [C.c_void_p, C.POINTER(HccvParams), C.POINTER(HccvInfo)]),
     "lsg_hccv_filter_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(HccvParams), C.POINTER(HccvInfo)]),
+    "lsg_step3_filter": (C.c_int, [C.c_void_p, C.POINTER(Step3Params), C.POINTER(Step3Info)]),
+    "lsg_step3_filter_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(Step3Params), C.POINTER(Step3Info)]),
     "lsg_load_posset": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32]),
     "lsg_probe_posset": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "lsg_load_alleleset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),

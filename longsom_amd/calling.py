@@ -758,3 +758,188 @@ def step3(step2_text, delta_vaf: float, delta_mcf: float, min_ac_reads: int, min
     keep = df[~df["STEP3FILTER"].str.contains("dist", regex=True)] if len(df) else df
     keep = keep[keep["STEP3FILTER"] == "PASS"]
     return head + keep.to_csv(sep="\t", index=False), unfiltered
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Step 3 with the rows decided and printed by the shared row code (csrc/step3_core.h) and its cluster test (csrc/step3_cluster.h): on the
+# host (liblongsom_io.so, lsio_step3_core_rows) or on the device (lsg_step3_filter over the resident TABLE_STEP3_ROWS, lsg_step3_filter_text
+# over an uploaded table)
+# ---------------------------------------------------------------------------------------------------------------------
+STEP3_REASONS = ("decided", "short row", "long row", "quote, carriage return, '#' or empty line", "missing cell", "not a number", "MAX == 0", "cell types",
+                 "FILTER too long", "':' in #CHROM, Start or ALT", "ALT is none of ACTG", "INDEX too long", "a PASS row's Start is no integer")
+
+
+def _step3_head(head_lines):
+    """(comment lines to copy, column names or None) from the lines a step-2 table starts with, as step3 reads them"""
+    comments, cols = [], None
+    for line in head_lines:
+        if not line.startswith("#"):
+            break
+        line = line.rstrip("\n")
+        if "#CHROM" in line:
+            cols = line.split("\t")
+        else:
+            comments.append(line + "\n")
+    return comments, cols
+
+
+def _step3_params(cols, delta_vaf, delta_mcf, min_ac_reads, min_ac_cells, clust_dist):
+    """lsg_step3_params for a table with these columns; None when the row code is not for it: a column missing (tsvio.step3_rows refuses it
+    too) or named twice, > 64 columns, or #CHROM, FILTER and Cell_types elsewhere than where step3's survivor scan reads them"""
+    from . import tsvio
+    from ._lib import Step3Params
+    if cols is None or len(cols) > 64 or len(set(cols)) != len(cols) or any(ch in c for c in cols for ch in '"\r\n'):
+        return None
+    if any(c not in cols for c in tsvio.STEP3_COLUMNS if c != "Non-Cancer"):
+        return None
+    if cols.index("#CHROM") != 0 or cols.index("FILTER") != 5 or not 5 <= cols.index("Cell_types") <= 7:
+        return None
+    p = Step3Params()
+    p.n_cols = len(cols)
+    for k, name in enumerate(tsvio.STEP3_COLUMNS):
+        p.col[k] = cols.index(name) if name in cols else -1
+    p.delta_vaf, p.delta_mcf = float(delta_vaf), float(delta_mcf)
+    p.min_ac_reads, p.min_ac_cells, p.clust_dist = int(min_ac_reads), int(min_ac_cells), int(clust_dist)
+    return p
+
+
+class _Step3HostRows:
+    """the host twin: lsio_step3_core_rows over the table's bytes"""
+    name = "native"
+
+    def __init__(self, text: bytes):
+        self.text, self.out = text, None
+
+    def decide(self, params):
+        import ctypes as C
+        from . import hostio
+        from ._lib import Step3Info, Step3Params
+        lib = hostio.load()
+        lib.lsio_step3_core_rows.restype = C.c_int
+        lib.lsio_step3_core_rows.argtypes = [C.c_char_p, C.c_int64, C.POINTER(Step3Params), C.POINTER(Step3Info)] + [C.POINTER(C.c_void_p)] * 2
+        lib.lsio_step3_core_last_error.restype = C.c_char_p
+        lib.lsio_free_text.argtypes = [C.c_void_p]
+        info, ptr = Step3Info(), [C.c_void_p(), C.c_void_p()]
+        if lib.lsio_step3_core_rows(self.text, len(self.text), C.byref(params), C.byref(info), *[C.byref(x) for x in ptr]) != 0:
+            raise RuntimeError(lib.lsio_step3_core_last_error().decode("utf-8", "replace"))
+        try:
+            self.out = [C.string_at(x, n) if x.value else b"" for x, n in zip(ptr, (info.bytes_all, info.bytes_pass))]
+        finally:
+            for x in ptr:
+                lib.lsio_free_text(x)
+        return info
+
+    def append(self, which: int, path: str) -> None:
+        with open(path, "ab") as f:
+            f.write(self.out[which])
+
+    def close(self) -> None:
+        self.out = None
+
+
+class _Step3DeviceRows:
+    """the device: the resident TABLE_STEP3_ROWS (text None) or an uploaded table; the two row sets are the engine's tables"""
+
+    def __init__(self, engine, text=None):
+        self.eng, self.text = engine, text
+        self.name = "device-resident" if text is None else "device-uploaded"
+
+    def decide(self, params):
+        return self.eng.step3_filter(params) if self.text is None else self.eng.step3_filter_text(self.text, params)
+
+    def append(self, which: int, path: str) -> None:
+        self.eng.append_table((self.eng.TABLE_STEP3_ALL, self.eng.TABLE_STEP3_PASS)[which], path)
+
+    def close(self) -> None:
+        for t in (self.eng.TABLE_STEP3_ALL, self.eng.TABLE_STEP3_PASS):
+            self.eng.free_table(t)
+
+
+def _step3_drive(rows, head_lines, out_final, out_unfiltered, args, kinds=None, fallback=None, report=None, background=None):
+    """The driver the host twin and the device share: the head lines of the two files, then the rows streamed from the row sets.  A table the
+    row code does not decide - a row reported undecided, column kinds whose printed form depends on the dtype pandas infers, a missing or
+    duplicate column, a run that asks for the pandas path - goes to calling.step3 as a whole: fallback() returns its (final, unfiltered)
+    bytes, which are written (fallback None: nothing is written and None returned; the caller runs it).  report (a dict, filled in): "path" =
+    rows.name or "fallback", "why", the counts of the call.  background(fn): where given, the unfiltered table's rows are written by
+    fn on a thread of the caller's, and the row sets are the caller's to close (rows.close) once that thread is done."""
+    from . import tsvio
+    report = report if report is not None else {}
+
+    def give_up(why):
+        report.update(path="fallback", why=why)
+        rows.close()
+        if fallback is None:
+            return None
+        final, unfiltered = fallback()
+        tsvio.write_bytes(out_final, final)
+        tsvio.write_bytes(out_unfiltered, unfiltered)
+        return out_final, out_unfiltered
+    if os.environ.get("LONGSOM_STEP3_FULL_PARSE", "0") == "1" or os.environ.get("LONGSOM_STEP3_PANDAS", "0") == "1":
+        return give_up("the pandas path was asked for")
+    comments, cols = _step3_head(head_lines)
+    params = _step3_params(cols, *args)
+    if params is None:
+        return give_up("columns")
+    try:
+        info = rows.decide(params)
+    except BaseException:
+        rows.close()
+        raise
+    report.update(rows_in=int(info.rows_in), rows_all=int(info.rows_all), rows_pass=int(info.rows_pass), rows_pass_unclustered=int(info.rows_pass_unclustered),
+                  n_clustered=int(info.n_clustered), n_undecided=int(info.n_undecided), first_undecided=int(info.first_undecided), reason=int(info.reason),
+                  ms=(float(info.ms_rows), float(info.ms_decide), float(info.ms_cluster), float(info.ms_print)))
+    if info.n_undecided:
+        return give_up("row %d: %s" % (info.first_undecided, STEP3_REASONS[info.reason]))
+    k = np.asarray(kinds, np.uint8) if kinds is not None else np.frombuffer(bytes(info.kinds), np.uint8)[:len(cols)]
+    if tsvio.kinds_dtype_sensitive(k):
+        return give_up("column kinds")
+    header = ("".join(comments) + FINAL_FILTER_LINE + "\t".join(cols + ["STEP3FILTER", "INDEX"]) + "\n").encode()
+    for path in (out_final, out_unfiltered):
+        with open(path, "wb") as f:
+            f.write(header)
+    report.update(path=rows.name, why="")
+    rows.append(1, out_final)
+    if background is not None:
+        background(lambda: rows.append(0, out_unfiltered))
+    else:
+        rows.append(0, out_unfiltered)
+        rows.close()
+    return out_final, out_unfiltered
+
+
+def _read_head_lines(path: str):
+    lines = []
+    with open(path) as src:
+        for line in src:
+            if not line.startswith("#"):
+                break
+            lines.append(line)
+    return lines
+
+
+def step3_native(step2_tsv: str, out_final: str, out_unfiltered: str, delta_vaf: float, delta_mcf: float, min_ac_reads: int, min_ac_cells: int, clust_dist: int,
+                 report: Optional[dict] = None):
+    """step3 over the file step2_tsv into its two files, every row decided and printed by the host twin of the device's row code
+    (lsio_step3_core_rows, csrc/step3_core.h): the same files, byte for byte; a table the row code does not decide runs through step3
+    (report["path"] tells)."""
+    args = (delta_vaf, delta_mcf, min_ac_reads, min_ac_cells, clust_dist)
+    with open(step2_tsv, "rb") as f:
+        text = f.read()
+    return _step3_drive(_Step3HostRows(text), _read_head_lines(step2_tsv), out_final, out_unfiltered, args, fallback=lambda: step3_bytes(text, *args), report=report)
+
+
+def step3_device(engine, step2_tsv: Optional[str], out_final: str, out_unfiltered: str, delta_vaf: float, delta_mcf: float, min_ac_reads: int, min_ac_cells: int,
+                 clust_dist: int, resident: bool = False, head: Optional[bytes] = None, kinds=None, report: Optional[dict] = None, background=None):
+    """step3 on the GPU, into its two files.  resident=False: the file step2_tsv is uploaded whole (lsg_step3_filter_text); a table the row
+    code does not decide runs through step3.  resident=True: the rows are the engine's TABLE_STEP3_ROWS as step2_summary left them
+    (lsg_step3_filter) - head is the step-2 table's head lines, kinds what step2_summary said of its columns; a table the row code does
+    not decide is left to the caller (None comes back, nothing is written), who still holds those rows.  background: see _step3_drive."""
+    args = (delta_vaf, delta_mcf, min_ac_reads, min_ac_cells, clust_dist)
+    if resident:
+        if head is None or kinds is None:
+            raise ValueError("step3_device(resident=True) takes the table's head lines and its column kinds (Engine.step2_summary)")
+        return _step3_drive(_Step3DeviceRows(engine), head.decode().splitlines(True), out_final, out_unfiltered, args, kinds=kinds, report=report, background=background)
+    with open(step2_tsv, "rb") as f:
+        text = f.read()
+    return _step3_drive(_Step3DeviceRows(engine, text), _read_head_lines(step2_tsv), out_final, out_unfiltered, args, fallback=lambda: step3_bytes(text, *args),
+                        report=report, background=background)

@@ -337,13 +337,25 @@ def calling_step2(argv=None):
 
 
 def calling_step3(argv=None):
-    """BaseCellCalling.step3.py --infile --outfile --deltaVAF --deltaMCF --chrM_contaminant --min_ac_reads --min_ac_cells --clust_dist  (step3.py:318-328)"""
+    """BaseCellCalling.step3.py --infile --outfile --deltaVAF --deltaMCF --chrM_contaminant --min_ac_reads --min_ac_cells --clust_dist  (step3.py:318-328).
+    Flags of this script alone: --device N decides and prints the rows on GPU N (the table is uploaded), --native with the host twin of the
+    same row code; a table the row code does not decide runs through calling.step3, as every table does without either flag."""
     ap = argparse.ArgumentParser(description="LongSom final filters")
     ap.add_argument("--infile", required=True); ap.add_argument("--outfile", required=True)
     ap.add_argument("--deltaVAF", type=float, required=True); ap.add_argument("--deltaMCF", type=float, required=True)
     ap.add_argument("--chrM_contaminant", default="True"); ap.add_argument("--min_ac_reads", type=int, default=2)
     ap.add_argument("--min_ac_cells", type=int, default=3); ap.add_argument("--clust_dist", type=int, default=5)
+    how = ap.add_mutually_exclusive_group()
+    how.add_argument("--device", type=int, default=None); how.add_argument("--native", action="store_true")
     a = ap.parse_args(argv)
+    if a.device is not None or a.native:
+        args = (a.infile, a.outfile + ".calling.step3.tsv", a.outfile + ".calling.step3.unfiltered.tsv", a.deltaVAF, a.deltaMCF, a.min_ac_reads, a.min_ac_cells, a.clust_dist)
+        if a.native:
+            calling.step3_native(*args)
+        else:
+            with Engine(a.device) as eng:
+                calling.step3_device(eng, *args)
+        return
     final, unfiltered = calling.step3(open(a.infile, "rb").read(), a.deltaVAF, a.deltaMCF, a.min_ac_reads, a.min_ac_cells, a.clust_dist)
     open(a.outfile + ".calling.step3.tsv", "w").write(final)
     open(a.outfile + ".calling.step3.unfiltered.tsv", "w").write(unfiltered)

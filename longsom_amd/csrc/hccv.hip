@@ -4,7 +4,7 @@
 // table and applies three Python functions to every row) for the fused re-annotation run, where that table was printed on the device
 // and is still resident (tables.hip, LSG_TABLE_STEP2), and for a table the caller uploads.  The row rules are hccv_core.h's, shared
 // with the host twin (hostio/hccvrows.cpp).  Both entries run the same kernels over the same form of input - the text and the place of
-// every row's first byte: a newline pass counts the row starts of every 256-byte piece, a scan places them, a second pass writes them
+// every row's first byte, found by text_rows.h's newline passes
 // (the resident table's rows lie contig after contig in the names' order, which its format's scratch does not index in: reading the
 // newlines again costs one pass over the text and leaves that scratch, and lsg_step2_summary's, alone).  Then one lane per row, twice,
 // like every table here: decide and measure (text_core.h's counting sink), places from the lengths (text_table.h), print (the storing
@@ -12,6 +12,7 @@
 // behind all others.
 #include "lsg_ctx.h"
 #include "hccv_core.h"
+#include "text_rows.h"
 #include "text_sink.h"
 #include "text_table.h"
 #include <cstring>
@@ -20,38 +21,6 @@ namespace lsg {
 void launch_text_kinds(const char* text, const uint32_t* len, const uint64_t* off, int64_t n, int n_cols, uint32_t* kinds, hipStream_t st);      // tables.hip
 
 namespace {
-
-constexpr int PIECE = 256;                            // bytes of text a lane of the newline passes reads: sixteen 16-byte loads
-
-// The row starts in piece t: byte 0 of the text, and every byte behind a newline that is still inside the text.  fn(place) per start, ascending.
-template <class F> __device__ __forceinline__ void piece_starts(const char* text, int64_t n_bytes, int64_t t, F fn) {
-    const int64_t base = t * PIECE;
-    if (t == 0 && n_bytes > 0) fn((int64_t)0);
-    const uint4* src = reinterpret_cast<const uint4*>(text + base);      // (the text's buffer is 256-byte aligned and padded beyond n_bytes: DevBuf)
-    for (int q = 0; q < PIECE / 16; ++q) {
-        const int64_t at = base + q * 16;
-        if (at >= n_bytes) break;
-        const uint4 v = src[q];
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-        for (int b = 0; b < 16; ++b)
-            if (((w[b >> 2] >> ((b & 3) * 8)) & 0xFFu) == (uint32_t)'\n' && at + b + 1 < n_bytes) fn(at + b + 1);
-    }
-}
-__global__ __launch_bounds__(256) void k_hccv_count_starts(const char* text, int64_t n_bytes, int64_t n_pieces, uint32_t* cnt) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > n_pieces) return;
-    uint32_t k = 0;
-    if (t < n_pieces) piece_starts(text, n_bytes, t, [&](int64_t) { ++k; });
-    cnt[t] = k;
-}
-// starts[n_rows] = one past the last row's newline, the one a last line may lack counted
-__global__ __launch_bounds__(256) void k_hccv_fill_starts(const char* text, int64_t n_bytes, int64_t n_pieces, const uint64_t* off, uint64_t* starts) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > n_pieces) return;
-    if (t == n_pieces) { starts[off[t]] = (uint64_t)n_bytes + (text[n_bytes - 1] != '\n' ? 1u : 0u); return; }
-    uint64_t w = off[t];
-    piece_starts(text, n_bytes, t, [&](int64_t at) { starts[w++] = (uint64_t)at; });
-}
 
 // what the decide pass leaves per row besides the lengths
 enum { RF_CHRM = 1, RF_PASS = 2 };
@@ -67,11 +36,6 @@ struct HccvArgs {
     unsigned long long* first_bad;                    // min over undecided rows of ordinal << 8 | reason
     char* out2; char* out3; char* outp;
 };
-
-__device__ __forceinline__ void tally(unsigned long long* at, bool mine) {
-    const unsigned long long m = __ballot(mine);
-    if (m && (int)(__ffsll((long long)m) - 1) == (int)(threadIdx.x & 63)) atomicAdd(at, (unsigned long long)__popcll(m));
-}
 
 __global__ __launch_bounds__(256) void k_hccv_decide(HccvArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,13 +57,9 @@ __global__ __launch_bounds__(256) void k_hccv_decide(HccvArgs a) {
         a.len2[i] = l2; a.len3[i] = l3; a.len3m[i] = is_m ? l3 : 0u; a.lenp[i] = pass ? l3 : 0u; a.lenpm[i] = (pass && is_m) ? l3 : 0u;
         if (i < a.n) a.flags[i] = (uint8_t)((is_m ? RF_CHRM : 0) | (pass ? RF_PASS : 0));
     }
-    tally(a.counts + CT_TSV2, l2 > 0); tally(a.counts + CT_TSV3, l3 > 0); tally(a.counts + CT_PASS, pass); tally(a.counts + CT_UNDECIDED, stage == lsgh::UNDECIDED);
+    wave_tally(a.counts + CT_TSV2, l2 > 0); wave_tally(a.counts + CT_TSV3, l3 > 0); wave_tally(a.counts + CT_PASS, pass); wave_tally(a.counts + CT_UNDECIDED, stage == lsgh::UNDECIDED);
 }
 
-// a row's place among n rows of which the chrM rows come last: off = its place among all, offm = among the chrM rows alone
-__device__ __forceinline__ int64_t chrm_last(const uint64_t* off, const uint64_t* offm, int64_t i, int64_t n, bool is_m) {
-    return is_m ? (int64_t)(off[n] - offm[n]) + (int64_t)offm[i] : (int64_t)(off[i] - offm[i]);
-}
 __global__ __launch_bounds__(256) void k_hccv_print(HccvArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n || a.len2[i] == 0) return;
@@ -114,36 +74,17 @@ __global__ __launch_bounds__(256) void k_hccv_print(HccvArgs a) {
     if (a.flags[i] & RF_PASS) { PutSink s{a.outp + chrm_last(a.offp, a.offpm, i, a.n, is_m)}; lsgh::print_row(s, r, n, a.p, st, true); }
 }
 
-struct Timer {                                        // HIP-event time of a phase on the stream
-    hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
-    explicit Timer(hipStream_t s) : st(s) { if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) a = b = nullptr; }
-    ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-    void start() { if (a) (void)hipEventRecord(a, st); }
-    void stop() { if (b) (void)hipEventRecord(b, st); }
-    float ms() { float v = 0; if (a && b && hipEventSynchronize(b) == hipSuccess) (void)hipEventElapsedTime(&v, a, b); return v; }
-};
-
 // the filter over n_bytes of text on the device (256-byte aligned, its buffer padded to whole 16 bytes)
 int run_hccv_rows(lsg_ctx* c, const char* text, int64_t n_bytes, const lsg_hccv_params* p, lsg_hccv_info* info, bool want_kinds) {
     hipStream_t st = c->stream;
     for (int t : {LSG_TABLE_HCCV2, LSG_TABLE_HCCV3, LSG_TABLE_HCCV_PASS}) c->tab_bytes[t] = -1;
     if (n_bytes == 0) { for (int t : {LSG_TABLE_HCCV2, LSG_TABLE_HCCV3, LSG_TABLE_HCCV_PASS}) c->tab_bytes[t] = 0; return 0; }
-    Timer t_rows(st), t_decide(st), t_print(st);
+    PhaseTimer t_rows(st), t_decide(st), t_print(st);
     // ---- the rows' starts
-    const int64_t n_pieces = (n_bytes + PIECE - 1) / PIECE;
-    if (n_pieces >= (int64_t)1 << 31) { set_error("lsg_hccv_filter: %lld bytes of text", (long long)n_bytes); return -2; }
-    RowPlaces pc;
-    if (row_places(c->hccv.pieces, n_pieces, -1, pc)) return -1;
     t_rows.start();
-    const unsigned pblocks = (unsigned)((n_pieces + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_hccv_count_starts, dim3(pblocks), dim3(256), 0, st, text, n_bytes, n_pieces, pc.len);
     int64_t n = 0;
-    if (finish_places(c, pc, &n)) return -1;
-    if (n >= (int64_t)1 << 31) { set_error("lsg_hccv_filter: %lld rows", (long long)n); return -2; }
-    if (c->hccv.starts.reserve((size_t)(n + 1) * 8)) return -1;
-    hipLaunchKernelGGL(k_hccv_fill_starts, dim3(pblocks), dim3(256), 0, st, text, n_bytes, n_pieces, pc.off, c->hccv.starts.as<uint64_t>());
+    if (int rc = find_row_starts(c, c->hccv.pieces, c->hccv.starts, text, n_bytes, "lsg_hccv_filter", &n)) return rc;
     t_rows.stop();
-    LSG_HIP(hipGetLastError());
     info->rows_in = n;
     // ---- decide and measure
     RowPlaces r[5];
@@ -216,31 +157,9 @@ int run_hccv_filter_text(lsg_ctx* c, const char* text, int64_t n_bytes, const ls
     memset(info, 0, sizeof *info);
     info->first_undecided = -1;
     if (int rc = check_params(p, "lsg_hccv_filter_text")) return rc;
-    int64_t at = 0;                                   // the comment lines a table starts with
-    while (at < n_bytes && text[at] == '#') { const void* e = memchr(text + at, '\n', (size_t)(n_bytes - at)); at = e ? (const char*)e - text + 1 : n_bytes; }
+    const int64_t at = skip_comment_lines(text, n_bytes);
     text += at; n_bytes -= at;
-    hipStream_t st = c->stream;
-    if (n_bytes > 0) {
-        if (c->hccv.text.reserve((size_t)n_bytes + 16)) return -1;
-        // the table's bytes through two pinned staging buffers, as lsg_load_bam takes a file's: the CPU fills one while the other drains
-        const size_t CH = 32u << 20;
-        const size_t each = (size_t)n_bytes < CH ? (size_t)n_bytes : CH;
-        char* pin[2] = {nullptr, nullptr}; hipEvent_t pe[2] = {nullptr, nullptr};
-        bool ok = true;
-        for (int i = 0; i < 2 && ok; ++i) ok = hipHostMalloc(reinterpret_cast<void**>(&pin[i]), each, hipHostMallocDefault) == hipSuccess && hipEventCreate(&pe[i]) == hipSuccess;
-        size_t off = 0; int slot = 0; bool used[2] = {false, false};
-        while (ok && off < (size_t)n_bytes) {
-            const size_t k = (size_t)n_bytes - off < each ? (size_t)n_bytes - off : each;
-            if (used[slot]) ok = hipEventSynchronize(pe[slot]) == hipSuccess;
-            if (!ok) break;
-            memcpy(pin[slot], text + off, k);
-            ok = hipMemcpyAsync(c->hccv.text.as<char>() + off, pin[slot], k, hipMemcpyHostToDevice, st) == hipSuccess && hipEventRecord(pe[slot], st) == hipSuccess;
-            used[slot] = true; off += k; slot ^= 1;
-        }
-        if (ok) ok = hipStreamSynchronize(st) == hipSuccess;
-        for (int i = 0; i < 2; ++i) { if (pe[i]) (void)hipEventDestroy(pe[i]); if (pin[i]) (void)hipHostFree(pin[i]); }
-        if (!ok) { set_error("lsg_hccv_filter_text: copying the table to the device failed: %s", hipGetErrorString(hipGetLastError())); return -1; }
-    }
+    if (int rc = upload_text(c, c->hccv.text, text, n_bytes, "lsg_hccv_filter_text")) return rc;
     return run_hccv_rows(c, c->hccv.text.as<char>(), n_bytes, p, info, true);
 }
 

@@ -11,18 +11,13 @@
 // zero, a missing ALT or FILTER, a short row ...) is reported as undecided with a reason; the caller then runs reanno.hccv_filter over
 // the whole table.  Nothing is guessed.
 #pragma once
-#include <cstdint>
-#include "text_core.h"
-#include "../../include/longsom_hip.h"
+#include "row_core.h"
 
 namespace lsgh {
-using lsgt::LenSink;
-using lsgt::PutSink;
 
 // lsg_hccv_params::col, by name in the header line
 enum { C_CHROM = 0, C_START, C_REF, C_ALT, C_FILTER, C_CTYPES, C_DP, C_NC, C_BC, C_CC, C_VAF, C_MCF, C_CANCER, C_NONCANCER, N_USED };
 static_assert(N_USED == LSG_HCCV_COLS, "lsg_hccv_params::col");
-constexpr int FILTER_MAX = 256;                      // the longest FILTER the Multi-allelic strip takes
 
 // how far a row came (in the reference's order), its verdict, and why it could not be decided
 enum Stage { DROP_CELL_TYPES = 0, DROP_MULTI, DROP_DEPTH, IN_TSV2, IN_TSV3, UNDECIDED };
@@ -33,64 +28,6 @@ struct Row {
     uint8_t multi, top;                              // multi: 0 the six fields print as they came, 1 / 2 replaced for one / two cell types; top: the base index
     int64_t bc[2], cc[2], vaf_k[2], mcf_k[2];        // the replaced values in printing order (two cell types: Non-Cancer, Cancer); ratios as k of k / 1e4
 };
-
-LSGT_HD bool is_dig(char c) { return c >= '0' && c <= '9'; }
-// int(text) for the plain form the tables print: 1 to 15 digits
-LSGT_HD bool parse_uint(const char* f, int n, int64_t& v) {
-    if (n < 1 || n > 15) return false;
-    int64_t x = 0;
-    for (int i = 0; i < n; ++i) { if (!is_dig(f[i])) return false; x = x * 10 + (f[i] - '0'); }
-    v = x;
-    return true;
-}
-// float(text) for digits[.digits] of at most 15 digits in all: an integer over a power of ten, both exact, one correctly rounded division
-LSGT_HD bool parse_dec(const char* f, int n, double& v) {
-    if (n < 1 || n > 16) return false;
-    int64_t m = 0; double p10 = 1.0; int nd = 0, ni = 0; bool dot = false;
-    for (int i = 0; i < n; ++i) {
-        if (f[i] == '.') { if (dot) return false; dot = true; ni = nd; continue; }
-        if (!is_dig(f[i])) return false;
-        m = m * 10 + (f[i] - '0'); ++nd;
-        if (dot) p10 *= 10.0;
-    }
-    if (!dot) ni = nd;
-    if (ni < 1 || nd > 15 || (dot && nd == ni)) return false;      // (".5" and "1." are numbers to Python, but not what a table prints)
-    v = (double)m / p10;
-    return true;
-}
-// field `idx` of f split by sep (str.split(sep)[idx]); false: there is none
-LSGT_HD bool nth_field(const char* f, int n, char sep, int idx, int& off, int& len) {
-    int a = 0;
-    for (int k = 0;; ++k) {
-        int b = a;
-        while (b < n && f[b] != sep) ++b;
-        if (k == idx) { off = a; len = b - a; return true; }
-        if (b >= n) return false;
-        a = b + 1;
-    }
-}
-// int(info.split("|")[part].split(":")[idx])
-LSGT_HD bool info_count(const char* f, int n, int part, int idx, int64_t& v) {
-    int o, l, o2, l2;
-    return nth_field(f, n, '|', part, o, l) && nth_field(f + o, l, ':', idx, o2, l2) && parse_uint(f + o + o2, l2, v);
-}
-// str.replace(pat, ""): out may not alias in
-LSGT_HD int remove_all(const char* in, int n, const char* pat, int m, char* out) {
-    int w = 0;
-    for (int i = 0; i < n;) {
-        int j = 0;
-        if (i + m <= n) while (j < m && in[i + j] == pat[j]) ++j;
-        if (j == m) i += m; else out[w++] = in[i++];
-    }
-    return w;
-}
-// the FILTER without its Multi-allelic tag (:134-136, the three replacements in the reference's order); n <= FILTER_MAX
-LSGT_HD int strip_multiallelic(const char* f, int n, char* out) {
-    char tmp[FILTER_MAX];
-    const int n1 = remove_all(f, n, "Multi-allelic,", 14, out);
-    const int n2 = remove_all(out, n1, ",Multi-allelic", 14, tmp);
-    return remove_all(tmp, n2, "Multi-allelic", 13, out);
-}
 
 // MCF_filtering's comparisons for two cell types (:230-251), the operations of the Python in their order; two_d_vaf = 2 * delta_vaf as
 // the host computed it.  No multiply-add may be fused in here.
@@ -167,31 +104,14 @@ LSGT_HD_CALL int decide(const char* r, int n, const lsg_hccv_params& p, Row& st)
         if (n_ct == 1 && !one_is_cancer) return stop(DROP_MULTI);
         if (L(C_CANCER) < 0 || na(C_CANCER)) return undecided(LSG_HCCV_MISSING);
         // the cancer column's strongest non-reference base; kept only when the runner-up has less than 1/20 of its reads (:108-117)
-        if (L(C_REF) != 1) return undecided(LSG_HCCV_NUMBER);
-        int ref = -1;
-        for (int b = 0; b < 4; ++b) if ("ACTG"[b] == F(C_REF)[0]) ref = b;
-        if (ref < 0) return undecided(LSG_HCCV_NUMBER);
-        int64_t cnt[4];
-        for (int b = 0; b < 4; ++b) if (!info_count(F(C_CANCER), L(C_CANCER), 3, b, cnt[b])) return undecided(LSG_HCCV_NUMBER);
-        cnt[ref] = 0;
-        int top = 0;
-        for (int b = 1; b < 4; ++b) if (cnt[b] > cnt[top]) top = b;
-        const int64_t best = cnt[top];
-        int64_t second = 0;
-        for (int b = 0; b < 4; ++b) if (b != top && cnt[b] > second) second = cnt[b];
-        if (best == 0) return undecided(LSG_HCCV_MAX_ZERO);
+        int top; int64_t best, second;
+        if (const int why = dominant_alt(F(C_REF), L(C_REF), F(C_CANCER), L(C_CANCER), top, best, second)) return undecided(why);
         if (!((double)second / (double)best < 0.05)) return stop(DROP_MULTI);
         st.top = (uint8_t)top;
         // the six fields' new values (:119-160)
         auto one = [&](int col, int i_ct, int slot, bool whole) {          // bc, cc, round(bc / dp, 4), round(cc / nc, 4) of one cell type's column
-            int64_t dp, nc; int o, l;
             if (L(col) < 0 || na(col)) return false;
-            if (!info_count(F(col), L(col), 3, top, st.bc[slot]) || !info_count(F(col), L(col), 2, top, st.cc[slot])) return false;
-            if (whole) { if (!parse_uint(F(C_DP), L(C_DP), dp) || !parse_uint(F(C_NC), L(C_NC), nc)) return false; }
-            else if (!nth_field(F(C_DP), L(C_DP), ',', i_ct, o, l) || !parse_uint(F(C_DP) + o, l, dp) || !nth_field(F(C_NC), L(C_NC), ',', i_ct, o, l) || !parse_uint(F(C_NC) + o, l, nc)) return false;
-            if (dp == 0 || nc == 0) return false;
-            st.vaf_k[slot] = lsgt::ratio_k4(st.bc[slot], dp); st.mcf_k[slot] = lsgt::ratio_k4(st.cc[slot], nc);
-            return true;
+            return celltype_values(F(col), L(col), top, F(C_DP), L(C_DP), F(C_NC), L(C_NC), whole ? -1 : i_ct, st.bc[slot], st.cc[slot], st.vaf_k[slot], st.mcf_k[slot]);
         };
         if (n_ct == 1) { if (!one(C_CANCER, 0, 0, true)) return undecided(LSG_HCCV_NUMBER); st.multi = 1; }
         else { if (!one(C_CANCER, i_c, 1, false) || !one(C_NONCANCER, 1 - i_c, 0, false)) return undecided(LSG_HCCV_NUMBER); st.multi = 2; }

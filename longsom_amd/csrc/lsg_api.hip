@@ -25,6 +25,8 @@ int run_free_table(lsg_ctx* c, int32_t table);
 int run_step2_summary(lsg_ctx* c, int32_t n_cols, uint8_t* kinds, int64_t* n_survivor_bytes);
 int run_hccv_filter(lsg_ctx* c, const lsg_hccv_params* p, lsg_hccv_info* info);
 int run_hccv_filter_text(lsg_ctx* c, const char* text, int64_t n_bytes, const lsg_hccv_params* p, lsg_hccv_info* info);
+int run_step3_filter(lsg_ctx* c, const lsg_step3_params* p, lsg_step3_info* info);
+int run_step3_filter_text(lsg_ctx* c, const char* text, int64_t n_bytes, const lsg_step3_params* p, lsg_step3_info* info);
 int run_genotype(lsg_ctx* c, const lsg_genotype_params* p, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
                  uint32_t* dp, uint32_t* alt, int on_device, int32_t max_depth, int64_t n_groups, const int64_t* group_off);
 int run_cellgeno_count(lsg_ctx* c, const lsg_genotype_params* p, int32_t max_depth, int64_t n_sites, const int64_t* site_keys, const uint8_t* alt_sym,
@@ -514,6 +516,16 @@ int lsg_hccv_filter_text(lsg_ctx* c, const char* text, int64_t n_bytes, const ls
     if (!c || !text || n_bytes < 0 || !params || !info) { set_error("lsg_hccv_filter_text: bad arguments"); return -2; }
     LSG_HIP(hipSetDevice(c->device));
     return run_hccv_filter_text(c, text, n_bytes, params, info);
+}
+int lsg_step3_filter(lsg_ctx* c, const lsg_step3_params* params, lsg_step3_info* info) {
+    if (!c || !params || !info) { set_error("lsg_step3_filter: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_step3_filter(c, params, info);
+}
+int lsg_step3_filter_text(lsg_ctx* c, const char* text, int64_t n_bytes, const lsg_step3_params* params, lsg_step3_info* info) {
+    if (!c || !text || n_bytes < 0 || !params || !info) { set_error("lsg_step3_filter_text: bad arguments"); return -2; }
+    LSG_HIP(hipSetDevice(c->device));
+    return run_step3_filter_text(c, text, n_bytes, params, info);
 }
 int lsg_free_table(lsg_ctx* c, int32_t table) {
     if (!c) { set_error("lsg_free_table: bad arguments"); return -2; }

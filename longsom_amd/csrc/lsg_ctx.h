@@ -142,10 +142,11 @@ struct GeneCounts {
 };
 
 // hccv.hip: an uploaded table's text, the newline pass's pieces, the rows' starts, per row its length and flags (and the call's few
-// counters), the places of the rows in the five scans of lsg_hccv_filter
+// counters), the places of the rows in the five scans of lsg_hccv_filter.  step3.hip's calls use the same scratch (one filter runs at a
+// time on a handle), and besides it the export of the PASS rows' INDEX texts and the cluster set that comes back
 struct Hccv {
-    DevBuf text, pieces, starts, rows, places[5];
-    void release() { for (DevBuf* b : {&text, &pieces, &starts, &rows}) b->release(); for (DevBuf& b : places) b.release(); }
+    DevBuf text, pieces, starts, rows, places[5], exported, cluster_set;
+    void release() { for (DevBuf* b : {&text, &pieces, &starts, &rows, &exported, &cluster_set}) b->release(); for (DevBuf& b : places) b.release(); }
 };
 
 // workspace buffers (lsg_ctx::ws)

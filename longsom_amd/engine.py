@@ -553,6 +553,23 @@ class Engine:
         _lib.check(self._lib.lsg_hccv_filter_text(self._h, text, len(text), C.byref(params), C.byref(info)), "lsg_hccv_filter_text")
         return info
 
+    # ---- step 3's final filters over a step-2 table's text (csrc/step3.hip; calling.step3_device drives it) ----
+    TABLE_STEP3_ALL, TABLE_STEP3_PASS = 21, 22
+
+    def step3_filter(self, params):
+        """After step2_summary: the rows of TABLE_STEP3_ROWS through BaseCellCalling.step3.py's row rules and its cluster test (an
+        _lib.Step3Params) into TABLE_STEP3_ALL (calling.step3.unfiltered.tsv's rows) and TABLE_STEP3_PASS (calling.step3.tsv's); returns
+        the _lib.Step3Info.  info.n_undecided > 0: no table was made, the rows are for calling.step3."""
+        info = _lib.Step3Info()
+        _lib.check(self._lib.lsg_step3_filter(self._h, C.byref(params), C.byref(info)), "lsg_step3_filter")
+        return info
+
+    def step3_filter_text(self, text: bytes, params):
+        """The same over a whole step-2 table in host memory (leading '#' lines skipped); info.kinds = the kinds of cell of its columns."""
+        info = _lib.Step3Info()
+        _lib.check(self._lib.lsg_step3_filter_text(self._h, text, len(text), C.byref(params), C.byref(info)), "lsg_step3_filter_text")
+        return info
+
     def load_posset(self, kind: int, keys, on_device: bool = False, n: Optional[int] = None):
         if on_device:
             _lib.check(self._lib.lsg_load_posset(self._h, kind, C.c_void_p(int(keys)), int(n), 1), "lsg_load_posset")

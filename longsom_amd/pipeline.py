@@ -84,6 +84,8 @@ class SnvOutputs:
     resident: Optional[dict] = field(default=None, repr=False, compare=False)      # a rank's region and decode summary (sharded two-pass loop)
     hccv: str = ""                         # run_chain(hccv=...): the .HCCV.tsv the device made from the resident step-2 text ("": it made none)
     hccv_report: Optional[dict] = field(default=None, repr=False, compare=False)      # ... and reanno.hccv_filter_device's report of that call
+    step3_report: Optional[dict] = field(default=None, repr=False, compare=False)     # calling.step3_device's report, where step 3 ran over the resident rows
+    step3_path: str = ""                   # ... and the path step 3 took there: "device-resident" or "host" (not in timings: those are seconds, all of them)
 
     @classmethod
     def under(cls, out_dir: str, sample_id: str, celltype_names, last: str = "step3", make_dirs: bool = False) -> "SnvOutputs":
@@ -449,8 +451,8 @@ def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, po
     finally:
         eng.load_alleleset(None)                      # (a later run on this engine without a source must not be tagged)
     kinds, n_surv = eng.step2_summary(len(cols))
-    survivors = eng.table_bytes(eng.TABLE_STEP3_ROWS, n_surv, prefix=hdr)
-    eng.free_table(eng.TABLE_STEP3_ROWS)
+    if not step3:
+        eng.free_table(eng.TABLE_STEP3_ROWS)
     out.start_background(lambda: eng.append_table(eng.TABLE_STEP2, out.step2))
     t["step2"] = time.time() - t0
     if hccv is not None:
@@ -465,15 +467,34 @@ def _device_steps23(out, head1: bytes, t, eng, contig_names, params, editing, po
         t["hccv_device"] = time.time() - t1
     try:
         if step3:
-            _write_step3(out, survivors, params, t, all_kinds=kinds, full_text=lambda: eng.table_bytes(eng.TABLE_STEP2, n2, prefix=hdr), survivors_only=True)
+            _device_step3(out, eng, hdr, kinds, n_surv, n2, params, t)
         t["tables_wait"] = out.wait_for_tables()
     finally:
         try:
             out.wait_for_tables()
         finally:
-            eng.free_table(eng.TABLE_STEP2)
+            for table in (eng.TABLE_STEP2, eng.TABLE_STEP3_ROWS, eng.TABLE_STEP3_ALL, eng.TABLE_STEP3_PASS):
+                eng.free_table(table)
     out.timings = t
     return out
+
+
+def _device_step3(out, eng, hdr: bytes, kinds, n_surv: int, n2: int, params, t) -> None:
+    """Step 3 of _device_steps23 over the rows step2_summary left resident (Engine.TABLE_STEP3_ROWS): decided and printed on the device
+    (calling.step3_device), the final table written here and the unfiltered one streamed into its file by the background writers.  Those
+    rows come to the host only when the row code hands the table back - or with LONGSOM_HOST_STEP3=1 -, for calling.step3 as before.
+    out.step3_path: "device-resident", or "host"."""
+    t0 = time.time()
+    done, out.step3_report = None, {}
+    if os.environ.get("LONGSOM_HOST_STEP3", "0") != "1":
+        done = calling.step3_device(eng, None, out.step3, out.step3_unfiltered, params.delta_vaf, params.delta_mcf, params.min_ac_reads, params.min_ac_cells,
+                                    params.clust_dist, resident=True, head=hdr, kinds=kinds, report=out.step3_report, background=out.start_background)
+    if done is None:
+        survivors = eng.table_bytes(eng.TABLE_STEP3_ROWS, n_surv, prefix=hdr)
+        eng.free_table(eng.TABLE_STEP3_ROWS)
+        _write_step3(out, survivors, params, t, all_kinds=kinds, full_text=lambda: eng.table_bytes(eng.TABLE_STEP2, n2, prefix=hdr), survivors_only=True)
+    t["step3"] = time.time() - t0
+    out.step3_path = out.step3_report["path"] if done is not None else "host"
 
 
 def _chain_steps23(out, s1, t, eng, contig_names, params, editing, pon_sr, pon_lr, gnomad, step3):

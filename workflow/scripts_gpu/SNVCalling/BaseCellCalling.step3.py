@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 # MI355X drop-in for LongSom's workflow/scripts/SNVCalling/BaseCellCalling.step3.py: same flags, same output files
-# (longsom_amd.cli.calling_step3).
+# (longsom_amd.cli.calling_step3).  Flags of this script alone: --device N decides and prints the rows on GPU N (csrc/step3.hip over
+# the uploaded table), --native with the host twin of the same row code; without either the host's step 3 runs, as before.
 import os
 import sys
 
