@@ -367,7 +367,11 @@ enum lsg_table { LSG_TABLE_COUNTS = 0, LSG_TABLE_MERGED = LSG_MAX_CELLTYPES, LSG
  * of tables its callers were built against, among them.  LSG_TABLE_ALL_SLOTS bounds every table index lsg_format_table,
  * lsg_copy_table, lsg_append_table and lsg_free_table serve. */
 enum lsg_table_more { LSG_TABLE_GENE_COUNTS = LSG_TABLE_SLOTS, LSG_TABLE_HCCV2, LSG_TABLE_HCCV3, LSG_TABLE_HCCV_PASS,
-                      LSG_TABLE_STEP3_ALL, LSG_TABLE_STEP3_PASS, LSG_TABLE_ALL_SLOTS };
+                      LSG_TABLE_STEP3_ALL, LSG_TABLE_STEP3_PASS, LSG_TABLE_MORE_SLOTS };
+/* ... and the file images lsg_split_bam and lsg_bgzf_compress make (below) continue it again: LSG_TABLE_SPLIT_BAM + t is cell type t's
+ * BAM file (t < LSG_MAX_CELLTYPES), LSG_TABLE_BGZF the BGZF file of lsg_bgzf_compress's bytes.  Bytes, not text: whole files, served by
+ * lsg_copy_table / lsg_append_table / lsg_free_table like any table, refused by lsg_format_table. */
+enum lsg_table_bgzf { LSG_TABLE_SPLIT_BAM = LSG_TABLE_MORE_SLOTS, LSG_TABLE_BGZF = LSG_TABLE_SPLIT_BAM + LSG_MAX_CELLTYPES, LSG_TABLE_ALL_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -513,6 +517,48 @@ typedef struct {
 } lsg_fastq_info;
 int lsg_bam_fastq(lsg_ctx* ctx, const uint8_t* file_bytes, int64_t n_bytes, int64_t first_record_offset, const char* barcodes, int32_t n_barcodes,
                   const int32_t* celltype_of, int32_t n_celltypes, int32_t min_mapq, lsg_fastq_info* info);
+
+/* ---- SplitBamCellTypes on the device: records routed, BGZF-deflated where they lie (csrc/split.hip) ---------------
+ * One BAM file per cell type out of the unsplit BAM's bytes, as tables LSG_TABLE_SPLIT_BAM + t.  Replaces split_bam
+ * (SplitBamCellTypes.py:39-192: pysam fetch, read.opt("CB"), the filters, outfile.write through htslib's bgzf + zlib on one thread); the
+ * host twin is lsio_split_bam_filtered.  Arguments as lsg_bam_fastq's routed mode; the limits are lsg_set_split_filters', and unlike the
+ * FASTQ call --n_trim is honoured.  The front half is lsg_load_bam's; -4 likewise means the record chain did not settle (split that
+ * file on the host), -3 that the device has no room for it (the library's out-of-memory code: likewise).  Reads and changes nothing of
+ * a resident load.
+ *   routed   a record goes to cell type celltype_of[i]'s file iff SplitBamCellTypes.py:65-124 writes it there: placed on a reference
+ *            (refID >= 0: infile.fetch()), a CB:Z field found (the FIRST one, as read.opt("CB") and lsio_split_bam_filtered take it; the
+ *            loads take the last), its cleaned barcode (up to the first '-') listed, filter reason 0 under min_mapq,
+ *            --max_nM and --max_NH - decided by lsg_load_bam's code (bamrec_core.h).  counters / reasons_n / reasons_first are the
+ *            report's: total, pass, CB not found, CB not matched, MAPQ; per reason (lsg_get_split_reasons' index) its records and the
+ *            smallest record ordinal (-1: none).  Record ordinals count every record of the file.
+ *   trim     with n_trim > 0 a written record's qualities inside its trim window are 0 (:129-170), everything else is the input's bytes
+ *   files    each file is the input's header (the bytes before first_record_offset; template=infile, :57) and the routed records in file
+ *            order, cut into BGZF blocks exactly as htslib's bgzf_write + bgzf_flush_try cut them (and lsio_split_bam_filtered's writer):
+ *            the header fills blocks of 0xff00 bytes; a record that does not fit the open block closes it first; a record longer than a
+ *            block spills in 0xff00-byte pieces and leaves its tail open.  So every block starts on a record boundary unless a record
+ *            is longer than a block, and lsg_load_bam reads the files back without -4.  Every block is one raw DEFLATE stream
+ *            (csrc/deflate_core.h: LZ77 + dynamic Huffman codes, literals-only Huffman, or stored - whichever is smallest), its CRC32
+ *            and ISIZE; a 28-byte EOF block ends the file.  The compressed bytes differ from zlib's, the inflated ones do not.  An
+ *            empty cell type gives a header block + EOF.  The .bai pysam.index writes (:189-192) is not written.
+ *   errors   a read on which the reference raises - a trim window longer than the read, no qualities to trim, a non-numeric nM / NH
+ *            on a listed barcode under its limit - ends the call with lsio_split_bam_filtered's message behind this call's name; bad_ordinal /
+ *            bad_kind (LSG_SPLIT_ERR_*) name the smallest such ordinal, and no table is kept. */
+enum { LSG_SPLIT_OK = 0, LSG_SPLIT_ERR_TRIM_LONG = 1, LSG_SPLIT_ERR_NO_QUAL = 2, LSG_SPLIT_ERR_NM_TYPE = 3, LSG_SPLIT_ERR_NH_TYPE = 4 };
+typedef struct {
+    int64_t n_records;                                             /* records of the file, unplaced ones included */
+    int64_t counters[5];                                           /* total, pass, cb_not_found, cb_not_matched, mapq */
+    int64_t reasons_n[18], reasons_first[18];
+    int64_t n_written[LSG_MAX_CELLTYPES], n_ubytes[LSG_MAX_CELLTYPES];      /* per cell type: records, uncompressed bytes (header included) */
+    int64_t n_blocks[LSG_MAX_CELLTYPES], n_file_bytes[LSG_MAX_CELLTYPES];   /* ... BGZF blocks (without the EOF block), the file's bytes */
+    int64_t bad_ordinal; int32_t bad_kind;
+    int32_t pad_;
+    float   ms_h2d, ms_inflate, ms_chain, ms_route, ms_cut, ms_gather, ms_deflate, ms_crc, ms_pack, ms_total;
+    /* HIP-event times: the front's three, route + place, gather, deflate, CRC, scan + pack; wall: the cut on the host, the call */
+} lsg_split_info;
+int lsg_split_bam(lsg_ctx* ctx, const uint8_t* file_bytes, int64_t n_bytes, int64_t first_record_offset, const char* barcodes, int32_t n_barcodes,
+                  const int32_t* celltype_of, int32_t n_celltypes, int32_t min_mapq, lsg_split_info* info);
+/* n bytes of host memory as one BGZF file (blocks of 0xff00 bytes, the EOF block) into table LSG_TABLE_BGZF; *n_bytes_out its size. */
+int lsg_bgzf_compress(lsg_ctx* ctx, const uint8_t* data, int64_t n, int64_t* n_bytes_out);
 
 /* Position sets (RNA-editing / PoN_SR / PoN_LR; build_dict, BaseCellCalling.step2.py:197-221):
  * sorted unique keys (tid<<32)|pos1 resident in HBM; kind in [0,3). */

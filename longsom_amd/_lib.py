@@ -129,6 +129,18 @@ class FastqInfo(C.Structure):
     ]
 
 
+class SplitInfo(C.Structure):
+    """lsg_split_info (lsg_split_bam): the report's counters and reasons, per cell type its records / uncompressed bytes / BGZF blocks / file
+    bytes, the smallest ordinal of a read the reference raises on and why (-1 / 0: none), the phases' times"""
+    _fields_ = [
+        ("n_records", C.c_int64), ("counters", C.c_int64 * 5), ("reasons_n", C.c_int64 * 18), ("reasons_first", C.c_int64 * 18),
+        ("n_written", C.c_int64 * 4), ("n_ubytes", C.c_int64 * 4), ("n_blocks", C.c_int64 * 4), ("n_file_bytes", C.c_int64 * 4),
+        ("bad_ordinal", C.c_int64), ("bad_kind", C.c_int32), ("pad_", C.c_int32),
+        ("ms_h2d", C.c_float), ("ms_inflate", C.c_float), ("ms_chain", C.c_float), ("ms_route", C.c_float), ("ms_cut", C.c_float), ("ms_gather", C.c_float),
+        ("ms_deflate", C.c_float), ("ms_crc", C.c_float), ("ms_pack", C.c_float), ("ms_total", C.c_float),
+    ]
+
+
 class BbfitInfo(C.Structure):
     """lsg_bbfit_info (lsg_bbfit_solve): per fit (0 the cell counts', 1 the base counts') the iterations, the status, the last step, the gradient norm"""
     _fields_ = [("iterations", C.c_int32 * 2), ("status", C.c_int32 * 2), ("last_step", C.c_double * 2), ("grad_norm", C.c_double * 2)]
@@ -296,6 +308,8 @@ SIGNATURES = {
     "lsg_load_bam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(BamInfo), C.c_void_p, C.c_void_p, C.c_int64]),
     "lsg_load_bam_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(BamInfo), C.c_void_p, C.c_void_p, C.c_int64]),
     "lsg_bam_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(FastqInfo)]),
+    "lsg_split_bam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SplitInfo)]),
+    "lsg_bgzf_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "lsg_set_load_filter": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32]),
     "lsg_set_events_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "lsg_max_live_reads_all": (C.c_int64, [C.c_void_p]),
@@ -332,7 +346,7 @@ def load():
 
 
 class LsgError(RuntimeError):
-    """a failed library call; .rc is the call's return value (-4: a BAM whose record chain the device cannot settle)"""
+    """a failed library call; .rc is the call's return value (-4: a BAM whose record chain the device cannot settle; -3: no device memory)"""
     rc = None
 
 

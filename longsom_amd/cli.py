@@ -24,12 +24,51 @@ def split_bam(argv=None):
     ap.add_argument("--bam", required=True); ap.add_argument("--meta", required=True); ap.add_argument("--id", default="Sample")
     ap.add_argument("--max_nM", type=_limit, default=None); ap.add_argument("--max_NH", type=_limit, default=None)
     ap.add_argument("--min_MQ", type=int, default=255); ap.add_argument("--n_trim", type=int, default=0); ap.add_argument("--outdir", default=".")
+    ap.add_argument("--device", type=int, default=None, help="make the BAMs on this GPU (default: on the host)")
     a = ap.parse_args(argv)
     t0 = time.time()
     table = hostio.read_barcodes(a.meta)
     outs = [os.path.join(a.outdir, "%s.%s.bam" % (a.id, ct)) for ct in table.celltype_names]
-    rep = hostio.split_bam(a.bam, table, outs, a.min_MQ, hostio.SplitFilters(a.max_nM, a.max_NH, a.n_trim))
+    filters = hostio.SplitFilters(a.max_nM, a.max_NH, a.n_trim)
+    rep = None
+    if a.device is not None:
+        rep = _split_bam_device(a.bam, table, outs, a.min_MQ, filters, a.device)
+    if rep is None:
+        rep = hostio.split_bam(a.bam, table, outs, a.min_MQ, filters)
     pipeline.write_report(os.path.join(a.outdir, a.id + ".report.txt"), rep, time.time() - t0)
+
+
+def _split_bam_device(bam, table, outs, min_mapq, filters, device):
+    """The cell types' BAMs made on the device (lsg_split_bam) and streamed into their files, one lsg_append_table per cell type on a thread
+    of its own; returns the report, or None - said on stderr - for a BAM the host twin has to split: its record chain does not settle
+    (rc -4) or it does not fit the device (rc -3)."""
+    import threading
+    from . import _lib
+    try:
+        with Engine(device) as eng:
+            eng.set_split_filters(filters)
+            info = eng.split_bam(bam, table.barcodes, table.celltype_of, len(table.celltype_names), min_mapq)
+            errors = []
+
+            def stream(t, path):
+                try:
+                    open(path, "wb").close()
+                    eng.append_table(eng.TABLE_SPLIT_BAM + t, path)
+                except Exception as e:      # noqa: BLE001 - handed to the caller's thread below
+                    errors.append(e)
+            threads = [threading.Thread(target=stream, args=(t, path)) for t, path in enumerate(outs)]
+            for th in threads:
+                th.start()
+            for th in threads:
+                th.join()
+            if errors:
+                raise errors[0]
+            return hostio.split_report(info["counters"], [(info["reasons_n"], info["reasons_first"])])
+    except _lib.LsgError as e:
+        if e.rc not in (-4, -3):
+            raise
+        print("%s: %s; splitting it on the host" % (bam, "its records straddle its BGZF blocks" if e.rc == -4 else "it does not fit the device"), file=sys.stderr)
+    return None
 
 
 def _print_fastq(bam, fastq, table, min_mapq, filters, device, host):

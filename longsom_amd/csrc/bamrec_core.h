@@ -90,7 +90,8 @@ LSR_FN bool aux_over(const AuxNum& a, int32_t max_v) { return a.is_float ? (doub
 
 // One pass over the aux fields: CB:Z as find_cb returns it (the LAST CB:Z wins) and the nM / NH tags.  A duplicated nM or NH follows
 // htslib's bam_aux_get, which pysam's opt() calls: the FIRST occurrence is the value.  Returns whether a CB:Z was found.
-LSR_FN bool scan_aux(const uint8_t* rec, uint32_t len, uint32_t* cb, uint32_t* raw, uint32_t* clean, AuxNum* nm, AuxNum* nh) {
+// first_cb: the FIRST CB:Z is the barcode, as bamio.cpp's find_cb and the host splitter take it (csrc/split.hip).
+LSR_FN bool scan_aux(const uint8_t* rec, uint32_t len, uint32_t* cb, uint32_t* raw, uint32_t* clean, AuxNum* nm, AuxNum* nh, bool first_cb = false) {
     const uint32_t l_name = rec[8], n_cigar = rd16(rec + 12), l_seq = rd32(rec + 16);
     uint64_t a = 32ull + l_name + 4ull * n_cigar + (l_seq + 1) / 2 + l_seq;
     const uint64_t end = len;
@@ -107,7 +108,7 @@ LSR_FN bool scan_aux(const uint8_t* rec, uint32_t len, uint32_t* cb, uint32_t* r
             uint64_t z = a;
             while (z < end && rec[z]) ++z;
             sz = (z - a) + 1;
-            if (t0 == 'C' && t1 == 'B' && ty == 'Z' && z < end) { *cb = (uint32_t)a; *raw = (uint32_t)(z - a); found = true; }
+            if (t0 == 'C' && t1 == 'B' && ty == 'Z' && z < end && !(first_cb && found)) { *cb = (uint32_t)a; *raw = (uint32_t)(z - a); found = true; }
         } else if (ty == 'B') {
             if (a + 5 > end) break;
             const uint8_t st = rec[a]; const uint64_t cnt = rd32(rec + a + 1);

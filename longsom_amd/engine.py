@@ -493,6 +493,56 @@ class Engine:
             raise
         return d
 
+    TABLE_SPLIT_BAM, TABLE_BGZF = 23, 27       # TABLE_SPLIT_BAM + t: cell type t's BAM file (t < 4); the file of bgzf_compress's bytes
+
+    def split_bam(self, path: str, barcodes, celltype_of, n_celltypes: int, min_mapq: int = 60, first_record_offset: Optional[int] = None) -> dict:
+        """lsg_split_bam: SplitBamCellTypes on the device (SplitBamCellTypes.py:39-192) - the BAM's records routed by cleaned CB to one BAM
+        file per cell type under min_mapq and set_split_filters' limits (--n_trim honoured: the window's qualities are written as 0), cut
+        into BGZF blocks as htslib cuts them, deflated on the device.  The files are tables TABLE_SPLIT_BAM + t: fetch them with
+        table_bytes(TABLE_SPLIT_BAM + t, info["n_file_bytes"][t]) or stream them into files with append_table.  Reads and changes nothing
+        of a resident load.  Returns the info dict (counters, reasons_n, reasons_first - hostio.split_report's inputs -, n_written,
+        n_ubytes, n_blocks, n_file_bytes, bad_ordinal, bad_kind, the phases' times).  Raises _lib.LsgError (.info holds the dict) for a
+        read the reference raises on, with rc -4 for a BAM to split on the host (hostio.split_bam) and rc -3 for one that does not fit."""
+        import mmap
+        from . import hostio
+        from ._lib import SplitInfo
+        if first_record_offset is None:
+            first_record_offset = hostio.bam_header(path)[2]
+        info = SplitInfo()
+        joined, n_cb = "\n".join(barcodes).encode(), len(barcodes)
+        ct = np.ascontiguousarray(celltype_of, np.int32)
+        if len(ct) != n_cb:
+            raise ValueError("celltype_of holds %d entries for %d barcodes" % (len(ct), n_cb))
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+                buf = np.frombuffer(mm, dtype=np.uint8)
+                try:
+                    rc = self._lib.lsg_split_bam(self._h, C.c_void_p(buf.ctypes.data), size, int(first_record_offset), joined, n_cb, _ptr(ct), int(n_celltypes),
+                                                 int(min_mapq), C.byref(info))
+                finally:
+                    del buf
+        d = {k: getattr(info, k) for k, _ in info._fields_}
+        for k in ("counters", "reasons_n", "reasons_first", "n_written", "n_ubytes", "n_blocks", "n_file_bytes"):
+            d[k] = [int(x) for x in d[k]]
+        try:
+            _lib.check(rc, "lsg_split_bam")
+        except _lib.LsgError as e:
+            e.info = d
+            raise
+        return d
+
+    def bgzf_compress(self, data) -> bytes:
+        """lsg_bgzf_compress: the bytes as one BGZF file (blocks of 0xff00 bytes deflated on the device, the EOF block) - what gzip,
+        htslib and load_bam read"""
+        data = bytes(data)
+        n = C.c_int64(0)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        _lib.check(self._lib.lsg_bgzf_compress(self._h, C.c_void_p(buf.ctypes.data) if len(data) else None, len(data), C.byref(n)), "lsg_bgzf_compress")
+        out = self.table_bytes(self.TABLE_BGZF, int(n.value))
+        self.free_table(self.TABLE_BGZF)
+        return out
+
     def set_table_names(self, contig_names, celltype_names) -> None:
         """Names the rows print (contigs in set_contigs order, cell types in index order)."""
         _lib.check(self._lib.lsg_set_table_names(self._h, len(contig_names), "\n".join(contig_names).encode(), len(celltype_names),

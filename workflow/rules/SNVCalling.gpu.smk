@@ -75,6 +75,7 @@ rule SplitBam_gpu:
         script=GPU_SCRIPTS+"/PreProcessing/SplitBamCellTypes.py",
         mapq=config['SNVCalling']['BaseCellCounter']['min_mapping_quality'],
         max_nm=SPLIT_FILTERS['max_nM'], max_nh=SPLIT_FILTERS['max_NH'], n_trim=SPLIT_FILTERS['n_trim'],
+        device=(config['SNVCalling'].get('SplitBam') or {}).get('device', 0),      # optional key SNVCalling.SplitBam.device: the GPU the BAMs are made on
     shell:
         "python {params.script} --bam {input.bam} --meta {input.barcodes} --id {wildcards.id} --outdir SNVCalling/SplitBam --min_MQ {params.mapq} "
-        "--max_nM={params.max_nm} --max_NH={params.max_nh} --n_trim={params.n_trim}"
+        "--max_nM={params.max_nm} --max_NH={params.max_nh} --n_trim={params.n_trim} --device {params.device}"
