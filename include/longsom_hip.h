@@ -371,7 +371,9 @@ enum lsg_table_more { LSG_TABLE_GENE_COUNTS = LSG_TABLE_SLOTS, LSG_TABLE_HCCV2, 
 /* ... and the file images lsg_split_bam and lsg_bgzf_compress make (below) continue it again: LSG_TABLE_SPLIT_BAM + t is cell type t's
  * BAM file (t < LSG_MAX_CELLTYPES), LSG_TABLE_BGZF the BGZF file of lsg_bgzf_compress's bytes.  Bytes, not text: whole files, served by
  * lsg_copy_table / lsg_append_table / lsg_free_table like any table, refused by lsg_format_table. */
-enum lsg_table_bgzf { LSG_TABLE_SPLIT_BAM = LSG_TABLE_MORE_SLOTS, LSG_TABLE_BGZF = LSG_TABLE_SPLIT_BAM + LSG_MAX_CELLTYPES, LSG_TABLE_ALL_SLOTS };
+enum lsg_table_bgzf { LSG_TABLE_SPLIT_BAM = LSG_TABLE_MORE_SLOTS, LSG_TABLE_BGZF = LSG_TABLE_SPLIT_BAM + LSG_MAX_CELLTYPES, LSG_TABLE_BGZF_SLOTS };
+/* ... and the .bai files of lsg_split_bam's BAMs (LSG_TABLE_SPLIT_BAI + t, under lsg_set_split_index) and of lsg_bam_index (LSG_TABLE_BAI). */
+enum lsg_table_bai { LSG_TABLE_SPLIT_BAI = LSG_TABLE_BGZF_SLOTS, LSG_TABLE_BAI = LSG_TABLE_SPLIT_BAI + LSG_MAX_CELLTYPES, LSG_TABLE_ALL_SLOTS };
 /* Names the rows print: contig_names / celltype_names are '\n'-joined, in lsg_set_contigs / cell-type index order. */
 int lsg_set_table_names(lsg_ctx* ctx, int32_t n_contigs, const char* contig_names, int32_t n_celltypes, const char* celltype_names);
 /* Prints one table into a device buffer the handle keeps for it (until lsg_free_table or the next format of the same table);
@@ -539,7 +541,8 @@ int lsg_bam_fastq(lsg_ctx* ctx, const uint8_t* file_bytes, int64_t n_bytes, int6
  *            is longer than a block, and lsg_load_bam reads the files back without -4.  Every block is one raw DEFLATE stream
  *            (csrc/deflate_core.h: LZ77 + dynamic Huffman codes, literals-only Huffman, or stored - whichever is smallest), its CRC32
  *            and ISIZE; a 28-byte EOF block ends the file.  The compressed bytes differ from zlib's, the inflated ones do not.  An
- *            empty cell type gives a header block + EOF.  The .bai pysam.index writes (:189-192) is not written.
+ *            empty cell type gives a header block + EOF.  The .bai pysam.index writes (:189-192) is not written unless
+ *            lsg_set_split_index asks for it (below).
  *   errors   a read on which the reference raises - a trim window longer than the read, no qualities to trim, a non-numeric nM / NH
  *            on a listed barcode under its limit - ends the call with lsio_split_bam_filtered's message behind this call's name; bad_ordinal /
  *            bad_kind (LSG_SPLIT_ERR_*) name the smallest such ordinal, and no table is kept. */
@@ -559,6 +562,50 @@ int lsg_split_bam(lsg_ctx* ctx, const uint8_t* file_bytes, int64_t n_bytes, int6
                   const int32_t* celltype_of, int32_t n_celltypes, int32_t min_mapq, lsg_split_info* info);
 /* n bytes of host memory as one BGZF file (blocks of 0xff00 bytes, the EOF block) into table LSG_TABLE_BGZF; *n_bytes_out its size. */
 int lsg_bgzf_compress(lsg_ctx* ctx, const uint8_t* data, int64_t n, int64_t* n_bytes_out);
+
+/* ---- The BAM index on the device: bins, chunks, the linear index, the file's bytes (csrc/bamindex.hip) -----------------------------
+ * The .bai of a coordinate-sorted BAM (SAM specification section 5.2) into table LSG_TABLE_BAI: what samtools index / pysam.index write
+ * (SplitBamCellTypes.py:189-192; rule IndexBarcodedBam_PoN).  The host twin is lsio_build_bai_full; both write this project's canonical
+ * form, byte for byte:
+ *   offsets   a record starts at (file offset of the non-empty BGZF block holding the first byte of its block_size word) << 16 | offset
+ *             inside it, and ends where the file's next record starts; the last one at (file offset behind the last non-empty block) << 16
+ *   interval  [pos, pos + rlen), rlen the reference bases its CIGAR consumes, 1 where that is 0; the flag is not consulted; the bin is
+ *             reg2bin of the interval, not the record's own bin field
+ *   chunks    per reference every maximal run of file-consecutive records of one bin is a chunk; a bin's chunks in file order, two
+ *             neighbours merged when the second starts in the block where the first ends (htslib's adjacent-block merge).  htslib's
+ *             roll-up of small bins into their parents is not made
+ *   bins      in ascending order; a reference with records ends with the pseudo-bin 37450: (first start, last end), (n_mapped,
+ *             n_unmapped by flag 0x4).  A reference without records: n_bin = 0, n_intv = 0
+ *   linear    n_intv = the last 16 kb window a record of the reference touches + 1; ioffset[w] = the smallest start of the records
+ *             overlapping w, an unset window the value before it, leading ones the reference's first set value (lsio_build_bai's values)
+ *   n_no_coor the records with refID < 0
+ *   refused   (rc -1, no table, bad_ordinal / bad_kind name the smallest such record ordinal; of several kinds at one record the smallest)
+ *             a file that is not coordinate-sorted - (refID, pos) non-decreasing over the placed records, the unplaced ones last;
+ *             a placed record with pos < 0; an interval that ends beyond 2^29
+ * The front half is lsg_load_bam's; -4 / -3 mean what they mean for lsg_split_bam: index that file on the host.  -3 is also what an
+ * index of 2^31 windows or more returns (about 65 536 references of 2^29 each): more than the device builder holds. */
+enum { LSG_BAI_OK = 0, LSG_BAI_ERR_UNSORTED = 1, LSG_BAI_ERR_NEG_POS = 2, LSG_BAI_ERR_TOO_FAR = 3 };
+typedef struct {
+    int64_t n_records, n_placed, n_no_coor;                        /* records of the file, those with refID >= 0, the others */
+    int64_t n_runs, n_chunks, n_bins, n_windows;                   /* runs, chunks after the merge, bins (both without the pseudo-bins), windows */
+    int64_t n_bytes;                                               /* the .bai file's bytes */
+    int64_t bad_ordinal; int32_t bad_kind;                         /* -1 / 0: none */
+    int32_t pad_;
+    float   ms_h2d, ms_inflate, ms_chain, ms_facts, ms_runs, ms_linear, ms_print, ms_total;
+    /* HIP-event times: the front's three (0 for a split's index), the records' facts and checks, runs + sort + chunks, the linear index,
+     * scans + print; wall: the call (for a split's index: the part of lsg_split_bam spent on this cell type's index) */
+} lsg_bai_info;
+int lsg_bam_index(lsg_ctx* ctx, const uint8_t* file_bytes, int64_t n_bytes, int64_t first_record_offset, lsg_bai_info* info);
+/* on != 0: lsg_split_bam also leaves the index of every cell type's file - of an empty one too - as table LSG_TABLE_SPLIT_BAI + t, made
+ * of the routing's own arrays (the routed records' facts, their offsets in their streams, the block cut, the packed blocks' sizes),
+ * not by reading the files again; an input the index refuses (above; ordinals count the records of that cell type's file) then fails
+ * the whole call, which keeps neither BAM nor BAI tables.  Off (the default): the call is what it was, and frees the BAI tables of an
+ * earlier call.  An index that finds no room on the device ends the call with -3 like any other reserve of it, after the BAMs were made:
+ * no table is kept, split and index that file on the host.  lsg_get_split_index_info: cell type t's index of the last lsg_split_bam
+ * under the switch; of a call that refused an input, the cell types up to and including the refused one.  -2 when there is none, and
+ * then the error text is left as it is: after a failed lsg_split_bam it stays that call's. */
+int lsg_set_split_index(lsg_ctx* ctx, int on);
+int lsg_get_split_index_info(lsg_ctx* ctx, int t, lsg_bai_info* info);
 
 /* Position sets (RNA-editing / PoN_SR / PoN_LR; build_dict, BaseCellCalling.step2.py:197-221):
  * sorted unique keys (tid<<32)|pos1 resident in HBM; kind in [0,3). */

@@ -141,6 +141,17 @@ class SplitInfo(C.Structure):
     ]
 
 
+class BaiInfo(C.Structure):
+    """lsg_bai_info (lsg_bam_index, lsg_get_split_index_info): the records, placed records and n_no_coor, runs / chunks / bins / windows, the
+    .bai's bytes, the smallest ordinal refused and why (-1 / 0: none; hostio.BAI_ERR_*), the phases' times"""
+    _fields_ = [
+        ("n_records", C.c_int64), ("n_placed", C.c_int64), ("n_no_coor", C.c_int64), ("n_runs", C.c_int64), ("n_chunks", C.c_int64), ("n_bins", C.c_int64),
+        ("n_windows", C.c_int64), ("n_bytes", C.c_int64), ("bad_ordinal", C.c_int64), ("bad_kind", C.c_int32), ("pad_", C.c_int32),
+        ("ms_h2d", C.c_float), ("ms_inflate", C.c_float), ("ms_chain", C.c_float), ("ms_facts", C.c_float), ("ms_runs", C.c_float), ("ms_linear", C.c_float),
+        ("ms_print", C.c_float), ("ms_total", C.c_float),
+    ]
+
+
 class BbfitInfo(C.Structure):
     """lsg_bbfit_info (lsg_bbfit_solve): per fit (0 the cell counts', 1 the base counts') the iterations, the status, the last step, the gradient norm"""
     _fields_ = [("iterations", C.c_int32 * 2), ("status", C.c_int32 * 2), ("last_step", C.c_double * 2), ("grad_norm", C.c_double * 2)]
@@ -310,6 +321,9 @@ SIGNATURES = {
     "lsg_bam_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(FastqInfo)]),
     "lsg_split_bam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(SplitInfo)]),
     "lsg_bgzf_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "lsg_bam_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(BaiInfo)]),
+    "lsg_set_split_index": (C.c_int, [C.c_void_p, C.c_int]),
+    "lsg_get_split_index_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BaiInfo)]),
     "lsg_set_load_filter": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_int32]),
     "lsg_set_events_layout": (C.c_int, [C.c_void_p, C.c_int32]),
     "lsg_max_live_reads_all": (C.c_int64, [C.c_void_p]),

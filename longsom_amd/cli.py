@@ -25,6 +25,7 @@ def split_bam(argv=None):
     ap.add_argument("--max_nM", type=_limit, default=None); ap.add_argument("--max_NH", type=_limit, default=None)
     ap.add_argument("--min_MQ", type=int, default=255); ap.add_argument("--n_trim", type=int, default=0); ap.add_argument("--outdir", default=".")
     ap.add_argument("--device", type=int, default=None, help="make the BAMs on this GPU (default: on the host)")
+    ap.add_argument("--index", action="store_true", help="also write {id}.{celltype}.bam.bai beside every BAM (pysam.index, SplitBamCellTypes.py:189-192)")
     a = ap.parse_args(argv)
     t0 = time.time()
     table = hostio.read_barcodes(a.meta)
@@ -32,13 +33,16 @@ def split_bam(argv=None):
     filters = hostio.SplitFilters(a.max_nM, a.max_NH, a.n_trim)
     rep = None
     if a.device is not None:
-        rep = _split_bam_device(a.bam, table, outs, a.min_MQ, filters, a.device)
+        rep = _split_bam_device(a.bam, table, outs, a.min_MQ, filters, a.device, a.index)
     if rep is None:
         rep = hostio.split_bam(a.bam, table, outs, a.min_MQ, filters)
+        if a.index:
+            for path in outs:
+                hostio.build_bai(path, full=True)
     pipeline.write_report(os.path.join(a.outdir, a.id + ".report.txt"), rep, time.time() - t0)
 
 
-def _split_bam_device(bam, table, outs, min_mapq, filters, device):
+def _split_bam_device(bam, table, outs, min_mapq, filters, device, index=False):
     """The cell types' BAMs made on the device (lsg_split_bam) and streamed into their files, one lsg_append_table per cell type on a thread
     of its own; returns the report, or None - said on stderr - for a BAM the host twin has to split: its record chain does not settle
     (rc -4) or it does not fit the device (rc -3)."""
@@ -47,6 +51,8 @@ def _split_bam_device(bam, table, outs, min_mapq, filters, device):
     try:
         with Engine(device) as eng:
             eng.set_split_filters(filters)
+            if index:
+                eng.set_split_index(True)
             info = eng.split_bam(bam, table.barcodes, table.celltype_of, len(table.celltype_names), min_mapq)
             errors = []
 
@@ -54,6 +60,9 @@ def _split_bam_device(bam, table, outs, min_mapq, filters, device):
                 try:
                     open(path, "wb").close()
                     eng.append_table(eng.TABLE_SPLIT_BAM + t, path)
+                    if index:                   # (after the BAM: an index older than its file is not used, hostio.find_bai)
+                        open(path + ".bai", "wb").close()
+                        eng.append_table(eng.TABLE_SPLIT_BAI + t, path + ".bai")
                 except Exception as e:      # noqa: BLE001 - handed to the caller's thread below
                     errors.append(e)
             threads = [threading.Thread(target=stream, args=(t, path)) for t, path in enumerate(outs)]
@@ -69,6 +78,35 @@ def _split_bam_device(bam, table, outs, min_mapq, filters, device):
             raise
         print("%s: %s; splitting it on the host" % (bam, "its records straddle its BGZF blocks" if e.rc == -4 else "it does not fit the device"), file=sys.stderr)
     return None
+
+
+def index_bam(argv=None):
+    """samtools index / pysam.index: --bam X [--out X.bai] [--device N] - the whole .bai (bins, chunks, linear index) of a coordinate-sorted
+    BAM in this project's canonical form; rule IndexBam_gpu, the drop-in for IndexBarcodedBam_PoN.  Without --device, and
+    for a BAM the device hands back (said on stderr), the host twin writes it."""
+    from . import _lib
+    ap = argparse.ArgumentParser(description="Index a coordinate-sorted BAM: write its .bai")
+    ap.add_argument("--bam", required=True); ap.add_argument("--out", default=None, help="the index file (default: <bam>.bai)")
+    ap.add_argument("--device", type=int, default=None, help="make the index on this GPU (default: on the host)")
+    a = ap.parse_args(argv)
+    t0 = time.time()
+    out = a.out or a.bam + ".bai"
+    where = "host"
+    if a.device is not None:
+        try:
+            with Engine(a.device) as eng:
+                info = eng.bam_index(a.bam)
+                open(out, "wb").close()
+                eng.append_table(eng.TABLE_BAI, out)
+                where = "device"
+        except _lib.LsgError as e:
+            if e.rc not in (-4, -3):
+                raise
+            print("%s: %s; indexing it on the host" % (a.bam, "its records straddle its BGZF blocks" if e.rc == -4 else "it does not fit the device"), file=sys.stderr)
+    if where == "host":
+        hostio.build_bai(a.bam, out, full=True)
+        info = {"n_records": None, "n_bytes": os.path.getsize(out)}
+    print(json.dumps({"bai": out, "records": info["n_records"], "bytes": info["n_bytes"], "indexed_on": where, "seconds": round(time.time() - t0, 3)}))
 
 
 def _print_fastq(bam, fastq, table, min_mapq, filters, device, host):

@@ -1127,3 +1127,178 @@ extern "C" int lsio_build_bai(const char* bam_path, const char* bai_path) {
     if (!ok) set_err("write to %s failed", bai_path);
     return bail(ok ? 0 : -1);
 }
+
+// ---- the whole BAM index: bins, chunks, the pseudo-bin, the linear index, n_no_coor ---------------------------
+// The host twin of lsg_bam_index (csrc/bamindex.hip): the same file, byte for byte, through bamindex_core.h, on one thread.  What
+// samtools index / pysam.index write for a coordinate-sorted BAM (SplitBamCellTypes.py:189-192), in this project's canonical form: every
+// run of file-consecutive records of one bin a chunk, neighbours merged when the second starts in the BGZF block where the first ends,
+// no roll-up of small bins into their parents, bins in ascending order.  info (or null): int64[10] = records, placed, n_no_coor, runs,
+// chunks after the merge, bins, windows, the file's bytes, bad_ordinal (-1), bad_kind (lsb::ERR_*).
+#include "../bamindex_core.h"
+#include <map>
+namespace {
+struct BaiRec { int32_t tid, pos; int64_t end; uint64_t vbeg; bool unmapped; };
+const char* bai_err_text(int kind) {
+    switch (kind) {
+        case lsb::ERR_UNSORTED: return "the file is not coordinate-sorted here";
+        case lsb::ERR_NEG_POS: return "it is placed on a reference at a negative position";
+        case lsb::ERR_TOO_FAR: return "it ends beyond 2^29, which a .bai cannot hold";
+        default: return "?";
+    }
+}
+}
+extern "C" int lsio_build_bai_full_info(const char* bam_path, const char* bai_path, int64_t* info) {
+    if (info) { for (int i = 0; i < 10; ++i) info[i] = 0; info[8] = -1; }
+    if (!bam_path || !bai_path) { set_err("lsio_build_bai_full: bad arguments"); return -2; }
+    int fd = open(bam_path, O_RDONLY);
+    if (fd < 0) { set_err("cannot open %s", bam_path); return -1; }
+    struct stat sb;
+    if (fstat(fd, &sb) != 0 || sb.st_size <= 0) { close(fd); set_err("cannot stat %s", bam_path); return -1; }
+    const size_t fsize = (size_t)sb.st_size;
+    const uint8_t* file = (const uint8_t*)mmap(nullptr, fsize, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (file == (const uint8_t*)MAP_FAILED) { close(fd); set_err("cannot map %s", bam_path); return -1; }
+    auto bail = [&](int rc) { munmap((void*)file, fsize); close(fd); return rc; };
+    std::vector<uint8_t> buf; uint64_t buf_g0 = 0;
+    std::vector<uint64_t> blk_ustart, blk_coff;              // the non-empty blocks: where each starts in the uncompressed stream / in the file
+    size_t bptr = 0;
+    uint64_t utotal = 0, data_end = 0; size_t off = 0;       // data_end: the file offset just past the last non-empty block
+    bool header_done = false; uint32_t n_ref = 0;
+    std::vector<uint8_t> out(65536);
+    std::vector<BaiRec> recs;
+    auto voffset = [&](uint64_t g) {                          // lsio_build_bai's rule: the non-empty block that holds byte g
+        while (bptr + 1 < blk_ustart.size() && blk_ustart[bptr + 1] <= g) ++bptr;
+        return (blk_coff[bptr] << 16) | (g - blk_ustart[bptr]);
+    };
+    size_t p = 0;
+    int64_t prev_key = INT64_MIN;
+    while (off < fsize) {
+        if (off + 18 > fsize) { set_err("%s: truncated BGZF block header", bam_path); return bail(-1); }
+        const uint8_t* h = file + off;
+        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) { set_err("%s is not BGZF", bam_path); return bail(-1); }
+        const uint32_t xlen = rd16(h + 10);
+        uint32_t bsize = 0; bool found = false;
+        if (off + 12 + (size_t)xlen > fsize) { set_err("%s: truncated BGZF extra field", bam_path); return bail(-1); }
+        for (uint32_t q = 0; q + 4 <= xlen;) {
+            const uint8_t* sf = h + 12 + q; const uint32_t slen = rd16(sf + 2);
+            if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && q + 6 <= xlen) { bsize = rd16(sf + 4) + 1u; found = true; }
+            q += 4 + slen;
+        }
+        if (!found || bsize < xlen + 20u || off + bsize > fsize) { set_err("%s: corrupt BGZF block", bam_path); return bail(-1); }
+        const uint32_t usize = rd32(h + bsize - 4);
+        if (usize > 65536u) { set_err("%s: BGZF block of %u bytes", bam_path, usize); return bail(-1); }
+        if (usize) {
+            z_stream zs; memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, -15) != Z_OK) { set_err("zlib"); return bail(-1); }
+            zs.next_in = (Bytef*)(h + 12 + xlen); zs.avail_in = bsize - xlen - 20; zs.next_out = out.data(); zs.avail_out = usize;
+            const int rc = inflate(&zs, Z_FINISH); inflateEnd(&zs);
+            if (rc != Z_STREAM_END || zs.avail_out != 0) { set_err("%s: inflate failed", bam_path); return bail(-1); }
+            blk_ustart.push_back(utotal); blk_coff.push_back((uint64_t)off);
+            buf.insert(buf.end(), out.begin(), out.begin() + usize);
+            utotal += usize; data_end = (uint64_t)off + bsize;
+        }
+        off += bsize;
+        const uint8_t* d = buf.data(); const size_t n = buf.size();
+        if (!header_done) {
+            if (n < 12) continue;
+            if (memcmp(d, "BAM\1", 4) != 0) { set_err("%s has no BAM magic", bam_path); return bail(-1); }
+            uint64_t q = 8 + (uint64_t)rd32(d + 4);
+            if (q + 4 > n) continue;
+            n_ref = rd32(d + q); q += 4;
+            bool complete = true;
+            for (uint32_t i = 0; i < n_ref; ++i) {
+                if (q + 4 > n) { complete = false; break; }
+                const uint64_t l_name = rd32(d + q);
+                if (q + 4 + l_name + 4 > n) { complete = false; break; }
+                q += 4 + l_name + 4;
+            }
+            if (!complete) continue;
+            if (n_ref > 0x7fffffffu) { set_err("%s: %u references", bam_path, n_ref); return bail(-1); }
+            header_done = true; p = (size_t)q;
+        }
+        while (p + 4 <= n) {
+            const uint64_t bs = rd32(d + p);
+            if (bs < 32 || bs > (1u << 30)) { set_err("%s: record with block_size %llu", bam_path, (unsigned long long)bs); return bail(-1); }
+            if (p + 4 + bs > n) break;
+            const uint8_t* rec = d + p + 4;
+            if (!record_ok(rec, (uint32_t)bs)) { set_err("%s: record whose fields exceed its block_size", bam_path); return bail(-1); }
+            const int32_t tid = rdi32(rec), pos = rdi32(rec + 4);
+            if (tid >= (int32_t)n_ref) { set_err("%s: a record on a reference the header does not list", bam_path); return bail(-1); }
+            const int64_t end = lsb::interval_end(pos, lsb::cigar_rlen(rec + 32 + rec[8], rd16(rec + 12), 0, 1));
+            const int64_t key = lsb::sort_key(tid, pos);
+            const int kind = key < prev_key ? (int)lsb::ERR_UNSORTED : lsb::record_error(tid, pos, end);
+            if (kind) {
+                if (info) { info[0] = (int64_t)recs.size(); info[8] = (int64_t)recs.size(); info[9] = kind; }
+                set_err("lsio_build_bai_full: %s: read '%s' (record %llu): %s", bam_path, read_name(rec).c_str(), (unsigned long long)recs.size(), bai_err_text(kind));
+                return bail(-1);
+            }
+            prev_key = key;
+            recs.push_back(BaiRec{tid, pos, end, voffset(buf_g0 + p), (rd16(rec + 14) & 0x4u) != 0});
+            p += 4 + (size_t)bs;
+        }
+        if (p > (1u << 22)) { buf.erase(buf.begin(), buf.begin() + (long)p); buf_g0 += p; p = 0; }
+    }
+    if (!header_done) { set_err("%s: truncated BAM header", bam_path); return bail(-1); }
+    if (p != buf.size()) { set_err("%s: truncated record at the end of the file", bam_path); return bail(-1); }
+    // ---- the index: per reference the bins' chunks (runs, merged as they arrive), the linear index, the pseudo-bin's numbers
+    const size_t N = recs.size();
+    const uint64_t v_eof = data_end << 16;
+    auto vend = [&](size_t i) { return i + 1 < N ? recs[i + 1].vbeg : v_eof; };
+    std::vector<uint8_t> bytes(lsb::HEAD_BYTES);
+    lsb::put_head(bytes.data(), n_ref);
+    int64_t n_runs = 0, n_chunks_all = 0, n_bins_all = 0, n_win_all = 0;
+    size_t i = 0;
+    for (uint32_t r = 0; r < n_ref; ++r) {
+        std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
+        std::vector<uint64_t> lin;
+        const size_t lo = i;
+        uint64_t n_unm = 0;
+        while (i < N && recs[i].tid == (int32_t)r) {
+            const uint32_t bin = lsb::reg2bin(recs[i].pos, recs[i].end);
+            size_t j = i;                                     // the run [i, j]: file-consecutive records of this bin
+            for (;; ++j) {
+                const BaiRec& x = recs[j];
+                n_unm += x.unmapped;
+                const size_t w0 = (size_t)(x.pos >> lsb::WIN_SHIFT), w1 = (size_t)((x.end - 1) >> lsb::WIN_SHIFT);
+                if (lin.size() <= w1) lin.resize(w1 + 1, 0);
+                for (size_t w = w0; w <= w1; ++w) if (lin[w] == 0 || x.vbeg < lin[w]) lin[w] = x.vbeg;
+                if (j + 1 >= N || recs[j + 1].tid != (int32_t)r || lsb::reg2bin(recs[j + 1].pos, recs[j + 1].end) != bin) break;
+            }
+            ++n_runs;
+            auto& ch = bins[bin];
+            if (!ch.empty() && lsb::chunks_merge(ch.back().second, recs[i].vbeg)) ch.back().second = vend(j);
+            else ch.emplace_back(recs[i].vbeg, vend(j));
+            i = j + 1;
+        }
+        const bool has = i > lo;
+        uint64_t first = 0; for (uint64_t x : lin) if (x) { first = x; break; }
+        for (size_t w = 0; w < lin.size(); ++w) if (lin[w] == 0) lin[w] = w ? lin[w - 1] : first;
+        uint64_t n_chunks = 0; for (auto& b : bins) n_chunks += b.second.size();
+        const size_t at = bytes.size();
+        bytes.resize(at + (size_t)lsb::ref_bytes(bins.size(), n_chunks, has, lin.size()));
+        uint8_t* o = bytes.data() + at;
+        lsb::put32(o, (uint32_t)(bins.size() + (has ? 1 : 0)));
+        uint64_t b_rel = 0, c_rel = 0;
+        for (auto& b : bins) {
+            uint8_t* q = o + lsb::bin_at(b_rel, c_rel);
+            lsb::put32(q, b.first); lsb::put32(q + 4, (uint32_t)b.second.size());
+            for (auto& c : b.second) { uint8_t* w = o + lsb::chunk_at(b_rel, c_rel); lsb::put64(w, c.first); lsb::put64(w + 8, c.second); ++c_rel; }
+            ++b_rel;
+        }
+        if (has) lsb::put_meta(o + lsb::meta_at(bins.size(), n_chunks), recs[lo].vbeg, vend(i - 1), (uint64_t)(i - lo) - n_unm, n_unm);
+        uint8_t* q = o + lsb::intv_at(bins.size(), n_chunks, has);
+        lsb::put32(q, (uint32_t)lin.size());
+        for (size_t w = 0; w < lin.size(); ++w) lsb::put64(q + 4 + 8 * w, lin[w]);
+        n_chunks_all += (int64_t)n_chunks; n_bins_all += (int64_t)bins.size(); n_win_all += (int64_t)lin.size();
+    }
+    const size_t n_placed = i;
+    bytes.resize(bytes.size() + lsb::TAIL_BYTES);
+    lsb::put64(bytes.data() + bytes.size() - 8, (uint64_t)(N - n_placed));
+    if (info) { info[0] = (int64_t)N; info[1] = (int64_t)n_placed; info[2] = (int64_t)(N - n_placed); info[3] = n_runs; info[4] = n_chunks_all; info[5] = n_bins_all; info[6] = n_win_all; info[7] = (int64_t)bytes.size(); }
+    FILE* f = fopen(bai_path, "wb");
+    if (!f) { set_err("cannot write %s", bai_path); return bail(-1); }
+    bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    if (fclose(f) != 0) ok = false;
+    if (!ok) set_err("write to %s failed", bai_path);
+    return bail(ok ? 0 : -1);
+}
+extern "C" int lsio_build_bai_full(const char* bam_path, const char* bai_path) { return lsio_build_bai_full_info(bam_path, bai_path, nullptr); }

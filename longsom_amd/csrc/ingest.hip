@@ -239,6 +239,7 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
     // ---- the BGZF blocks (every length field checked against the bytes that are there)
     std::vector<IngBlk> blocks;
     uint64_t utotal = 0;
+    f.blk_ustart.clear(); f.blk_coff.clear(); f.data_end = 0;
     for (uint64_t off = 0; off < (uint64_t)n_bytes;) {
         if (off + 18 > (uint64_t)n_bytes) { set_error("%s: truncated BGZF block header at offset %llu", who, (unsigned long long)off); return -1; }
         const uint8_t* h = file + off;
@@ -255,6 +256,7 @@ int ingest_front(lsg_ctx* c, const char* who, const uint8_t* file, int64_t n_byt
         const uint32_t usize = lsr::rd32(h + bsize - 4);
         if (usize > 65536u) { set_error("%s: BGZF block at offset %llu claims %u uncompressed bytes", who, (unsigned long long)off, usize); return -1; }
         blocks.push_back(IngBlk{off + 12 + xlen, utotal, bsize - xlen - 20, usize, lsr::rd32(h + bsize - 8), 0u});
+        if (usize) { f.blk_ustart.push_back(utotal); f.blk_coff.push_back(off); f.data_end = off + bsize; }
         utotal += usize; off += bsize;
     }
     const uint32_t n_blk = (uint32_t)blocks.size();

@@ -240,6 +240,8 @@ struct lsg_ctx {
     bool keep_unlisted = false;           // lsg_set_keep_unlisted: the BAM loads keep reads without a listed barcode (cb = -1; never counted, but in the genotyping pileup's buffer)
     int32_t split_max_nm = -1, split_max_nh = -1, split_n_trim = 0;      // lsg_set_split_filters: SplitBam's --max_nM / --max_NH / --n_trim for the BAM loads (off)
     int64_t split_n[18] = {}, split_first[18] = {};                      // lsg_get_split_reasons: the last BAM load's records per filter reason, first ordinals
+    bool split_index = false;             // lsg_set_split_index: lsg_split_bam also makes every cell type's .bai (bamindex.hip)
+    int split_bai_n = 0; lsg_bai_info split_bai[LSG_MAX_CELLTYPES] = {};      // lsg_get_split_index_info: the last such call's cell types and their indexes
     bool keep_reads = false;              // lsg_set_keep_reads: the compact events stay resident beside the store (rd.events; tests, sampling)
     // tile store (see above) and the plan of a count over it
     lsg::DevBuf d_tile_cap, d_tile_off;   // entries per tile and their exclusive prefix

@@ -18,6 +18,8 @@
 //   scan + k_sp_pack   the blocks' places in their file image; one wave per block writes header, payload, CRC32, ISIZE
 // Every launch is sized by its work (a lane per block: ceil(n_blocks / 64) workgroups of 64; a wave per record or block: a quarter of
 // a 256-thread workgroup each).
+// Under lsg_set_split_index every cell type's .bai is made as well (bamindex.hip): the routed records' facts while the inflated input is
+// resident, the index itself once the packed blocks' sizes say where every block lies in its file.
 #include "lsg_ctx.h"
 #include "ingest_front.h"
 #include "bamrec_core.h"
@@ -25,6 +27,7 @@
 #include "crc_core.h"
 #include "deflate_core.h"
 #include "cub_tmp.h"
+#include "bamindex.h"
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -124,6 +127,12 @@ __global__ __launch_bounds__(256) void k_sp_route(SpRouteArgs a) {
 }
 
 struct SpLenOf { const uint32_t* len; const int8_t* ct; int32_t t; __host__ __device__ unsigned long long operator()(const uint32_t& i) const { return ct[i] == t ? (unsigned long long)len[i] : 0ull; } };
+struct SpIsOf { const int8_t* ct; int32_t t; uint64_t n; __host__ __device__ uint32_t operator()(const uint32_t& i) const { return i < n && ct[i] == t ? 1u : 0u; } };
+// the ordinals of cell type t's records, in file order (rank: the exclusive count of its records)
+__global__ void k_sp_select(const int8_t* ct, int32_t t, const uint32_t* rank, uint64_t n_rec, uint32_t* sel) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_rec && ct[i] == t) sel[rank[i]] = (uint32_t)i;
+}
 __global__ void k_sp_place(const int8_t* ct, int32_t t, const unsigned long long* off_t, unsigned long long base, uint64_t n_rec, unsigned long long* off) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_rec && ct[i] == t) off[i] = base + off_t[i];
@@ -241,7 +250,9 @@ static int sp_reserve(DevBuf& b, size_t bytes, const char* who, const char* what
 struct SpTimes { float deflate = 0, crc = 0, pack = 0; };
 // The streams' blocks -> one file image per stream in the tables `table0 + s`: deflate, CRC32, scan, pack, the EOF block.  `blocks` is
 // sorted by stream.  `streams` is released once the blocks are compressed.  file_bytes[s]: the image's size.
-static int sp_compress(lsg_ctx* c, const char* who, DevBuf& streams, const std::vector<SpBlk>& blocks, int n_streams, int table0, int64_t* file_bytes, SpTimes* times) {
+// csize_out: every block's compressed bytes (its place in its file follows from them: 26 bytes of framing a block).
+static int sp_compress(lsg_ctx* c, const char* who, DevBuf& streams, const std::vector<SpBlk>& blocks, int n_streams, int table0, int64_t* file_bytes, SpTimes* times,
+                       std::vector<uint32_t>* csize_out = nullptr) {
     hipStream_t st = c->stream;
     const uint32_t n_blk = (uint32_t)blocks.size();
     static const uint8_t eof[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -287,6 +298,7 @@ static int sp_compress(lsg_ctx* c, const char* who, DevBuf& streams, const std::
         LSG_HIP_OR(hipMemcpy(h_cs.data(), d_csize.p, (size_t)n_blk * 4, hipMemcpyDeviceToHost), done(-1));
         for (uint32_t b = 0; b < n_blk; ++b)
             if (h_cs[b] == 0 || h_cs[b] > blocks[b].n + 5u) { set_error("%s: block %u of %u bytes was not compressed (%u)", who, b, blocks[b].n, h_cs[b]); return done(-1); }
+        if (csize_out) *csize_out = h_cs;
     }
     streams.release();
     SpPackArgs pa{};
@@ -307,22 +319,6 @@ static int sp_compress(lsg_ctx* c, const char* who, DevBuf& streams, const std::
     if (n_blk && times) { (void)hipEventElapsedTime(&times->deflate, ev[0], ev[1]); (void)hipEventElapsedTime(&times->crc, ev[1], ev[2]); (void)hipEventElapsedTime(&times->pack, ev[2], ev[3]); }
     for (int s = 0; s < n_streams; ++s) c->tab_bytes[table0 + s] = file_bytes[s];
     return done(0);
-}
-
-// the reference table of the BAM header in the first `n` bytes of the uncompressed stream (n = first_record_offset: it must end there)
-static bool sp_parse_refs(const std::vector<uint8_t>& h, std::vector<int64_t>& lens) {
-    const size_t n = h.size();
-    if (n < 12 || memcmp(h.data(), "BAM\1", 4) != 0) return false;
-    uint64_t p = 8ull + lsr::rd32(h.data() + 4);
-    if (p + 4 > n) return false;
-    const uint32_t n_ref = lsr::rd32(h.data() + p); p += 4;
-    for (uint32_t i = 0; i < n_ref; ++i) {
-        if (p + 4 > n) return false;
-        p += 4ull + lsr::rd32(h.data() + p);
-        if (p + 4 > n) return false;
-        lens.push_back((int64_t)lsr::rd32(h.data() + p)); p += 4;
-    }
-    return p == n;
 }
 
 // BgzfWriter's cuts (bamio.cpp): write() fills the open block to 0xff00 and spills; write_record() closes an open block the record does not fit
@@ -371,14 +367,23 @@ extern "C" int lsg_split_bam(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
     LSG_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const auto t_all = std::chrono::steady_clock::now();
-    for (int t = 0; t < LSG_MAX_CELLTYPES; ++t) { c->tab_text[LSG_TABLE_SPLIT_BAM + t].release(); c->tab_bytes[LSG_TABLE_SPLIT_BAM + t] = -1; }      // whatever fails below: no table is kept, and none of an earlier call's
+    auto drop_tables = [&] {
+        for (int t = 0; t < LSG_MAX_CELLTYPES; ++t)
+            for (int tab : {LSG_TABLE_SPLIT_BAM + t, LSG_TABLE_SPLIT_BAI + t}) { c->tab_text[tab].release(); c->tab_bytes[tab] = -1; }
+    };
+    drop_tables();                                                 // whatever fails below: no table is kept, and none of an earlier call's
+    c->split_bai_n = 0;
+    const bool with_index = c->split_index;
     lsr::CbTableHost cbt;
     cbt.build(barcodes, n_barcodes, celltype_of);                  // the table's "id" of a barcode is its cell type
     IngestFront fr;
-    DevBuf d_h, d_id, d_so, d_sl, d_str, d_reflen, d_len, d_ct, d_trim, d_offt, d_off, d_small, d_streams;
+    DevBuf d_h, d_id, d_so, d_sl, d_str, d_reflen, d_len, d_ct, d_trim, d_offt, d_off, d_small, d_streams, d_sel, d_bai_tmp;
+    BaiFacts bai_f[LSG_MAX_CELLTYPES];                             // lsg_set_split_index: what the indexes need of the records, kept across the compression
+    lsg_bai_info bai_i[LSG_MAX_CELLTYPES] = {};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     auto done = [&](int rc) {
-        for (DevBuf* b : {&d_h, &d_id, &d_so, &d_sl, &d_str, &d_reflen, &d_len, &d_ct, &d_trim, &d_offt, &d_off, &d_small, &d_streams}) b->release();
+        for (DevBuf* b : {&d_h, &d_id, &d_so, &d_sl, &d_str, &d_reflen, &d_len, &d_ct, &d_trim, &d_offt, &d_off, &d_small, &d_streams, &d_sel, &d_bai_tmp}) b->release();
+        for (auto& f : bai_f) f.release();
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         fr.release();
         return rc;
@@ -403,7 +408,7 @@ extern "C" int lsg_split_bam(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
         std::vector<uint8_t> head((size_t)H);
         LSG_HIP_OR(hipMemcpyAsync(head.data(), u, head.size(), hipMemcpyDeviceToHost, st), done(-1));
         LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
-        if (!sp_parse_refs(head, ref_len)) { set_error("lsg_split_bam: no BAM header that ends at first_record_offset %lld", (long long)first_record_offset); return done(-1); }
+        if (!parse_bam_refs(head, ref_len)) { set_error("lsg_split_bam: no BAM header that ends at first_record_offset %lld", (long long)first_record_offset); return done(-1); }
     }
     constexpr int N_SMALL = 1 + 5 + 2 * lsr::N_REASONS + LSG_MAX_CELLTYPES;      // err, counters, reasons, first ordinals, records per cell type
     if (sp_reserve(d_reflen, (ref_len.size() + 1) * 8, who, "the reference lengths") || sp_reserve(d_small, N_SMALL * 8, who, "the counters")) return done(-3);
@@ -512,13 +517,55 @@ extern "C" int lsg_split_bam(lsg_ctx* c, const uint8_t* file, int64_t n_bytes, i
     LSG_HIP_OR(hipGetLastError(), done(-1));
     LSG_HIP_OR(hipStreamSynchronize(st), done(-1));
     (void)hipEventElapsedTime(&info->ms_route, ev[0], ev[1]); (void)hipEventElapsedTime(&info->ms_gather, ev[2], ev[3]);
+    // ---- 5b. lsg_set_split_index: per cell type its records' facts (refID, pos, end, flag 0x4, offset in its stream), checked for the order
+    if (with_index)
+        for (int32_t t = 0; t < n_celltypes; ++t) {
+            const auto t_bai = std::chrono::steady_clock::now();
+            const uint64_t n_t = (uint64_t)info->n_written[t];
+            bai_i[t].bad_ordinal = -1;
+            if (n_t) {
+                if (int rc = sp_reserve(d_sel, n_t * 4 + 16, who, "a cell type's record list")) return done(rc);
+                uint32_t* rank = d_offt.as<uint32_t>();          // (n_rec + 1 words of the scan's buffer, free since the place)
+                hipcub::TransformInputIterator<uint32_t, SpIsOf, hipcub::CountingInputIterator<uint32_t>> it(iota, SpIsOf{d_ct.as<int8_t>(), t, n_rec});
+                if (exclusive_sum(fr.d_tmp, it, rank, (int64_t)n_rec + 1, st)) return done(-1);
+                hipLaunchKernelGGL(k_sp_select, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, d_ct.as<int8_t>(), t, rank, n_rec, d_sel.as<uint32_t>());
+            }
+            const int rc = bai_facts(c, who, u, utotal, fr.d_recoff.as<uint64_t>(), d_sel.as<uint32_t>(), n_t, (int32_t)ref_len.size(), d_off.as<unsigned long long>(),
+                                     (unsigned long long)base[t], status, bai_f[t], &bai_i[t]);
+            bai_i[t].ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_bai).count();
+            if (rc) {                                              // (a refusal names the ordinal in cell type t's file)
+                c->split_bai[t] = bai_i[t]; c->split_bai_n = t + 1;
+                if (bai_i[t].bad_kind) set_error("lsg_split_bam: cell type %d's file cannot be indexed: record %lld of it: %s (without lsg_set_split_index the files are written)", t,
+                                                 (long long)bai_i[t].bad_ordinal, bai_err_text(bai_i[t].bad_kind));
+                return done(rc);
+            }
+        }
     // ---- 6. deflate, CRC, pack - with the inflated input and every per-record array gone
     fr.release();
-    for (DevBuf* b : {&d_len, &d_ct, &d_trim, &d_offt, &d_off}) b->release();
+    for (DevBuf* b : {&d_len, &d_ct, &d_trim, &d_offt, &d_off, &d_sel}) b->release();
     SpTimes tm;
-    if (const int rc = sp_compress(c, who, d_streams, blocks, n_celltypes, LSG_TABLE_SPLIT_BAM, info->n_file_bytes, &tm)) {
-        for (int t = 0; t < LSG_MAX_CELLTYPES; ++t) { c->tab_text[LSG_TABLE_SPLIT_BAM + t].release(); c->tab_bytes[LSG_TABLE_SPLIT_BAM + t] = -1; }
+    std::vector<uint32_t> h_cs;
+    if (const int rc = sp_compress(c, who, d_streams, blocks, n_celltypes, LSG_TABLE_SPLIT_BAM, info->n_file_bytes, &tm, with_index ? &h_cs : nullptr)) {
+        drop_tables();
         return done(rc);
+    }
+    // ---- 7. lsg_set_split_index: every block's place in its file is known now -> the indexes
+    if (with_index) {
+        size_t b = 0;
+        for (int32_t t = 0; t < n_celltypes; ++t) {
+            const auto t_bai = std::chrono::steady_clock::now();
+            std::vector<uint64_t> blk_ustart, blk_coff;
+            uint64_t coff = 0;
+            for (; b < blocks.size() && blocks[b].stream == (uint32_t)t; ++b) { blk_ustart.push_back(blocks[b].off - base[t]); blk_coff.push_back(coff); coff += (uint64_t)h_cs[b] + 26u; }
+            int rc = coff + 28 == (uint64_t)info->n_file_bytes[t] ? 0 : -1;
+            if (rc) set_error("lsg_split_bam: cell type %d's blocks end at %llu of %lld bytes", t, (unsigned long long)coff, (long long)info->n_file_bytes[t]);
+            else rc = bai_build(c, who, bai_f[t], blk_ustart, blk_coff, coff << 16, LSG_TABLE_SPLIT_BAI + t, d_bai_tmp, &bai_i[t]);
+            if (rc) { drop_tables(); return done(rc); }
+            bai_f[t].release();
+            bai_i[t].ms_total += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_bai).count();
+            c->split_bai[t] = bai_i[t];
+        }
+        c->split_bai_n = n_celltypes;
     }
     info->ms_deflate = tm.deflate; info->ms_crc = tm.crc; info->ms_pack = tm.pack;
     info->ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_all).count();

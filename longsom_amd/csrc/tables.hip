@@ -494,7 +494,7 @@ static int allele_limits(lsg_ctx* c, const char* who) {
 
 int run_format_table(lsg_ctx* c, int32_t table, int64_t* n_bytes) {
     if (n_bytes) *n_bytes = 0;
-    if (table >= LSG_TABLE_SPLIT_BAM && table < LSG_TABLE_ALL_SLOTS) { set_error("lsg_format_table: table %d is made by lsg_split_bam / lsg_bgzf_compress", table); return -2; }
+    if (table >= LSG_TABLE_SPLIT_BAM && table < LSG_TABLE_ALL_SLOTS) { set_error("lsg_format_table: table %d is made by lsg_split_bam / lsg_bgzf_compress / lsg_bam_index", table); return -2; }
     if (table < 0 || table >= LSG_TABLE_SLOTS) { set_error("lsg_format_table: no table %d", table); return -2; }
     if (table == LSG_TABLE_FASTQ) { set_error("lsg_format_table: table %d is made by lsg_bam_fastq", table); return -2; }
     if (!c->counted) { set_error("lsg_format_table: no count rows (lsg_pileup_count or lsg_load_counts first)"); return -2; }

@@ -525,8 +525,55 @@ class Engine:
         d = {k: getattr(info, k) for k, _ in info._fields_}
         for k in ("counters", "reasons_n", "reasons_first", "n_written", "n_ubytes", "n_blocks", "n_file_bytes"):
             d[k] = [int(x) for x in d[k]]
-        try:
+        failed = None
+        try:                                            # (the call's own error text, read before anything else is asked of the library)
             _lib.check(rc, "lsg_split_bam")
+        except _lib.LsgError as e:
+            failed = e
+        if self._split_index:                           # set_split_index: the cell types' indexes the call made (up to the one it refused)
+            d["index"] = []
+            for t in range(int(n_celltypes)):
+                bi = _lib.BaiInfo()
+                if self._lib.lsg_get_split_index_info(self._h, t, C.byref(bi)) != 0:
+                    break
+                d["index"].append({k: getattr(bi, k) for k, _ in bi._fields_ if k != "pad_"})
+        if failed is not None:
+            failed.info = d
+            raise failed
+        return d
+
+    TABLE_SPLIT_BAI, TABLE_BAI = 28, 32        # TABLE_SPLIT_BAI + t: the .bai of cell type t's BAM (set_split_index); bam_index's .bai
+    _split_index = False
+
+    def set_split_index(self, on: bool) -> None:
+        """lsg_set_split_index: split_bam also makes the .bai of every cell type's BAM (tables TABLE_SPLIT_BAI + t, their infos as
+        info["index"][t]; fetch with table_bytes(TABLE_SPLIT_BAI + t, info["index"][t]["n_bytes"])) out of the routing's own arrays.  An
+        input that is not coordinate-sorted then fails the call.  Off by default: split_bam is what it was."""
+        _lib.check(self._lib.lsg_set_split_index(self._h, 1 if on else 0), "lsg_set_split_index")
+        self._split_index = bool(on)
+
+    def bam_index(self, path: str, first_record_offset: Optional[int] = None) -> dict:
+        """lsg_bam_index: the .bai of a coordinate-sorted BAM - bins, chunks, the linear index, n_no_coor: samtools index / pysam.index in
+        this project's canonical form (the host twin is hostio.build_bai(full=True)) - made on the device into table
+        TABLE_BAI: fetch it with table_bytes(TABLE_BAI, info["n_bytes"]) or stream it into a file with append_table.  Returns the info dict.
+        Raises _lib.LsgError (.info holds the dict: bad_ordinal / bad_kind = hostio.BAI_ERR_*) for a file that is not sorted, a negative
+        position or an end beyond 2^29; with rc -4 / -3 for a BAM to index on the host."""
+        import mmap
+        from . import hostio
+        if first_record_offset is None:
+            first_record_offset = hostio.bam_header(path)[2]
+        info = _lib.BaiInfo()
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+                buf = np.frombuffer(mm, dtype=np.uint8)
+                try:
+                    rc = self._lib.lsg_bam_index(self._h, C.c_void_p(buf.ctypes.data), size, int(first_record_offset), C.byref(info))
+                finally:
+                    del buf
+        d = {k: getattr(info, k) for k, _ in info._fields_ if k != "pad_"}
+        try:
+            _lib.check(rc, "lsg_bam_index")
         except _lib.LsgError as e:
             e.info = d
             raise

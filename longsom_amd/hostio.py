@@ -458,15 +458,98 @@ def write_barcodes_tsv(path: str, barcodes: Sequence[str], celltype_of, celltype
             f.write("%s%s\t%s\n" % (b, suffix, celltype_names[int(c)]))
 
 
-# ---- the BAM index (.bai): linear index only ---------------------------------------------------------------------------------------
-def build_bai(bam: str, bai: Optional[str] = None) -> str:
-    """writes <bam>.bai with the linear index of a coordinate-sorted BAM (lsio_build_bai; no binning index — what samtools index
-    writes has both, read_bai takes either).  For the synthetic and fixture BAMs: real data comes with its .bai (rules/SNVCalling.smk:6-7)."""
+# ---- the BAM index (.bai): the linear index alone (lsio_build_bai) or the whole file (lsio_build_bai_full), and its readers --------
+BAI_ERR_UNSORTED, BAI_ERR_NEG_POS, BAI_ERR_TOO_FAR = 1, 2, 3      # lsg_bai_info's bad_kind (bamindex_core.h ERR_*)
+BAI_INFO_KEYS = ("n_records", "n_placed", "n_no_coor", "n_runs", "n_chunks", "n_bins", "n_windows", "n_bytes", "bad_ordinal", "bad_kind")
+
+
+class BaiError(RuntimeError):
+    """a BAM the index builder refuses; .info holds bad_ordinal / bad_kind (BAI_ERR_*)"""
+    info: dict = {}
+
+
+def build_bai(bam: str, bai: Optional[str] = None, full: bool = False) -> str:
+    """writes <bam>.bai for a coordinate-sorted BAM.  full=False: the linear index only (lsio_build_bai; n_bin = 0 — enough for read_bai and
+    regions.BaiPlan, nothing a reader of bins finds anything in).  full=True: the whole index - bins, chunks, the pseudo-bin, the
+    linear index, n_no_coor - in this project's canonical form (lsio_build_bai_full, the host twin of Engine.bam_index):
+    what samtools index / pysam.index are run for.  Raises BaiError for an unsorted file, a negative position or an end beyond 2^29."""
     lib = load()
     bai = bai or bam + ".bai"
+    if full:
+        info = (C.c_int64 * 10)()
+        lib.lsio_build_bai_full_info.restype = C.c_int
+        lib.lsio_build_bai_full_info.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p]
+        if lib.lsio_build_bai_full_info(os.fsencode(bam), os.fsencode(bai), info) != 0:
+            e = BaiError(lib.lsio_last_error().decode("utf-8", "replace"))
+            e.info = dict(zip(BAI_INFO_KEYS, (int(x) for x in info)))
+            raise e
+        return bai
     if lib.lsio_build_bai(os.fsencode(bam), os.fsencode(bai)) != 0:
         raise RuntimeError(lib.lsio_last_error().decode("utf-8", "replace"))
     return bai
+
+
+BAI_META_BIN = 37450
+
+
+def read_bai_full(path_or_bytes) -> dict:
+    """a whole .bai (SAM specification 5.2; a path, or the file's bytes) as {"refs": [per reference {"bins": {bin: [(beg, end), ...]} in the file's
+    order, without the pseudo-bin; "meta": None or (first start, last end, n_mapped, n_unmapped) - the pseudo-bin 37450's two chunks;
+    "ioffset": uint64 array}], "n_no_coor": int or None when the file ends without it}"""
+    import struct
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+    else:
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    if data[:4] != b"BAI\x01":
+        raise ValueError("not a BAI file")
+    (n_ref,) = struct.unpack_from("<i", data, 4)
+    at = 8
+    refs = []
+    for _ in range(n_ref):
+        (n_bin,) = struct.unpack_from("<i", data, at); at += 4
+        bins, meta = {}, None
+        for _ in range(n_bin):
+            b, n_chunk = struct.unpack_from("<Ii", data, at); at += 8
+            chunks = [struct.unpack_from("<QQ", data, at + 16 * k) for k in range(n_chunk)]; at += 16 * n_chunk
+            if b == BAI_META_BIN:
+                meta = tuple(int(x) for c in chunks for x in c)
+            else:
+                bins[int(b)] = [(int(a), int(e)) for a, e in chunks]
+        (n_intv,) = struct.unpack_from("<i", data, at); at += 4
+        io = np.frombuffer(data, dtype="<u8", count=n_intv, offset=at).copy(); at += 8 * n_intv
+        refs.append({"bins": bins, "meta": meta, "ioffset": io})
+    n_no_coor = None
+    if at + 8 <= len(data):
+        (n_no_coor,) = struct.unpack_from("<Q", data, at); at += 8
+    if at != len(data):
+        raise ValueError("BAI file of %d bytes, %d of them read" % (len(data), at))
+    return {"refs": refs, "n_no_coor": n_no_coor}
+
+
+def reg2bins(beg: int, end: int) -> List[int]:
+    """the bins that may hold an alignment overlapping [beg, end) (the specification's reg2bins)"""
+    end -= 1
+    out = [0]
+    for shift, first in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+        out.extend(range(first + (beg >> shift), first + (end >> shift) + 1))
+    return out
+
+
+def bai_query(index: dict, tid: int, beg: int, end: int) -> List[tuple]:
+    """the chunks (beg, end virtual offsets, sorted) a reader visits for the alignments of reference tid overlapping [beg, end): those of
+    reg2bins' bins, without the ones that end at or before the linear index's bound for the window of beg"""
+    ref = index["refs"][tid]
+    io = ref["ioffset"]
+    w = beg >> 14
+    bound = int(io[w]) if w < len(io) else (int(io[-1]) if len(io) else 0)
+    out = []
+    for b in reg2bins(beg, end):
+        for c in ref["bins"].get(b, ()):
+            if c[1] > bound:
+                out.append(c)
+    return sorted(out)
 
 
 def find_bai(bam: str) -> Optional[str]:

@@ -109,3 +109,26 @@ if config['PoN'].get('fit_on_gpu', False):
 else:
     ruleorder: BetaBinEstimation_PoN > BetaBinEstimation_gpu > PoN_fit_gpu
     ruleorder: PoN_gpu > PoN_fit_gpu
+
+# The drop-in for IndexBarcodedBam_PoN (PoN.smk:78-96: samtools index of a normal's tagged BAM): the whole .bai - bins, chunks, linear
+# index - made on the GPU (longsom_amd.cli index_bam; DESIGN.md section 16 has the file's form).  Optional key PoN.index_device: the GPU.
+# It makes the file the reference's rule makes, which stays beside it (the mapping rules of PoN.smk are kept): the `ruleorder:` behind the
+# rule leaves IndexBarcodedBam_PoN in charge unless the optional key PoN.index_on_gpu is true.  Like the one above it has not been
+# executed: snakemake is not installed where this file is tested.
+rule IndexBam_gpu:
+    input:
+        taggedbam=f"{DATA}/bam/{{norm}}.bam",
+    output:
+        bai_bc=f"{DATA}/bam/{{norm}}.bam.bai"
+    wildcard_constraints:
+        norm="([a-zA-Z]+)_Norm"
+    params:
+        script=GPU_SCRIPTS+"/PreProcessing/IndexBam.py",
+        device=(config.get('PoN') or {}).get('index_device', 0),
+    shell:
+        "python {params.script} --bam {input.taggedbam} --out {output.bai_bc} --device {params.device}"
+
+if config['PoN'].get('index_on_gpu', False):
+    ruleorder: IndexBam_gpu > IndexBarcodedBam_PoN
+else:
+    ruleorder: IndexBarcodedBam_PoN > IndexBam_gpu

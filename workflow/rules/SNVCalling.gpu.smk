@@ -79,3 +79,31 @@ rule SplitBam_gpu:
     shell:
         "python {params.script} --bam {input.bam} --meta {input.barcodes} --id {wildcards.id} --outdir SNVCalling/SplitBam --min_MQ {params.mapq} "
         "--max_nM={params.max_nm} --max_NH={params.max_nh} --n_trim={params.n_trim} --device {params.device}"
+
+# SplitBam_gpu with the indexes the reference's SplitBamCellTypes.py also leaves (pysam.index, :189-192): {id}.{celltype}.bam.bai beside
+# every BAM, made on the GPU out of the routing's own arrays.  Needed by whatever opens the split BAMs through their index: the
+# reference's BaseCellCounter.py (bam.pileup(contig, start, end)) when its rules are mixed with these (Option B), samtools view of a
+# region, IGV.  A rule of its own, so that SplitBam_gpu's outputs stay what they were.  Both rules make the BAMs, so the `ruleorder:` behind
+# this rule says which one a DAG that asks for a split BAM takes: SplitBam_gpu unless the optional key SNVCalling.SplitBam.index is true
+# (a target that asks for a .bai can only come from this rule either way).  The `ruleorder:` has not been executed: snakemake is not
+# installed where this file is tested (tests/test_rules_cpu.py parses the rules' shell lines against the scripts' parsers).
+rule SplitBamIndexed_gpu:
+    input:
+        bam=f"{INPUT}/bam/{{id}}.bam",
+        barcodes="CellTypeReannotation/ReannotatedCellTypes/{id}.tsv" if REANNO else "Barcodes/{id}.tsv",
+    output:
+        bam=expand("SNVCalling/SplitBam/{{id}}.{celltype}.bam", celltype=['Cancer','Non-Cancer']),
+        bai=expand("SNVCalling/SplitBam/{{id}}.{celltype}.bam.bai", celltype=['Cancer','Non-Cancer']),
+    params:
+        script=GPU_SCRIPTS+"/PreProcessing/SplitBamCellTypes.py",
+        mapq=config['SNVCalling']['BaseCellCounter']['min_mapping_quality'],
+        max_nm=SPLIT_FILTERS['max_nM'], max_nh=SPLIT_FILTERS['max_NH'], n_trim=SPLIT_FILTERS['n_trim'],
+        device=(config['SNVCalling'].get('SplitBam') or {}).get('device', 0),
+    shell:
+        "python {params.script} --bam {input.bam} --meta {input.barcodes} --id {wildcards.id} --outdir SNVCalling/SplitBam --min_MQ {params.mapq} "
+        "--max_nM={params.max_nm} --max_NH={params.max_nh} --n_trim={params.n_trim} --device {params.device} --index"
+
+if (config['SNVCalling'].get('SplitBam') or {}).get('index', False):
+    ruleorder: SplitBamIndexed_gpu > SplitBam_gpu
+else:
+    ruleorder: SplitBam_gpu > SplitBamIndexed_gpu
